@@ -12,9 +12,15 @@ ranks (strong scaling).  Barrier + synchronize bracket the K timed steps, the ti
 ranks.
 
 Prints ONE JSON line (rank 0) with `roofline` (algorithmic bytes of a step / device time per step,
-from HIP events on the bench stream around the timed region; the dominant kernel's own rate as
-kernel_only_*), `ceiling` (this device's rates for the same traffic: memory-only twins, probes) and
-`cpu_baseline` (the Java-algorithm restatement, oracle/, timed on the host cores at N=1).
+from HIP events on the bench stream around the timed region).
+
+A plain run does what the headline figure needs and nothing else: set up, settle, warm up, time the K
+steps, write the outputs (--dump-outputs DIR) and print the line.  --full adds the measurements that
+take runs of their own: the dominant kernel's own rate from a separate events pass (roofline.kernel_ms,
+aux_ms, kernel_only_*), `ceiling` (this device's rates for the same traffic: memory-only twins,
+probes), the decode configs' `round_trip` against the encoder input and `cpu_baseline` (the
+Java-algorithm restatement, oracle/, timed on the host cores at N=1).  Without --full those fields
+are null.
 """
 from __future__ import annotations
 
@@ -90,9 +96,17 @@ def parse():
                     help="strong scaling: one job of this many stacks split over the ranks (sharding.shard); "
                          "the default for c4_encode_4k is 64")
     ap.add_argument("--kind", default="ramp", choices=["ramp", "uniform"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the separate kernel-events pass "
+                         "(roofline.kernel_ms, aux_ms, kernel_only_*), the live ceiling probes, the decode "
+                         "configs' round trip against the encoder input and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the rows of an output above the size "
+                         "cap); N > 1: rank r > 0 writes DIR/<name>.rank<r>.npy")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ceiling", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-ceiling", action="store_true", help="--full without the ceiling probes")
     ap.add_argument("--xgmi", action="store_true",
                     help="N>1, encode configs: also time the optional host-of-record distribution (SURVEY.md §8e): "
                          "rank 0 scatters every rank's u8 stacks and gathers the int32 cubes back over RCCL p2p "
@@ -110,7 +124,10 @@ def parse():
                          "options change how results are reached, never the results")
     ap.add_argument("--eg-two-step", action="store_true",
                     help="c7 / c8: the int32 cube-major intermediate plus the stand-alone Exp-Golomb stage (A/B)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def rank_stacks(config: str, stacks_override, job_override, world: int, rank: int):
@@ -218,6 +235,8 @@ def bench_c1(a):
         q = plan.encode_q(fr, threads=threads)
         times.append(time.perf_counter() - t0)
     elapsed = time.perf_counter() - t_all
+    if a.dump_outputs:
+        dump_array(a.dump_outputs, "q", q, 64 * depth)
     cubes = (width // 8) * (height // 8)  # one stack
     ms = sorted(1e3 * t for t in times)
     value = cubes * a.steps / sum(times)
@@ -284,6 +303,35 @@ def job_roofline(per_rank, bytes_per_cube, peak_per_gpu=HBM_PEAK_GBS):
     return {"achieved": achieved, "peak": n * peak_per_gpu, "frac": achieved / (n * peak_per_gpu),
             "job_bytes_per_step": job_bytes, "max_rank_device_ms_per_step": t_ms,
             "min_rank_frac": min(r["frac"] for r in per_rank)}
+
+
+DUMP_CAP_BYTES = 32 << 20  # per array; a run writes at most two (EG: stream + bits), under 64 MB in all
+DUMP_SEED = 0x3DDC7
+
+
+def dump_array(out_dir, name, arr, row, rank=0):
+    """Write one output of the last timed step as out_dir/<name>.npy (rank r > 0: <name>.rank<r>.npy).
+    arr: a flat torch tensor (device or host) or numpy array, taken as rows of `row` elements (a cube, an
+    image line, a run of stream bytes).  Integers go out as float64 (exact), floats as float32.  Above
+    DUMP_CAP_BYTES a fixed sample of whole rows is written: ascending row indices drawn by a generator
+    seeded with DUMP_SEED, so two builds given the same arguments write the same rows."""
+    import numpy as np
+    import torch
+
+    t = torch.as_tensor(arr).reshape(-1)
+    dt = torch.float32 if t.dtype.is_floating_point and t.element_size() <= 4 else torch.float64
+    out_size = 4 if dt == torch.float32 else 8
+    if t.numel() % row == 0:
+        t = t.view(-1, row)
+    if t.numel() * out_size > DUMP_CAP_BYTES:
+        t = t.reshape(-1)
+        t = t[:t.numel() // row * row].view(-1, row)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        idx = torch.randperm(t.shape[0], generator=g)[:DUMP_CAP_BYTES // (row * out_size)].sort().values
+        t = t.index_select(0, idx.to(t.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), t.to(dt).cpu().numpy())
 
 
 def measure_ceiling(ctx, torch, frames, q, reps, geom=None, dec_geom=None):
@@ -547,7 +595,17 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     dev_step_ms = ev_a.elapsed_time(ev_b) / a.steps
-    if not events_timed:  # the kernel-timing pass: the same steps again, each launch between events
+    if a.dump_outputs and stacks:  # what the last timed step left in the caller's buffers, before any other pass
+        if direction in ("decode", "decode_eg"):
+            dump_array(a.dump_outputs, "frames", out, width, rank)
+        elif direction == "encode_eg":  # the stream's whole bytes and its length in bits
+            dump_array(a.dump_outputs, "eg_stream", eg_out.view(torch.uint8)[:eg_info["bits"] // 8], 4096, rank)
+            dump_array(a.dump_outputs, "eg_bits", [eg_info["bits"]], 1, rank)
+        elif direction in ("forward_f32", "inverse_f32"):
+            dump_array(a.dump_outputs, "cubes_f32", f_out, cs, rank)
+        else:
+            dump_array(a.dump_outputs, "q", q, cs, rank)
+    if a.full and not events_timed:  # the kernel-timing pass: the same steps again, each launch between events
         ctx.set_profiling(True)
         ctx.reset_timers()
         for _ in range(a.steps):
@@ -556,14 +614,14 @@ def main():
     st = ctx.stats()
     ctx.set_profiling(False)
     round_trip = None
-    if direction in ("decode", "decode_eg") and stacks:  # the codec's round trip
+    if a.full and direction in ("decode", "decode_eg") and stacks:  # the codec's round trip
         d = out.to(torch.int16) - frames.to(torch.int16)
         mse = float((d.to(torch.float64) ** 2).mean())
         round_trip = {"vs": "encoder input frames (lossy: quantisation); bit-exactness against the Java-semantics "
                             "decode is pinned by tests/test_gpu_parity.py",
                       "max_abs_err": int(d.abs().max()), "mean_abs_err": float(d.abs().to(torch.float64).mean()),
                       "psnr_db": (10.0 * math.log10(255.0 ** 2 / mse)) if mse > 0 else None}
-    ceiling = None if a.no_ceiling or q is None or not stacks else measure_ceiling(
+    ceiling = None if not a.full or a.no_ceiling or q is None or not stacks else measure_ceiling(
         ctx, torch, frames, q, max(3, a.steps // 2),
         geom=(width, height, stacks, cs * 5) if direction == "encode" else None,
         dec_geom=(width, height, stacks, torch.empty_like(frames)) if direction == "decode" else None)
@@ -577,6 +635,7 @@ def main():
     fused_dec = direction == "decode_eg" and not a.eg_two_step
     if fused_dec:  # the cube's share of the stream in, u8 out
         bytes_per_cube = cs + eg_info["bits"] / 8 / max(1, n_cubes)
+    kernel_timed = st["n_timed"] > 0  # the library's per-launch events ran (--full, or --kernel-events timed)
     kernel_ms = st["kernel_ms_total"] / max(1, st["n_timed"])
     aux_ms = st["aux_ms_total"] / max(1, st["n_timed"])
     alg_bytes = n_cubes * bytes_per_cube
@@ -658,10 +717,10 @@ def main():
             "bytes_per_cube": bytes_per_cube,
             "device_ms_per_step": dev_step_ms,
             "kernel": kname,
-            "kernel_ms": kernel_ms,
-            "aux_ms": aux_ms,
-            "kernel_only_achieved": kernel_achieved,
-            "kernel_only_frac": kernel_achieved / HBM_PEAK_GBS,
+            "kernel_ms": kernel_ms if kernel_timed else None,
+            "aux_ms": aux_ms if kernel_timed else None,
+            "kernel_only_achieved": kernel_achieved if kernel_timed else None,
+            "kernel_only_frac": kernel_achieved / HBM_PEAK_GBS if kernel_timed else None,
         },
         "ceiling": ceiling,
         "flagged_units_last_step": st["n_flagged"],
@@ -670,7 +729,7 @@ def main():
         "mcubes_per_s_per_gpu": value / world / 1e6,
         "eg_stage": None if direction not in ("encode_eg", "decode_eg") else {
             "path": ("fused" if fused_dec else "two-step") if direction == "decode_eg" else ("fused" if fused else "two-step"),
-            "ms_per_step": (aux_ms if fused else dev_step_ms if fused_dec
+            "ms_per_step": ((aux_ms if kernel_timed else None) if fused else dev_step_ms if fused_dec
                             else sum(x.elapsed_time(y) for x, y in eg_ev[-a.steps:]) / a.steps),
             "bits_per_value": eg_info["bits"] / (max(1, n_cubes) * cs),
             "stream_bytes_per_step": (eg_info["bits"] + 7) // 8},
@@ -691,7 +750,7 @@ def main():
                         "time per step / (N x 8 TB/s); rank0_* and per_rank hold the per-rank rates")
     if xgmi is not None:
         res["xgmi"] = xgmi
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(width, height, depth, a.cpu_baseline_seconds, a.kind)
         except Exception as e:  # the baseline is reported, never the target

@@ -32,3 +32,18 @@ def test_c1_line_parses_and_matches_golden():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and "availableProcessors()" in cb["pool_rule"]
     gold = np.load(os.path.join(REPO, "tests", "golden", "c1_64x64x8.npz"))["q"]
     assert d["output_sha256"] == hashlib.sha256(np.ascontiguousarray(gold, dtype=np.int32).tobytes()).hexdigest()
+
+
+def test_c1_dump_outputs_is_the_golden_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's quantised cubes as DIR/q.npy, float64 (exact for int32), one row
+    per cube; small enough to be written whole."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "c1_java_cpu_64x64",
+                        "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout)["steps"] == 2
+    assert os.listdir(tmp_path / "out") == ["q.npy"]
+    q = np.load(tmp_path / "out" / "q.npy")
+    gold = np.load(os.path.join(REPO, "tests", "golden", "c1_64x64x8.npz"))["q"]
+    assert q.dtype == np.float64 and q.shape == (64, 512)
+    assert np.array_equal(q.reshape(-1), np.asarray(gold, dtype=np.float64).reshape(-1))

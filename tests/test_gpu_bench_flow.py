@@ -57,6 +57,38 @@ def test_two_rank_bench_line(config, args, scaling):
     assert abs(d["value"] - cubes / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
 
 
+def test_plain_line_and_dumped_outputs(pkg, plan8, tmp_path):
+    """A plain run (no --full): the headline fields, none of the separate passes (their fields are null), and
+    --dump-outputs writes the last timed step's cubes -- here one 1080p stack, 32,400 cubes, above the size cap,
+    so the seeded sample of whole cubes -- equal to the oracle's encode of the same synthetic frames."""
+    import importlib
+
+    import numpy as np
+    import torch
+
+    bench = importlib.import_module("bench")
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--settle-ms", "0", "--stacks", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["metric"] == bench.HEADLINE_METRIC and d["unit"] == "cubes/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 32400 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["cpu_baseline"] is None and d["ceiling"] is None and d["roofline"]["kernel_ms"] is None
+    assert 0 < d["roofline"]["frac"] <= 1
+    assert os.listdir(out) == ["q.npy"]
+    q = np.load(out / "q.npy")
+    rows = bench.DUMP_CAP_BYTES // (512 * 8)
+    assert q.dtype == np.float64 and q.shape == (rows, 512)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(bench.DUMP_SEED)
+    idx = torch.randperm(32400, generator=g)[:rows].sort().values.numpy()
+    ref = plan8.encode_q(pkg.synthetic.frames(1920, 1080, 8, kind="ramp")).reshape(32400, 512)
+    assert np.array_equal(q, ref[idx].astype(np.float64))
+
+
 def test_rccl_path_single_rank():
     """The RCCL ("nccl") branch of the N > 1 flow -- init_process_group with the rank's device, barrier,
     the per-rank all_gather, the max / sum all-reduces and the --xgmi leg's collectives -- executed for

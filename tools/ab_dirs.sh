@@ -11,7 +11,7 @@ for i in $(seq 1 ${ROUNDS:-2}); do
     label=${v%%|*}; args=${v#*|}
     for side in ${SIDES:-base cur}; do
       dir=.; [ $side != cur ] && dir=ab/$side
-      (cd $dir && timeout -k 10 180 python bench.py $args --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-ceiling) \
+      (cd $dir && timeout -k 10 180 python bench.py $args --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --no-ceiling) \
          > $OUT/${label}_${side}_$i.log 2>&1
       rc=$?; [ $rc -ne 0 ] && { tail -5 $OUT/${label}_${side}_$i.log; echo "stopping: $label $side rc=$rc"; exit $rc; }
       tail -1 $OUT/${label}_${side}_$i.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$label', '$side', $i, 'ms/step', round(d['ms_per_step'],4), 'kernel', round(r['kernel_ms'],4), 'frac', round(r['frac'],4), 'rechecked', d.get('rechecked_units_last_step'))"

@@ -21,7 +21,7 @@ first=$1; label=${first%%|*}; args=${first#*|}
 for side in ${SIDES:-base cur}; do
   dir=.; [ $side != cur ] && dir=ab/$side
   (cd $dir && timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof_$side -o run --output-format csv -- \
-     python3 bench.py $args --steps 20 --warmup 5 --no-cpu-baseline --no-ceiling) > $O/prof_$side.log 2>&1
+     python3 bench.py $args --steps 20 --warmup 5 --full --no-cpu-baseline --no-ceiling) > $O/prof_$side.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "rocprof $side rc=$rc"; tail -3 $O/prof_$side.log; exit $rc; }
   f=$(find $O/prof_$side -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats_${label}_$side.csv
   python3 -c "

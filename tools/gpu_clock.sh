@@ -12,7 +12,7 @@ for v in "$@"; do
   label=${v%%|*}; args=${v#*|}
   timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace \
      -d $OUT/$label -o pmc --output-format csv -- \
-     python3 bench.py $args --steps 10 --warmup 3 --no-cpu-baseline --no-ceiling > $OUT/$label.log 2>&1
+     python3 bench.py $args --steps 10 --warmup 3 --full --no-cpu-baseline --no-ceiling > $OUT/$label.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { tail -5 $OUT/$label.log; echo "stopping: $label rc=$rc"; exit $rc; }
   echo "clock $label collected"
 done

@@ -19,7 +19,7 @@ for r in $(seq 1 ${ROUNDS:-1}); do
 for v in "$@"; do
   IFS='|' read -r label dir args <<< "$v"
   (cd $dir && timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof_${label}_$r -o run --output-format csv -- \
-     python3 bench.py $args --steps 20 --warmup 5 --no-cpu-baseline --no-ceiling) > $O/prof_${label}_$r.log 2>&1
+     python3 bench.py $args --steps 20 --warmup 5 --full --no-cpu-baseline --no-ceiling) > $O/prof_${label}_$r.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "rocprof $label rc=$rc"; tail -3 $O/prof_${label}_$r.log; exit $rc; }
   f=$(find $O/prof_${label}_$r -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats_${label}_$r.csv
   [ -z "$KEEP_TRACE" ] && rm -rf $O/prof_${label}_$r  # the traces: 10+ MiB each (gpurun copies back <= 64 MiB)

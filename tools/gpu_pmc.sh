@@ -10,7 +10,7 @@ mkdir -p $OUT profiles/pmc
 for cfg in ${CONFIGS:-c2_encode_1080p c3_decode_1080p}; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $ctr -d $OUT/${cfg}_$ctr -o pmc --output-format csv -- \
-       python3 bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-ceiling > $OUT/${cfg}_$ctr.log 2>&1
+       python3 bench.py --config $cfg --steps 3 --warmup 1 --full --no-cpu-baseline --no-ceiling > $OUT/${cfg}_$ctr.log 2>&1
     rc=$?; [ $rc -ne 0 ] && { tail -5 $OUT/${cfg}_$ctr.log; echo "stopping: $cfg $ctr rc=$rc"; exit $rc; }
   done
   echo "pmc $cfg collected"

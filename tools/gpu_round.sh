@@ -22,13 +22,13 @@ declare -A CFG=( [c2]="--config c2_encode_1080p" [c2u]="--config c2_encode_1080p
                  [c9]="--config c9_forward_f32_1080p" [c10]="--config c10_inverse_f32_1080p" )
 for c in ${CONFIGS:-c2 c2u c3 c4}; do
   extra="--no-cpu-baseline"; [ "$c" = c2 ] && extra=""
-  timeout -k 10 240 python bench.py ${CFG[$c]} --steps ${STEPS:-20} --warmup 5 $extra > $OUT/bench_$c.log 2>&1
+  timeout -k 10 240 python bench.py ${CFG[$c]} --steps ${STEPS:-20} --warmup 5 --full $extra > $OUT/bench_$c.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { tail -5 $OUT/bench_$c.log; stop $rc bench_$c; }
   tail -1 $OUT/bench_$c.log > $OUT/bench_$c.json
   python3 -c "import json; r=json.load(open('$OUT/bench_$c.json')); f=r.get('roofline') or {}; print('$c', round(r['value']/1e9,4), 'G/s ms/step', round(r['ms_per_step'],4), 'frac', f.get('frac'), 'kernel_ms', f.get('kernel_ms'))"
   if [ -z "$NO_PROF" ]; then
     timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/prof_$c -o run --output-format csv -- \
-       python3 bench.py ${CFG[$c]} --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-ceiling > $OUT/prof_$c.log 2>&1
+       python3 bench.py ${CFG[$c]} --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --no-ceiling > $OUT/prof_$c.log 2>&1
     rc=$?; [ $rc -ne 0 ] && { tail -5 $OUT/prof_$c.log; stop $rc prof_$c; }
     f=$(find $OUT/prof_$c -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $OUT/kernel_stats_$c.csv
     [ -z "$KEEP_TRACE" ] && rm -rf $OUT/prof_$c  # the traces (10+ MiB each; gpurun copies back <= 64 MiB)

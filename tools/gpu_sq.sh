@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out/sq${SQ_TAG:+_$SQ_TAG}; mkdir -p $OUT
-ARGS=${BENCH_ARGS:-"--steps 6 --warmup 2 --no-cpu-baseline --no-ceiling"}
+ARGS=${BENCH_ARGS:-"--steps 6 --warmup 2 --full --no-cpu-baseline --no-ceiling"}
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU" \

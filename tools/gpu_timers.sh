@@ -12,7 +12,7 @@ for c in ${CONFIGS:-c2}; do
     c5) args="--config c5_encode_1080p_d4"; k=encode_kernel;;
   esac
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/prof_$c -o run --output-format csv -- \
-     python3 bench.py $args --steps 20 --warmup 5 --no-cpu-baseline --no-ceiling > $O/prof_$c.log 2>&1 \
+     python3 bench.py $args --steps 20 --warmup 5 --full --no-cpu-baseline --no-ceiling > $O/prof_$c.log 2>&1 \
      || { echo "rocprof $c failed"; tail -3 $O/prof_$c.log; exit 1; }
   f=$(find $O/prof_$c -name '*kernel_trace.csv' | head -1)
   python3 tools/timed_trace.py "$f" $O/prof_$c.log $k --out $O/timed_trace_$c.json | grep -v '^  *[0-9]' | head -30

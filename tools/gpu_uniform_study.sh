@@ -10,7 +10,7 @@ OUT=$O bash tools/gpu_clock.sh "c2|--config c2_encode_1080p" "c2u|--config c2_en
 for v in "c2|--config c2_encode_1080p" "c2u|--config c2_encode_1080p --kind uniform" \
          "c3|--config c3_decode_1080p" "c3u|--config c3_decode_1080p --kind uniform"; do
   label=${v%%|*}; args=${v#*|}
-  SQ_TAG=${O}_$label BENCH_ARGS="$args --steps 6 --warmup 2 --no-cpu-baseline --no-ceiling --settle-ms 0" \
+  SQ_TAG=${O}_$label BENCH_ARGS="$args --steps 6 --warmup 2 --full --no-cpu-baseline --no-ceiling --settle-ms 0" \
      SQ_EXTRA="SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" bash tools/gpu_sq.sh > /dev/null || exit $?
   echo "sq $label collected"
 done
