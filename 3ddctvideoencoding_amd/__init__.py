@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "dct3d_plan_query",
     "dct3d_eg_encode_dev", "dct3d_encode_eg", "dct3d_eg_fetch", "dct3d_diagonal_order",
     "dct3d_eg_decode_dev", "dct3d_decode_eg", "dct3d_encode_eg_dev", "dct3d_decode_eg_dev",
+    "dct3d_encode_stacks_rgb", "dct3d_encode_stacks_rgb_dev", "dct3d_decode_stacks_rgb", "dct3d_decode_stacks_rgb_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -105,6 +106,9 @@ def lib() -> C.CDLL:
         for name in ("dct3d_encode_stacks", "dct3d_encode_stacks_dev"):
             getattr(L, name).argtypes = [vp, vp, i32, i32, i32, vp, vp]
         for name in ("dct3d_decode_stacks", "dct3d_decode_stacks_dev"):
+            getattr(L, name).argtypes = [vp, vp, i32, i32, i32, vp]
+        for name in ("dct3d_encode_stacks_rgb", "dct3d_encode_stacks_rgb_dev", "dct3d_decode_stacks_rgb",
+                     "dct3d_decode_stacks_rgb_dev"):
             getattr(L, name).argtypes = [vp, vp, i32, i32, i32, vp]
         for name in ("dct3d_forward_f32", "dct3d_inverse_f32", "dct3d_forward_f32_dev", "dct3d_inverse_f32_dev"):
             getattr(L, name).argtypes = [vp, vp, sz, vp]
@@ -280,6 +284,33 @@ class Context:
                "dct3d_decode_stacks")
         return out
 
+    # packed RGB24 (uint8 [frame][y][x][3]); q is laid out [stack][channel][cube]: block (s, ch) is what
+    # encode_stacks gives for stack s of channel ch's plane (include/dct3d.h)
+    def encode_stacks_rgb(self, frames: np.ndarray) -> np.ndarray:
+        """packed RGB24 frames [n_stacks*bd, H, W, 3] -> quantised int32 cubes [3 * n_cubes, bd, bh, bw],
+        equal to encode_stacks of the planar-stacked raster (per stack: its R, then G, then B frames)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        if frames.ndim != 4 or frames.shape[3] != 3:
+            raise ValueError("packed RGB24 frames must have shape [F, H, W, 3]")
+        F, H, W, _ = frames.shape
+        if F % self.bd:
+            raise ValueError("frame count must be a multiple of the block depth")
+        n = self.n_cubes(W, H, F // self.bd)
+        q = np.empty((3 * n, self.bd, self.bh, self.bw), np.int32)
+        _check(lib().dct3d_encode_stacks_rgb(self._h, _ptr(frames), W, H, F // self.bd, _ptr(q)),
+               "dct3d_encode_stacks_rgb")
+        return q
+
+    def decode_stacks_rgb(self, q: np.ndarray, width: int, height: int, n_stacks: int) -> np.ndarray:
+        """the inverse of encode_stacks_rgb: packed RGB24 frames [n_stacks*bd, H, W, 3]"""
+        q = np.ascontiguousarray(q, np.int32)
+        if q.size != 3 * self.n_cubes(width, height, n_stacks) * self.cube_size:
+            raise ValueError("q must hold 3 * n_cubes cubes")
+        out = np.empty((n_stacks * self.bd, height, width, 3), np.uint8)
+        _check(lib().dct3d_decode_stacks_rgb(self._h, _ptr(q), width, height, n_stacks, _ptr(out)),
+               "dct3d_decode_stacks_rgb")
+        return out
+
     def forward_f32(self, cubes: np.ndarray) -> np.ndarray:
         cubes = np.ascontiguousarray(cubes, np.float32)
         n = cubes.size // self.cube_size
@@ -303,6 +334,14 @@ class Context:
     def decode_stacks_dev(self, d_q, width: int, height: int, n_stacks: int, d_frames) -> None:
         _check(lib().dct3d_decode_stacks_dev(self._h, _tptr(d_q), width, height, n_stacks, _tptr(d_frames)),
                "dct3d_decode_stacks_dev")
+
+    def encode_stacks_rgb_dev(self, d_frames, width: int, height: int, n_stacks: int, d_q) -> None:
+        _check(lib().dct3d_encode_stacks_rgb_dev(self._h, _tptr(d_frames), width, height, n_stacks, _tptr(d_q)),
+               "dct3d_encode_stacks_rgb_dev")
+
+    def decode_stacks_rgb_dev(self, d_q, width: int, height: int, n_stacks: int, d_frames) -> None:
+        _check(lib().dct3d_decode_stacks_rgb_dev(self._h, _tptr(d_q), width, height, n_stacks, _tptr(d_frames)),
+               "dct3d_decode_stacks_rgb_dev")
 
     def forward_f32_dev(self, d_in, n_cubes: int, d_out) -> None:
         _check(lib().dct3d_forward_f32_dev(self._h, _tptr(d_in), n_cubes, _tptr(d_out)), "dct3d_forward_f32_dev")

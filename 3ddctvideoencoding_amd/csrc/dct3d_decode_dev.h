@@ -239,13 +239,18 @@ __device__ __forceinline__ int dec_cube_of_lane(int lane) { return (lane >> 5) *
 // the block must call this (the barrier); a full block has no early-returning wave.
 // LOOP: called inside a caller's loop (decode_eg_kernel's groups): the lane's addresses are made here, not
 // hoisted out of the loop and held across the transform.
-template <int D, bool LOOP = false>
+// PX = 3: a packed RGB24 raster (P.plane, P.stack_stride: bytes, P.width: pixels).  outw holds the lane's
+// pixels interleaved, 3 NXC bytes per plane; a cube's row is 24 bytes, so a 16-byte chunk lies in one cube or
+// in an even cube and the odd one after it (3 chunks per pair): with nbx even it never straddles a block-row,
+// as in the grey case, and it is 16-byte aligned (rows, block-rows and stacks are multiples of 48 bytes).
+template <int D, bool LOOP = false, int PX = 1>
 __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
-                                               const uint32_t (&outw)[D][(D == 8) ? 1 : 2], bool valid) {
+                                               const uint32_t (&outw)[D][((D == 8) ? 1 : 2) * PX], bool valid) {
     using G = DecGeom<D>;
     constexpr int CPW = G::CPW;
     constexpr int NXC = (D == 8) ? 4 : 8;
-    constexpr int W = CPW * 8;  // bytes of one row of the wave's cubes
+    constexpr int W = CPW * 8 * PX;  // bytes of one row of the wave's cubes
+    static_assert(D * 8 * W <= kDecWaveLds && W % 16 == 0, "the wave's rows fit its region, in whole chunks");
     const int h = (lane >> 4) & 1, k = lane & (D - 1);
     const int y = (D == 8) ? k : (4 * h + k);
     const int x0 = (D == 8) ? 4 * h : 0;
@@ -255,9 +260,15 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
     if (P.blk_store && blk0 + kWavesPerBlock * CPW <= P.n_cubes) {  // block-uniform
 #pragma unroll
         for (int z = 0; z < D; z++) {
-            char* t = wl + z * 8 * W + y * W + c * 8 + x0;
-            if constexpr (NXC == 4) *(uint32_t*)t = outw[z][0];
-            else *(uint2*)t = make_uint2(outw[z][0], outw[z][1]);
+            if constexpr (PX == 3) {
+                char* t = wl + z * 8 * W + y * W + (c * 8 + x0) * 3;
+#pragma unroll
+                for (int i = 0; i < NXC / 4 * 3; i++) *(uint32_t*)(t + 4 * i) = outw[z][i];
+            } else {
+                char* t = wl + z * 8 * W + y * W + c * 8 + x0;
+                if constexpr (NXC == 4) *(uint32_t*)t = outw[z][0];
+                else *(uint2*)t = make_uint2(outw[z][0], outw[z][1]);
+            }
         }
         __syncthreads();
         const char* lds0 = wl - wave * kDecWaveLds;
@@ -271,14 +282,26 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
         const uint32_t rr0 = b0 - s0 * P.cubes_per_stack;
         const uint32_t by0 = fdiv(rr0, P.div_nbx), bx0 = rr0 - by0 * P.nbx;
         const bool one_row = bx0 + kWavesPerBlock * CPW <= P.nbx;
-        uint8_t* const base0 = P.out + (size_t)s0 * P.stack_stride + (size_t)(by0 * 8) * P.width + bx0 * 8;
+        uint8_t* const base0 = PX == 3 ? P.out + (size_t)s0 * P.stack_stride + ((size_t)(by0 * 8) * P.width + bx0 * 8) * 3
+                                       : P.out + (size_t)s0 * P.stack_stride + (size_t)(by0 * 8) * P.width + bx0 * 8;
 #pragma unroll
         for (int i = 0; i < D * 8 * CPR / kBlock; i++) {
             const int q = tid + kBlock * i;
             const int z = q / (8 * CPR), r = q % (8 * CPR), yy = r / CPR, j = r % CPR;
             const int4 v = *(const int4*)(lds0 + (j * 16 / W) * kDecWaveLds + z * 8 * W + yy * W + (j * 16) % W);
             uint8_t* dst;
-            if (one_row) {
+            if constexpr (PX == 3) {
+                if (one_row) {
+                    dst = base0 + ((uint32_t)z * (uint32_t)P.plane + (uint32_t)yy * P.width * 3u + (uint32_t)j * 16u);  // < 2^32 within a stack
+                } else {
+                    const uint32_t gc = blk0 + 2 * j / 3;  // the cube of the chunk's first byte, byte 16 j % 24 of its row
+                    const uint32_t s = fdiv(gc, P.div_cps);
+                    const uint32_t rr = gc - s * P.cubes_per_stack;
+                    const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+                    dst = P.out + (size_t)s * P.stack_stride + (size_t)z * P.plane +
+                          ((size_t)(by * 8 + yy) * P.width + bx * 8) * 3 + j * 16 % 24;
+                }
+            } else if (one_row) {
                 dst = base0 + ((uint32_t)z * (uint32_t)P.plane + (uint32_t)yy * P.width + (uint32_t)j * 16u);  // < 2^32 within a stack
             } else {
                 const uint32_t gc = blk0 + 2 * j;
@@ -294,10 +317,14 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
         const uint32_t s = fdiv(g, P.div_cps);
         const uint32_t rr = g - s * P.cubes_per_stack;
         const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
-        uint8_t* dst = P.out + (size_t)s * P.stack_stride + (size_t)(by * 8 + y) * P.width + bx * 8 + x0;
+        uint8_t* dst = PX == 3 ? P.out + (size_t)s * P.stack_stride + ((size_t)(by * 8 + y) * P.width + bx * 8 + x0) * 3
+                               : P.out + (size_t)s * P.stack_stride + (size_t)(by * 8 + y) * P.width + bx * 8 + x0;
 #pragma unroll
         for (int z = 0; z < D; z++, dst += P.plane) {  // one 64-bit add per plane
-            if constexpr (NXC == 4) *(uint32_t*)dst = outw[z][0];
+            if constexpr (PX == 3) {  // the lane's own 3 NXC bytes (4-byte aligned), nothing else
+#pragma unroll
+                for (int i = 0; i < NXC / 4 * 3; i++) *(uint32_t*)(dst + 4 * i) = outw[z][i];
+            } else if constexpr (NXC == 4) *(uint32_t*)dst = outw[z][0];
             else *(uint2*)dst = make_uint2(outw[z][0], outw[z][1]);
         }
     }
@@ -315,9 +342,12 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
 // fp64 product and fp64 L1 sum.  A lane holding a code >= 2^16 (|q| >= 2^15: a code of 33+ bits, never
 // written for 8-bit frames) reports L1 = inf, so its whole cube goes to the exact replay, which reloads the
 // values from the stream.
-template <int D, int PG, bool LOOP = false, bool CODES = false, class AfterA, class Reload>
+// KEEP (decode_rgb_kernel): no stores; the lane's words outw[z][wd] go to keep[z * NXC / 4 + wd] and the
+// lane's `valid` to *keep_valid.
+template <int D, int PG, bool LOOP = false, bool CODES = false, bool KEEP = false, class AfterA, class Reload>
 __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
-                                            AfterA&& after_a, const Reload& reload) {
+                                            AfterA&& after_a, const Reload& reload, uint32_t* keep = nullptr,
+                                            bool* keep_valid = nullptr) {
     using G = DecGeom<D>;
     constexpr int CPW = G::CPW;
     constexpr int NXC = (D == 8) ? 4 : 8;  // x values per lane in layout C
@@ -518,6 +548,14 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
         }
         if (lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), nrep);
     }
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NXC / 4; wd++) keep[z * (NXC / 4) + wd] = outw[z][wd];
+        *keep_valid = valid;
+        return;
+    }
     __builtin_amdgcn_s_setprio(2);  // the store phase ahead of the computing waves (as encode16_kernel)
     dec_store_tile<D, LOOP>(P, wl, lane, cube0, outw, valid);
 }
@@ -545,6 +583,102 @@ __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     dec_stage_tile<D>(wl, lane, v);
     wave_lds_sync();
     decode_tile<D, PG>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed RGB24 decode (dct3d_decode_stacks_rgb_dev).  The input is laid out [stack][channel][cube]; P.n_cubes
+// counts RGB cubes g (stack s = g / cubes_per_stack), and cube g of channel ch is cube
+// g + (2 s + ch) cubes_per_stack of the input.  The wave decodes the three channels of its tile one after
+// the other (decode_tile<KEEP>) and merges each channel's bytes into the lane's interleaved output words
+// (one v_perm_b32 per word: byte 3 p + ch of the lane's 3 NXC bytes is pixel p of channel ch), which stay
+// in registers (3 NXC / 4 per plane) until dec_store_tile<PX = 3> writes R, G, B together.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t dec_rgb_cube(const DecodeParams& P, uint32_t g, int ch) {
+    return g + (2u * fdiv(g, P.div_cps) + (uint32_t)ch) * P.cubes_per_stack;
+}
+// selector of word j of 3: a byte of the channel's word where one belongs there, else the word's own byte
+constexpr uint32_t rgb_put_sel(int ch, int j) {
+    uint32_t s = 0;
+    for (int i = 0; i < 4; i++) {
+        const int o = 4 * j + i;
+        s |= (uint32_t)(o % 3 == ch ? o / 3 : 4 + i) << (8 * i);
+    }
+    return s;
+}
+// dec_load_tile for channel ch: a load instruction lies within one cube (CS / 4 >= 64 chunks per cube), so
+// its cube's place in the input is wave-uniform
+template <int D>
+__device__ __forceinline__ void dec_load_tile_rgb(const DecodeParams& P, uint32_t cube0, int ch, int lane, int4 (&v)[8]) {
+    using G = DecGeom<D>;
+    constexpr int CPC = G::CS / 4;  // 16-byte chunks per cube
+    static_assert(CPC % 64 == 0, "whole load instructions per cube");
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const uint32_t g = cube0 + t * 64 / CPC;
+        i32x4_t x = {0, 0, 0, 0};
+        if (g < P.n_cubes) {  // wave-uniform
+            const char* src = (const char*)(P.in + (size_t)dec_rgb_cube(P, g, ch) * G::CS);
+            x = __builtin_nontemporal_load((const i32x4_t*)(src + (size_t)((t * 64 + lane) % CPC) * 16));
+        }
+        v[t] = make_int4(x.x, x.y, x.z, x.w);
+    }
+}
+template <int D>
+struct ReloadCubesRgb {  // ReloadCubes for cube g of channel ch (dec_rgb_cube, by value: no copy of P in memory)
+    const int32_t* in;
+    FastDiv div_cps;
+    uint32_t cubes_per_stack;
+    int ch;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        ReloadCubes<D>{in}(g + (2u * fdiv(g, div_cps) + (uint32_t)ch) * cubes_per_stack, cf, lane);
+    }
+};
+
+template <int D, int PG>
+__global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
+    constexpr int NW = (D == 8) ? 1 : 2;  // words per plane and channel
+    __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
+    const int wave = threadIdx.x >> 6;
+    char* wl = lds + wave * kDecWaveLds;
+    const uint32_t cube0 = (xcd_tile() * kWavesPerBlock + wave) * DecGeom<D>::CPW;
+    dec_clear_next_slot(P);
+    uint32_t out3[D][3 * NW];
+#pragma unroll
+    for (int z = 0; z < D; z++)
+#pragma unroll
+        for (int i = 0; i < 3 * NW; i++) out3[z][i] = 0u;
+    bool valid = false;
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ch++) {
+        // (an opaque lane index: the lane's indices and addresses are made again for each channel, not
+        // hoisted out of the loop and held across the transform)
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));
+        {
+            int4 v[8];
+            __builtin_amdgcn_s_setprio(3);  // the loads ahead of the computing waves
+            dec_load_tile_rgb<D>(P, cube0, ch, lane, v);
+            __builtin_amdgcn_s_setprio(0);
+            wave_lds_sync();  // the previous channel's use of the region is over
+            dec_stage_tile<D>(wl, lane, v);
+        }
+        wave_lds_sync();
+        uint32_t outw[D][NW];
+        decode_tile<D, PG, false, false, true>(P, wl, lane, cube0, [] {}, ReloadCubesRgb<D>{P.in, P.div_cps, P.cubes_per_stack, ch}, &outw[0][0], &valid);
+        const uint32_t s0 = ch == 0 ? rgb_put_sel(0, 0) : ch == 1 ? rgb_put_sel(1, 0) : rgb_put_sel(2, 0);
+        const uint32_t s1 = ch == 0 ? rgb_put_sel(0, 1) : ch == 1 ? rgb_put_sel(1, 1) : rgb_put_sel(2, 1);
+        const uint32_t s2 = ch == 0 ? rgb_put_sel(0, 2) : ch == 1 ? rgb_put_sel(1, 2) : rgb_put_sel(2, 2);
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NW; wd++) {
+                out3[z][3 * wd] = __builtin_amdgcn_perm(out3[z][3 * wd], outw[z][wd], s0);
+                out3[z][3 * wd + 1] = __builtin_amdgcn_perm(out3[z][3 * wd + 1], outw[z][wd], s1);
+                out3[z][3 * wd + 2] = __builtin_amdgcn_perm(out3[z][3 * wd + 2], outw[z][wd], s2);
+            }
+    }
+    __builtin_amdgcn_s_setprio(2);  // the store phase ahead of the computing waves
+    dec_store_tile<D, false, 3>(P, wl, (int)(threadIdx.x & 63), cube0, out3, valid);
 }
 
 }  // namespace dct3d

@@ -33,6 +33,84 @@ __device__ __forceinline__ void load_rows(const EncodeParams& P, uint32_t g, boo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Packed RGB24 rasters (PX = 3: uint8 [frame][y][x][3], R, G, B).  A lane loads the 24 bytes of its 8
+// pixels once (8-byte aligned: the width is a multiple of 8) and picks a channel's 8 bytes out of them
+// with two v_perm_b32 per dword; the selectors depend on the channel alone (scalar registers).  Byte
+// 3 p + ch of the 12 bytes {w0, w1, w2} is pixel p of channel ch.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t rgb_pick_sel1(int ch) {  // perm(w1, w0, .): the bytes that lie in w0 / w1, in place
+    uint32_t s = 0;
+    for (int i = 0; i < 4; i++) {
+        const int b = ch + 3 * i, d = b >> 2;
+        s |= (uint32_t)(d == 0 ? (b & 3) : d == 1 ? 4 + (b & 3) : 0) << (8 * i);
+    }
+    return s;
+}
+constexpr uint32_t rgb_pick_sel2(int ch) {  // perm(w2, t, .): the bytes of w2 added
+    uint32_t s = 0;
+    for (int i = 0; i < 4; i++) {
+        const int b = ch + 3 * i, d = b >> 2;
+        s |= (uint32_t)(d < 2 ? i : 4 + (b & 3)) << (8 * i);
+    }
+    return s;
+}
+__device__ __forceinline__ void rgb_load24(const uint8_t* src, uint2 (&w)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) w[i] = *(const uint2*)(src + 8 * i);
+}
+__device__ __forceinline__ uint2 rgb_pick8(const uint2 (&w)[3], int ch) {
+    const uint32_t s1 = ch == 0 ? rgb_pick_sel1(0) : ch == 1 ? rgb_pick_sel1(1) : rgb_pick_sel1(2);
+    const uint32_t s2 = ch == 0 ? rgb_pick_sel2(0) : ch == 1 ? rgb_pick_sel2(1) : rgb_pick_sel2(2);
+    return make_uint2(__builtin_amdgcn_perm(w[1].x, __builtin_amdgcn_perm(w[0].y, w[0].x, s1), s2),
+                      __builtin_amdgcn_perm(w[2].y, __builtin_amdgcn_perm(w[2].x, w[1].y, s1), s2));
+}
+// Cube g of a packed RGB24 raster (stack s = g / cubes_per_stack) -> its cube in channel ch's block of
+// the output, layout [stack][channel][cube]; grey: g itself
+template <int PX>
+__device__ __forceinline__ uint32_t enc_out_cube(const EncodeParams& P, uint32_t g, int ch) {
+    if constexpr (PX == 1) return g;
+    else return g + (2u * fdiv(g, P.div_cps) + (uint32_t)ch) * P.cubes_per_stack;
+}
+// load_rows for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
+template <int D>
+__device__ __forceinline__ void load_rows_rgb(const EncodeParams& P, uint32_t g, bool valid, int j, uint2 (&raw)[D][3]) {
+    if (valid) {
+        const uint32_t s = fdiv(g, P.div_cps);
+        const uint32_t r = g - s * P.cubes_per_stack;
+        const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
+        const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
+#pragma unroll
+        for (int z = 0; z < D; z++) rgb_load24(src + (size_t)z * P.plane, raw[z]);
+    } else {
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) raw[z][i] = make_uint2(0u, 0u);
+    }
+}
+
+// the rows of channel ch alone (the rare path's reload), one row's 24 bytes in registers at a time
+template <int D>
+__device__ __forceinline__ void load_rows_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int j, int ch,
+                                                 uint2 (&raw)[D]) {
+#pragma unroll
+    for (int z = 0; z < D; z++) raw[z] = make_uint2(0u, 0u);
+    if (valid) {
+        const uint32_t s = fdiv(g, P.div_cps);
+        const uint32_t r = g - s * P.cubes_per_stack;
+        const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
+        const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
+#pragma unroll
+        for (int z = 0; z < D; z++) {
+            uint2 w[3];
+            rgb_load24(src + (size_t)z * P.plane, w);
+            raw[z] = rgb_pick8(w, ch);
+            asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
+        }
+    }
+}
+
 template <int D>
 __device__ __forceinline__ void to_float(const uint2 (&raw)[D], float (&a)[D][8]) {
 #pragma unroll
@@ -172,9 +250,10 @@ __device__ __forceinline__ void store16(void* p, const int4& v) {
 
 // Stage the wave's 8 quantised cubes through LDS (face-padded cube-major) and store them 1 KiB per
 // instruction (lane (c, j) holds qv[ky][kx'] of cube c, kz = j (8x8x8) / j >> 1 (8x8x4)).
-template <int D, bool NT>
+// PX = 3 (packed RGB24): the cubes of channel ch, each to its place in the [stack][channel] blocks.
+template <int D, bool NT, int PX = 1>
 __device__ __forceinline__ void enc_stage_store(const EncodeParams& P, const int32_t (&qv)[8][(D == 8) ? 8 : 4],
-                                                char* wl, int lane, uint32_t cube0) {
+                                                char* wl, int lane, uint32_t cube0, int ch = 0) {
     constexpr int CS = 64 * D;
     const int c = lane >> 3, j = lane & 7;
     const int kz = (D == 8) ? j : (j >> 1);
@@ -210,7 +289,13 @@ __device__ __forceinline__ void enc_stage_store(const EncodeParams& P, const int
             const int w = q & 15;
             if (rcube0 + cc < P.n_cubes) {
                 const int4 v = *(const int4*)(wl + (cc * D + face) * kFace + w * 16);
-                store16<NT>(outb + (size_t)q * 16, v);
+                if constexpr (PX == 1) {
+                    store16<NT>(outb + (size_t)q * 16, v);
+                } else {  // a store instruction lies within one cube: its cube is wave-uniform
+                    static_assert((CS / 4) % 64 == 0, "whole store instructions per cube");
+                    char* ob = (char*)(P.out + (size_t)enc_out_cube<PX>(P, rcube0 + t * 64 / (CS / 4), ch) * CS);
+                    store16<NT>(ob + (size_t)(q % (CS / 4)) * 16, v);
+                }
             }
         }
         wave_lds_sync();
@@ -269,8 +354,9 @@ __device__ __forceinline__ void tab_window(const float4* tab, int& sz, int ky, f
 // after the stores: kGM4 int sums + kGM4 fp64 products per cube.
 constexpr int kGM4 = kGM4Dev;  // >= the most Java groups of any 8x8x4 coefficient (40; the plan checks it)
 static_assert(8 * kGM4 * (4 + 8) <= enc_wave_lds<4>(), "8x8x4 replay scratch fits the wave's region");
+template <int PX = 1>
 __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (&px)[4], uint32_t fm, char* wl,
-                                            int lane, uint32_t cube0) {
+                                            int lane, uint32_t cube0, int ch = 0) {
     constexpr int CS = 256;
     const int c = lane >> 3, j = lane & 7;
     int* const ssum = (int*)wl + c * kGM4;
@@ -323,7 +409,7 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
             for (int gi = 0; gi < ng; gi++) acc = __dadd_rn(acc, prod[gi]);  // DCT.java:50, in order
             const int q = java_round_dev(__ddiv_rn(acc, (double)max(1, 5 * (kx + ky + kz))));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // after the wave's staged stores (one in-order count)
-            P.out[(size_t)(cube0 + c) * CS + k] = q;
+            P.out[(size_t)enc_out_cube<PX>(P, cube0 + c, ch) * CS + k] = q;
         }
         nrep += (uint32_t)__builtin_popcountll(__ballot(act && j == 0));
         if (act && lane == src) fm &= fm - 1u;
@@ -334,9 +420,10 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
 
 // Everything after the row loads, for the 8 cubes from cube0 (8x8x4): statistics, transform, quantise +
 // certify, staged 1 KiB stores, the exact fold of the uncertified coefficients (enc4_replay).
-template <int D, bool NT>
+// PX = 3 (packed RGB24): raw = the rows of channel ch, whose cubes go to its [stack][channel] blocks.
+template <int D, bool NT, int PX = 1>
 __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (&raw)[D], char* wl,
-                                            const float4* tab, int lane, uint32_t cube0) {
+                                            const float4* tab, int lane, uint32_t cube0, int ch = 0) {
     static_assert(D == 4, "8x8x8 encodes in encode16_kernel");
     constexpr int NB = (D == 8) ? 8 : 4;      // kx values per lane in the face layout
     constexpr int NI = 7 + NB;                // distinct (ky + kx') sums per lane
@@ -394,13 +481,17 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
     }
     if (!valid) fm = 0u;
 
-    enc_stage_store<D, NT>(P, qv, wl, lane, cube0);
+    enc_stage_store<D, NT, PX>(P, qv, wl, lane, cube0, ch);
 
     // rare path: the rows again (after the stores: held across them they cost occupancy), the fold
     if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {  // wave-uniform
         uint2 px[D];
-        load_rows<D>(P, g, valid, j, px);
-        enc4_replay(P, px, fm, wl, lane, cube0);
+        if constexpr (PX == 1) {
+            load_rows<D>(P, g, valid, j, px);
+        } else {
+            load_rows_rgb_ch<D>(P, g, valid, j, ch, px);
+        }
+        enc4_replay<PX>(P, px, fm, wl, lane, cube0, ch);
     }
 }
 
@@ -425,6 +516,40 @@ __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     encode_body<D, NT>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
 }
 
+// Packed RGB24 (dct3d_encode_stacks_rgb_dev, 8x8x4): the wave owns the three channels of its 8 cubes'
+// tile.  Each lane loads its rows' 24 bytes once and keeps them packed (24 registers); per channel the
+// rows are picked out of them (rgb_pick8) and encode_body runs as for a grey plane, its cubes going to
+// the channel's [stack][channel] block.  P.n_cubes counts RGB cubes (a third of the output's).
+template <int D, bool NT>
+__global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
+    __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
+    __shared__ float4 s_tab[kTabN];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;
+    uint2 raw3[D][3];
+    __builtin_amdgcn_s_setprio(3);
+    load_rows_rgb<D>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw3);
+    __builtin_amdgcn_s_setprio(0);
+    if (blockIdx.x == 0 && P.replay_clear) {
+#pragma unroll
+        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
+    }
+    if (cube0 >= P.n_cubes) return;  // wave-uniform
+    enc_tables(P, s_tab, lane);
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ch++) {
+        uint2 raw[D];
+#pragma unroll
+        for (int z = 0; z < D; z++) raw[z] = rgb_pick8(raw3[z], ch);
+        // (an opaque lane index: the lane's indices and addresses are made again for each channel, not
+        // hoisted out of the loop and held across the body)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        encode_body<D, NT, 3>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
+        wave_lds_sync();  // the next channel reuses the wave's region
+    }
+}
+
 // =============================================================================================
 // Exact Java fold for flagged (cube, k): out = JavaRound(fold_g(S_g * coef_g) / step)
 // =============================================================================================
@@ -441,6 +566,7 @@ struct ReplayGeom {
     const int32_t* ngroups;
     const double* coef;
     const uint8_t* group_of;
+    int ch = 0;  // packed RGB24 (replay_load<D, 3>): the channel whose plane cube g belongs to
 };
 // The global loads of one replay (split from the fold so that a caller can issue them early: on gfx9
 // a load issued after a wave's stores waits for those stores too, vmcnt being one in-order counter).
@@ -449,7 +575,7 @@ struct ReplayIn {
     double cf;
     uint2 px, gr;
 };
-template <int D>
+template <int D, int PX = 1>
 __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g, uint32_t k, int lane) {
     constexpr int CS = 64 * D;
     ReplayIn in;
@@ -461,9 +587,16 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
         const uint32_t s = g / R.cubes_per_stack;
         const uint32_t r = g - s * R.cubes_per_stack;
         const uint32_t by = r / R.nbx, bx = r - by * R.nbx;
-        const uint8_t* src = R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
-                             (size_t)(by * 8 + y) * R.width + bx * 8;
-        in.px = *(const uint2*)src;
+        if constexpr (PX == 1) {
+            const uint8_t* src = R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
+                                 (size_t)(by * 8 + y) * R.width + bx * 8;
+            in.px = *(const uint2*)src;
+        } else {  // (R.plane, R.stack_stride: bytes, R.width: pixels)
+            uint2 w[3];
+            rgb_load24(R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
+                           3 * ((size_t)(by * 8 + y) * R.width + bx * 8), w);
+            in.px = rgb_pick8(w, R.ch);
+        }
         in.gr = *(const uint2*)(R.group_of + (size_t)k * CS + lane * 8);
     }
     return in;
@@ -554,6 +687,46 @@ __device__ __forceinline__ void e16_load(const EncodeParams& P, uint32_t g, bool
     } else {
 #pragma unroll
         for (int r = 0; r < 4; r++) raw[r] = make_uint2(0u, 0u);
+    }
+}
+
+// e16_load for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
+__device__ __forceinline__ void e16_load_rgb(const EncodeParams& P, uint32_t g, bool valid, int k, int h,
+                                             uint2 (&raw)[4][3]) {
+    if (valid) {
+        const uint32_t st = fdiv(g, P.div_cps);
+        const uint32_t rr = g - st * P.cubes_per_stack;
+        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
+                             (size_t)(4 * h) * P.plane;
+#pragma unroll
+        for (int r = 0; r < 4; r++) rgb_load24(src + (size_t)r * P.plane, raw[r]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) raw[r][i] = make_uint2(0u, 0u);
+    }
+}
+
+// the rows of channel ch alone (the rare paths' reload), one row's 24 bytes in registers at a time
+__device__ __forceinline__ void e16_load_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int k, int h, int ch,
+                                                uint2 (&raw)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) raw[r] = make_uint2(0u, 0u);
+    if (valid) {
+        const uint32_t st = fdiv(g, P.div_cps);
+        const uint32_t rr = g - st * P.cubes_per_stack;
+        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
+                             (size_t)(4 * h) * P.plane;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            uint2 w[3];
+            rgb_load24(src + (size_t)r * P.plane, w);
+            raw[r] = rgb_pick8(w, ch);
+            asm volatile("" : "+v"(raw[r].x), "+v"(raw[r].y));
+        }
     }
 }
 
@@ -935,6 +1108,114 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
             if (lane == src) fm &= fm - 1u;
         }
         if (lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), n);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed RGB24 (dct3d_encode_stacks_rgb_dev, 8x8x8): encode16_kernel's geometry and steps, the wave owning
+// the three channels of its 4 cubes' tile.  Each lane loads its rows' 24 bytes once and keeps them packed
+// (24 registers) across three passes, one per channel: the channel's rows are picked out of them
+// (rgb_pick8), e16_body, the int16 staging, the second certificate, the stores and the exact fold run as
+// for a grey plane, and the cubes go to the channel's [stack][channel] block.  The replay paths reload
+// their rows through the same pick (e16_load_rgb_ch, replay_load<8, 3>).  P.n_cubes counts RGB cubes (a
+// third of the output's).  Occupancy: the packed rows on top of the main path's 72 registers do not fit 7
+// waves per SIMD (73 registers); the kernel takes what it needs up to 4 waves per SIMD (128).
+// ---------------------------------------------------------------------------------------------
+template <bool NT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void encode16_rgb_kernel(EncodeParams P) {
+    constexpr int CS = 512;
+    __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kE16Lds];
+    __shared__ float4 s_tab[kTabN];
+    __shared__ double s_b64[96];  // second certificate tables (rare path)
+    const int wave = threadIdx.x >> 6;
+    const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kE16CPW;
+    uint2 raw3[4][3];
+    {
+        const int lane = threadIdx.x & 63;
+        const uint32_t g = cube0 + (lane >> 5) * 2 + ((lane & 15) >> 3);
+        __builtin_amdgcn_s_setprio(3);
+        e16_load_rgb(P, g, g < P.n_cubes, lane & 7, (lane >> 4) & 1, raw3);
+        __builtin_amdgcn_s_setprio(0);
+    }
+    if (blockIdx.x == 0 && P.replay_clear) {
+#pragma unroll
+        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
+    }
+    if (cube0 >= P.n_cubes) return;  // wave-uniform
+    enc_tables(P, s_tab, threadIdx.x & 63);
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ch++) {
+        // the lane's indices and addresses are made again for each channel (an opaque lane index), not
+        // hoisted out of the loop and held across the body: hoisted, they spill
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));
+        const int k = lane & 7, h = (lane >> 4) & 1;
+        const int c = (lane >> 5) * 2 + ((lane & 15) >> 3);
+        const uint32_t g = cube0 + c;
+        const bool valid = g < P.n_cubes;
+        char* wl = lds + wave * kE16Lds;
+        uint2 raw[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) raw[r] = rgb_pick8(raw3[r], ch);
+        int32_t qv[8][4];
+        uint32_t fm = 0u;
+        e16_body(P, raw, wl, s_tab, lane, valid, qv, fm);
+        const bool rare = P.recheck && __builtin_expect(__ballot(fm != 0u) != 0ull, 0);  // wave-uniform
+        {  // int16 staging of the 4 cubes, the second certificate in it, 8 stores of 1 KiB (as encode16_kernel)
+            char* dst = wl + c * kE16S16C + k * kE16S16F + h * 8;
+#pragma unroll
+            for (int ky = 0; ky < 8; ky++)
+                *(uint2*)(dst + ky * 16) = make_uint2(__builtin_amdgcn_perm(qv[ky][1], qv[ky][0], 0x05040100u),
+                                                      __builtin_amdgcn_perm(qv[ky][3], qv[ky][2], 0x05040100u));
+        }
+        wave_lds_sync();
+        if (rare) {
+            uint2 raw2[4];
+            e16_load_rgb_ch(P, g, valid, k, h, ch, raw2);
+            const double bv = P.tab64[lane];
+            const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
+            uint32_t nset;
+            e16_recheck64(raw2, bv, tv, s_b64, wl, lane, fm, nset);
+            for (int o = 1; o < 64; o <<= 1) nset += __shfl_xor(nset, o, 64);
+            if (lane == 0 && nset && P.replay_count)
+                atomicAdd(P.replay_count + kCountSpread + (blockIdx.x & (kCountSpread - 1)), nset);
+        }
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            // 16-byte chunk (q & 127) of cube t / 2 (wave-uniform: a store instruction is half a cube)
+            const int q = t * 64 + lane;
+            const int cc = t >> 1, face = (q >> 4) & 7, w = q & 15;
+            if (cube0 + cc < P.n_cubes) {
+                const uint2 v = *(const uint2*)(wl + cc * kE16S16C + face * kE16S16F + w * 8);
+                char* ob = (char*)(P.out + (size_t)enc_out_cube<3>(P, cube0 + cc, ch) * CS);
+                store16<NT>(ob + (q & 127) * 16, make_int4((int)(int16_t)v.x, (int)v.x >> 16, (int)(int16_t)v.y,
+                                                           (int)v.y >> 16));
+            }
+        }
+        wave_lds_sync();
+        // rarest path: the exact Java fold of what both certificates left open (as encode16_kernel)
+        if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {
+            const ReplayGeom R{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride,
+                               P.ngroups, P.coef, P.group_of, ch};
+            uint32_t n = 0;
+            for (;;) {
+                const uint64_t who = __ballot(fm != 0u);
+                if (who == 0ull) break;
+                const int src = (int)__builtin_ctzll(who);
+                uint32_t rg, rk;
+                e16_flag_pos(fm, src, cube0, rg, rk);
+                const int q = replay_fold<8, true>(replay_load<8, 3>(R, rg, rk, lane), rk, lane, (int*)wl,
+                                                   (double*)(wl + kMaxGroupsDev * 4));
+                if (lane == 0) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    P.out[(size_t)enc_out_cube<3>(P, rg, ch) * CS + rk] = q;
+                }
+                n++;
+                if (lane == src) fm &= fm - 1u;
+            }
+            if (lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), n);
+        }
+        wave_lds_sync();  // the next channel reuses the wave's region
     }
 }
 

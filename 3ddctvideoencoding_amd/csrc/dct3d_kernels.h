@@ -78,6 +78,9 @@ struct Fwd64Params {
 int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n_cubes, hipStream_t st);
 int launch_fwd64_raster(int D, const Fwd64Params& P, hipStream_t st);
 int launch_encode(int D, const EncodeParams& P, hipStream_t st);
+// Packed RGB24 (uint8 [frame][y][x][3]) <-> int32 cubes laid out [stack][channel][cube]: n_cubes counts the
+// RGB cubes (a third of the int32 side's), plane and stack_stride are in bytes (3 per pixel), width in pixels
+int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st);
 struct EgParams {
     const int32_t* q;          // cube-major quantised values
     uint64_t n_cubes;
@@ -194,6 +197,7 @@ __device__ __forceinline__ uint64_t mark_serial(const uint16_t* mark, const uint
 }
 
 int launch_decode(int D, const DecodeParams& P, hipStream_t st);
+int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st);
 int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =

@@ -536,6 +536,59 @@ static int forward_f64_raster(dct3d_ctx* c, const uint8_t* d_raster, int w, int 
     return launch_fwd64_raster(c->bd, P, c->stream) ? DCT3D_EKERNEL : DCT3D_OK;
 }
 
+// The encode and decode kernels' parameters for n_cubes cubes of a w x h raster with px bytes per pixel (1:
+// grey; 3: packed RGB24, n_cubes counting RGB cubes): plane and stack_stride in bytes, width in pixels.
+static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_raster, int32_t* d_q, int w, int h,
+                               uint64_t n_cubes, int px) {
+    const uint64_t plane = (uint64_t)px * w * h;
+    memset(&P, 0, sizeof(P));
+    P.raster = d_raster;
+    P.out = d_q;
+    P.n_cubes = (uint32_t)n_cubes;
+    P.g_base = 0;
+    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
+    P.nbx = (uint32_t)(w / 8);
+    set_fast_div(P);
+    P.width = (uint32_t)w;
+    P.plane = plane;
+    P.stack_stride = plane * c->bd;
+    P.coef_dc = c->plan.coef_dc;
+    const float* tabs = (const float*)c->d_tabs.p;
+    P.tab_rstep = tabs;
+    P.tab_G = tabs + kMaxS;
+    P.tab_E = tabs + 2 * kMaxS;
+    P.ngroups = (const int32_t*)c->d_ngroups.p;
+    P.coef = (const double*)c->d_coef.p;
+    P.group_of = (const uint8_t*)c->d_group_of.p;
+    set_count_slot(c, P.replay_count, P.replay_clear);
+    P.tab64 = (const double*)c->d_tabs64.p;
+    P.recheck = c->opt_enc_no_recheck ? 0u : 1u;
+}
+static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q, uint8_t* d_raster, int w, int h,
+                               uint64_t n_cubes, int px) {
+    const uint64_t plane = (uint64_t)px * w * h;
+    P.in = d_q;
+    P.out = d_raster;
+    P.n_cubes = (uint32_t)n_cubes;
+    P.cube_base = 0;
+    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
+    P.nbx = (uint32_t)(w / 8);
+    set_fast_div(P);
+    P.width = (uint32_t)w;
+    P.plane = plane;
+    P.stack_stride = plane * c->bd;
+    P.dec_G = c->plan.dec_G;
+    P.dec_E = c->plan.dec_E;
+    P.dec_l1_max = c->plan.dec_l1_max;
+    // dec_store_tile's conditions: nbx even (a 16-byte chunk -- two grey cubes, or part of a 48-byte pair of
+    // RGB cubes -- never straddles a block-row), 32-bit byte offsets within a stack
+    P.blk_store = (w / 8) % 2 == 0 && plane * c->bd < (1ull << 32) ? 1u : 0u;
+    // test option: widen the certification margin so that most pixels are uncertified and their cubes
+    // take the whole-cube replay path (tests/test_gpu_parity.py); a wider margin is never unsafe
+    P.dec_E += c->opt_dec_margin;
+    set_dec_replay(c, P);
+}
+
 int dct3d_encode_stacks_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, int32_t* d_q,
                             double* d_dct) {
     if (!c || (!d_raster && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
@@ -550,30 +603,8 @@ int dct3d_encode_stacks_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h,
     if (n_cubes == 0) return DCT3D_OK;
     const int D = c->bd;
     // one launch: uncertified coefficients are replayed inside the wave (exact Java fold)
-    const uint64_t plane = (uint64_t)w * h;
     EncodeParams P;
-    memset(&P, 0, sizeof(P));
-    P.raster = d_raster;
-    P.out = d_q;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.g_base = 0;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)w;
-    P.plane = plane;
-    P.stack_stride = plane * D;
-    P.coef_dc = c->plan.coef_dc;
-    const float* tabs = (const float*)c->d_tabs.p;
-    P.tab_rstep = tabs;
-    P.tab_G = tabs + kMaxS;
-    P.tab_E = tabs + 2 * kMaxS;
-    P.ngroups = (const int32_t*)c->d_ngroups.p;
-    P.coef = (const double*)c->d_coef.p;
-    P.group_of = (const uint8_t*)c->d_group_of.p;
-    set_count_slot(c, P.replay_count, P.replay_clear);
-    P.tab64 = (const double*)c->d_tabs64.p;
-    P.recheck = c->opt_enc_no_recheck ? 0u : 1u;
+    fill_encode_params(c, P, d_raster, d_q, w, h, n_cubes, 1);
     hipEvent_t* ev = timing_slot(c);
     if (ev) (void)hipEventRecord(ev[0], c->stream);
     if (launch_encode(D, P, c->stream)) return DCT3D_EKERNEL;
@@ -599,26 +630,8 @@ int dct3d_decode_stacks_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int 
     }
     if (n_cubes == 0) return DCT3D_OK;
     const int D = c->bd;
-    const uint64_t plane = (uint64_t)w * h;
     DecodeParams P;
-    P.in = d_q;
-    P.out = d_raster;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.cube_base = 0;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)w;
-    P.plane = plane;
-    P.stack_stride = plane * D;
-    P.dec_G = c->plan.dec_G;
-    P.dec_E = c->plan.dec_E;
-    P.dec_l1_max = c->plan.dec_l1_max;
-    P.blk_store = (w / 8) % 2 == 0 && plane * D < (1ull << 32) ? 1u : 0u;  // dec_store_tile's conditions
-    // test option: widen the certification margin so that most pixels are uncertified and their cubes
-    // take the whole-cube replay path (tests/test_gpu_parity.py); a wider margin is never unsafe
-    P.dec_E += c->opt_dec_margin;
-    set_dec_replay(c, P);
+    fill_decode_params(c, P, d_q, d_raster, w, h, n_cubes, 1);
     hipEvent_t* ev = timing_slot(c);
     if (ev) (void)hipEventRecord(ev[0], c->stream);
     if (launch_decode(D, P, c->stream)) return DCT3D_EKERNEL;
@@ -628,6 +641,66 @@ int dct3d_decode_stacks_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int 
         (void)hipEventRecord(ev[3], c->stream);
     }
     count_slot_used(c, n_cubes * (uint64_t)c->plan.cs);
+    return DCT3D_OK;
+}
+
+// ---- packed RGB24 (dct3d.h, ABI 9): the grey calls' parameters over the RGB cubes, strides in bytes ----
+// 3 x cubes must satisfy the grey calls' limit (the int32 side's cube indices)
+static int check_geometry_rgb(const dct3d_ctx* c, int w, int h, int n_stacks, uint64_t* n_cubes) {
+    int rc = check_geometry(c, w, h, n_stacks, n_cubes);
+    if (rc) return rc;
+    return 3 * *n_cubes >= (1ull << 31) / 8 ? DCT3D_EINVAL : DCT3D_OK;
+}
+
+int dct3d_encode_stacks_rgb_dev(dct3d_ctx* c, const uint8_t* d_rgb, int w, int h, int n_stacks, int32_t* d_q) {
+    if (!c || (!d_rgb && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    uint64_t n_cubes;
+    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (!c->batch) {
+        c->last_valid = false;
+        c->last_count_slot = -1;
+    }
+    if (n_cubes == 0) return DCT3D_OK;
+    const int D = c->bd;
+    EncodeParams P;  // over the RGB cubes: each is three cubes of the output
+    fill_encode_params(c, P, d_rgb, d_q, w, h, n_cubes, 3);
+    hipEvent_t* ev = timing_slot(c);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    if (launch_encode_rgb(D, P, c->stream)) return DCT3D_EKERNEL;
+    if (ev) {  // single launch: the second event pair brackets nothing
+        (void)hipEventRecord(ev[1], c->stream);
+        (void)hipEventRecord(ev[2], c->stream);
+        (void)hipEventRecord(ev[3], c->stream);
+    }
+    count_slot_used(c, 3 * n_cubes * (uint64_t)c->plan.cs);
+    return DCT3D_OK;
+}
+
+int dct3d_decode_stacks_rgb_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int n_stacks, uint8_t* d_rgb) {
+    if (!c || (!d_rgb && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    uint64_t n_cubes;
+    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (!c->batch) {
+        c->last_valid = false;
+        c->last_count_slot = -1;
+    }
+    if (n_cubes == 0) return DCT3D_OK;
+    const int D = c->bd;
+    DecodeParams P;  // over the RGB cubes: each is three cubes of the input
+    fill_decode_params(c, P, d_q, d_rgb, w, h, n_cubes, 3);
+    hipEvent_t* ev = timing_slot(c);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    if (launch_decode_rgb(D, P, c->stream)) return DCT3D_EKERNEL;
+    if (ev) {  // one launch: the second event pair brackets nothing
+        (void)hipEventRecord(ev[1], c->stream);
+        (void)hipEventRecord(ev[2], c->stream);
+        (void)hipEventRecord(ev[3], c->stream);
+    }
+    count_slot_used(c, 3 * n_cubes * (uint64_t)c->plan.cs);
     return DCT3D_OK;
 }
 
@@ -782,6 +855,39 @@ int dct3d_decode_stacks(dct3d_ctx* c, const int32_t* q, int w, int h, int n_stac
     batch_begin(c);
     rc = run_pipeline(c, n_stacks, px * sizeof(int32_t), px, q, raster, [&](const void* din, void* dout, int, int ns) {
         return dct3d_decode_stacks_dev(c, (const int32_t*)din, w, h, ns, (uint8_t*)dout);
+    });
+    batch_end(c);
+    return rc;
+}
+
+// ---- packed RGB24, host pointers: chunks of whole stacks (contiguous on both sides) through the pipeline ----
+int dct3d_encode_stacks_rgb(dct3d_ctx* c, const uint8_t* rgb, int w, int h, int n_stacks, int32_t* q) {
+    if (!c || (!rgb && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    uint64_t n_cubes;
+    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (n_cubes == 0) return DCT3D_OK;
+    const size_t px = 3 * n_cubes * c->plan.cs / n_stacks;  // bytes of a packed stack
+    batch_begin(c);  // every chunk counts into one slot: dct3d_get_stats reports the whole call
+    rc = run_pipeline(c, n_stacks, px, px * sizeof(int32_t), rgb, q, [&](const void* din, void* dout, int, int ns) {
+        return dct3d_encode_stacks_rgb_dev(c, (const uint8_t*)din, w, h, ns, (int32_t*)dout);
+    });
+    batch_end(c);
+    return rc;
+}
+
+int dct3d_decode_stacks_rgb(dct3d_ctx* c, const int32_t* q, int w, int h, int n_stacks, uint8_t* rgb) {
+    if (!c || (!rgb && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    uint64_t n_cubes;
+    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (n_cubes == 0) return DCT3D_OK;
+    const size_t px = 3 * n_cubes * c->plan.cs / n_stacks;
+    batch_begin(c);
+    rc = run_pipeline(c, n_stacks, px * sizeof(int32_t), px, q, rgb, [&](const void* din, void* dout, int, int ns) {
+        return dct3d_decode_stacks_rgb_dev(c, (const int32_t*)din, w, h, ns, (uint8_t*)dout);
     });
     batch_end(c);
     return rc;

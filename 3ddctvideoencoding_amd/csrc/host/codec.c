@@ -644,6 +644,170 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
     return status;
 }
 
+/* ---- packed RGB24 ---------------------------------------------------------------------------- */
+/* The upstream colour workflow (RGBUtils split -> encode each plane -> decode each -> RGBUtils mix) with
+ * the split and the mix fused into the device transform: one packed RGB24 file <-> three streams named
+ * as RGBUtils names its planes, <pattern>.red / .green / .blue, each the very .bin of encode_ex for that
+ * plane.  A plain loop per batch: dct3d_encode_stacks_rgb, then the host entropy coder per stack into the
+ * three streams (dct3d_decode_stacks_rgb after three pulls per stack on the way back). */
+static const char *const kRgbSuffix[3] = {".red", ".green", ".blue"};
+
+static FILE *open_plane(const char *pattern, int ch, const char *mode) {
+    const size_t n = strlen(pattern) + 8;
+    char *name = (char *)malloc(n);
+    if (!name) return NULL;
+    snprintf(name, n, "%s%s", pattern, kRgbSuffix[ch]);
+    FILE *f = fopen(name, mode);
+    if (!f) printf("Cannot open %s file %s\n", mode[0] == 'r' ? "input" : "output", name);
+    free(name);
+    return f;
+}
+
+int encode_rgb_ex(const char *inName, const char *outPattern, int width, int height, int frames, int platformIndex,
+                  int depth, int batch) {
+    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
+        printf("Invalid geometry: %dx%d, %d frames, block depth %d (width/height must be multiples of 8)\n", width,
+               height, frames, depth);
+        return 1;
+    }
+    if (batch <= 0) batch = default_batch();
+    FILE *in = fopen(inName, "rb");
+    if (!in) {
+        printf("Cannot open input file %s\n", inName);
+        return 1;
+    }
+    FILE *out[3] = {NULL, NULL, NULL};
+    dct3d_entropy_enc *ent[3] = {NULL, NULL, NULL};
+    dct3d_ctx *ctx = NULL;
+    uint8_t *rgb = NULL;
+    int32_t *q = NULL;
+    int status = 0;
+    for (int ch = 0; ch < 3 && !status; ch++)
+        if (!(out[ch] = open_plane(outPattern, ch, "wb"))) status = 1;
+    if (!status) {
+        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        if (rc) {
+            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
+            status = 1;
+        }
+    }
+    const size_t stack_px = (size_t)width * height * depth;  /* pixels of a stack = values of a plane's stack */
+    const int n_stacks = (frames + depth - 1) / depth;
+    if (!status) {
+        rgb = (uint8_t *)malloc(3 * stack_px * batch);
+        q = (int32_t *)malloc(3 * stack_px * batch * sizeof(int32_t));
+        for (int ch = 0; ch < 3; ch++) ent[ch] = dct3d_entropy_enc_create(width, height, depth, out[ch]);
+        if (!rgb || !q || !ent[0] || !ent[1] || !ent[2]) {
+            printf("Out of memory\n");
+            status = 1;
+        }
+    }
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        size_t got = 0, r;
+        const size_t want = 3 * stack_px * nb;
+        while (got < want && (r = fread(rgb + got, 1, want - got, in)) > 0) got += r;
+        if (got < want) memset(rgb + got, 0, want - got);  /* a short last stack is zero-filled, as encode_ex */
+        const int rc = dct3d_encode_stacks_rgb(ctx, rgb, width, height, nb, q);
+        if (rc) {
+            printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        for (int s = 0; s < nb && !status; s++)
+            for (int ch = 0; ch < 3; ch++)  /* block (s, ch) of the [stack][channel] layout */
+                if (dct3d_entropy_enc_push(ent[ch], q + stack_px * (3 * (size_t)s + ch), s0 + s == n_stacks - 1)) {
+                    printf("Error in the entropy coder\n");
+                    status = 1;
+                    break;
+                }
+        for (int s = 0; !status && s < nb; s++) printf("Frames processed: %d\n", (s0 + s + 1) * depth);
+    }
+    for (int ch = 0; ch < 3; ch++) {
+        if (ent[ch]) dct3d_entropy_enc_destroy(ent[ch]);  /* the last deflate output and its write */
+        if (out[ch] && (fflush(out[ch]) || fclose(out[ch]))) status = 1;
+    }
+    free(rgb);
+    free(q);
+    if (ctx) dct3d_ctx_destroy(ctx);
+    fclose(in);
+    if (!status) printf("Encoding process completed\n");
+    return status;
+}
+
+int decode_rgb_ex(const char *inPattern, const char *outName, int width, int height, int frames, int platformIndex,
+                  int depth, int batch) {
+    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
+        printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
+        return 1;
+    }
+    if (batch <= 0) batch = default_batch();
+    FILE *in[3] = {NULL, NULL, NULL};
+    dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
+    FILE *out = NULL;
+    dct3d_ctx *ctx = NULL;
+    uint8_t *rgb = NULL;
+    int32_t *q = NULL;
+    int status = 0;
+    for (int ch = 0; ch < 3 && !status; ch++)
+        if (!(in[ch] = open_plane(inPattern, ch, "rb"))) status = 1;
+    if (!status && !(out = fopen(outName, "wb"))) {
+        printf("Cannot open output file %s\n", outName);
+        status = 1;
+    }
+    if (!status) {
+        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        if (rc) {
+            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
+            status = 1;
+        }
+    }
+    const size_t stack_px = (size_t)width * height * depth;
+    const int n_stacks = (frames + depth - 1) / depth;
+    if (!status) {
+        rgb = (uint8_t *)malloc(3 * stack_px * batch);
+        q = (int32_t *)malloc(3 * stack_px * batch * sizeof(int32_t));
+        for (int ch = 0; ch < 3; ch++) ent[ch] = dct3d_entropy_dec_create(width, height, depth, in[ch], NULL, 0);
+        if (!rgb || !q || !ent[0] || !ent[1] || !ent[2]) {
+            printf("Out of memory\n");
+            status = 1;
+        }
+    }
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        for (int s = 0; s < nb && !status; s++)
+            for (int ch = 0; ch < 3; ch++)
+                if (dct3d_entropy_dec_pull(ent[ch], q + stack_px * (3 * (size_t)s + ch))) {
+                    printf("Truncated or corrupt input stream\n");
+                    status = 1;
+                    break;
+                }
+        if (status) break;
+        const int rc = dct3d_decode_stacks_rgb(ctx, q, width, height, nb, rgb);
+        if (rc) {
+            printf("Error running the inverse 3D DCT: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        if (fwrite(rgb, 1, 3 * stack_px * nb, out) != 3 * stack_px * nb) {
+            printf("Error writing the output file\n");
+            status = 1;
+            break;
+        }
+        printf("Frames processed: %d\n", (s0 + nb) * depth);
+    }
+    for (int ch = 0; ch < 3; ch++) {
+        if (ent[ch]) dct3d_entropy_dec_destroy(ent[ch]);
+        if (in[ch]) fclose(in[ch]);
+    }
+    free(rgb);
+    free(q);
+    if (ctx) dct3d_ctx_destroy(ctx);
+    if (out && (fflush(out) || fclose(out))) status = 1;
+    if (!status) printf("Decoding process completed\n");
+    return status;
+}
+
 int encode(char *inName, char *outName, int width, int height, int frames, int platformIndex) {
     return encode_ex(inName, outName, width, height, frames, platformIndex, DCT_BLOCK_DEPTH, 0);
 }

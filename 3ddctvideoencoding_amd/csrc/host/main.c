@@ -1,6 +1,9 @@
 /* main.c -- CLI with the reference's argument convention (main.c:5-49):
  *   dct3d_codec list_devices
  *   dct3d_codec encode|decode <input> <output> <width> <height> <frames> [device_index (1-based)] [block_depth 8|4]
+ *   dct3d_codec encode_rgb <rgb24 file> <name pattern> <width> <height> <frames> [device_index] [block_depth 8|4]
+ *   dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <frames> [device_index] [block_depth 8|4]
+ *     (packed RGB24 <-> <name pattern>.red / .green / .blue, the RGBUtils plane names; one device)
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
  * ("1,2,3"): encode_multi / decode_multi over those devices. */
 #include <errno.h>
@@ -17,6 +20,12 @@ static void usage(void) {
     printf("dct3d_codec encode|decode <input file> <output file> <width> <height> <nr of frames> "
            "<device_index (optional, 1-based; a list a,b,... uses several)> <block depth 8|4 (optional)> -> "
            "Encode/Decode given file\n");
+    printf("dct3d_codec encode_rgb <rgb24 file> <name pattern> <width> <height> <nr of frames> "
+           "<device_index (optional)> <block depth 8|4 (optional)> -> Encode packed RGB24 into "
+           "<name pattern>.red/.green/.blue\n");
+    printf("dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <nr of frames> "
+           "<device_index (optional)> <block depth 8|4 (optional)> -> Decode <name pattern>.red/.green/.blue "
+           "into packed RGB24\n");
 }
 
 /* "1" or "1,2,3": 1-based device numbers (the reference's platformIndex, main.c:33-37).  Every entry must
@@ -73,6 +82,14 @@ int main(int argc, char *argv[]) {
     if (!strcmp(argv[1], "decode"))
         return n_dev > 1 ? decode_multi(argv[2], argv[3], width, height, frames, devs, n_dev, depth, 0)
                          : decode_ex(argv[2], argv[3], width, height, frames, devs[0], depth, 0);
+    if (!strcmp(argv[1], "encode_rgb") || !strcmp(argv[1], "decode_rgb")) {
+        if (n_dev > 1) {
+            printf("%s runs on one device\n", argv[1]);
+            return 1;
+        }
+        return argv[1][0] == 'e' ? encode_rgb_ex(argv[2], argv[3], width, height, frames, devs[0], depth, 0)
+                                 : decode_rgb_ex(argv[2], argv[3], width, height, frames, devs[0], depth, 0);
+    }
     usage();
     return 1;
 }

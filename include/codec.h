@@ -46,6 +46,17 @@ int encode_multi(const char *inputFileName, const char *outputFileName, int widt
 int decode_multi(const char *inputFileName, const char *outputFileName, int width, int height, int framesToDecode,
                  const int *platformIndices, int nDevices, int blockDepth, int stacksPerBatch);
 
+/* Packed RGB24 video (the upstream capture format: 3 bytes per pixel, R, G, B) <-> three streams named as
+ * RGBUtils names the split planes: <namePattern>.red, .green, .blue.  Each is byte for byte the .bin that
+ * encode_ex writes for that plane after `RGBUtils split`; decode_rgb_ex writes what `RGBUtils mix` makes of
+ * the three decode_ex outputs.  The split and the mix run inside the device transform
+ * (dct3d_encode_stacks_rgb / dct3d_decode_stacks_rgb).  One device, host entropy coder.  Same return
+ * convention. */
+int encode_rgb_ex(const char *inputFileName, const char *outputNamePattern, int width, int height, int framesToEncode,
+                  int platformIndex, int blockDepth, int stacksPerBatch);
+int decode_rgb_ex(const char *inputNamePattern, const char *outputFileName, int width, int height, int framesToDecode,
+                  int platformIndex, int blockDepth, int stacksPerBatch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,7 +60,7 @@ extern "C" {
 #define DCT3D_ENOSPC 5      /* an output buffer is too small (nothing was written past its end) */
 #define DCT3D_ENODATA 6     /* an input stream ends before the requested data is complete */
 
-#define DCT3D_ABI_VERSION 8
+#define DCT3D_ABI_VERSION 9
 
 typedef struct dct3d_ctx dct3d_ctx;
 
@@ -167,6 +167,35 @@ int dct3d_decode_stacks(dct3d_ctx *ctx, const int32_t *q_cubes, int width, int h
                         uint8_t *raster);
 int dct3d_decode_stacks_dev(dct3d_ctx *ctx, const int32_t *d_q_cubes, int width, int height,
                             int n_stacks, uint8_t *d_raster);
+
+/* ---------------------------------------------------------------------------------------------
+ * Packed RGB24 video (ABI 9): the upstream capture / player format, frame-major, row-major, 3 bytes
+ * per pixel in R, G, B order: uint8 [n_stacks * D][height][width][3].  The colour split and mix are
+ * fused into the transform kernels: every packed byte is read (encode) or written (decode) once.
+ *   rgb      n_stacks stacks of D packed frames (width, height: pixels, multiples of 8)
+ *   q_cubes  int32, cube-major, laid out [stack][channel][cube][cube_size], channel = 0 R, 1 G, 2 B
+ * The values are defined by the grey calls: with the planar-stacked raster that holds, for every
+ * stack, its D red frames, then its D green frames, then its D blue frames,
+ *   planar = rgb.reshape(n, D, H, W, 3).transpose(0, 4, 1, 2, 3).reshape(3 * n * D, H, W)
+ * dct3d_encode_stacks_rgb(rgb, n) writes exactly what dct3d_encode_stacks(planar, 3 n) writes, and
+ * dct3d_decode_stacks_rgb(q, n) is dct3d_decode_stacks(q, 3 n) re-interleaved.  So each (stack,
+ * channel) block is byte for byte the grey path's block for that plane's stack (it can go unchanged
+ * to dct3d_entropy_enc_push or dct3d_eg_encode_dev), and chunks of whole stacks stay contiguous on
+ * both sides.  Statistics cover the whole call (n_units = 3 * cubes * cube_size); the options act as
+ * on the grey calls.  DCT3D_EINVAL when 3 * cubes exceeds the grey calls' cube limit.
+ * Conventions as the grey calls: *_dev asynchronous on the context stream, the host calls
+ * synchronous and chunked by stacks.
+ * Encode replaces RGBUtils split (RGBUtils.java:39-84) + per plane the work of encoder.c:206-260;
+ * decode replaces per plane decoder.c:246-295 + RGBUtils mix (RGBUtils.java:86-131).
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_encode_stacks_rgb(dct3d_ctx *ctx, const uint8_t *rgb, int width, int height, int n_stacks,
+                            int32_t *q_cubes);
+int dct3d_encode_stacks_rgb_dev(dct3d_ctx *ctx, const uint8_t *d_rgb, int width, int height,
+                                int n_stacks, int32_t *d_q_cubes);
+int dct3d_decode_stacks_rgb(dct3d_ctx *ctx, const int32_t *q_cubes, int width, int height, int n_stacks,
+                            uint8_t *rgb);
+int dct3d_decode_stacks_rgb_dev(dct3d_ctx *ctx, const int32_t *d_q_cubes, int width, int height,
+                                int n_stacks, uint8_t *d_rgb);
 
 /* ---------------------------------------------------------------------------------------------
  * Reference-faithful drop-in (A): the exact data flow of the OpenCL block, float cube-major in,
