@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "dct3d_eg_encode_dev", "dct3d_encode_eg", "dct3d_eg_fetch", "dct3d_diagonal_order",
     "dct3d_eg_decode_dev", "dct3d_decode_eg", "dct3d_encode_eg_dev", "dct3d_decode_eg_dev",
     "dct3d_encode_stacks_rgb", "dct3d_encode_stacks_rgb_dev", "dct3d_decode_stacks_rgb", "dct3d_decode_stacks_rgb_dev",
+    "dct3d_encode_frames", "dct3d_encode_frames_dev", "dct3d_decode_frames", "dct3d_decode_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -110,6 +111,8 @@ def lib() -> C.CDLL:
         for name in ("dct3d_encode_stacks_rgb", "dct3d_encode_stacks_rgb_dev", "dct3d_decode_stacks_rgb",
                      "dct3d_decode_stacks_rgb_dev"):
             getattr(L, name).argtypes = [vp, vp, i32, i32, i32, vp]
+        for name in ("dct3d_encode_frames", "dct3d_encode_frames_dev", "dct3d_decode_frames", "dct3d_decode_frames_dev"):
+            getattr(L, name).argtypes = [vp, vp, i32, i32, i32, i32, vp]
         for name in ("dct3d_forward_f32", "dct3d_inverse_f32", "dct3d_forward_f32_dev", "dct3d_inverse_f32_dev"):
             getattr(L, name).argtypes = [vp, vp, sz, vp]
         L.dct3d_ctx_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
@@ -199,6 +202,24 @@ def diagonal_order(block_w: int = 8, block_h: int = 8, block_d: int = 8) -> np.n
     out = np.empty(block_w * block_h * block_d, np.uint16)
     _check(lib().dct3d_diagonal_order(block_w, block_h, block_d, _ptr(out)), "dct3d_diagonal_order")
     return out
+
+
+def padded_size(width: int, height: int) -> tuple[int, int]:
+    """(Wp, Hp): width and height rounded up to multiples of 8, the size of the padded raster that
+    encode_frames / decode_frames are defined on."""
+    return (width + 7) // 8 * 8, (height + 7) // 8 * 8
+
+
+def pad_frames(frames: np.ndarray) -> np.ndarray:
+    """The padded raster of frames [F, H, W] (grey) or [F, H, W, 3] (packed RGB24): each frame's last column
+    and last row repeated up to padded_size (per channel).  This is the definition of what encode_frames
+    encodes -- the calls themselves never build it."""
+    frames = np.asarray(frames)
+    if frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] != 3):
+        raise ValueError("frames must have shape [F, H, W] or [F, H, W, 3]")
+    H, W = frames.shape[1:3]
+    Wp, Hp = padded_size(W, H)
+    return np.pad(frames, ((0, 0), (0, Hp - H), (0, Wp - W)) + ((0, 0),) * (frames.ndim - 3), mode="edge")
 
 
 def eg_stream_bytes(total_bits: int) -> int:
@@ -311,6 +332,38 @@ class Context:
                "dct3d_decode_stacks_rgb")
         return out
 
+    # frames of any size (include/dct3d.h): the results are those of encode_stacks[_rgb] / decode_stacks[_rgb]
+    # on pad_frames(frames), cropped on the way back; the padding and the crop happen inside the kernels
+    def encode_frames(self, frames: np.ndarray) -> np.ndarray:
+        """u8 frames [n_stacks*bd, H, W] (grey) or [n_stacks*bd, H, W, 3] (packed RGB24), any H, W >= 1 ->
+        quantised int32 cubes [channels * n_cubes, bd, bh, bw] of the edge-padded raster (pad_frames)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        if frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] != 3):
+            raise ValueError("frames must have shape [F, H, W] or [F, H, W, 3]")
+        channels = 1 if frames.ndim == 3 else 3
+        F, H, W = frames.shape[:3]
+        if F % self.bd:
+            raise ValueError("frame count must be a multiple of the block depth")
+        Wp, Hp = padded_size(W, H)
+        q = np.empty((channels * self.n_cubes(Wp, Hp, F // self.bd), self.bd, self.bh, self.bw), np.int32)
+        _check(lib().dct3d_encode_frames(self._h, _ptr(frames), W, H, channels, F // self.bd, _ptr(q)),
+               "dct3d_encode_frames")
+        return q
+
+    def decode_frames(self, q: np.ndarray, width: int, height: int, n_stacks: int, channels: int = 1) -> np.ndarray:
+        """the inverse of encode_frames: u8 frames [n_stacks*bd, height, width] (channels = 1) or
+        [n_stacks*bd, height, width, 3] (channels = 3), the top-left part of the padded raster's decode"""
+        q = np.ascontiguousarray(q, np.int32)
+        if channels not in (1, 3):
+            raise Dct3dError(DCT3D_EINVAL, "dct3d_decode_frames")
+        Wp, Hp = padded_size(width, height)
+        if q.size != channels * self.n_cubes(Wp, Hp, n_stacks) * self.cube_size:
+            raise ValueError("q must hold channels * n_cubes cubes of the padded raster")
+        out = np.empty((n_stacks * self.bd, height, width) + ((3,) if channels == 3 else ()), np.uint8)
+        _check(lib().dct3d_decode_frames(self._h, _ptr(q), width, height, channels, n_stacks, _ptr(out)),
+               "dct3d_decode_frames")
+        return out
+
     def forward_f32(self, cubes: np.ndarray) -> np.ndarray:
         cubes = np.ascontiguousarray(cubes, np.float32)
         n = cubes.size // self.cube_size
@@ -342,6 +395,14 @@ class Context:
     def decode_stacks_rgb_dev(self, d_q, width: int, height: int, n_stacks: int, d_frames) -> None:
         _check(lib().dct3d_decode_stacks_rgb_dev(self._h, _tptr(d_q), width, height, n_stacks, _tptr(d_frames)),
                "dct3d_decode_stacks_rgb_dev")
+
+    def encode_frames_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, d_q) -> None:
+        _check(lib().dct3d_encode_frames_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks, _tptr(d_q)),
+               "dct3d_encode_frames_dev")
+
+    def decode_frames_dev(self, d_q, width: int, height: int, channels: int, n_stacks: int, d_frames) -> None:
+        _check(lib().dct3d_decode_frames_dev(self._h, _tptr(d_q), width, height, channels, n_stacks, _tptr(d_frames)),
+               "dct3d_decode_frames_dev")
 
     def forward_f32_dev(self, d_in, n_cubes: int, d_out) -> None:
         _check(lib().dct3d_forward_f32_dev(self._h, _tptr(d_in), n_cubes, _tptr(d_out)), "dct3d_forward_f32_dev")

@@ -243,7 +243,13 @@ __device__ __forceinline__ int dec_cube_of_lane(int lane) { return (lane >> 5) *
 // pixels interleaved, 3 NXC bytes per plane; a cube's row is 24 bytes, so a 16-byte chunk lies in one cube or
 // in an even cube and the odd one after it (3 chunks per pair): with nbx even it never straddles a block-row,
 // as in the grey case, and it is 16-byte aligned (rows, block-rows and stacks are multiples of 48 bytes).
-template <int D, bool LOOP = false, int PX = 1>
+// EDGE = 1 (frames of any size, dct3d_edge.hip): the cubes tile the padded raster (nbx,
+// cubes_per_stack) and the output is the dense w x h frame (P.width, P.height; row stride w pixels, so rows
+// are byte aligned).  Every lane stores its own row piece: nothing for a row >= h, the whole piece (a 4-byte
+// word at a time, the alignment in the type) when it ends inside the row, and else its pixels < w byte by
+// byte.  No store leaves the frames.
+typedef unsigned dec_u32_u_t __attribute__((aligned(1)));
+template <int D, bool LOOP = false, int PX = 1, int EDGE = 0>
 __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
                                                const uint32_t (&outw)[D][((D == 8) ? 1 : 2) * PX], bool valid) {
     using G = DecGeom<D>;
@@ -255,6 +261,29 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
     const int y = (D == 8) ? k : (4 * h + k);
     const int x0 = (D == 8) ? 4 * h : 0;
     const int c = dec_cube_of_lane<D>(lane);
+    if constexpr (EDGE) {
+        if (!valid) return;
+        const uint32_t g = cube0 + c;
+        const uint32_t s = fdiv(g, P.div_cps);
+        const uint32_t rr = g - s * P.cubes_per_stack;
+        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        const uint32_t row = by * 8 + y, col = bx * 8 + x0;
+        if (row >= P.height || col >= P.width) return;
+        const uint32_t npx = min((uint32_t)NXC, P.width - col);  // the lane's pixels inside the frame
+        uint8_t* dst = P.out + (size_t)s * P.stack_stride + ((size_t)row * P.width + col) * PX;
+#pragma unroll
+        for (int z = 0; z < D; z++, dst += P.plane) {
+            if (npx == NXC) {
+#pragma unroll
+                for (int i = 0; i < NXC / 4 * PX; i++) *(dec_u32_u_t*)(dst + 4 * i) = outw[z][i];
+            } else {
+#pragma unroll
+                for (int b = 0; b < (NXC - 1) * PX; b++)
+                    if (b < (int)npx * PX) dst[b] = (uint8_t)(outw[z][b >> 2] >> (8 * (b & 3)));
+            }
+        }
+        return;
+    }
     const int wave = (int)(threadIdx.x >> 6);
     const uint32_t blk0 = cube0 - (uint32_t)wave * CPW;
     if (P.blk_store && blk0 + kWavesPerBlock * CPW <= P.n_cubes) {  // block-uniform
@@ -344,7 +373,7 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
 // values from the stream.
 // KEEP (decode_rgb_kernel): no stores; the lane's words outw[z][wd] go to keep[z * NXC / 4 + wd] and the
 // lane's `valid` to *keep_valid.
-template <int D, int PG, bool LOOP = false, bool CODES = false, bool KEEP = false, class AfterA, class Reload>
+template <int D, int PG, bool LOOP = false, bool CODES = false, bool KEEP = false, int EDGE = 0, class AfterA, class Reload>
 __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
                                             AfterA&& after_a, const Reload& reload, uint32_t* keep = nullptr,
                                             bool* keep_valid = nullptr) {
@@ -557,7 +586,7 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
         return;
     }
     __builtin_amdgcn_s_setprio(2);  // the store phase ahead of the computing waves (as encode16_kernel)
-    dec_store_tile<D, LOOP>(P, wl, lane, cube0, outw, valid);
+    dec_store_tile<D, LOOP, 1, EDGE>(P, wl, lane, cube0, outw, valid);
 }
 
 // Block 0 zeroes the next call's counter slot, both halves (the two slots alternate between the
@@ -569,7 +598,7 @@ __device__ __forceinline__ void dec_clear_next_slot(const DecodeParams& P) {
     }
 }
 
-template <int D, int PG>
+template <int D, int PG, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -582,7 +611,7 @@ __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     dec_clear_next_slot(P);
     dec_stage_tile<D>(wl, lane, v);
     wave_lds_sync();
-    decode_tile<D, PG>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
+    decode_tile<D, PG, false, false, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -634,7 +663,7 @@ struct ReloadCubesRgb {  // ReloadCubes for cube g of channel ch (dec_rgb_cube, 
     }
 };
 
-template <int D, int PG>
+template <int D, int PG, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
     constexpr int NW = (D == 8) ? 1 : 2;  // words per plane and channel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
@@ -678,7 +707,7 @@ __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
             }
     }
     __builtin_amdgcn_s_setprio(2);  // the store phase ahead of the computing waves
-    dec_store_tile<D, false, 3>(P, wl, (int)(threadIdx.x & 63), cube0, out3, valid);
+    dec_store_tile<D, false, 3, EDGE>(P, wl, (int)(threadIdx.x & 63), cube0, out3, valid);
 }
 
 }  // namespace dct3d

@@ -11,12 +11,87 @@ namespace dct3d {
 // =============================================================================================
 // Loads row y = j of frames 0..D-1 of cube g (row layout).
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-template <int D, bool NTL = false>
+
+// ---------------------------------------------------------------------------------------------
+// Frames of any size (EDGE = 1, dct3d_edge.hip).  The cubes tile the padded raster
+// (Wp = 8 ceil(w / 8), Hp = 8 ceil(h / 8): nbx, cubes_per_stack), which repeats each frame's last column
+// and last row and exists nowhere in memory: row y of a cube is frame row min(y, h - 1), and the cube of
+// the last column, when w % 8 = n != 0, holds its n pixels and then pixel w - 1 again.  The frames are
+// dense (row stride w pixels), so a row is byte aligned: the 8-byte accesses carry that alignment in their
+// type.  When w >= 8 the ragged cube loads the 8 pixels that end at w - 1 (edge_src moves the address back
+// by sh = 8 - n pixels) and edge_fix shifts them down and fills the tail; when w < 8 (one cube column) the
+// pixels are loaded one byte at a time, clamped.  No access leaves the frames.
+// ---------------------------------------------------------------------------------------------
+typedef u32x2_t u32x2_u_t __attribute__((aligned(1)));
+struct EdgeSrc {
+    const uint8_t* p;  // PX bytes per pixel: the row's first loaded pixel, frame 0 of the stack
+    uint32_t sh;       // pixels the loaded 8 lie before the cube's column (0: a cube inside the frame, or w < 8)
+};
+template <int PX>
+__device__ __forceinline__ EdgeSrc edge_src(const uint8_t* raster, uint64_t stack_stride, uint32_t width,
+                                            uint32_t height, uint32_t s, uint32_t by, uint32_t bx, int y) {
+    const uint32_t row = min(by * 8 + (uint32_t)y, height - 1);
+    uint32_t x0 = bx * 8, sh = 0;
+    if (x0 + 8 > width && width >= 8) {
+        sh = x0 + 8 - width;
+        x0 = width - 8;
+    }
+    return EdgeSrc{raster + (size_t)s * stack_stride + (size_t)PX * ((size_t)row * width + x0), sh};
+}
+// the 8 PX bytes of 8 pixels from p (width >= 8), or of pixels min(i, width - 1) (width < 8: p is the row's start)
+template <int PX>
+__device__ __forceinline__ void edge_load(const uint8_t* p, uint32_t width, uint2 (&w)[PX]) {
+    if (width >= 8) {  // uniform
+#pragma unroll
+        for (int i = 0; i < PX; i++) {
+            const u32x2_t t = *(const u32x2_u_t*)(p + 8 * i);
+            w[i] = make_uint2(t.x, t.y);
+        }
+    } else {
+        uint32_t d[2 * PX];
+#pragma unroll
+        for (int i = 0; i < 2 * PX; i++) d[i] = 0u;
+#pragma unroll
+        for (int b = 0; b < 8 * PX; b++)
+            d[b >> 2] |= (uint32_t)p[PX * min((uint32_t)(b / PX), width - 1) + b % PX] << (8 * (b & 3));
+#pragma unroll
+        for (int i = 0; i < PX; i++) w[i] = make_uint2(d[2 * i], d[2 * i + 1]);
+    }
+}
+// 8 pixels of one channel loaded sh pixels before the cube's column -> the cube's row: its 8 - sh pixels,
+// then the last one repeated
+__device__ __forceinline__ uint2 edge_fix(uint2 v, uint32_t sh) {
+    if (sh) {  // 1..7
+        const uint64_t t = ((uint64_t)v.y << 32) | v.x;
+        const uint64_t rep = (uint64_t)(v.y >> 24) * 0x0101010101010101ull;
+        const uint64_t o = (t >> (8 * sh)) | (rep << (8 * (8 - sh)));
+        v = make_uint2((uint32_t)o, (uint32_t)(o >> 32));
+    }
+    return v;
+}
+// sh of cube g (the RGB kernels apply edge_fix after the channel pick)
+__device__ __forceinline__ uint32_t edge_sh(const EncodeParams& P, uint32_t g) {
+    const uint32_t r = g - fdiv(g, P.div_cps) * P.cubes_per_stack;
+    const uint32_t bx = r - fdiv(r, P.div_nbx) * P.nbx;
+    return (bx * 8 + 8 > P.width && P.width >= 8) ? bx * 8 + 8 - P.width : 0u;
+}
+
+template <int D, bool NTL = false, int EDGE = 0>
 __device__ __forceinline__ void load_rows(const EncodeParams& P, uint32_t g, bool valid, int j, uint2 (&raw)[D]) {
     if (valid) {
         const uint32_t s = fdiv(g, P.div_cps);
         const uint32_t r = g - s * P.cubes_per_stack;
         const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<1>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
+#pragma unroll
+            for (int z = 0; z < D; z++) {
+                uint2 w[1];
+                edge_load<1>(e.p + (size_t)z * P.plane, P.width, w);
+                raw[z] = edge_fix(w[0], e.sh);
+            }
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)s * P.stack_stride + (size_t)(by * 8 + j) * P.width + bx * 8;
 #pragma unroll
         for (int z = 0; z < D; z++) {
@@ -73,12 +148,19 @@ __device__ __forceinline__ uint32_t enc_out_cube(const EncodeParams& P, uint32_t
     else return g + (2u * fdiv(g, P.div_cps) + (uint32_t)ch) * P.cubes_per_stack;
 }
 // load_rows for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
-template <int D>
+// (EDGE: the ragged cube's 8 pixels end at w - 1; the caller applies edge_fix to each picked channel)
+template <int D, int EDGE = 0>
 __device__ __forceinline__ void load_rows_rgb(const EncodeParams& P, uint32_t g, bool valid, int j, uint2 (&raw)[D][3]) {
     if (valid) {
         const uint32_t s = fdiv(g, P.div_cps);
         const uint32_t r = g - s * P.cubes_per_stack;
         const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
+#pragma unroll
+            for (int z = 0; z < D; z++) edge_load<3>(e.p + (size_t)z * P.plane, P.width, raw[z]);
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
 #pragma unroll
         for (int z = 0; z < D; z++) rgb_load24(src + (size_t)z * P.plane, raw[z]);
@@ -91,7 +173,7 @@ __device__ __forceinline__ void load_rows_rgb(const EncodeParams& P, uint32_t g,
 }
 
 // the rows of channel ch alone (the rare path's reload), one row's 24 bytes in registers at a time
-template <int D>
+template <int D, int EDGE = 0>
 __device__ __forceinline__ void load_rows_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int j, int ch,
                                                  uint2 (&raw)[D]) {
 #pragma unroll
@@ -100,6 +182,17 @@ __device__ __forceinline__ void load_rows_rgb_ch(const EncodeParams& P, uint32_t
         const uint32_t s = fdiv(g, P.div_cps);
         const uint32_t r = g - s * P.cubes_per_stack;
         const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
+#pragma unroll
+            for (int z = 0; z < D; z++) {
+                uint2 w[3];
+                edge_load<3>(e.p + (size_t)z * P.plane, P.width, w);
+                raw[z] = edge_fix(rgb_pick8(w, ch), e.sh);
+                asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
+            }
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
 #pragma unroll
         for (int z = 0; z < D; z++) {
@@ -421,7 +514,7 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
 // Everything after the row loads, for the 8 cubes from cube0 (8x8x4): statistics, transform, quantise +
 // certify, staged 1 KiB stores, the exact fold of the uncertified coefficients (enc4_replay).
 // PX = 3 (packed RGB24): raw = the rows of channel ch, whose cubes go to its [stack][channel] blocks.
-template <int D, bool NT, int PX = 1>
+template <int D, bool NT, int PX = 1, int EDGE = 0>
 __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (&raw)[D], char* wl,
                                             const float4* tab, int lane, uint32_t cube0, int ch = 0) {
     static_assert(D == 4, "8x8x8 encodes in encode16_kernel");
@@ -487,9 +580,9 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
     if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {  // wave-uniform
         uint2 px[D];
         if constexpr (PX == 1) {
-            load_rows<D>(P, g, valid, j, px);
+            load_rows<D, false, EDGE>(P, g, valid, j, px);
         } else {
-            load_rows_rgb_ch<D>(P, g, valid, j, ch, px);
+            load_rows_rgb_ch<D, EDGE>(P, g, valid, j, ch, px);
         }
         enc4_replay<PX>(P, px, fm, wl, lane, cube0, ch);
     }
@@ -497,7 +590,7 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
 
 // One wave = one group of 8 consecutive cubes (register-prefetch loops over several groups spill
 // and were 25-40 % slower: profiles/r01/encode_variant_sweep.txt).
-template <int D, bool NT, bool NTL = false>
+template <int D, bool NT, bool NTL = false, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
     __shared__ float4 s_tab[kTabN];
@@ -505,7 +598,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;
     uint2 raw[D];
     __builtin_amdgcn_s_setprio(3);
-    load_rows<D, NTL>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);  // in flight first
+    load_rows<D, NTL, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);  // in flight first
     __builtin_amdgcn_s_setprio(0);
     if (blockIdx.x == 0 && P.replay_clear) {
 #pragma unroll
@@ -513,14 +606,14 @@ __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     }
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     enc_tables(P, s_tab, lane);
-    encode_body<D, NT>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
+    encode_body<D, NT, 1, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
 }
 
 // Packed RGB24 (dct3d_encode_stacks_rgb_dev, 8x8x4): the wave owns the three channels of its 8 cubes'
 // tile.  Each lane loads its rows' 24 bytes once and keeps them packed (24 registers); per channel the
 // rows are picked out of them (rgb_pick8) and encode_body runs as for a grey plane, its cubes going to
 // the channel's [stack][channel] block.  P.n_cubes counts RGB cubes (a third of the output's).
-template <int D, bool NT>
+template <int D, bool NT, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
     __shared__ float4 s_tab[kTabN];
@@ -528,7 +621,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
     const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;
     uint2 raw3[D][3];
     __builtin_amdgcn_s_setprio(3);
-    load_rows_rgb<D>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw3);
+    load_rows_rgb<D, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw3);
     __builtin_amdgcn_s_setprio(0);
     if (blockIdx.x == 0 && P.replay_clear) {
 #pragma unroll
@@ -545,7 +638,12 @@ __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
         // hoisted out of the loop and held across the body)
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        encode_body<D, NT, 3>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
+        if constexpr (EDGE) {
+            const uint32_t sh = edge_sh(P, min(cube0 + (ln >> 3), P.n_cubes - 1));
+#pragma unroll
+            for (int z = 0; z < D; z++) raw[z] = edge_fix(raw[z], sh);
+        }
+        encode_body<D, NT, 3, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
         wave_lds_sync();  // the next channel reuses the wave's region
     }
 }
@@ -567,6 +665,7 @@ struct ReplayGeom {
     const double* coef;
     const uint8_t* group_of;
     int ch = 0;  // packed RGB24 (replay_load<D, 3>): the channel whose plane cube g belongs to
+    uint32_t height = 0;  // frames of any size (replay_load<D, PX, 1>)
 };
 // The global loads of one replay (split from the fold so that a caller can issue them early: on gfx9
 // a load issued after a wave's stores waits for those stores too, vmcnt being one in-order counter).
@@ -575,7 +674,7 @@ struct ReplayIn {
     double cf;
     uint2 px, gr;
 };
-template <int D, int PX = 1>
+template <int D, int PX = 1, int EDGE = 0>
 __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g, uint32_t k, int lane) {
     constexpr int CS = 64 * D;
     ReplayIn in;
@@ -587,7 +686,13 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
         const uint32_t s = g / R.cubes_per_stack;
         const uint32_t r = g - s * R.cubes_per_stack;
         const uint32_t by = r / R.nbx, bx = r - by * R.nbx;
-        if constexpr (PX == 1) {
+        if constexpr (EDGE) {  // the main path's padded values (edge_src, edge_load, edge_fix)
+            const EdgeSrc e = edge_src<PX>(R.raster, R.stack_stride, R.width, R.height, s, by, bx, y);
+            uint2 w[PX];
+            edge_load<PX>(e.p + (size_t)z * R.plane, R.width, w);
+            if constexpr (PX == 1) in.px = edge_fix(w[0], e.sh);
+            else in.px = edge_fix(rgb_pick8(w, R.ch), e.sh);
+        } else if constexpr (PX == 1) {
             const uint8_t* src = R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
                                  (size_t)(by * 8 + y) * R.width + bx * 8;
             in.px = *(const uint2*)src;
@@ -675,11 +780,22 @@ constexpr int kE16S16C = 8 * kE16S16F;
 static_assert(4 * kE16S16C <= kE16Lds, "int16 staging of the wave's 4 cubes fits its region");
 
 // rows of the lane's cube (row y = k of frames 4h .. 4h + 3), zero past the end
+template <int EDGE = 0>
 __device__ __forceinline__ void e16_load(const EncodeParams& P, uint32_t g, bool valid, int k, int h, uint2 (&raw)[4]) {
     if (valid) {
         const uint32_t st = fdiv(g, P.div_cps);
         const uint32_t rr = g - st * P.cubes_per_stack;
         const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<1>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                uint2 w[1];
+                edge_load<1>(e.p + (size_t)(4 * h + r) * P.plane, P.width, w);
+                raw[r] = edge_fix(w[0], e.sh);
+            }
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)st * P.stack_stride + (size_t)(by * 8 + k) * P.width + bx * 8 +
                              (size_t)(4 * h) * P.plane;
 #pragma unroll
@@ -691,12 +807,20 @@ __device__ __forceinline__ void e16_load(const EncodeParams& P, uint32_t g, bool
 }
 
 // e16_load for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
+// (EDGE: as load_rows_rgb)
+template <int EDGE = 0>
 __device__ __forceinline__ void e16_load_rgb(const EncodeParams& P, uint32_t g, bool valid, int k, int h,
                                              uint2 (&raw)[4][3]) {
     if (valid) {
         const uint32_t st = fdiv(g, P.div_cps);
         const uint32_t rr = g - st * P.cubes_per_stack;
         const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
+#pragma unroll
+            for (int r = 0; r < 4; r++) edge_load<3>(e.p + (size_t)(4 * h + r) * P.plane, P.width, raw[r]);
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
                              (size_t)(4 * h) * P.plane;
 #pragma unroll
@@ -710,6 +834,7 @@ __device__ __forceinline__ void e16_load_rgb(const EncodeParams& P, uint32_t g, 
 }
 
 // the rows of channel ch alone (the rare paths' reload), one row's 24 bytes in registers at a time
+template <int EDGE = 0>
 __device__ __forceinline__ void e16_load_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int k, int h, int ch,
                                                 uint2 (&raw)[4]) {
 #pragma unroll
@@ -718,6 +843,17 @@ __device__ __forceinline__ void e16_load_rgb_ch(const EncodeParams& P, uint32_t 
         const uint32_t st = fdiv(g, P.div_cps);
         const uint32_t rr = g - st * P.cubes_per_stack;
         const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
+        if constexpr (EDGE) {
+            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                uint2 w[3];
+                edge_load<3>(e.p + (size_t)(4 * h + r) * P.plane, P.width, w);
+                raw[r] = edge_fix(rgb_pick8(w, ch), e.sh);
+                asm volatile("" : "+v"(raw[r].x), "+v"(raw[r].y));
+            }
+            return;
+        }
         const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
                              (size_t)(4 * h) * P.plane;
 #pragma unroll
@@ -977,7 +1113,7 @@ __device__ __forceinline__ uint32_t strip_cube(const EncodeParams& P, uint32_t s
     const uint32_t by = fdiv(rr, P.div_strip_w);
     return st * P.cubes_per_stack + by * P.nbx + strip * P.strip_w + (rr - by * P.strip_w);
 }
-template <bool NT, int MODE = 0>
+template <bool NT, int MODE = 0, int EDGE = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) void encode16_kernel(EncodeParams P) {
     constexpr int CS = 512;
     // MODE 4 / 5: MODE 1 / 0 with the strip traversal (diagnostic sweep)
@@ -1010,7 +1146,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
         // default oldest-first issue they queue behind the computing waves' VALU work, and a box whose
         // encode loses the overlap of memory and compute that way runs 10 % slower (variant_sweep.txt)
         if constexpr (!MEM) __builtin_amdgcn_s_setprio(3);
-        e16_load(P, g, valid, k, h, raw);
+        e16_load<EDGE>(P, g, valid, k, h, raw);
         if constexpr (!MEM) __builtin_amdgcn_s_setprio(0);
     }
     if (!MEM && !COMP && blockIdx.x == 0 && P.replay_clear) {
@@ -1034,7 +1170,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
     const bool rare = !MEM && !COMP && P.recheck && __builtin_expect(__ballot(fm != 0u) != 0ull, 0);  // wave-uniform
 
     const ReplayGeom R{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride,
-                       P.ngroups, P.coef, P.group_of};
+                       P.ngroups, P.coef, P.group_of, 0, EDGE ? P.height : 0u};
 
     {
         // ---- all 4 cubes staged as int16 at once; the second certificate settles its coefficients in
@@ -1050,7 +1186,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
         wave_lds_sync();
         if (rare) {
             uint2 raw2[4];
-            e16_load(P, g, valid, k, h, raw2);
+            e16_load<EDGE>(P, g, valid, k, h, raw2);
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
@@ -1098,7 +1234,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
             const int src = (int)__builtin_ctzll(who);
             uint32_t rg, rk;
             e16_flag_pos(fm, src, cube0, rg, rk);
-            const int q = replay_fold<8, true>(replay_load<8>(R, rg, rk, lane), rk, lane, (int*)rs,
+            const int q = replay_fold<8, true>(replay_load<8, 1, EDGE>(R, rg, rk, lane), rk, lane, (int*)rs,
                                                (double*)(rs + kMaxGroupsDev * 4));
             if (lane == 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1121,7 +1257,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
 // third of the output's).  Occupancy: the packed rows on top of the main path's 72 registers do not fit 7
 // waves per SIMD (73 registers); the kernel takes what it needs up to 4 waves per SIMD (128).
 // ---------------------------------------------------------------------------------------------
-template <bool NT>
+template <bool NT, int EDGE = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void encode16_rgb_kernel(EncodeParams P) {
     constexpr int CS = 512;
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kE16Lds];
@@ -1134,7 +1270,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         const int lane = threadIdx.x & 63;
         const uint32_t g = cube0 + (lane >> 5) * 2 + ((lane & 15) >> 3);
         __builtin_amdgcn_s_setprio(3);
-        e16_load_rgb(P, g, g < P.n_cubes, lane & 7, (lane >> 4) & 1, raw3);
+        e16_load_rgb<EDGE>(P, g, g < P.n_cubes, lane & 7, (lane >> 4) & 1, raw3);
         __builtin_amdgcn_s_setprio(0);
     }
     if (blockIdx.x == 0 && P.replay_clear) {
@@ -1157,6 +1293,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         uint2 raw[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) raw[r] = rgb_pick8(raw3[r], ch);
+        if constexpr (EDGE) {
+            const uint32_t sh = edge_sh(P, min(g, P.n_cubes - 1));
+#pragma unroll
+            for (int r = 0; r < 4; r++) raw[r] = edge_fix(raw[r], sh);
+        }
         int32_t qv[8][4];
         uint32_t fm = 0u;
         e16_body(P, raw, wl, s_tab, lane, valid, qv, fm);
@@ -1171,7 +1312,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         wave_lds_sync();
         if (rare) {
             uint2 raw2[4];
-            e16_load_rgb_ch(P, g, valid, k, h, ch, raw2);
+            e16_load_rgb_ch<EDGE>(P, g, valid, k, h, ch, raw2);
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
@@ -1196,7 +1337,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         // rarest path: the exact Java fold of what both certificates left open (as encode16_kernel)
         if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {
             const ReplayGeom R{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride,
-                               P.ngroups, P.coef, P.group_of, ch};
+                               P.ngroups, P.coef, P.group_of, ch, EDGE ? P.height : 0u};
             uint32_t n = 0;
             for (;;) {
                 const uint64_t who = __ballot(fm != 0u);
@@ -1204,7 +1345,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
                 const int src = (int)__builtin_ctzll(who);
                 uint32_t rg, rk;
                 e16_flag_pos(fm, src, cube0, rg, rk);
-                const int q = replay_fold<8, true>(replay_load<8, 3>(R, rg, rk, lane), rk, lane, (int*)wl,
+                const int q = replay_fold<8, true>(replay_load<8, 3, EDGE>(R, rg, rk, lane), rk, lane, (int*)wl,
                                                    (double*)(wl + kMaxGroupsDev * 4));
                 if (lane == 0) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

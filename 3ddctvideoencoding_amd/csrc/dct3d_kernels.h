@@ -30,6 +30,10 @@ struct EncodeParams {
     uint32_t nbx;              // cubes per block-row
     FastDiv div_cps, div_nbx;  // the two divisions of the cube -> raster address map
     uint32_t width;
+    // frames of any size (dct3d_edge.hip): the frame's height in rows; width, plane and stack_stride are then
+    // the unpadded frame's, nbx and cubes_per_stack the padded raster's.  Unused by every other kernel (it
+    // fills the struct's padding before `plane`: no other member moves, no kernel argument grows).
+    uint32_t height;
     uint64_t plane;            // width * height
     uint64_t stack_stride;     // D * plane
     double coef_dc;            // Java DC group coefficient
@@ -58,6 +62,7 @@ struct DecodeParams {
     uint32_t n_cubes, cubes_per_stack, nbx, width;
     FastDiv div_cps, div_nbx;
     uint32_t cube_base;        // decode_eg_kernel: first cube of this launch (a chunk of whole stacks)
+    uint32_t height;           // frames of any size (dct3d_edge.hip), as EncodeParams::height (in the padding)
     uint64_t plane, stack_stride;
     double dec_G, dec_E;       // certificate: margin = dec_G * sum |dequantised| + dec_E
     float dec_l1_max;          // sum |dequantised| >= this: the cube goes to the exact replay
@@ -67,6 +72,8 @@ struct DecodeParams {
     unsigned int* replay_count;  // this call's counter slot: [0, S) cubes replayed (S = kCountSpread), or nullptr
     unsigned int* replay_clear;  // the other slot (2S words): zeroed by block 0 for the next call
 };
+
+static_assert(sizeof(EncodeParams) == 192 && sizeof(DecodeParams) == 120, "the kernels' argument layout");
 
 struct Fwd64Params {
     const uint8_t* raster;
@@ -81,6 +88,10 @@ int launch_encode(int D, const EncodeParams& P, hipStream_t st);
 // Packed RGB24 (uint8 [frame][y][x][3]) <-> int32 cubes laid out [stack][channel][cube]: n_cubes counts the
 // RGB cubes (a third of the int32 side's), plane and stack_stride are in bytes (3 per pixel), width in pixels
 int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st);
+// Frames whose width or height is no multiple of 8 (px = 1 grey, 3 packed RGB24): the same kernels with the
+// edge padding (encode) and the crop (decode) in their addressing; P describes the unpadded frames (width,
+// height, plane, stack_stride) and the padded raster's cubes (nbx, cubes_per_stack, n_cubes)
+int launch_encode_edge(int D, int px, const EncodeParams& P, hipStream_t st);
 struct EgParams {
     const int32_t* q;          // cube-major quantised values
     uint64_t n_cubes;
@@ -198,6 +209,7 @@ __device__ __forceinline__ uint64_t mark_serial(const uint16_t* mark, const uint
 
 int launch_decode(int D, const DecodeParams& P, hipStream_t st);
 int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st);
+int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st);
 int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =

@@ -571,6 +571,7 @@ static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q
     P.out = d_raster;
     P.n_cubes = (uint32_t)n_cubes;
     P.cube_base = 0;
+    P.height = 0;  // (dct3d_decode_frames_dev sets it)
     P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
     P.nbx = (uint32_t)(w / 8);
     set_fast_div(P);
@@ -701,6 +702,89 @@ int dct3d_decode_stacks_rgb_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, 
         (void)hipEventRecord(ev[3], c->stream);
     }
     count_slot_used(c, 3 * n_cubes * (uint64_t)c->plan.cs);
+    return DCT3D_OK;
+}
+
+// ---- frames of any size (dct3d.h: dct3d_encode_frames* / dct3d_decode_frames*) ----
+// The cubes tile the padded raster (wp x hp = the next multiples of 8), which repeats each frame's last
+// column and last row and exists nowhere in memory: the kernels of dct3d_edge.hip clamp their row loads
+// (encode) and crop their stores (decode).  A geometry that is a multiple of 8 both ways is the *_stacks*
+// call's: the very same kernels.
+static int check_geometry_frames(const dct3d_ctx* c, int w, int h, int channels, int n_stacks, int* wp, int* hp,
+                                 uint64_t* n_cubes) {
+    if (channels != 1 && channels != 3) return DCT3D_EINVAL;
+    if (w <= 0 || h <= 0 || w > INT32_MAX - 7 || h > INT32_MAX - 7) return DCT3D_EINVAL;
+    *wp = (w + 7) / 8 * 8;
+    *hp = (h + 7) / 8 * 8;
+    return channels == 3 ? check_geometry_rgb(c, *wp, *hp, n_stacks, n_cubes) : check_geometry(c, *wp, *hp, n_stacks, n_cubes);
+}
+
+int dct3d_encode_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                            int32_t* d_q) {
+    if (!c || (!d_frames && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    int wp, hp;
+    uint64_t n_cubes;
+    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
+    if (rc) return rc;
+    if (wp == w && hp == h)
+        return channels == 3 ? dct3d_encode_stacks_rgb_dev(c, d_frames, w, h, n_stacks, d_q)
+                             : dct3d_encode_stacks_dev(c, d_frames, w, h, n_stacks, d_q, nullptr);
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (!c->batch) {
+        c->last_valid = false;
+        c->last_count_slot = -1;
+    }
+    if (n_cubes == 0) return DCT3D_OK;
+    EncodeParams P;  // the padded raster's cubes over the unpadded frames' bytes
+    fill_encode_params(c, P, d_frames, d_q, wp, hp, n_cubes, channels);
+    P.width = (uint32_t)w;
+    P.height = (uint32_t)h;
+    P.plane = (uint64_t)channels * w * h;
+    P.stack_stride = P.plane * c->bd;
+    hipEvent_t* ev = timing_slot(c);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    if (launch_encode_edge(c->bd, channels, P, c->stream)) return DCT3D_EKERNEL;
+    if (ev) {  // single launch: the second event pair brackets nothing
+        (void)hipEventRecord(ev[1], c->stream);
+        (void)hipEventRecord(ev[2], c->stream);
+        (void)hipEventRecord(ev[3], c->stream);
+    }
+    count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
+    return DCT3D_OK;
+}
+
+int dct3d_decode_frames_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int channels, int n_stacks,
+                            uint8_t* d_frames) {
+    if (!c || (!d_frames && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    int wp, hp;
+    uint64_t n_cubes;
+    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
+    if (rc) return rc;
+    if (wp == w && hp == h)
+        return channels == 3 ? dct3d_decode_stacks_rgb_dev(c, d_q, w, h, n_stacks, d_frames)
+                             : dct3d_decode_stacks_dev(c, d_q, w, h, n_stacks, d_frames);
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (!c->batch) {
+        c->last_valid = false;
+        c->last_count_slot = -1;
+    }
+    if (n_cubes == 0) return DCT3D_OK;
+    DecodeParams P;  // the padded raster's cubes, stored cropped into the unpadded frames
+    fill_decode_params(c, P, d_q, d_frames, wp, hp, n_cubes, channels);
+    P.width = (uint32_t)w;
+    P.height = (uint32_t)h;
+    P.plane = (uint64_t)channels * w * h;
+    P.stack_stride = P.plane * c->bd;
+    P.blk_store = 0;  // (the 16-byte block stores need 16-byte aligned rows)
+    hipEvent_t* ev = timing_slot(c);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    if (launch_decode_edge(c->bd, channels, P, c->stream)) return DCT3D_EKERNEL;
+    if (ev) {  // one launch: the second event pair brackets nothing
+        (void)hipEventRecord(ev[1], c->stream);
+        (void)hipEventRecord(ev[2], c->stream);
+        (void)hipEventRecord(ev[3], c->stream);
+    }
+    count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
     return DCT3D_OK;
 }
 
@@ -888,6 +972,44 @@ int dct3d_decode_stacks_rgb(dct3d_ctx* c, const int32_t* q, int w, int h, int n_
     batch_begin(c);
     rc = run_pipeline(c, n_stacks, px * sizeof(int32_t), px, q, rgb, [&](const void* din, void* dout, int, int ns) {
         return dct3d_decode_stacks_rgb_dev(c, (const int32_t*)din, w, h, ns, (uint8_t*)dout);
+    });
+    batch_end(c);
+    return rc;
+}
+
+// ---- frames of any size, host pointers: chunks of whole stacks through the pipeline; the copies move the
+//      unpadded frames' bytes only ----
+int dct3d_encode_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks, int32_t* q) {
+    if (!c || (!frames && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    int wp, hp;
+    uint64_t n_cubes;
+    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (n_cubes == 0) return DCT3D_OK;
+    const size_t in_ps = (size_t)channels * w * h * c->bd;
+    const size_t out_ps = (size_t)channels * wp * hp * c->bd * sizeof(int32_t);
+    batch_begin(c);  // every chunk counts into one slot: dct3d_get_stats reports the whole call
+    rc = run_pipeline(c, n_stacks, in_ps, out_ps, frames, q, [&](const void* din, void* dout, int, int ns) {
+        return dct3d_encode_frames_dev(c, (const uint8_t*)din, w, h, channels, ns, (int32_t*)dout);
+    });
+    batch_end(c);
+    return rc;
+}
+
+int dct3d_decode_frames(dct3d_ctx* c, const int32_t* q, int w, int h, int channels, int n_stacks, uint8_t* frames) {
+    if (!c || (!frames && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    int wp, hp;
+    uint64_t n_cubes;
+    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (n_cubes == 0) return DCT3D_OK;
+    const size_t out_ps = (size_t)channels * w * h * c->bd;
+    const size_t in_ps = (size_t)channels * wp * hp * c->bd * sizeof(int32_t);
+    batch_begin(c);
+    rc = run_pipeline(c, n_stacks, in_ps, out_ps, q, frames, [&](const void* din, void* dout, int, int ns) {
+        return dct3d_decode_frames_dev(c, (const int32_t*)din, w, h, channels, ns, (uint8_t*)dout);
     });
     batch_end(c);
     return rc;

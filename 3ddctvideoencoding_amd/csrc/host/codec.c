@@ -47,6 +47,20 @@ static int timing_on(void) {
         (acc) += now_s() - t_0_;      \
     } while (0)
 
+/* A frame size that is no multiple of 8 (1366 x 768, ...): see "frames of any size" below */
+static int encode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
+                      int depth, int batch, int channels);
+static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
+                      int depth, int batch, int channels);
+static int geometry_ok(int width, int height, int frames, int depth) {
+    return width > 0 && height > 0 && frames > 0 && (depth == 8 || depth == 4);
+}
+static int invalid_geometry(int width, int height, int frames, int depth) {
+    printf("Invalid geometry: %dx%d, %d frames, block depth %d (width, height and frames must be positive, the "
+           "block depth 8 or 4)\n", width, height, frames, depth);
+    return 1;
+}
+
 static int default_batch(void) {
     const char *e = getenv("DCT3D_CODEC_BATCH");
     int b = e ? atoi(e) : 16;
@@ -55,11 +69,9 @@ static int default_batch(void) {
 
 int encode_ex(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
               int depth, int batch) {
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
-        printf("Invalid geometry: %dx%d, %d frames, block depth %d (width/height must be multiples of 8)\n", width,
-               height, frames, depth);
-        return 1;
-    }
+    if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
+    if (width % 8 || height % 8)
+        return encode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -178,10 +190,9 @@ int encode_ex(const char *inName, const char *outName, int width, int height, in
 
 int decode_ex(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
               int depth, int batch) {
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
-        printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
-        return 1;
-    }
+    if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
+    if (width % 8 || height % 8)
+        return decode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -447,8 +458,8 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
         return 1;
     }
     if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
-        printf("Invalid geometry: %dx%d, %d frames, block depth %d (width/height must be multiples of 8)\n", width,
-               height, frames, depth);
+        printf("Invalid geometry: %dx%d, %d frames, block depth %d (several devices: width/height must be multiples "
+               "of 8)\n", width, height, frames, depth);
         return 1;
     }
     if (batch <= 0) batch = default_batch();
@@ -665,11 +676,9 @@ static FILE *open_plane(const char *pattern, int ch, const char *mode) {
 
 int encode_rgb_ex(const char *inName, const char *outPattern, int width, int height, int frames, int platformIndex,
                   int depth, int batch) {
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
-        printf("Invalid geometry: %dx%d, %d frames, block depth %d (width/height must be multiples of 8)\n", width,
-               height, frames, depth);
-        return 1;
-    }
+    if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
+    if (width % 8 || height % 8)
+        return encode_any(inName, outPattern, width, height, frames, platformIndex, depth, batch, 3);
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -737,10 +746,9 @@ int encode_rgb_ex(const char *inName, const char *outPattern, int width, int hei
 
 int decode_rgb_ex(const char *inPattern, const char *outName, int width, int height, int frames, int platformIndex,
                   int depth, int batch) {
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || frames <= 0 || (depth != 8 && depth != 4)) {
-        printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
-        return 1;
-    }
+    if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
+    if (width % 8 || height % 8)
+        return decode_any(inPattern, outName, width, height, frames, platformIndex, depth, batch, 3);
     if (batch <= 0) batch = default_batch();
     FILE *in[3] = {NULL, NULL, NULL};
     dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
@@ -801,6 +809,165 @@ int decode_rgb_ex(const char *inPattern, const char *outName, int width, int hei
         if (in[ch]) fclose(in[ch]);
     }
     free(rgb);
+    free(q);
+    if (ctx) dct3d_ctx_destroy(ctx);
+    if (out && (fflush(out) || fclose(out))) status = 1;
+    if (!status) printf("Decoding process completed\n");
+    return status;
+}
+
+/* ---- frames of any size ---------------------------------------------------------------------- */
+/* A width or height that is no multiple of 8, grey (channels = 1: one stream, outName / inName) or packed
+ * RGB24 (channels = 3: <pattern>.red / .green / .blue).  The device pads by repeating each frame's last
+ * column and last row up to wp x hp (the next multiples of 8) inside its kernels (dct3d_encode_frames) and
+ * crops on the way back (dct3d_decode_frames); the entropy coder works on wp x hp.  So the streams are, byte
+ * for byte, what the same command writes for the edge-padded video at wp x hp.  A plain loop per batch, as the
+ * RGB commands: the quantised ints over PCIe, the host entropy coder per stack. */
+static FILE *open_stream(const char *name, int channels, int ch, const char *mode) {
+    if (channels == 3) return open_plane(name, ch, mode);
+    FILE *f = fopen(name, mode);
+    if (!f) printf("Cannot open %s file %s\n", mode[0] == 'r' ? "input" : "output", name);
+    return f;
+}
+
+static int encode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
+                      int depth, int batch, int channels) {
+    if (batch <= 0) batch = default_batch();
+    FILE *in = fopen(inName, "rb");
+    if (!in) {
+        printf("Cannot open input file %s\n", inName);
+        return 1;
+    }
+    const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    FILE *out[3] = {NULL, NULL, NULL};
+    dct3d_entropy_enc *ent[3] = {NULL, NULL, NULL};
+    dct3d_ctx *ctx = NULL;
+    uint8_t *fr = NULL;
+    int32_t *q = NULL;
+    int status = 0;
+    for (int ch = 0; ch < channels && !status; ch++)
+        if (!(out[ch] = open_stream(outName, channels, ch, "wb"))) status = 1;
+    if (!status) {
+        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        if (rc) {
+            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
+            status = 1;
+        }
+    }
+    const size_t stack_bytes = (size_t)channels * width * height * depth; /* of the frames as they are */
+    const size_t stack_px = (size_t)wp * hp * depth;                       /* values of a padded plane's stack */
+    const int n_stacks = (frames + depth - 1) / depth;
+    if (!status) {
+        fr = (uint8_t *)malloc(stack_bytes * batch);
+        q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
+        int ok = fr && q;
+        for (int ch = 0; ch < channels; ch++)
+            if (!(ent[ch] = dct3d_entropy_enc_create(wp, hp, depth, out[ch]))) ok = 0;
+        if (!ok) {
+            printf("Out of memory\n");
+            status = 1;
+        }
+    }
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        size_t got = 0, r;
+        const size_t want = stack_bytes * nb;
+        while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
+        if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as encode_ex */
+        const int rc = dct3d_encode_frames(ctx, fr, width, height, channels, nb, q);
+        if (rc) {
+            printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        for (int s = 0; s < nb && !status; s++)
+            for (int ch = 0; ch < channels; ch++) /* block (s, ch) of the [stack][channel] layout */
+                if (dct3d_entropy_enc_push(ent[ch], q + stack_px * ((size_t)channels * s + ch),
+                                           s0 + s == n_stacks - 1)) {
+                    printf("Error in the entropy coder\n");
+                    status = 1;
+                    break;
+                }
+        for (int s = 0; !status && s < nb; s++) printf("Frames processed: %d\n", (s0 + s + 1) * depth);
+    }
+    for (int ch = 0; ch < channels; ch++) {
+        if (ent[ch]) dct3d_entropy_enc_destroy(ent[ch]); /* the last deflate output and its write */
+        if (out[ch] && (fflush(out[ch]) || fclose(out[ch]))) status = 1;
+    }
+    free(fr);
+    free(q);
+    if (ctx) dct3d_ctx_destroy(ctx);
+    fclose(in);
+    if (!status) printf("Encoding process completed\n");
+    return status;
+}
+
+static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
+                      int depth, int batch, int channels) {
+    if (batch <= 0) batch = default_batch();
+    const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    FILE *in[3] = {NULL, NULL, NULL};
+    dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
+    FILE *out = NULL;
+    dct3d_ctx *ctx = NULL;
+    uint8_t *fr = NULL;
+    int32_t *q = NULL;
+    int status = 0;
+    for (int ch = 0; ch < channels && !status; ch++)
+        if (!(in[ch] = open_stream(inName, channels, ch, "rb"))) status = 1;
+    if (!status && !(out = fopen(outName, "wb"))) {
+        printf("Cannot open output file %s\n", outName);
+        status = 1;
+    }
+    if (!status) {
+        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        if (rc) {
+            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
+            status = 1;
+        }
+    }
+    const size_t stack_bytes = (size_t)channels * width * height * depth;
+    const size_t stack_px = (size_t)wp * hp * depth;
+    const int n_stacks = (frames + depth - 1) / depth;
+    if (!status) {
+        fr = (uint8_t *)malloc(stack_bytes * batch);
+        q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
+        int ok = fr && q;
+        for (int ch = 0; ch < channels; ch++)
+            if (!(ent[ch] = dct3d_entropy_dec_create(wp, hp, depth, in[ch], NULL, 0))) ok = 0;
+        if (!ok) {
+            printf("Out of memory\n");
+            status = 1;
+        }
+    }
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        for (int s = 0; s < nb && !status; s++)
+            for (int ch = 0; ch < channels; ch++)
+                if (dct3d_entropy_dec_pull(ent[ch], q + stack_px * ((size_t)channels * s + ch))) {
+                    printf("Truncated or corrupt input stream\n");
+                    status = 1;
+                    break;
+                }
+        if (status) break;
+        const int rc = dct3d_decode_frames(ctx, q, width, height, channels, nb, fr);
+        if (rc) {
+            printf("Error running the inverse 3D DCT: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        if (fwrite(fr, 1, stack_bytes * nb, out) != stack_bytes * nb) {
+            printf("Error writing the output file\n");
+            status = 1;
+            break;
+        }
+        printf("Frames processed: %d\n", (s0 + nb) * depth);
+    }
+    for (int ch = 0; ch < channels; ch++) {
+        if (ent[ch]) dct3d_entropy_dec_destroy(ent[ch]);
+        if (in[ch]) fclose(in[ch]);
+    }
+    free(fr);
     free(q);
     if (ctx) dct3d_ctx_destroy(ctx);
     if (out && (fflush(out) || fclose(out))) status = 1;

@@ -4,6 +4,8 @@
  *   dct3d_codec encode_rgb <rgb24 file> <name pattern> <width> <height> <frames> [device_index] [block_depth 8|4]
  *   dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <frames> [device_index] [block_depth 8|4]
  *     (packed RGB24 <-> <name pattern>.red / .green / .blue, the RGBUtils plane names; one device)
+ *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
+ *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
  * ("1,2,3"): encode_multi / decode_multi over those devices. */
 #include <errno.h>
@@ -26,6 +28,9 @@ static void usage(void) {
     printf("dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <nr of frames> "
            "<device_index (optional)> <block depth 8|4 (optional)> -> Decode <name pattern>.red/.green/.blue "
            "into packed RGB24\n");
+    printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
+           "last column and row (the stream is that of the padded video) and cropped again by decode; with "
+           "several devices they must be multiples of 8\n");
 }
 
 /* "1" or "1,2,3": 1-based device numbers (the reference's platformIndex, main.c:33-37).  Every entry must

@@ -29,7 +29,12 @@ extern "C" {
 int encode(char *inputFileName, char *outputFileName, int width, int height, int framesToEncode, int platformIndex);
 int decode(char *inputFileName, char *outputFileName, int width, int height, int framesToDecode, int platformIndex);
 
-/* Same, with the block depth (8 or 4) and the number of stacks per device call explicit. */
+/* Same, with the block depth (8 or 4) and the number of stacks per device call explicit.
+ * width and height may be any size >= 1.  Multiples of 8 are coded as the reference codes them.  Any other size
+ * (the reference overruns its buffers there) is padded to the next multiples of 8 by repeating each frame's last
+ * column and last row inside the device transform (dct3d_encode_frames), and cropped again by decode_ex
+ * (dct3d_decode_frames): the .bin is byte for byte the one encode_ex writes for the edge-padded video.  The
+ * same holds for encode_rgb_ex / decode_rgb_ex; encode_multi / decode_multi need multiples of 8. */
 int encode_ex(const char *inputFileName, const char *outputFileName, int width, int height, int framesToEncode,
               int platformIndex, int blockDepth, int stacksPerBatch);
 int decode_ex(const char *inputFileName, const char *outputFileName, int width, int height, int framesToDecode,

@@ -21,9 +21,11 @@
  *     clEnqueueWrite/ReadBuffer, encoder.c:209,254); *_dev entry points take device pointers and
  *     are asynchronous on the context stream (use dct3d_synchronize).  The context's own stream is a
  *     blocking stream (ordered with the legacy default stream); dct3d_ctx_set_stream selects another;
- *   - frame width must be a multiple of the block width and height of the block height
- *     (1080 = 135 * 8); the reference silently overruns otherwise, this library returns
- *     DCT3D_EINVAL.
+ *   - the *_stacks*, *_eg* and dct_opt entry points need a frame width that is a multiple of the
+ *     block width and a height that is a multiple of the block height (1080 = 135 * 8); the
+ *     reference silently overruns otherwise, these calls return DCT3D_EINVAL.  Frames of any other
+ *     size (1366 x 768, 1680 x 1050, ...) go through dct3d_encode_frames* / dct3d_decode_frames*,
+ *     which pad by edge replication and crop inside the transform kernels.
  *
  * Layouts:
  *   raster  : u8 frames, frame-major, row-major (the raw grayscale file format, encoder.c:21-27);
@@ -196,6 +198,33 @@ int dct3d_decode_stacks_rgb(dct3d_ctx *ctx, const int32_t *q_cubes, int width, i
                             uint8_t *rgb);
 int dct3d_decode_stacks_rgb_dev(dct3d_ctx *ctx, const int32_t *d_q_cubes, int width, int height,
                                 int n_stacks, uint8_t *d_rgb);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frames of any size (additive to ABI 9; detect by symbol): width >= 1, height >= 1, channels = 1 (grey,
+ * uint8 [n_stacks * D][height][width]) or 3 (packed RGB24, uint8 [n_stacks * D][height][width][3]),
+ * dense (no row padding).  With Wp = 8 ceil(width / 8), Hp = 8 ceil(height / 8), the padded raster
+ * repeats each frame's last column and last row up to Wp x Hp (per channel; numpy: np.pad(frames,
+ * ((0, 0), (0, Hp - height), (0, Wp - width)), mode = "edge")).  It exists nowhere in memory: the
+ * kernels clamp their loads and crop their stores, and the host copies move the unpadded bytes only.
+ *   encode  writes exactly what dct3d_encode_stacks (channels = 1) or dct3d_encode_stacks_rgb
+ *           (channels = 3) writes for the padded raster at Wp x Hp: (Wp / 8) (Hp / 8) cubes per stack
+ *           (RGB: per stack and channel, [stack][channel][cube]);
+ *   decode  writes the top-left height x width part of what dct3d_decode_stacks[_rgb] writes at
+ *           Wp x Hp, densely, and nothing else.
+ * When width and height are multiples of 8 these calls are the *_stacks* calls (the same kernels).
+ * Statistics count the padded work (n_units = cubes * cube_size, x 3 for RGB); the options act as on
+ * the *_stacks* calls.  DCT3D_EINVAL: NULL context or buffers, channels not 1 or 3, width or height
+ * <= 0, channels * padded cubes past the cube limit.  Conventions as the *_stacks* calls: *_dev
+ * asynchronous on the context stream, the host calls synchronous and chunked by stacks.
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_encode_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                        int n_stacks, int32_t *q_cubes);
+int dct3d_encode_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                            int n_stacks, int32_t *d_q_cubes);
+int dct3d_decode_frames(dct3d_ctx *ctx, const int32_t *q_cubes, int width, int height, int channels,
+                        int n_stacks, uint8_t *frames);
+int dct3d_decode_frames_dev(dct3d_ctx *ctx, const int32_t *d_q_cubes, int width, int height, int channels,
+                            int n_stacks, uint8_t *d_frames);
 
 /* ---------------------------------------------------------------------------------------------
  * Reference-faithful drop-in (A): the exact data flow of the OpenCL block, float cube-major in,
