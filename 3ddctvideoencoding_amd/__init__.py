@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "dct3d_eg_decode_dev", "dct3d_decode_eg", "dct3d_encode_eg_dev", "dct3d_decode_eg_dev",
     "dct3d_encode_stacks_rgb", "dct3d_encode_stacks_rgb_dev", "dct3d_decode_stacks_rgb", "dct3d_decode_stacks_rgb_dev",
     "dct3d_encode_frames", "dct3d_encode_frames_dev", "dct3d_decode_frames", "dct3d_decode_frames_dev",
+    "dct3d_encode_eg_frames", "dct3d_encode_eg_frames_dev", "dct3d_eg_fetch_channel",
+    "dct3d_decode_eg_frames", "dct3d_decode_eg_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -125,6 +127,12 @@ def lib() -> C.CDLL:
         L.dct3d_eg_decode_dev.argtypes = [vp, vp, u64, u64, u64, vp, C.POINTER(u64)]
         L.dct3d_decode_eg.argtypes = [vp, vp, u64, i32, i32, i32, i32, vp, C.POINTER(u64)]
         L.dct3d_decode_eg_dev.argtypes = [vp, vp, u64, u64, i32, i32, i32, vp, C.POINTER(u64)]
+        # (the per-channel arrays as plain addresses: ctypes arrays convert, None is NULL)
+        L.dct3d_encode_eg_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.dct3d_encode_eg_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+        L.dct3d_eg_fetch_channel.argtypes = [vp, i32, vp, u64]
+        L.dct3d_decode_eg_frames_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.dct3d_decode_eg_frames.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -444,7 +452,9 @@ class Context:
     # ---- Exp-Golomb stage ----
     def eg_encode_dev(self, d_q, n_cubes: int, d_out, out_cap: int, carry_byte: int = 0, carry_bits: int = 0) -> int:
         """Device Exp-Golomb stream of n_cubes int32 cubes into d_out (4-byte aligned words); returns the
-        total bits (carry included).  Raises Dct3dError(DCT3D_ENOSPC) when out_cap is too small."""
+        total bits (carry included) as soon as they are known: the last words of d_out complete on the context
+        stream (synchronize() or stream order), and d_q / d_out must stay valid until then.  Raises
+        Dct3dError(DCT3D_ENOSPC) when out_cap is too small."""
         tb = C.c_uint64(0)
         _check(lib().dct3d_eg_encode_dev(self._h, _tptr(d_q), n_cubes, carry_byte, carry_bits, _tptr(d_out), out_cap,
                                          C.byref(tb)), "dct3d_eg_encode_dev")
@@ -453,8 +463,9 @@ class Context:
     def encode_eg_dev(self, d_frames, width: int, height: int, n_stacks: int, d_out, out_cap: int,
                       carry_byte: int = 0, carry_bits: int = 0) -> int:
         """Fused device path: u8 frames (device) -> Exp-Golomb stream words in d_out, no int32
-        intermediate; returns the total bits (carry included).  Dct3dError(DCT3D_ENOSPC) if out_cap is
-        too small."""
+        intermediate; returns the total bits (carry included) as soon as they are known: the last words of
+        d_out complete on the context stream (synchronize() or stream order), and d_frames / d_out must stay
+        valid until then.  Dct3dError(DCT3D_ENOSPC) if out_cap is too small."""
         tb = C.c_uint64(0)
         _check(lib().dct3d_encode_eg_dev(self._h, _tptr(d_frames), width, height, n_stacks, carry_byte, carry_bits,
                                          _tptr(d_out), out_cap, C.byref(tb)), "dct3d_encode_eg_dev")
@@ -501,6 +512,89 @@ class Context:
         _check(lib().dct3d_decode_eg(self._h, _ptr(b) if b.size else None, b.size, start_bit, width, height, n_stacks,
                                      _ptr(out), C.byref(eb)), "dct3d_decode_eg")
         return out, eb.value
+
+    # ---- fused stream calls for frames of any size, grey or packed RGB24: one stream per channel ----
+    @staticmethod
+    def _frames_shape(frames: np.ndarray, bd: int):
+        if frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] != 3):
+            raise ValueError("frames must have shape [F, H, W] or [F, H, W, 3]")
+        if frames.shape[0] % bd:
+            raise ValueError("frame count must be a multiple of the block depth")
+        return 1 if frames.ndim == 3 else 3, frames.shape[0] // bd, frames.shape[1], frames.shape[2]
+
+    def encode_eg_frames(self, frames: np.ndarray, carry=None) -> list:
+        """u8 frames [n_stacks*bd, H, W] (grey) or [n_stacks*bd, H, W, 3] (packed RGB24), any H, W >= 1 -> one
+        (Exp-Golomb stream bytes, total bits) per channel: the stream of that channel's cubes of
+        encode_frames(frames), in stack order.  carry: per channel (carry_byte, carry_bits), default (0, 0)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        carry = list(carry) if carry is not None else [(0, 0)] * channels
+        if len(carry) != channels:
+            raise ValueError("one (carry_byte, carry_bits) per channel")
+        cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
+        cn = (C.c_int * channels)(*[n for _, n in carry])
+        tb = (C.c_uint64 * channels)()
+        _check(lib().dct3d_encode_eg_frames(self._h, _ptr(frames), W, H, channels, n_stacks, cb, cn, tb),
+               "dct3d_encode_eg_frames")
+        res = []
+        for ch in range(channels):
+            out = np.empty(eg_stream_bytes(tb[ch]), np.uint8)
+            _check(lib().dct3d_eg_fetch_channel(self._h, ch, _ptr(out) if out.size else None, out.size),
+                   "dct3d_eg_fetch_channel")
+            res.append((out.tobytes(), int(tb[ch])))
+        return res
+
+    def decode_eg_frames(self, streams, width: int, height: int, n_stacks: int, start_bits=None):
+        """one Exp-Golomb stream (bytes) per channel, each from bit start_bits[ch] (0..7) -> (u8 frames
+        [n_stacks*bd, height, width] for one stream, [n_stacks*bd, height, width, 3] for three; end bits)."""
+        channels = len(streams)
+        if channels not in (1, 3):
+            raise Dct3dError(DCT3D_EINVAL, "dct3d_decode_eg_frames")
+        start_bits = list(start_bits) if start_bits is not None else [0] * channels
+        bufs = [np.frombuffer(b, np.uint8) for b in streams]
+        ptrs = (C.c_void_p * channels)(*[_ptr(b) if b.size else None for b in bufs])
+        nb = (C.c_uint64 * channels)(*[b.size for b in bufs])
+        sb = (C.c_int * channels)(*start_bits)
+        eb = (C.c_uint64 * channels)()
+        out = np.empty((n_stacks * self.bd, height, width) + ((3,) if channels == 3 else ()), np.uint8)
+        _check(lib().dct3d_decode_eg_frames(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(out), eb),
+               "dct3d_decode_eg_frames")
+        return out, [int(e) for e in eb]
+
+    def encode_eg_frames_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, d_outs, out_caps,
+                             carry=None) -> list:
+        """Fused device path: u8 frames (device) -> channel ch's stream words in d_outs[ch] (tensors or
+        addresses, 4-byte aligned, out_caps[ch] bytes), no int32 intermediate; returns the total bits per
+        channel.  Dct3dError(DCT3D_ENOSPC) if a capacity is too small (its .total_bits holds the totals)."""
+        carry = list(carry) if carry is not None else [(0, 0)] * channels
+        cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
+        cn = (C.c_int * channels)(*[n for _, n in carry])
+        outs = (C.c_void_p * channels)(*[_tptr(t) for t in d_outs])
+        caps = (C.c_uint64 * channels)(*out_caps)
+        tb = (C.c_uint64 * channels)()
+        rc = lib().dct3d_encode_eg_frames_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks, cb, cn, outs,
+                                              caps, tb)
+        if rc != DCT3D_OK:
+            e = Dct3dError(rc, "dct3d_encode_eg_frames_dev")
+            e.total_bits = [int(t) for t in tb]
+            raise e
+        return [int(t) for t in tb]
+
+    def decode_eg_frames_dev(self, d_streams, nbytes, start_bits, width: int, height: int, n_stacks: int, d_frames) -> list:
+        """Fused device path: one Exp-Golomb stream per channel (tensors or addresses, 4-byte aligned) -> u8
+        frames (device), no int32 intermediate; returns the end bit per channel.  On a short or corrupt stream
+        the Dct3dError's .end_bits holds the end bits of the streams that were good."""
+        channels = len(d_streams)
+        ptrs = (C.c_void_p * channels)(*[_tptr(t) for t in d_streams])
+        nb = (C.c_uint64 * channels)(*nbytes)
+        sb = (C.c_uint64 * channels)(*start_bits)
+        eb = (C.c_uint64 * channels)()
+        rc = lib().dct3d_decode_eg_frames_dev(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _tptr(d_frames), eb)
+        if rc != DCT3D_OK:
+            e = Dct3dError(rc, "dct3d_decode_eg_frames_dev")
+            e.end_bits = [int(t) for t in eb]
+            raise e
+        return [int(t) for t in eb]
 
     def fill_synthetic_dev(self, d_frames, width: int, height: int, n_frames: int,
                            seed: int = synthetic.DEFAULT_SEED, frame0: int = 0, kind: str = "ramp") -> None:

@@ -749,10 +749,10 @@ __device__ __forceinline__ int replay_fold(const ReplayIn& in, uint32_t k, int l
     wave_lds_sync();
     return q;
 }
-template <int D>
+template <int D, int PX = 1, int EDGE = 0>
 __device__ __forceinline__ int exact_coef(const ReplayGeom& R, uint32_t g, uint32_t k, int lane, int* ssum,
                                           double* prod) {
-    return replay_fold<D>(replay_load<D>(R, g, k, lane), k, lane, ssum, prod);
+    return replay_fold<D>(replay_load<D, PX, EDGE>(R, g, k, lane), k, lane, ssum, prod);
 }
 
 // ---------------------------------------------------------------------------------------------

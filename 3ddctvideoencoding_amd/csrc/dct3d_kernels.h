@@ -168,6 +168,22 @@ struct EgDecParams {
     uint64_t* status_clear;
 };
 
+// Packed RGB24 stream -> raster decode (decode_eg_rgb_kernel): what the consumer reads of each channel's stream
+// and front (EgDecParams' members of the same names; status: [1] end bit, [2] flags, [3] long codes, [4] the
+// values the chunk scan counted)
+struct EgDecStream {
+    const uint32_t* words;
+    uint64_t n_words;
+    uint64_t n_values;
+    const uint16_t* mark;
+    const uint64_t* mark_base;
+    const uint64_t* status;
+};
+struct EgDecRgbParams {
+    EgDecStream s[3];
+    const uint16_t* diag;
+};
+
 // Fused encode + Exp-Golomb (dct3d_encode_eg_dev): the encode kernel's transform / quantise /
 // certify, the exact Java replay of uncertified coefficients inside the wave, then the wave's 8
 // cubes coded straight into a private slot (no int32 cube-major round trip).  Segment = one wave = 8
@@ -181,6 +197,9 @@ struct EgFusedParams {
     uint32_t* slot;            // [n_seg * seg_cap]: the segment's stream, MSB-first words, its first bit
                                // at bit 31 of word 0
     uint32_t seg_cap;          // 64 * words per lane (worst case cs/8 values x 27 bits)
+    // packed RGB24 (dct3d_eg_frames.hip): the channel this launch codes.  Unused by every other kernel (it
+    // fills the struct's padding before `seg_bits`: no other member moves, no kernel argument grows).
+    int ch;
     uint32_t* seg_bits;        // [n_seg] bits per segment (the scan's input)
 };
 
@@ -211,6 +230,14 @@ int launch_decode(int D, const DecodeParams& P, hipStream_t st);
 int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st);
 int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st);
 int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+// Frames of any size and packed RGB24 through the fused Exp-Golomb kernels (dct3d_eg_frames.hip).  Encode: px =
+// 1 grey (edge = 1 only), 3 packed RGB24 (edge = 0 or 1), channel E.ch of the RGB cubes per launch; P as
+// launch_encode_rgb's / launch_encode_edge's.  Decode: grey with the crop (P as launch_decode_edge's, 8 groups
+// per wave), or packed RGB24 from three streams (edge = 0: P as launch_decode_rgb's).  P.cube_base as
+// launch_decode_eg's.
+int launch_encode_eg_frames(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+int launch_decode_eg_edge(int D, const DecodeParams& P, const EgDecParams& E, hipStream_t st);
+int launch_decode_eg_rgb(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =
 // segments, P.bits = seg_bits)

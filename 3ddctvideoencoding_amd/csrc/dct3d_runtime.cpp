@@ -29,6 +29,9 @@ namespace {
 // the stream decode's status words (d_egd_status): [0, 4) the sync / mark passes' (EgDecParams::status),
 // [4, 6) the chunk scan's (EgParams::status)
 constexpr size_t kEgdStatusBytes = 6 * sizeof(uint64_t);
+// the pinned host words (h_status): [0, 6) a call's status words, [6] and [7] the decode's and the encode's
+// hand-off tags, [8, 26) the three fronts' words of a packed RGB24 stream decode
+constexpr size_t kHostStatusBytes = (8 + 18) * sizeof(uint64_t);
 
 struct DevBuf {
     void* p = nullptr;
@@ -113,6 +116,11 @@ struct dct3d_ctx {
     hipEvent_t pe_in[2] = {}, pe_done[2] = {};
     DevBuf p_in[2], p_out[2];
     uint64_t eg_last_bytes = 0;
+    // frames of any size / packed RGB24 through the fused Exp-Golomb calls (dct3d_*_eg_frames*): channels 1
+    // and 2 of the host calls' device streams (channel 0: d_eg_out / d_egd_in), a gathered channel for the
+    // two-step option, and the three fronts' status words (3 x 6; their marks share d_egd_mark)
+    DevBuf d_eg_out_x[2], d_egd_in_x[2], d_eg_q_ch, d_egd_status3;
+    uint64_t eg_last_bytes_x[2] = {0, 0};
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -311,11 +319,12 @@ int dct3d_ctx_create(int device, int block_w, int block_h, int block_d, dct3d_ct
     if (!rc && hipMemset(c->d_eg_status.p, 0, 32) != hipSuccess) rc = DCT3D_EDEVICE;
     if (!rc) rc = c->d_egd_status.grow(2 * kEgdStatusBytes);
     if (!rc && hipMemset(c->d_egd_status.p, 0, 2 * kEgdStatusBytes) != hipSuccess) rc = DCT3D_EDEVICE;
-    if (!rc && hipHostMalloc((void**)&c->h_status, kEgdStatusBytes + 16, hipHostMallocDefault) != hipSuccess) {
+    if (!rc && hipHostMalloc((void**)&c->h_status, kHostStatusBytes, hipHostMallocDefault) != hipSuccess) {
         c->h_status = nullptr;
         rc = DCT3D_ENOMEM;
     }
-    if (!rc) memset(c->h_status, 0, kEgdStatusBytes + 16);
+    if (!rc) memset(c->h_status, 0, kHostStatusBytes);
+    if (!rc) rc = c->d_egd_status3.grow(3 * kEgdStatusBytes);
     if (!rc && hipHostGetDevicePointer((void**)&c->h_status_dev, c->h_status, 0) != hipSuccess) c->h_status_dev = nullptr;
     if (rc) {
         dct3d_ctx_destroy(c);
@@ -328,12 +337,16 @@ int dct3d_ctx_create(int device, int block_w, int block_h, int block_d, dct3d_ct
 void dct3d_ctx_destroy(dct3d_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    // work may still be queued on the context's stream -- its own or a caller's (dct3d_ctx_set_stream) -- that
+    // reads the buffers released below
+    if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (DevBuf* b : {&c->d_ngroups, &c->d_coef, &c->d_group_of, &c->d_inv_coef, &c->d_tabs, &c->d_tabs64,
                       &c->d_enc_counts, &c->h_in, &c->h_out, &c->h_aux, &c->d_diag, &c->d_eg_bits,
                       &c->d_eg_off, &c->d_eg_bsum, &c->d_eg_status, &c->d_eg_out, &c->d_eg_q, &c->d_eg_ht,
                       &c->d_egd_exit, &c->d_egd_status, &c->d_egd_in, &c->d_egd_raster, &c->d_egd_mark, &c->d_egd_desc,
-                      &c->d_egf_slot})
+                      &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
+                      &c->d_eg_q_ch, &c->d_egd_status3})
         b->release();
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (auto& q : c->ev)
@@ -1122,19 +1135,24 @@ int dct3d_eg_encode_dev(dct3d_ctx* c, const int32_t* d_q, uint64_t n_cubes, uint
     return eg_run(c, d_q, n_cubes, carry_byte, carry_bits, (uint32_t*)d_out, out_cap, total_bits);
 }
 
-// Fused device path: encode_eg_kernel (transform, quantise, in-wave exact replay, lane-level
-// Exp-Golomb into slots) -> scan over segments -> eg_compact_kernel -> eg_stitch_kernel.
-int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, uint8_t carry_byte,
-                        int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
-    if (!c || (!d_raster && n_stacks) || carry_bits < 0 || carry_bits > 7 || ((uintptr_t)d_out & 3)) return DCT3D_EINVAL;
-    uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->last_valid = false;
-    c->last_count_slot = -1;
-    if (n_cubes == 0) return dct3d_eg_encode_dev(c, nullptr, 0, carry_byte, carry_bits, d_out, out_cap, total_bits);
-    if (!d_out) return DCT3D_EINVAL;
+// The geometry of a fused Exp-Golomb call: w x h frames of px bytes per pixel (1 grey, 3 packed RGB24), dense;
+// the cubes tile the padded wp x hp raster (wp = w, hp = h for the calls that need multiples of 8).
+struct EgGeom {
+    int w, h, wp, hp, px;
+    bool edge() const { return wp != w || hp != h; }
+    uint64_t cps() const { return (uint64_t)(wp / 8) * (uint64_t)(hp / 8); }  // cubes per stack and channel
+    uint64_t plane() const { return (uint64_t)px * w * h; }                   // bytes of a frame
+};
+
+// One fused launch chain on the context stream: encode_eg_kernel (transform, quantise, in-wave exact replay,
+// lane-level Exp-Golomb into slots) -> scan over segments -> eg_compact_kernel -> eg_stitch_kernel, for
+// channel ch of the n_cubes cubes of d_raster.  Returns once *total_bits is known.  A packed RGB24 call runs
+// one chain per channel back to back, reusing the slot, bits, offset and head / tail buffers.
+static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const EgGeom& g, int ch, uint64_t n_cubes,
+                           uint8_t carry_byte, int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
+    const int w = g.w, h = g.h;
+    const bool plain = g.px == 1 && !g.edge();  // dct3d_encode_eg_dev's geometry: its kernel
+    int rc;
     const int D = c->bd;
     const uint64_t n_seg = (n_cubes + 7) / 8, n_chunks = (n_seg + 4095) / 4096;
     // worst case per lane: cs/8 values x 27 bits (|q| <= 255 sqrt(cs) -> codes <= 27 bits)
@@ -1148,16 +1166,17 @@ int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int
         return rc;
     uint64_t* const sw = eg_status_begin(c, &rc);
     if (rc) return rc;
-    const uint64_t plane = (uint64_t)w * h;
+    const uint64_t plane = g.plane();
     EncodeParams P{};
     P.raster = d_raster;
     P.out = nullptr;
     P.n_cubes = (uint32_t)n_cubes;
     P.g_base = 0;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
+    P.cubes_per_stack = (uint32_t)g.cps();
+    P.nbx = (uint32_t)(g.wp / 8);
     set_fast_div(P);
     P.width = (uint32_t)w;
+    P.height = g.edge() ? (uint32_t)h : 0u;
     P.plane = plane;
     P.stack_stride = plane * D;
     P.coef_dc = c->plan.coef_dc;
@@ -1165,7 +1184,10 @@ int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int
     P.tab_rstep = tabs;
     P.tab_G = tabs + kMaxS;
     P.tab_E = tabs + 2 * kMaxS;
+    // (the new geometries' kernels count their exact replays; dct3d_encode_eg_dev's reports none)
+    if (!plain) set_count_slot(c, P.replay_count, P.replay_clear);
     EgFusedParams E;
+    E.ch = ch;
     E.ngroups = (const int32_t*)c->d_ngroups.p;
     E.coef = (const double*)c->d_coef.p;
     E.group_of = (const uint8_t*)c->d_group_of.p;
@@ -1194,7 +1216,9 @@ int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timing_slot(c);
     if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_encode_eg(D, P, E, c->stream)) return DCT3D_EKERNEL;
+    if (plain ? launch_encode_eg(D, P, E, c->stream) : launch_encode_eg_frames(D, g.px, g.edge() ? 1 : 0, P, E, c->stream))
+        return DCT3D_EKERNEL;
+    if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
     if (ev) (void)hipEventRecord(ev[2], c->stream);
     if (launch_eg_compact(G, E.slot, seg_cap, c->stream)) return DCT3D_EKERNEL;
@@ -1206,6 +1230,21 @@ int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int
     return DCT3D_OK;
 }
 
+// Fused device path, grey frames whose width and height are multiples of 8.
+int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, uint8_t carry_byte,
+                        int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
+    if (!c || (!d_raster && n_stacks) || carry_bits < 0 || carry_bits > 7 || ((uintptr_t)d_out & 3)) return DCT3D_EINVAL;
+    uint64_t n_cubes;
+    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    c->last_valid = false;
+    c->last_count_slot = -1;
+    if (n_cubes == 0) return dct3d_eg_encode_dev(c, nullptr, 0, carry_byte, carry_bits, d_out, out_cap, total_bits);
+    if (!d_out) return DCT3D_EINVAL;
+    return encode_eg_chain(c, d_raster, EgGeom{w, h, w, h, 1}, 0, n_cubes, carry_byte, carry_bits, d_out, out_cap, total_bits);
+}
+
 int dct3d_encode_eg(dct3d_ctx* c, const uint8_t* raster, int w, int h, int n_stacks, uint8_t carry_byte,
                     int carry_bits, uint64_t* total_bits) {
     if (!c || (!raster && n_stacks) || carry_bits < 0 || carry_bits > 7) return DCT3D_EINVAL;
@@ -1213,7 +1252,7 @@ int dct3d_encode_eg(dct3d_ctx* c, const uint8_t* raster, int w, int h, int n_sta
     int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
     if (rc) return rc;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->eg_last_bytes = 0;
+    c->eg_last_bytes = c->eg_last_bytes_x[0] = c->eg_last_bytes_x[1] = 0;
     const size_t in_bytes = n_cubes * c->plan.cs;
     if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1)) || (rc = c->d_eg_q.grow((in_bytes ? in_bytes : 1) * sizeof(int32_t))))
         return rc;
@@ -1263,6 +1302,133 @@ int dct3d_eg_fetch(dct3d_ctx* c, uint8_t* out, uint64_t nbytes) {
     return DCT3D_OK;
 }
 
+// ---- frames of any size and packed RGB24 -> one Exp-Golomb stream per channel (dct3d.h) ----
+// the arguments the frames calls share; *aligned: grey at multiples of 8 (the call hands over to the grey one)
+static int check_eg_frames(const dct3d_ctx* c, int w, int h, int channels, int n_stacks, EgGeom* g, uint64_t* n_cubes,
+                           bool* aligned) {
+    if (!c) return DCT3D_EINVAL;
+    int wp, hp;
+    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, n_cubes);
+    if (rc) return rc;
+    *g = EgGeom{w, h, wp, hp, channels};
+    *aligned = channels == 1 && !g->edge();
+    return DCT3D_OK;
+}
+
+int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                               const uint8_t carry_byte[], const int carry_bits[], uint8_t* const d_out[],
+                               const uint64_t out_cap[], uint64_t total_bits[]) {
+    EgGeom g;
+    uint64_t n_cubes;
+    bool aligned;
+    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
+    if (rc) return rc;
+    if (!carry_byte || !carry_bits || !d_out || !out_cap || !total_bits) return DCT3D_EINVAL;
+    if (aligned)
+        return dct3d_encode_eg_dev(c, d_frames, w, h, n_stacks, carry_byte[0], carry_bits[0], d_out[0], out_cap[0], total_bits);
+    if (!d_frames && n_stacks) return DCT3D_EINVAL;
+    for (int ch = 0; ch < channels; ch++)
+        if (carry_bits[ch] < 0 || carry_bits[ch] > 7 || ((uintptr_t)d_out[ch] & 3) || (n_cubes && !d_out[ch])) return DCT3D_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    c->last_valid = false;
+    c->last_count_slot = -1;
+    c->slot_used = false;
+    int first = DCT3D_OK;  // every channel runs (each total_bits[ch] is set); the first error is returned
+    for (int ch = 0; ch < channels; ch++) {
+        total_bits[ch] = 0;
+        rc = n_cubes ? encode_eg_chain(c, d_frames, g, ch, n_cubes, carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch])
+                     : dct3d_eg_encode_dev(c, nullptr, 0, carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch]);
+        if (rc && !first) first = rc;
+        if (rc && rc != DCT3D_ENOSPC) break;
+    }
+    if (c->slot_used) count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
+    return first;
+}
+
+// channel ch's host-call stream buffer on the device
+static DevBuf& eg_out_buf(dct3d_ctx* c, int ch) { return ch == 0 ? c->d_eg_out : c->d_eg_out_x[ch - 1]; }
+
+int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                           const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]) {
+    EgGeom g;
+    uint64_t n_cubes;
+    bool aligned;
+    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
+    if (rc) return rc;
+    if (!carry_byte || !carry_bits || !total_bits) return DCT3D_EINVAL;
+    if (aligned) return dct3d_encode_eg(c, frames, w, h, n_stacks, carry_byte[0], carry_bits[0], total_bits);
+    if (!frames && n_stacks) return DCT3D_EINVAL;
+    for (int ch = 0; ch < channels; ch++)
+        if (carry_bits[ch] < 0 || carry_bits[ch] > 7) return DCT3D_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    c->eg_last_bytes = c->eg_last_bytes_x[0] = c->eg_last_bytes_x[1] = 0;
+    const size_t in_bytes = (size_t)g.plane() * c->bd * n_stacks;  // the unpadded frames: one copy
+    const size_t ch_vals = n_cubes * c->plan.cs;                   // values of one channel
+    if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1))) return rc;
+    if (in_bytes && hipMemcpyAsync(c->h_in.p, frames, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    uint64_t cap[3], tb[3] = {0, 0, 0};
+    uint8_t* outs[3] = {nullptr, nullptr, nullptr};
+    for (int ch = 0; ch < channels; ch++) cap[ch] = ch_vals + 64;  // 8 bits per value first, grown to fit on ENOSPC
+    if (!c->opt_eg_two_step || n_cubes == 0) {
+        for (int attempt = 0; attempt < 2; attempt++) {
+            for (int ch = 0; ch < channels; ch++) {
+                if ((rc = eg_out_buf(c, ch).grow(cap[ch]))) return rc;
+                outs[ch] = (uint8_t*)eg_out_buf(c, ch).p;
+                cap[ch] = eg_out_buf(c, ch).bytes;
+            }
+            rc = dct3d_encode_eg_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, carry_byte, carry_bits,
+                                            outs, cap, tb);
+            if (rc != DCT3D_ENOSPC) break;
+            for (int ch = 0; ch < channels; ch++) cap[ch] = (tb[ch] + 31) / 32 * 4 + 64;
+        }
+        if (rc) return rc;
+    } else {
+        // A/B option: the int32 cubes ([stack][channel][cube]), then the stand-alone Exp-Golomb stage over each
+        // channel's blocks (gathered: they lie 3 blocks apart)
+        const size_t blk = (size_t)g.cps() * c->plan.cs * sizeof(int32_t);  // one (stack, channel) block
+        if ((rc = c->d_eg_q.grow(channels * ch_vals * sizeof(int32_t))) ||
+            (channels == 3 && (rc = c->d_eg_q_ch.grow(ch_vals * sizeof(int32_t)))))
+            return rc;
+        if ((rc = dct3d_encode_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, (int32_t*)c->d_eg_q.p)))
+            return rc;
+        for (int ch = 0; ch < channels; ch++) {
+            const int32_t* q = (const int32_t*)c->d_eg_q.p;
+            if (channels == 3) {
+                if (hipMemcpy2DAsync(c->d_eg_q_ch.p, blk, (const char*)c->d_eg_q.p + ch * blk, 3 * blk, blk, (size_t)n_stacks,
+                                     hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                    return DCT3D_EDEVICE;
+                q = (const int32_t*)c->d_eg_q_ch.p;
+            }
+            for (int attempt = 0; attempt < 2; attempt++) {
+                if ((rc = eg_out_buf(c, ch).grow(cap[ch]))) return rc;
+                rc = eg_run(c, q, n_cubes, carry_byte[ch], carry_bits[ch], (uint32_t*)eg_out_buf(c, ch).p,
+                            eg_out_buf(c, ch).bytes, &tb[ch]);
+                if (rc != DCT3D_ENOSPC) break;
+                cap[ch] = (tb[ch] + 31) / 32 * 4 + 64;
+            }
+            if (rc) return rc;
+        }
+    }
+    for (int ch = 0; ch < channels; ch++) {
+        total_bits[ch] = tb[ch];
+        (ch == 0 ? c->eg_last_bytes : c->eg_last_bytes_x[ch - 1]) = (tb[ch] + 7) / 8;
+    }
+    return DCT3D_OK;
+}
+
+int dct3d_eg_fetch_channel(dct3d_ctx* c, int channel, uint8_t* out, uint64_t nbytes) {
+    if (!c || channel < 0 || channel > 2) return DCT3D_EINVAL;
+    if (channel == 0) return dct3d_eg_fetch(c, out, nbytes);
+    if ((nbytes && !out) || nbytes > c->eg_last_bytes_x[channel - 1]) return DCT3D_EINVAL;
+    if (nbytes == 0) return DCT3D_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (hipMemcpyAsync(out, c->d_eg_out_x[channel - 1].p, nbytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    return DCT3D_OK;
+}
+
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,
 // the mark pass (bit position of every 32nd value).  No host wait after the last pass; the caller's
 // consumer kernel (emit / fused decode) skips itself on a corrupt or short stream, and eg_decode_status
@@ -1272,8 +1438,12 @@ int dct3d_eg_fetch(dct3d_ctx* c, uint8_t* out, uint64_t nbytes) {
 // bit 4, the consumer skips itself, and eg_decode_status asks the caller to rerun without speculation
 // (kEgRetry).  This takes the host round trip between pass 0 and the scan off every call.
 constexpr int kEgRetry = 1000;
+// set >= 0 (a packed RGB24 stream decode: one front per channel, all three alive for the consumer): the front
+// keeps its marks in region `set` of three in d_egd_mark and its status words in d_egd_status3[set], zeroed
+// here; the other work buffers are reused from front to front in stream order.  set < 0: the grey calls' one
+// front, whose status words alternate between two slots.
 static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint64_t start_bit, uint64_t n_cubes,
-                           EgDecParams& D, bool spec) {
+                           EgDecParams& D, bool spec, int set = -1) {
     const uint64_t limit = nbytes * 8;
     const uint64_t n_chunks = (limit - start_bit + kEgChunkBits - 1) / kEgChunkBits;
     const uint64_t n_scan = (n_chunks + 4095) / 4096;
@@ -1283,7 +1453,8 @@ static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     if (!rc) rc = c->d_eg_bsum.grow((n_scan + 1) * sizeof(uint64_t));
     const uint64_t n_marks = n_cubes * (uint64_t)c->plan.cs / 32;
     const uint64_t n_mark_groups = n_marks / kMarkGroup + 1;
-    if (!rc) rc = c->d_egd_mark.grow(n_mark_groups * sizeof(uint64_t) + (n_marks + 1) * sizeof(uint16_t));
+    const size_t mark_bytes = (n_mark_groups * sizeof(uint64_t) + (n_marks + 1) * sizeof(uint16_t) + 7) & ~(size_t)7;
+    if (!rc) rc = c->d_egd_mark.grow((set < 0 ? 1 : 3) * mark_bytes);
     if (rc) return rc;
     D.words = (const uint32_t*)d_bytes;
     D.n_words = (nbytes + 3) / 4;
@@ -1298,12 +1469,13 @@ static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     D.off = nullptr;
     D.part = (uint32_t*)c->d_eg_off.p;
     D.bsum = (uint64_t*)c->d_eg_bsum.p;
-    uint64_t* const st = (uint64_t*)c->d_egd_status.p + 6 * c->egd_slot;  // this call's words
-    const bool clean = c->egd_clean[c->egd_slot];
-    c->egd_clean[c->egd_slot] = false;
+    uint64_t* const st = set < 0 ? (uint64_t*)c->d_egd_status.p + 6 * c->egd_slot  // this call's words
+                                 : (uint64_t*)c->d_egd_status3.p + 6 * set;
+    const bool clean = set < 0 && c->egd_clean[c->egd_slot];
+    if (set < 0) c->egd_clean[c->egd_slot] = false;
     D.status = st;
     D.status_clear = nullptr;
-    D.mark_base = (uint64_t*)c->d_egd_mark.p;
+    D.mark_base = (uint64_t*)((char*)c->d_egd_mark.p + (set < 0 ? 0 : set) * mark_bytes);
     D.mark = (uint16_t*)(D.mark_base + n_mark_groups);
     D.q = nullptr;
     D.status_host = nullptr;
@@ -1398,6 +1570,16 @@ static int egd_wait_verdict(dct3d_ctx* c, const EgDecParams& D, uint64_t* w) {
     w[4] = (fl & 8u) ? 0u : D.n_values;
     return DCT3D_OK;
 }
+// a front's six status words -> the call's result and end bit
+static int egd_verdict(const uint64_t* w, uint64_t n_values, uint64_t* end_bit) {
+    const uint64_t* st = w;         // the decode's words
+    const uint64_t* total = w + 4;  // the scan's: total bits, flags
+    if (st[2] & 4) return kEgRetry;  // a speculative front whose pass 0 did not resolve: rerun
+    if (st[2] & 1) return DCT3D_EINVAL;
+    if ((st[2] & 2) || total[0] < n_values) return DCT3D_ENODATA;
+    if (end_bit) *end_bit = st[1];
+    return DCT3D_OK;
+}
 static int eg_decode_status(dct3d_ctx* c, const EgDecParams& D, uint64_t* end_bit) {
     uint64_t w[6] = {0, 0, 0, 0, 0, 0};
     if (D.status_host) {
@@ -1406,13 +1588,7 @@ static int eg_decode_status(dct3d_ctx* c, const EgDecParams& D, uint64_t* end_bi
         return DCT3D_EDEVICE;
     }
     c->egd_slot ^= 1;  // the next call's words
-    const uint64_t* st = w;         // the decode's words
-    const uint64_t* total = w + 4;  // the scan's: total bits, flags
-    if (st[2] & 4) return kEgRetry;  // a speculative front whose pass 0 did not resolve: rerun
-    if (st[2] & 1) return DCT3D_EINVAL;
-    if ((st[2] & 2) || total[0] < D.n_values) return DCT3D_ENODATA;
-    if (end_bit) *end_bit = st[1];
-    return DCT3D_OK;
+    return egd_verdict(w, D.n_values, end_bit);
 }
 
 int dct3d_eg_decode_dev(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint64_t start_bit, uint64_t n_cubes,
@@ -1454,10 +1630,11 @@ static int eg_stack_align(const dct3d_ctx* c, int w, int h) {
     }
     return (int)(grp / b);
 }
-static int decode_eg_range(dct3d_ctx* c, const EgDecParams& E, int w, int h, int st0, int ns, uint8_t* out_stack0) {
+// E: the front of each of g.px streams (packed RGB24: one per channel)
+static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const EgGeom& g, int st0, int ns, uint8_t* out_stack0) {
     const int D = c->bd;
-    const uint64_t plane = (uint64_t)w * h;
-    const uint64_t cps = (uint64_t)(w / 8) * (h / 8);
+    const uint64_t plane = g.plane();
+    const uint64_t cps = g.cps();
     uint8_t* out = out_stack0 - (size_t)st0 * plane * D;  // rebased: stack st0 at out_stack0
     DecodeParams P;
     P.in = nullptr;
@@ -1465,27 +1642,96 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams& E, int w, int h, int
     P.cube_base = (uint32_t)(st0 * cps);
     P.n_cubes = (uint32_t)((st0 + ns) * cps);
     P.cubes_per_stack = (uint32_t)cps;
-    P.nbx = (uint32_t)(w / 8);
+    P.nbx = (uint32_t)(g.wp / 8);
     set_fast_div(P);
-    P.width = (uint32_t)w;
+    P.width = (uint32_t)g.w;
+    P.height = g.edge() ? (uint32_t)g.h : 0u;
     P.plane = plane;
     P.stack_stride = plane * D;
     P.dec_G = c->plan.dec_G;
     P.dec_E = c->plan.dec_E;
     P.dec_l1_max = c->plan.dec_l1_max;
-    P.blk_store = (w / 8) % 2 == 0 && plane * D < (1ull << 32) ? 1u : 0u;  // dec_store_tile's conditions
+    // dec_store_tile's conditions (the cropped stores of frames of any size go lane by lane)
+    P.blk_store = !g.edge() && (g.w / 8) % 2 == 0 && plane * D < (1ull << 32) ? 1u : 0u;
     P.dec_E += c->opt_dec_margin;  // test option (see above)
     set_dec_replay(c, P);
     hipEvent_t* ev = timing_slot(c);
     if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_decode_eg(D, P, E, c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream)) return DCT3D_EKERNEL;
+    int lrc;
+    if (g.px == 3) {
+        EgDecRgbParams R;
+        for (int ch = 0; ch < 3; ch++)
+            R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
+        R.diag = E[0].diag;
+        lrc = launch_decode_eg_rgb(D, g.edge() ? 1 : 0, P, R, c->stream);
+    } else if (g.edge()) {
+        lrc = launch_decode_eg_edge(D, P, E[0], c->stream);
+    } else {
+        lrc = launch_decode_eg(D, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
+    }
+    if (lrc) return DCT3D_EKERNEL;
     if (ev) {
         (void)hipEventRecord(ev[1], c->stream);
         (void)hipEventRecord(ev[2], c->stream);
         (void)hipEventRecord(ev[3], c->stream);
     }
-    count_slot_used(c, (uint64_t)ns * cps * (uint64_t)c->plan.cs);
+    count_slot_used(c, (uint64_t)g.px * ns * cps * (uint64_t)c->plan.cs);
     return DCT3D_OK;
+}
+
+// The fused stream -> raster decode of n_stacks stacks: the front of each of the g.px device streams, then the
+// consumer -- to d_out (host_out == nullptr: asynchronous, the call returning once the verdicts are known), or
+// in chunks of stacks through the pipeline to host_out.  end_bit[ch] (start_bit[ch] on entry) is set for
+// every stream whose own verdict is good; the first bad verdict is returned.  One grey stream to a device
+// raster hands its verdict over from the consumer; the other cases read the status words back.
+static int decode_eg_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint64_t* nbytes, const uint64_t* start_bit,
+                         const EgGeom& g, int n_stacks, uint64_t n_cubes, uint8_t* d_out, uint8_t* host_out,
+                         uint64_t* end_bit) {
+    const bool handoff = !host_out && g.px == 1;
+    int rc;
+    for (int spec = 1;; spec = 0) {
+        EgDecParams E[3] = {};
+        for (int ch = 0; ch < g.px; ch++)
+            if ((rc = eg_decode_front(c, d_bytes[ch], nbytes[ch], start_bit[ch], n_cubes, E[ch],
+                                      spec && !c->opt_eg_no_resolve, g.px == 1 ? -1 : ch)))
+                return rc;
+        if (handoff) {
+            E[0].status_host = c->h_status_dev;  // the consumer hands the verdict to the host (nullptr: a copy)
+            E[0].seq = ++c->egd_seq;
+            E[0].status_clear = (uint64_t*)c->d_egd_status.p + 6 * (c->egd_slot ^ 1);  // and zeroes the next call's
+        }
+        if (host_out) {
+            // the raster leaves in chunks of stacks while the next chunk decodes (the stream is small: no upload)
+            const size_t per_stack = (size_t)g.plane() * c->bd;
+            batch_begin(c);
+            rc = run_pipeline(c, n_stacks, 0, per_stack, nullptr, host_out, [&](const void*, void* dout, int st0, int ns) {
+                return decode_eg_range(c, E, g, st0, ns, (uint8_t*)dout);
+            }, eg_stack_align(c, g.wp, g.hp));  // each chunk's first cube on a consumer group
+            batch_end(c);
+        } else {
+            rc = decode_eg_range(c, E, g, 0, n_stacks, d_out);
+        }
+        if (rc) return rc;
+        if (handoff) c->egd_clean[c->egd_slot ^ 1] = true;
+        if (g.px == 1) {
+            rc = eg_decode_status(c, E[0], end_bit);
+        } else {  // the three fronts' words in one read-back
+            uint64_t w[18];
+            if (hipMemcpyAsync(c->h_status + 8, c->d_egd_status3.p, sizeof(w), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                stream_wait(c))
+                return DCT3D_EDEVICE;
+            memcpy(w, c->h_status + 8, sizeof(w));
+            int v[3];
+            bool retry = false;
+            for (int ch = 0; ch < 3; ch++) retry |= (v[ch] = egd_verdict(w + 6 * ch, E[ch].n_values, nullptr)) == kEgRetry;
+            rc = retry ? kEgRetry : DCT3D_OK;
+            for (int ch = 0; ch < 3 && !retry; ch++) {
+                if (!v[ch]) end_bit[ch] = w[6 * ch + 1];
+                else if (!rc) rc = v[ch];
+            }
+        }
+        if (rc != kEgRetry || !spec) return rc == kEgRetry ? DCT3D_EDEVICE : rc;
+    }
 }
 extern "C" {
 
@@ -1503,17 +1749,7 @@ int dct3d_decode_eg_dev(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, u
     if (end_bit) *end_bit = start_bit;
     if (n_cubes == 0) return DCT3D_OK;
     if (start_bit >= nbytes * 8) return DCT3D_ENODATA;
-    for (int spec = 1;; spec = 0) {
-        EgDecParams E{};
-        if ((rc = eg_decode_front(c, d_bytes, nbytes, start_bit, n_cubes, E, spec && !c->opt_eg_no_resolve))) return rc;
-        E.status_host = c->h_status_dev;  // the consumer hands the verdict to the host (nullptr: a copy)
-        E.seq = ++c->egd_seq;
-        E.status_clear = (uint64_t*)c->d_egd_status.p + 6 * (c->egd_slot ^ 1);  // and zeroes the next call's
-        if ((rc = decode_eg_range(c, E, w, h, 0, n_stacks, d_raster))) return rc;
-        c->egd_clean[c->egd_slot ^ 1] = true;
-        rc = eg_decode_status(c, E, end_bit);
-        if (rc != kEgRetry || !spec) return rc == kEgRetry ? DCT3D_EDEVICE : rc;
-    }
+    return decode_eg_run(c, &d_bytes, &nbytes, &start_bit, EgGeom{w, h, w, h, 1}, n_stacks, n_cubes, d_raster, nullptr, end_bit);
 }
 
 int dct3d_decode_eg(dct3d_ctx* c, const uint8_t* bytes, uint64_t nbytes, int start_bit, int w, int h, int n_stacks,
@@ -1528,22 +1764,92 @@ int dct3d_decode_eg(dct3d_ctx* c, const uint8_t* bytes, uint64_t nbytes, int sta
     if ((uint64_t)start_bit >= nbytes * 8) return DCT3D_ENODATA;
     if ((rc = c->d_egd_in.grow((nbytes + 8) & ~(uint64_t)3))) return rc;
     if (hipMemcpyAsync(c->d_egd_in.p, bytes, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return DCT3D_EDEVICE;
-    for (int spec = 1;; spec = 0) {
-        EgDecParams E{};
-        if ((rc = eg_decode_front(c, (const uint8_t*)c->d_egd_in.p, nbytes, (uint64_t)start_bit, n_cubes, E,
-                                  spec && !c->opt_eg_no_resolve)))
+    const uint8_t* const d_bytes = (const uint8_t*)c->d_egd_in.p;
+    const uint64_t sb = (uint64_t)start_bit;
+    return decode_eg_run(c, &d_bytes, &nbytes, &sb, EgGeom{w, h, w, h, 1}, n_stacks, n_cubes, nullptr, raster, end_bit);
+}
+
+// ---- one Exp-Golomb stream per channel -> frames of any size, grey or packed RGB24 (dct3d.h) ----
+int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], const uint64_t nbytes[],
+                               const uint64_t start_bit[], int w, int h, int channels, int n_stacks, uint8_t* d_frames,
+                               uint64_t end_bit[]) {
+    EgGeom g;
+    uint64_t n_cubes;
+    bool aligned;
+    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
+    if (rc) return rc;
+    if (!d_bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
+    if (aligned) return dct3d_decode_eg_dev(c, d_bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, d_frames, end_bit);
+    if (n_stacks && !d_frames) return DCT3D_EINVAL;
+    for (int ch = 0; ch < channels; ch++)
+        if ((n_stacks && !d_bytes[ch]) || ((uintptr_t)d_bytes[ch] & 3)) return DCT3D_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    c->last_valid = false;
+    c->last_count_slot = -1;
+    for (int ch = 0; ch < channels; ch++) end_bit[ch] = start_bit[ch];
+    if (n_cubes == 0) return DCT3D_OK;
+    for (int ch = 0; ch < channels; ch++)
+        if (start_bit[ch] >= nbytes[ch] * 8) return DCT3D_ENODATA;
+    if (c->opt_eg_two_step) {
+        // A/B option: each stream through the stand-alone stage into its blocks of the int32 cubes
+        // ([stack][channel][cube]), then dct3d_decode_frames_dev
+        const size_t ch_vals = n_cubes * c->plan.cs, blk = (size_t)g.cps() * c->plan.cs * sizeof(int32_t);
+        if ((rc = c->d_eg_q.grow(channels * ch_vals * sizeof(int32_t))) ||
+            (channels == 3 && (rc = c->d_eg_q_ch.grow(ch_vals * sizeof(int32_t)))))
             return rc;
-        // the raster leaves in chunks of stacks while the next chunk decodes (the stream is small: no upload)
-        const size_t px = n_cubes * c->plan.cs / n_stacks;
-        batch_begin(c);
-        rc = run_pipeline(c, n_stacks, 0, px, nullptr, raster, [&](const void*, void* dout, int st0, int ns) {
-            return decode_eg_range(c, E, w, h, st0, ns, (uint8_t*)dout);
-        }, eg_stack_align(c, w, h));  // each chunk's first cube on a consumer group
-        batch_end(c);
-        if (rc) return rc;
-        rc = eg_decode_status(c, E, end_bit);
-        if (rc != kEgRetry || !spec) return rc == kEgRetry ? DCT3D_EDEVICE : rc;
+        int first = DCT3D_OK;
+        for (int ch = 0; ch < channels; ch++) {
+            int32_t* q = channels == 3 ? (int32_t*)c->d_eg_q_ch.p : (int32_t*)c->d_eg_q.p;
+            rc = dct3d_eg_decode_dev(c, d_bytes[ch], nbytes[ch], start_bit[ch], n_cubes, q, &end_bit[ch]);
+            if (rc && !first) first = rc;
+            if (rc && rc != DCT3D_ENODATA && rc != DCT3D_EINVAL) return rc;
+            if (channels == 3 && hipMemcpy2DAsync((char*)c->d_eg_q.p + ch * blk, 3 * blk, q, blk, blk, (size_t)n_stacks,
+                                                  hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                return DCT3D_EDEVICE;
+        }
+        if (first) return first;
+        return dct3d_decode_frames_dev(c, (const int32_t*)c->d_eg_q.p, w, h, channels, n_stacks, d_frames);
     }
+    return decode_eg_run(c, d_bytes, nbytes, start_bit, g, n_stacks, n_cubes, d_frames, nullptr, end_bit);
+}
+
+// channel ch's host-call stream buffer on the device
+static DevBuf& egd_in_buf(dct3d_ctx* c, int ch) { return ch == 0 ? c->d_egd_in : c->d_egd_in_x[ch - 1]; }
+
+int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uint64_t nbytes[], const int start_bit[],
+                           int w, int h, int channels, int n_stacks, uint8_t* frames, uint64_t end_bit[]) {
+    EgGeom g;
+    uint64_t n_cubes;
+    bool aligned;
+    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
+    if (rc) return rc;
+    if (!bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
+    if (aligned) return dct3d_decode_eg(c, bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, frames, end_bit);
+    if (n_stacks && !frames) return DCT3D_EINVAL;
+    for (int ch = 0; ch < channels; ch++)
+        if ((n_stacks && !bytes[ch]) || start_bit[ch] < 0 || start_bit[ch] > 7) return DCT3D_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    uint64_t sb[3] = {0, 0, 0};
+    for (int ch = 0; ch < channels; ch++) end_bit[ch] = sb[ch] = (uint64_t)start_bit[ch];
+    if (n_cubes == 0) return DCT3D_OK;
+    for (int ch = 0; ch < channels; ch++)
+        if (sb[ch] >= nbytes[ch] * 8) return DCT3D_ENODATA;
+    const uint8_t* d_bytes[3] = {nullptr, nullptr, nullptr};
+    for (int ch = 0; ch < channels; ch++) {
+        if ((rc = egd_in_buf(c, ch).grow((nbytes[ch] + 8) & ~(uint64_t)3))) return rc;
+        d_bytes[ch] = (const uint8_t*)egd_in_buf(c, ch).p;
+        if (hipMemcpyAsync(egd_in_buf(c, ch).p, bytes[ch], nbytes[ch], hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return DCT3D_EDEVICE;
+    }
+    if (c->opt_eg_two_step) {  // A/B option: through the int32 cubes, the frames in one copy
+        const size_t out_bytes = (size_t)g.plane() * c->bd * n_stacks;
+        if ((rc = c->d_egd_raster.grow(out_bytes))) return rc;
+        if ((rc = dct3d_decode_eg_frames_dev(c, d_bytes, nbytes, sb, w, h, channels, n_stacks, (uint8_t*)c->d_egd_raster.p, end_bit)))
+            return rc;
+        if (hipMemcpyAsync(frames, c->d_egd_raster.p, out_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return DCT3D_EDEVICE;
+        return hipStreamSynchronize(c->stream) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
+    }
+    return decode_eg_run(c, d_bytes, nbytes, sb, g, n_stacks, n_cubes, nullptr, frames, end_bit);
 }
 
 }  // extern "C"

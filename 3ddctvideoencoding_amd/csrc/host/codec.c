@@ -655,12 +655,19 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
     return status;
 }
 
-/* ---- packed RGB24 ---------------------------------------------------------------------------- */
+/* ---- packed RGB24 and frames of any size ------------------------------------------------------ */
 /* The upstream colour workflow (RGBUtils split -> encode each plane -> decode each -> RGBUtils mix) with
  * the split and the mix fused into the device transform: one packed RGB24 file <-> three streams named
  * as RGBUtils names its planes, <pattern>.red / .green / .blue, each the very .bin of encode_ex for that
- * plane.  A plain loop per batch: dct3d_encode_stacks_rgb, then the host entropy coder per stack into the
- * three streams (dct3d_decode_stacks_rgb after three pulls per stack on the way back). */
+ * plane.  And a width or height that is no multiple of 8, grey (channels = 1: one stream, outName / inName)
+ * or packed RGB24: the device pads by repeating each frame's last column and last row up to wp x hp (the
+ * next multiples of 8) inside its kernels and crops on the way back; the entropy coder works on wp x hp, so
+ * the streams are, byte for byte, what the same command writes for the edge-padded video at wp x hp.
+ * Both go through encode_any / decode_any.  Default: the fused stream calls (dct3d_encode_eg_frames /
+ * dct3d_decode_eg_frames) -- each channel's Exp-Golomb stream is built and parsed on the device, only the
+ * frames and the streams cross PCIe, as in encode_ex / decode_ex.  DCT3D_CODEC_HOST_EG=1: the quantised ints
+ * over PCIe (dct3d_encode_frames / dct3d_decode_frames) and the host entropy coder per stack; the same
+ * files. */
 static const char *const kRgbSuffix[3] = {".red", ".green", ".blue"};
 
 static FILE *open_plane(const char *pattern, int ch, const char *mode) {
@@ -677,157 +684,25 @@ static FILE *open_plane(const char *pattern, int ch, const char *mode) {
 int encode_rgb_ex(const char *inName, const char *outPattern, int width, int height, int frames, int platformIndex,
                   int depth, int batch) {
     if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
-    if (width % 8 || height % 8)
-        return encode_any(inName, outPattern, width, height, frames, platformIndex, depth, batch, 3);
-    if (batch <= 0) batch = default_batch();
-    FILE *in = fopen(inName, "rb");
-    if (!in) {
-        printf("Cannot open input file %s\n", inName);
-        return 1;
-    }
-    FILE *out[3] = {NULL, NULL, NULL};
-    dct3d_entropy_enc *ent[3] = {NULL, NULL, NULL};
-    dct3d_ctx *ctx = NULL;
-    uint8_t *rgb = NULL;
-    int32_t *q = NULL;
-    int status = 0;
-    for (int ch = 0; ch < 3 && !status; ch++)
-        if (!(out[ch] = open_plane(outPattern, ch, "wb"))) status = 1;
-    if (!status) {
-        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
-        if (rc) {
-            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
-            status = 1;
-        }
-    }
-    const size_t stack_px = (size_t)width * height * depth;  /* pixels of a stack = values of a plane's stack */
-    const int n_stacks = (frames + depth - 1) / depth;
-    if (!status) {
-        rgb = (uint8_t *)malloc(3 * stack_px * batch);
-        q = (int32_t *)malloc(3 * stack_px * batch * sizeof(int32_t));
-        for (int ch = 0; ch < 3; ch++) ent[ch] = dct3d_entropy_enc_create(width, height, depth, out[ch]);
-        if (!rgb || !q || !ent[0] || !ent[1] || !ent[2]) {
-            printf("Out of memory\n");
-            status = 1;
-        }
-    }
-    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
-        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
-        size_t got = 0, r;
-        const size_t want = 3 * stack_px * nb;
-        while (got < want && (r = fread(rgb + got, 1, want - got, in)) > 0) got += r;
-        if (got < want) memset(rgb + got, 0, want - got);  /* a short last stack is zero-filled, as encode_ex */
-        const int rc = dct3d_encode_stacks_rgb(ctx, rgb, width, height, nb, q);
-        if (rc) {
-            printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
-            status = 1;
-            break;
-        }
-        for (int s = 0; s < nb && !status; s++)
-            for (int ch = 0; ch < 3; ch++)  /* block (s, ch) of the [stack][channel] layout */
-                if (dct3d_entropy_enc_push(ent[ch], q + stack_px * (3 * (size_t)s + ch), s0 + s == n_stacks - 1)) {
-                    printf("Error in the entropy coder\n");
-                    status = 1;
-                    break;
-                }
-        for (int s = 0; !status && s < nb; s++) printf("Frames processed: %d\n", (s0 + s + 1) * depth);
-    }
-    for (int ch = 0; ch < 3; ch++) {
-        if (ent[ch]) dct3d_entropy_enc_destroy(ent[ch]);  /* the last deflate output and its write */
-        if (out[ch] && (fflush(out[ch]) || fclose(out[ch]))) status = 1;
-    }
-    free(rgb);
-    free(q);
-    if (ctx) dct3d_ctx_destroy(ctx);
-    fclose(in);
-    if (!status) printf("Encoding process completed\n");
-    return status;
+    return encode_any(inName, outPattern, width, height, frames, platformIndex, depth, batch, 3);
 }
 
 int decode_rgb_ex(const char *inPattern, const char *outName, int width, int height, int frames, int platformIndex,
                   int depth, int batch) {
     if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
-    if (width % 8 || height % 8)
-        return decode_any(inPattern, outName, width, height, frames, platformIndex, depth, batch, 3);
-    if (batch <= 0) batch = default_batch();
-    FILE *in[3] = {NULL, NULL, NULL};
-    dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
-    FILE *out = NULL;
-    dct3d_ctx *ctx = NULL;
-    uint8_t *rgb = NULL;
-    int32_t *q = NULL;
-    int status = 0;
-    for (int ch = 0; ch < 3 && !status; ch++)
-        if (!(in[ch] = open_plane(inPattern, ch, "rb"))) status = 1;
-    if (!status && !(out = fopen(outName, "wb"))) {
-        printf("Cannot open output file %s\n", outName);
-        status = 1;
-    }
-    if (!status) {
-        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
-        if (rc) {
-            printf("Error creating the device context: %s\n", dct3d_strerror(rc));
-            status = 1;
-        }
-    }
-    const size_t stack_px = (size_t)width * height * depth;
-    const int n_stacks = (frames + depth - 1) / depth;
-    if (!status) {
-        rgb = (uint8_t *)malloc(3 * stack_px * batch);
-        q = (int32_t *)malloc(3 * stack_px * batch * sizeof(int32_t));
-        for (int ch = 0; ch < 3; ch++) ent[ch] = dct3d_entropy_dec_create(width, height, depth, in[ch], NULL, 0);
-        if (!rgb || !q || !ent[0] || !ent[1] || !ent[2]) {
-            printf("Out of memory\n");
-            status = 1;
-        }
-    }
-    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
-        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
-        for (int s = 0; s < nb && !status; s++)
-            for (int ch = 0; ch < 3; ch++)
-                if (dct3d_entropy_dec_pull(ent[ch], q + stack_px * (3 * (size_t)s + ch))) {
-                    printf("Truncated or corrupt input stream\n");
-                    status = 1;
-                    break;
-                }
-        if (status) break;
-        const int rc = dct3d_decode_stacks_rgb(ctx, q, width, height, nb, rgb);
-        if (rc) {
-            printf("Error running the inverse 3D DCT: %s\n", dct3d_strerror(rc));
-            status = 1;
-            break;
-        }
-        if (fwrite(rgb, 1, 3 * stack_px * nb, out) != 3 * stack_px * nb) {
-            printf("Error writing the output file\n");
-            status = 1;
-            break;
-        }
-        printf("Frames processed: %d\n", (s0 + nb) * depth);
-    }
-    for (int ch = 0; ch < 3; ch++) {
-        if (ent[ch]) dct3d_entropy_dec_destroy(ent[ch]);
-        if (in[ch]) fclose(in[ch]);
-    }
-    free(rgb);
-    free(q);
-    if (ctx) dct3d_ctx_destroy(ctx);
-    if (out && (fflush(out) || fclose(out))) status = 1;
-    if (!status) printf("Decoding process completed\n");
-    return status;
+    return decode_any(inPattern, outName, width, height, frames, platformIndex, depth, batch, 3);
 }
 
-/* ---- frames of any size ---------------------------------------------------------------------- */
-/* A width or height that is no multiple of 8, grey (channels = 1: one stream, outName / inName) or packed
- * RGB24 (channels = 3: <pattern>.red / .green / .blue).  The device pads by repeating each frame's last
- * column and last row up to wp x hp (the next multiples of 8) inside its kernels (dct3d_encode_frames) and
- * crops on the way back (dct3d_decode_frames); the entropy coder works on wp x hp.  So the streams are, byte
- * for byte, what the same command writes for the edge-padded video at wp x hp.  A plain loop per batch, as the
- * RGB commands: the quantised ints over PCIe, the host entropy coder per stack. */
 static FILE *open_stream(const char *name, int channels, int ch, const char *mode) {
     if (channels == 3) return open_plane(name, ch, mode);
     FILE *f = fopen(name, mode);
     if (!f) printf("Cannot open %s file %s\n", mode[0] == 'r' ? "input" : "output", name);
     return f;
+}
+
+static int host_eg_on(void) {
+    const char *he = getenv("DCT3D_CODEC_HOST_EG");
+    return he && he[0] == '1';
 }
 
 static int encode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
@@ -839,16 +714,22 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         return 1;
     }
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    const int host_eg = host_eg_on();
     FILE *out[3] = {NULL, NULL, NULL};
     dct3d_entropy_enc *ent[3] = {NULL, NULL, NULL};
     dct3d_ctx *ctx = NULL;
     uint8_t *fr = NULL;
     int32_t *q = NULL;
+    unsigned char *eg = NULL;
+    size_t eg_cap = 0;
     int status = 0;
+    const double t_start = now_s();
+    double t_ctx = 0, t_read = 0, t_dev = 0, t_fetch = 0, t_ent = 0;
     for (int ch = 0; ch < channels && !status; ch++)
         if (!(out[ch] = open_stream(outName, channels, ch, "wb"))) status = 1;
     if (!status) {
-        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        int rc;
+        STAGE(t_ctx, rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx));
         if (rc) {
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
@@ -859,8 +740,10 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     const int n_stacks = (frames + depth - 1) / depth;
     if (!status) {
         fr = (uint8_t *)malloc(stack_bytes * batch);
-        q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
-        int ok = fr && q;
+        if (host_eg) q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
+        eg_cap = stack_px * batch / 2 + 64;
+        if (!host_eg) eg = (unsigned char *)malloc(eg_cap);
+        int ok = fr && (host_eg ? q != NULL : eg != NULL);
         for (int ch = 0; ch < channels; ch++)
             if (!(ent[ch] = dct3d_entropy_enc_create(wp, hp, depth, out[ch]))) ok = 0;
         if (!ok) {
@@ -872,32 +755,77 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
         size_t got = 0, r;
         const size_t want = stack_bytes * nb;
-        while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
+        STAGE(t_read, while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r);
         if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as encode_ex */
-        const int rc = dct3d_encode_frames(ctx, fr, width, height, channels, nb, q);
-        if (rc) {
-            printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
-            status = 1;
-            break;
-        }
-        for (int s = 0; s < nb && !status; s++)
-            for (int ch = 0; ch < channels; ch++) /* block (s, ch) of the [stack][channel] layout */
-                if (dct3d_entropy_enc_push(ent[ch], q + stack_px * ((size_t)channels * s + ch),
-                                           s0 + s == n_stacks - 1)) {
+        const int last = s0 + nb == n_stacks;
+        int rc;
+        if (host_eg) { /* quantised ints over PCIe, Exp-Golomb on the host */
+            STAGE(t_dev, rc = dct3d_encode_frames(ctx, fr, width, height, channels, nb, q));
+            if (rc) {
+                printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
+                status = 1;
+                break;
+            }
+            const double t_e0 = now_s();
+            for (int s = 0; s < nb && !status; s++)
+                for (int ch = 0; ch < channels; ch++) /* block (s, ch) of the [stack][channel] layout */
+                    if (dct3d_entropy_enc_push(ent[ch], q + stack_px * ((size_t)channels * s + ch),
+                                               s0 + s == n_stacks - 1)) {
+                        printf("Error in the entropy coder\n");
+                        status = 1;
+                        break;
+                    }
+            t_ent += now_s() - t_e0;
+        } else { /* each channel's stream built on the device, continuing its file's partial byte */
+            uint8_t cb[3] = {0, 0, 0};
+            int cbits[3] = {0, 0, 0};
+            uint64_t tb[3] = {0, 0, 0};
+            for (int ch = 0; ch < channels; ch++) dct3d_entropy_enc_carry(ent[ch], &cb[ch], &cbits[ch]);
+            STAGE(t_dev, rc = dct3d_encode_eg_frames(ctx, fr, width, height, channels, nb, cb, cbits, tb));
+            for (int ch = 0; ch < channels && !rc; ch++) {
+                const size_t nbytes = (size_t)((tb[ch] + 7) / 8);
+                if (nbytes > eg_cap) {
+                    free(eg);
+                    eg_cap = nbytes + nbytes / 4;
+                    eg = (unsigned char *)malloc(eg_cap);
+                    if (!eg) {
+                        rc = DCT3D_ENOMEM;
+                        break;
+                    }
+                }
+                STAGE(t_fetch, rc = dct3d_eg_fetch_channel(ctx, ch, eg, nbytes));
+                if (rc) break;
+                int perr;
+                STAGE(t_ent, perr = dct3d_entropy_enc_push_stream(ent[ch], eg, tb[ch], last));
+                if (perr) {
                     printf("Error in the entropy coder\n");
                     status = 1;
                     break;
                 }
+            }
+            if (rc) {
+                printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
+                status = 1;
+                break;
+            }
+        }
         for (int s = 0; !status && s < nb; s++) printf("Frames processed: %d\n", (s0 + s + 1) * depth);
     }
     for (int ch = 0; ch < channels; ch++) {
-        if (ent[ch]) dct3d_entropy_enc_destroy(ent[ch]); /* the last deflate output and its write */
+        if (ent[ch]) STAGE(t_ent, dct3d_entropy_enc_destroy(ent[ch])); /* the last deflate output and its write */
         if (out[ch] && (fflush(out[ch]) || fclose(out[ch]))) status = 1;
     }
     free(fr);
     free(q);
+    free(eg);
     if (ctx) dct3d_ctx_destroy(ctx);
     fclose(in);
+    if (timing_on())
+        fprintf(stderr,
+                "{\"stage_s\": {\"ctx_create\": %.6f, \"read\": %.6f, \"device\": %.6f, \"eg_fetch\": %.6f, "
+                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"channels\": %d}\n",
+                t_ctx, t_read, t_dev, t_fetch, host_eg ? "eg_deflate_write" : "deflate_write", t_ent, now_s() - t_start,
+                host_eg, channels);
     if (!status) printf("Encoding process completed\n");
     return status;
 }
@@ -906,6 +834,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
                       int depth, int batch, int channels) {
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    const int host_eg = host_eg_on();
     FILE *in[3] = {NULL, NULL, NULL};
     dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
     FILE *out = NULL;
@@ -913,6 +842,8 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     uint8_t *fr = NULL;
     int32_t *q = NULL;
     int status = 0;
+    const double t_start = now_s();
+    double t_ctx = 0, t_inf = 0, t_dev = 0, t_write = 0;
     for (int ch = 0; ch < channels && !status; ch++)
         if (!(in[ch] = open_stream(inName, channels, ch, "rb"))) status = 1;
     if (!status && !(out = fopen(outName, "wb"))) {
@@ -920,7 +851,8 @@ static int decode_any(const char *inName, const char *outName, int width, int he
         status = 1;
     }
     if (!status) {
-        const int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
+        int rc;
+        STAGE(t_ctx, rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx));
         if (rc) {
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
@@ -929,10 +861,11 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     const size_t stack_bytes = (size_t)channels * width * height * depth;
     const size_t stack_px = (size_t)wp * hp * depth;
     const int n_stacks = (frames + depth - 1) / depth;
+    double bits_per_value = 4.0; /* window estimate for the first batch; then the measured rate */
     if (!status) {
         fr = (uint8_t *)malloc(stack_bytes * batch);
-        q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
-        int ok = fr && q;
+        if (host_eg) q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
+        int ok = fr && (!host_eg || q);
         for (int ch = 0; ch < channels; ch++)
             if (!(ent[ch] = dct3d_entropy_dec_create(wp, hp, depth, in[ch], NULL, 0))) ok = 0;
         if (!ok) {
@@ -942,21 +875,70 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     }
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
-        for (int s = 0; s < nb && !status; s++)
-            for (int ch = 0; ch < channels; ch++)
-                if (dct3d_entropy_dec_pull(ent[ch], q + stack_px * ((size_t)channels * s + ch))) {
-                    printf("Truncated or corrupt input stream\n");
-                    status = 1;
+        int rc = 0;
+        if (host_eg) {
+            const double t_i0 = now_s();
+            for (int s = 0; s < nb && !status; s++)
+                for (int ch = 0; ch < channels; ch++)
+                    if (dct3d_entropy_dec_pull(ent[ch], q + stack_px * ((size_t)channels * s + ch))) {
+                        printf("Truncated or corrupt input stream\n");
+                        status = 1;
+                        break;
+                    }
+            t_inf += now_s() - t_i0;
+            if (status) break;
+            STAGE(t_dev, rc = dct3d_decode_frames(ctx, q, width, height, channels, nb, fr));
+        } else { /* the device parses each channel's inflated stream; the ENODATA-then-refill loop of decode_ex */
+            const double values = (double)stack_px * nb;
+            size_t need = (size_t)(values * bits_per_value / 8 * 1.25) + 65536;
+            for (;;) {
+                const unsigned char *p[3] = {NULL, NULL, NULL};
+                uint64_t len[3] = {0, 0, 0}, eb[3] = {0, 0, 0};
+                int bit[3] = {0, 0, 0};
+                int werr = 0;
+                for (int ch = 0; ch < channels && !werr; ch++) {
+                    size_t l = 0;
+                    STAGE(t_inf, werr = dct3d_entropy_dec_window(ent[ch], need, &p[ch], &l, &bit[ch]));
+                    len[ch] = l;
+                }
+                if (werr) {
+                    rc = DCT3D_EINVAL;
                     break;
                 }
-        if (status) break;
-        const int rc = dct3d_decode_frames(ctx, q, width, height, channels, nb, fr);
+                STAGE(t_dev, rc = dct3d_decode_eg_frames(ctx, p, len, bit, width, height, channels, nb, fr, eb));
+                if (rc == DCT3D_ENODATA) { /* some channel needs more of its stream than estimated? */
+                    int more = 0;
+                    for (int ch = 0; ch < channels; ch++)
+                        if (!dct3d_entropy_dec_eof(ent[ch]) && len[ch] >= need) more = 1;
+                    if (more) {
+                        need *= 2;
+                        continue;
+                    }
+                }
+                if (!rc) {
+                    bits_per_value = 0.0;
+                    for (int ch = 0; ch < channels; ch++) {
+                        dct3d_entropy_dec_consume(ent[ch], eb[ch]);
+                        const double b = (double)(eb[ch] - (uint64_t)bit[ch]) / values;
+                        if (b > bits_per_value) bits_per_value = b;
+                    }
+                }
+                break;
+            }
+            if (rc == DCT3D_ENODATA || rc == DCT3D_EINVAL) {
+                printf("Truncated or corrupt input stream\n");
+                status = 1;
+                break;
+            }
+        }
         if (rc) {
             printf("Error running the inverse 3D DCT: %s\n", dct3d_strerror(rc));
             status = 1;
             break;
         }
-        if (fwrite(fr, 1, stack_bytes * nb, out) != stack_bytes * nb) {
+        size_t wrote;
+        STAGE(t_write, wrote = fwrite(fr, 1, stack_bytes * nb, out));
+        if (wrote != stack_bytes * nb) {
             printf("Error writing the output file\n");
             status = 1;
             break;
@@ -970,7 +952,13 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     free(fr);
     free(q);
     if (ctx) dct3d_ctx_destroy(ctx);
-    if (out && (fflush(out) || fclose(out))) status = 1;
+    STAGE(t_write, if (out && (fflush(out) || fclose(out))) status = 1);
+    if (timing_on())
+        fprintf(stderr,
+                "{\"stage_s\": {\"ctx_create\": %.6f, \"%s\": %.6f, \"device\": %.6f, \"write\": %.6f}, "
+                "\"total_s\": %.6f, \"host_eg\": %d, \"channels\": %d}\n",
+                t_ctx, host_eg ? "read_inflate_eg" : "read_inflate", t_inf, t_dev, t_write, now_s() - t_start, host_eg,
+                channels);
     if (!status) printf("Decoding process completed\n");
     return status;
 }

@@ -21,11 +21,12 @@
  *     clEnqueueWrite/ReadBuffer, encoder.c:209,254); *_dev entry points take device pointers and
  *     are asynchronous on the context stream (use dct3d_synchronize).  The context's own stream is a
  *     blocking stream (ordered with the legacy default stream); dct3d_ctx_set_stream selects another;
- *   - the *_stacks*, *_eg* and dct_opt entry points need a frame width that is a multiple of the
- *     block width and a height that is a multiple of the block height (1080 = 135 * 8); the
- *     reference silently overruns otherwise, these calls return DCT3D_EINVAL.  Frames of any other
- *     size (1366 x 768, 1680 x 1050, ...) go through dct3d_encode_frames* / dct3d_decode_frames*,
- *     which pad by edge replication and crop inside the transform kernels.
+ *   - the *_stacks*, dct3d_encode_eg*, dct3d_decode_eg* and dct_opt entry points need a frame width that
+ *     is a multiple of the block width and a height that is a multiple of the block height (1080 =
+ *     135 * 8); the reference silently overruns otherwise, these calls return DCT3D_EINVAL.  Frames of
+ *     any other size (1366 x 768, 1680 x 1050, ...) go through dct3d_encode_frames* / dct3d_decode_frames*
+ *     (int32 cubes) or dct3d_encode_eg_frames* / dct3d_decode_eg_frames* (Exp-Golomb streams), which pad
+ *     by edge replication and crop inside the transform kernels.
  *
  * Layouts:
  *   raster  : u8 frames, frame-major, row-major (the raw grayscale file format, encoder.c:21-27);
@@ -132,12 +133,15 @@ int dct3d_ctx_info(const dct3d_ctx *ctx, int *device, int *block_d, void **hip_s
                                          exact replay */
 #define DCT3D_OPT_ENC_NO_RECHECK 3    /* 1: the 8x8x8 encode skips its fp64 second certificate, so every
                                          coefficient the fp32 certificate leaves open takes the Java fold */
-#define DCT3D_OPT_EG_TWO_STEP 5       /* 1: dct3d_encode_eg / dct3d_decode_eg through int32 cubes */
+#define DCT3D_OPT_EG_TWO_STEP 5       /* 1: dct3d_encode_eg / dct3d_decode_eg through int32 cubes; also
+                                         dct3d_encode_eg_frames, dct3d_decode_eg_frames[_dev] */
 #define DCT3D_OPT_EG_NO_RESOLVE 6     /* 1: Exp-Golomb decode sync by plain confirming passes only */
 #define DCT3D_OPT_EG_FORCE_RETRY 8    /* test: the Exp-Golomb decode's speculative front reports an unresolved
                                          pass 0, so the call takes its skip-and-rerun path (same results) */
 #define DCT3D_OPT_EG_DEC_GROUPS 9     /* stream -> raster decode: groups of 2,048 values per wave, the next
-                                         group's loads in flight during the current one (1, 2, 4, 8; 0: 8) */
+                                         group's loads in flight during the current one (1, 2, 4, 8; 0: 8).
+                                         Does not act on dct3d_decode_eg_frames*'s own kernels (grey frames
+                                         of any size: always 8; packed RGB24: always 1) */
 #define DCT3D_OPT_EG_FUSED_FRONT 10   /* 1: the Exp-Golomb decode's speculative front as ONE launch (the
                                          resolving sync pass, the chunk scan and the mark pass fused, a
                                          decoupled look-back for the chunks' value indices) instead of three
@@ -250,7 +254,8 @@ int dct3d_inverse_f32_dev(dct3d_ctx *ctx, const float *d_coeffs, size_t n_cubes,
  * Values must satisfy |v| < 2^30 (quantised 8-bit content stays below 2^13), else DCT3D_EINVAL.
  * DCT3D_ENOSPC when out_cap is too small (*total_bits is still set; d_out is untouched).
  * Returns once *total_bits is known (the last kernel, eg_stitch_kernel, hands it to the host as it
- * starts); the last words of d_out complete on the context stream (dct3d_synchronize, or stream order). */
+ * starts); the last words of d_out complete on the context stream (dct3d_synchronize, or stream order).
+ * d_q and d_out must stay valid, and d_q unchanged, until the context stream reaches that point. */
 int dct3d_eg_encode_dev(dct3d_ctx *ctx, const int32_t *d_q, uint64_t n_cubes, uint8_t carry_byte, int carry_bits,
                         uint8_t *d_out, uint64_t out_cap, uint64_t *total_bits);
 
@@ -267,7 +272,8 @@ int dct3d_encode_eg(dct3d_ctx *ctx, const uint8_t *raster, int width, int height
  * carry, d_out and *total_bits are those of dct3d_eg_encode_dev (the bytes are identical to
  * dct3d_encode_stacks_dev followed by dct3d_eg_encode_dev).  DCT3D_ENOSPC when out_cap is too small
  * (*total_bits is still set; d_out is untouched).  Returns as dct3d_eg_encode_dev: once *total_bits is
- * known, the last words completing on the context stream. */
+ * known, the last words completing on the context stream; d_raster and d_out must stay valid, and d_raster
+ * unchanged, until the context stream reaches that point. */
 int dct3d_encode_eg_dev(dct3d_ctx *ctx, const uint8_t *d_raster, int width, int height, int n_stacks,
                         uint8_t carry_byte, int carry_bits, uint8_t *d_out, uint64_t out_cap, uint64_t *total_bits);
 
@@ -294,7 +300,9 @@ int dct3d_eg_decode_dev(dct3d_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
  * Stream arguments, *end_bit and errors as dct3d_eg_decode_dev; the raster as dct3d_decode_stacks_dev:
  * the call returns once *end_bit and the verdict are known (the decode kernel hands them to the host as
  * it starts), and the raster completes asynchronously on the context stream (use dct3d_synchronize, or
- * read it in stream order). */
+ * read it in stream order).  d_bytes and d_raster must stay valid, and d_bytes unchanged, until the context
+ * stream reaches that point: the decode kernel, and its rare exact replay, still read the stream after the
+ * call has returned. */
 int dct3d_decode_eg_dev(dct3d_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes, uint64_t start_bit, int width,
                         int height, int n_stacks, uint8_t *d_raster, uint64_t *end_bit);
 
@@ -303,6 +311,59 @@ int dct3d_decode_eg_dev(dct3d_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
  * stream and the u8 frames cross PCIe.  bytes[0..nbytes) holds the stream from bit start_bit (0..7). */
 int dct3d_decode_eg(dct3d_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int start_bit, int width, int height,
                     int n_stacks, uint8_t *raster, uint64_t *end_bit);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused stream encode and decode for frames of any size, grey or packed RGB24 (additive to ABI 9; detect by
+ * symbol): raster -> Exp-Golomb streams and back with no int32 intermediate, as dct3d_encode_eg* /
+ * dct3d_decode_eg* do for grey frames at multiples of 8.  width, height >= 1, channels = 1 or 3, frames
+ * dense, as for dct3d_encode_frames.  Arrays marked [] have `channels` entries.
+ * ONE STREAM PER CHANNEL (the codec's file format: .red, .green, .blue, each the grey format of its plane).
+ * With q = dct3d_encode_frames(frames) viewed as [n_stacks][channels][C][cube_size], C the cubes of the
+ * padded raster per stack and channel:
+ *   encode  stream ch is exactly what dct3d_eg_encode_dev writes for the n_stacks * C cubes q[:, ch] in stack
+ *           order, continuing carry_byte[ch] / carry_bits[ch]; word padding, 4-byte alignment of d_out[ch]
+ *           and total_bits[ch] as there.  Cube g of stream ch is RGB cube g.
+ *   decode  the inverse: d_frames receives what dct3d_decode_frames gives for the q whose channel blocks
+ *           the streams hold -- the cropped height x width frames and nothing else.  end_bit[ch] as
+ *           dct3d_decode_eg_dev's.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_encode_frames, a NULL array, a misaligned d_out[ch] /
+ * d_bytes[ch], carry_bits[ch] outside 0..7 (start_bit[ch] outside 0..7 for the host decode).  DCT3D_ENOSPC:
+ * some out_cap[ch] is too small; every total_bits[ch] is still set and no byte at or past any out_cap[ch] is
+ * written (channels that fit may have been written).  DCT3D_ENODATA / DCT3D_EINVAL: a stream is short /
+ * corrupt; end_bit[ch] is set for every stream whose own verdict is good (the others keep start_bit[ch]), the
+ * first bad stream's code is returned, and the frames are then unspecified.
+ * With channels == 1 and width, height multiples of 8 the calls ARE dct3d_encode_eg[_dev] /
+ * dct3d_decode_eg[_dev] (handed over before anything else: the same code, the same early return).
+ * Returns (otherwise):
+ *   dct3d_encode_eg_frames_dev  one launch chain per channel, back to back on the context stream; the call
+ *       waits for each chain's total before it queues the next and returns once the last total_bits[ch] is
+ *       known, as dct3d_encode_eg_dev: the last channel's last words complete on the context stream.
+ *   dct3d_decode_eg_frames_dev  channels == 1: as dct3d_decode_eg_dev, once the verdict is known, the frames
+ *       completing on the context stream.  channels == 3: only after all its stream work is queued and
+ *       the three verdicts are read back (a copy behind the decode kernel: the frames are complete then).
+ *   In every case d_frames, d_out[ch] / d_bytes[ch] must stay valid, and the inputs unchanged, until the
+ *   context stream reaches that point (dct3d_synchronize, or stream order).
+ *   The host calls are synchronous on return as dct3d_encode_eg (fetch with dct3d_eg_fetch_channel) /
+ *   dct3d_decode_eg: one copy of the unpadded frames in, per-channel device streams, the decode in chunks of
+ *   stacks.  dct3d_eg_fetch stays as is and equals channel 0.
+ * Statistics count the padded work of all channels (n_units); n_flagged counts the exact replays of these
+ * calls' own kernels, encode included (dct3d_encode_eg_dev's kernel reports none).  DCT3D_OPT_DEC_MARGIN,
+ * DCT3D_OPT_EG_NO_RESOLVE and DCT3D_OPT_EG_FORCE_RETRY act as on the grey calls, on every channel.
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_encode_eg_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                               int n_stacks, const uint8_t carry_byte[], const int carry_bits[],
+                               uint8_t *const d_out[], const uint64_t out_cap[], uint64_t total_bits[]);
+int dct3d_encode_eg_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                           int n_stacks, const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]);
+/* Copies the first `nbytes` bytes of channel `channel`'s stream of the last dct3d_encode_eg_frames (or, channel
+ * 0, dct3d_encode_eg) to host memory. */
+int dct3d_eg_fetch_channel(dct3d_ctx *ctx, int channel, uint8_t *out, uint64_t nbytes);
+int dct3d_decode_eg_frames_dev(dct3d_ctx *ctx, const uint8_t *const d_bytes[], const uint64_t nbytes[],
+                               const uint64_t start_bit[], int width, int height, int channels, int n_stacks,
+                               uint8_t *d_frames, uint64_t end_bit[]);
+int dct3d_decode_eg_frames(dct3d_ctx *ctx, const uint8_t *const bytes[], const uint64_t nbytes[],
+                           const int start_bit[], int width, int height, int channels, int n_stacks,
+                           uint8_t *frames, uint64_t end_bit[]);
 
 #ifdef __cplusplus
 }
