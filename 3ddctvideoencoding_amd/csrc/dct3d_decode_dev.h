@@ -44,6 +44,10 @@ struct DecGeom {
     // slot of row y in face z (D=4 swizzles rows by z: bank spread of the 8-lane-per-cube reads)
     static __device__ __forceinline__ int tslot(int z, int y) { return (D == 8) ? y : (y ^ z); }
 };
+// (host) the grid of the decode kernels over n cubes (the stream decode: groups_per_wave groups of CPW cubes a wave)
+inline uint32_t dec_grid(int D, uint32_t n, int groups_per_wave = 1) {
+    return grid_blocks(n, (D == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * groups_per_wave);
+}
 
 __device__ __forceinline__ void swap16(double& a, double& b) {
     const uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);

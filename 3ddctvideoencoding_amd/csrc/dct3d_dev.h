@@ -17,6 +17,8 @@ constexpr int kWave = 64;
 constexpr int kCubesPerWave = 8;
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
+// (host) the grid of a kernel whose waves take cpw cubes each: blocks of kWavesPerBlock waves over n cubes
+inline uint32_t grid_blocks(uint32_t n, uint32_t cpw) { return (n + cpw * kWavesPerBlock - 1) / (cpw * kWavesPerBlock); }
 constexpr int kSlot = 144;                 // transpose slot: 8 rows x 16 B + 16 B pad (bank spread)
 constexpr int kWaveLds = kSlot * 64;       // 9216 B per wave
 constexpr int kFace = 272;                 // staging face: 256 B + 16 B pad

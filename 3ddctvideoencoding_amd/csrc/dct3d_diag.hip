@@ -197,15 +197,6 @@ static int launch_ceiling(const uint8_t* in, uint8_t* out, long long n_px, int m
 
 namespace {
 
-FastDiv fast_div(uint32_t d) {  // as dct3d_runtime.cpp: s = 31 + ceil(log2 d), m = ceil(2^s / d)
-    uint32_t l = 0;
-    while ((1ull << l) < d) l++;
-    FastDiv f;
-    f.s = 31 + l;
-    f.m = (uint32_t)(((1ull << f.s) + d - 1) / d);
-    return f;
-}
-
 struct CtxView {
     int device = 0, bd = 8;
     hipStream_t stream = nullptr;
@@ -216,12 +207,8 @@ int view(dct3d_ctx* c, CtxView& v) {
     v.stream = (hipStream_t)st;
     return hipSetDevice(v.device) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
 }
-int geometry(int w, int h, int n_stacks, uint64_t* n_cubes) {
-    if (w <= 0 || h <= 0 || n_stacks < 0 || w % 8 || h % 8) return DCT3D_EINVAL;
-    const uint64_t n = (uint64_t)(w / 8) * (uint64_t)(h / 8) * (uint64_t)n_stacks;
-    if (n >= (1ull << 31) / 8) return DCT3D_EINVAL;
-    *n_cubes = n;
-    return DCT3D_OK;
+int geometry(int w, int h, int n_stacks, Geom* g, uint64_t* n_cubes) {  // grey, multiples of 8
+    return make_geom(w, h, 1, n_stacks, false, g, n_cubes) ? DCT3D_OK : DCT3D_EINVAL;
 }
 
 // Per-device scratch of the diagnostics (grown, never freed: a diagnostic library), allocated before
@@ -352,8 +339,9 @@ static int encode_diag(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int 
     CtxView v;
     if ((!d_raster || !d_q) && n_stacks) return DCT3D_EINVAL;
     int rc = view(c, v);
+    Geom g;
     uint64_t n_cubes = 0;
-    if (rc || (rc = geometry(w, h, n_stacks, &n_cubes))) return rc;
+    if (rc || (rc = geometry(w, h, n_stacks, &g, &n_cubes))) return rc;
     if (mode != 1 && !((mode >= 2 && mode <= 5) && v.bd == 8)) return DCT3D_EINVAL;
     if (mode == 3 && !d_trace) return DCT3D_EINVAL;
     if (n_cubes == 0) return DCT3D_OK;
@@ -361,23 +349,15 @@ static int encode_diag(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int 
     memset(&P, 0, sizeof(P));
     P.raster = d_raster;
     P.out = d_q;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    P.div_cps = fast_div(P.cubes_per_stack);
-    P.div_nbx = fast_div(P.nbx);
-    P.width = (uint32_t)w;
-    P.plane = (uint64_t)w * h;
-    P.stack_stride = P.plane * v.bd;
+    set_address_fields(P, g, v.bd, n_cubes);
     if (strip_w) {
         P.strip_w = (uint32_t)strip_w;
         P.strip_cubes = (uint32_t)strip_w * (uint32_t)(h / 8);
         P.div_strip_w = fast_div(P.strip_w);
         P.div_strip_cubes = fast_div(P.strip_cubes);
     }
+    const dim3 grid(enc_grid(v.bd, P));
     if (v.bd == 8) {  // the twins of encode16_kernel
-        const uint32_t groups = (P.n_cubes + kE16CPW - 1) / kE16CPW;
-        const dim3 grid((groups + kWavesPerBlock - 1) / kWavesPerBlock);
         if (mode == 1 || mode == 4) {
             if (mode == 1) hipLaunchKernelGGL((encode16_kernel<true, 1>), grid, dim3(kBlock), 0, v.stream, P);
             else hipLaunchKernelGGL((encode16_kernel<true, 4>), grid, dim3(kBlock), 0, v.stream, P);
@@ -399,9 +379,7 @@ static int encode_diag(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int 
             else hipLaunchKernelGGL((encode16_kernel<true, 5>), grid, dim3(kBlock), 0, v.stream, P);
         }
     } else {
-        const uint32_t groups = (P.n_cubes + kCubesPerWave - 1) / kCubesPerWave;
-        hipLaunchKernelGGL((encode_memonly_kernel<4>), dim3((groups + kWavesPerBlock - 1) / kWavesPerBlock),
-                           dim3(kBlock), 0, v.stream, P);
+        hipLaunchKernelGGL((encode_memonly_kernel<4>), grid, dim3(kBlock), 0, v.stream, P);
     }
     return hipGetLastError() == hipSuccess ? DCT3D_OK : DCT3D_EKERNEL;
 }
@@ -410,31 +388,24 @@ int dct3d_decode_diag_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int n_
     CtxView v;
     if ((mode != 1 && mode != 2) || ((!d_q || !d_raster) && n_stacks)) return DCT3D_EINVAL;
     int rc = view(c, v);
+    Geom g;
     uint64_t n_cubes = 0;
-    if (rc || (rc = geometry(w, h, n_stacks, &n_cubes))) return rc;
+    if (rc || (rc = geometry(w, h, n_stacks, &g, &n_cubes))) return rc;
     if (n_cubes == 0) return DCT3D_OK;
     DecodeParams P;
     memset(&P, 0, sizeof(P));
     P.in = d_q;
     P.out = d_raster;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    P.div_cps = fast_div(P.cubes_per_stack);
-    P.div_nbx = fast_div(P.nbx);
-    P.width = (uint32_t)w;
-    P.plane = (uint64_t)w * h;
-    P.stack_stride = P.plane * v.bd;
-    P.blk_store = mode == 1 && P.nbx % 2 == 0 && P.stack_stride < (1ull << 32) ? 1u : 0u;  // as the product (mode 2 stores nothing)
+    set_address_fields(P, g, v.bd, n_cubes);
+    P.blk_store = mode == 1 ? blk_store(g, v.bd) : 0u;  // as the product (mode 2 stores nothing)
     P.inv_coef_t = nullptr;  // no replay: mode 1 certifies nothing, mode 2 stores (and so flags) nothing
-    const uint32_t per = (v.bd == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * kWavesPerBlock;
-    const uint32_t groups = (uint32_t)((n_cubes + per - 1) / per);
+    const dim3 grid(dec_grid(v.bd, P.n_cubes));
     if (v.bd == 8) {
-        if (mode == 1) hipLaunchKernelGGL((decode_kernel_diag<8, 1>), dim3(groups), dim3(kBlock), 0, v.stream, P);
-        else hipLaunchKernelGGL((decode_kernel_diag<8, 2>), dim3(groups), dim3(kBlock), 0, v.stream, P);
+        if (mode == 1) hipLaunchKernelGGL((decode_kernel_diag<8, 1>), grid, dim3(kBlock), 0, v.stream, P);
+        else hipLaunchKernelGGL((decode_kernel_diag<8, 2>), grid, dim3(kBlock), 0, v.stream, P);
     } else {
-        if (mode == 1) hipLaunchKernelGGL((decode_kernel_diag<4, 1>), dim3(groups), dim3(kBlock), 0, v.stream, P);
-        else hipLaunchKernelGGL((decode_kernel_diag<4, 2>), dim3(groups), dim3(kBlock), 0, v.stream, P);
+        if (mode == 1) hipLaunchKernelGGL((decode_kernel_diag<4, 1>), grid, dim3(kBlock), 0, v.stream, P);
+        else hipLaunchKernelGGL((decode_kernel_diag<4, 2>), grid, dim3(kBlock), 0, v.stream, P);
     }
     return hipGetLastError() == hipSuccess ? DCT3D_OK : DCT3D_EKERNEL;
 }

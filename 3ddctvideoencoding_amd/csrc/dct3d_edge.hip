@@ -13,30 +13,26 @@ namespace dct3d {
 
 int launch_encode_edge(int D, int px, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
+    const dim3 grid(enc_grid(D, P));
     if (D == 8) {
-        const uint32_t groups = (P.n_cubes - P.g_base + kE16CPW - 1) / kE16CPW;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (px == 1) hipLaunchKernelGGL((encode16_kernel<true, 0, 1>), dim3(blocks), dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((encode16_rgb_kernel<true, 1>), dim3(blocks), dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((encode16_kernel<true, 0, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((encode16_rgb_kernel<true, 1>), grid, dim3(kBlock), 0, st, P);
     } else {
-        const uint32_t groups = (P.n_cubes - P.g_base + kCubesPerWave - 1) / kCubesPerWave;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (px == 1) hipLaunchKernelGGL((encode_kernel<4, true, false, 1>), dim3(blocks), dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((encode_rgb_kernel<4, true, 1>), dim3(blocks), dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((encode_kernel<4, true, false, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((encode_rgb_kernel<4, true, 1>), grid, dim3(kBlock), 0, st, P);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
-    const uint32_t per = (D == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * kWavesPerBlock;
-    const uint32_t groups = (uint32_t)((P.n_cubes + per - 1) / per);
+    const dim3 grid(dec_grid(D, P.n_cubes));
     if (D == 8) {
-        if (px == 1) hipLaunchKernelGGL((decode_kernel<8, 1, 1>), dim3(groups), dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((decode_rgb_kernel<8, 1, 1>), dim3(groups), dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((decode_kernel<8, 1, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((decode_rgb_kernel<8, 1, 1>), grid, dim3(kBlock), 0, st, P);
     } else {
-        if (px == 1) hipLaunchKernelGGL((decode_kernel<4, 1, 1>), dim3(groups), dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((decode_rgb_kernel<4, 1, 1>), dim3(groups), dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((decode_kernel<4, 1, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((decode_rgb_kernel<4, 1, 1>), grid, dim3(kBlock), 0, st, P);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -11,9 +11,8 @@ namespace dct3d {
 namespace {
 template <int D, int PX, int EDGE>
 void launch_enc_egf_t(const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
-    const uint32_t groups = (P.n_cubes + kCubesPerWave - 1) / kCubesPerWave;
-    const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL((encode_eg_kernel<D, PX, EDGE>), dim3(blocks), dim3(kBlock), 0, st, P, E);
+    const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
+    hipLaunchKernelGGL((encode_eg_kernel<D, PX, EDGE>), grid, dim3(kBlock), 0, st, P, E);
 }
 template <int D>
 void launch_enc_egf_d(int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
@@ -23,17 +22,13 @@ void launch_enc_egf_d(int px, int edge, const EncodeParams& P, const EgFusedPara
 }
 template <int D, int NG>
 void launch_dec_ege_t(const DecodeParams& P, const EgDecParams& E, hipStream_t st) {
-    constexpr uint32_t cpw = DecGeom<D>::CPW;
-    const uint32_t groups = (P.n_cubes - P.cube_base + cpw - 1) / cpw;  // cube_base: a multiple of cpw
-    const uint32_t blocks = (groups + kWavesPerBlock * NG - 1) / (kWavesPerBlock * NG);
-    hipLaunchKernelGGL((decode_eg_kernel<D, NG, 1>), dim3(blocks), dim3(kBlock), 0, st, P, E);
+    const dim3 grid(dec_grid(D, P.n_cubes - P.cube_base, NG));  // cube_base: a multiple of the cubes per wave
+    hipLaunchKernelGGL((decode_eg_kernel<D, NG, 1>), grid, dim3(kBlock), 0, st, P, E);
 }
 template <int D, int EDGE>
 void launch_dec_egr_t(const DecodeParams& P, const EgDecRgbParams& E, hipStream_t st) {
-    constexpr uint32_t cpw = DecGeom<D>::CPW;
-    const uint32_t groups = (P.n_cubes - P.cube_base + cpw - 1) / cpw;
-    const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL((decode_eg_rgb_kernel<D, EDGE>), dim3(blocks), dim3(kBlock), 0, st, P, E);
+    const dim3 grid(dec_grid(D, P.n_cubes - P.cube_base));
+    hipLaunchKernelGGL((decode_eg_rgb_kernel<D, EDGE>), grid, dim3(kBlock), 0, st, P, E);
 }
 }  // namespace
 

@@ -768,6 +768,10 @@ __device__ __forceinline__ int exact_coef(const ReplayGeom& R, uint32_t g, uint3
 // values, and so the certification bounds, are identical.  32 floats per lane instead of 64, 4.5 KiB
 // of LDS per wave: more waves per CU to hide each wave's transform latency.
 constexpr int kE16CPW = 4;     // cubes per wave
+// (host) the grid of the int32 encode kernels: encode16_* at 8x8x8, encode_*<4> at 8x8x4
+inline uint32_t enc_grid(int D, const EncodeParams& P) {
+    return grid_blocks(P.n_cubes - P.g_base, D == 8 ? kE16CPW : kCubesPerWave);
+}
 constexpr int kE16TZ = 144;    // transpose: kz stride (4 y x 16 B per h, 2 h, + 16 B: bank spread)
 constexpr int kE16TC = 8 * kE16TZ;
 constexpr int kE16Lds = 4 * kE16TC;

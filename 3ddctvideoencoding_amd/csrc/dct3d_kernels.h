@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "dct3d_geom.h"
+
 namespace dct3d {
 
 constexpr int kMaxGroupsDev = 64;  // == kMaxGroups in dct3d_plan.h; one LDS slot per lane
@@ -14,13 +16,7 @@ constexpr int kGM4Dev = 48;        // == kMaxGroups4 in dct3d_plan.h (8x8x4 in-w
 // (~12 ns each, longer than the whole kernel); the host sums the words.
 constexpr int kCountSpread = 512;
 
-// n / d for n < 2^31 as one 32x32->64 multiply and a shift (Granlund-Montgomery: s = 31 + ceil(log2 d),
-// m = ceil(2^s / d) < 2^32 gives floor(n m / 2^s) = floor(n / d) for every n < 2^31); set_fast_div
-// (dct3d_runtime.cpp) fills m and s on the host
-struct FastDiv {
-    uint32_t m, s;
-};
-
+// (FastDiv and the host side of the address fields below -- n_cubes .. stack_stride, blk_store: dct3d_geom.h)
 struct EncodeParams {
     const uint8_t* raster;
     int32_t* out;

@@ -143,8 +143,7 @@ __global__ __launch_bounds__(kBlock, 4) void cube_f32_kernel(const float* __rest
 }
 
 int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n_cubes, hipStream_t st) {
-    const uint32_t per = (D == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * kWavesPerBlock;
-    const uint32_t blocks = (n_cubes + per - 1) / per;
+    const uint32_t blocks = dec_grid(D, n_cubes);
     if (!blocks) return 0;
     if (D == 8) {
         if (inverse) hipLaunchKernelGGL((cube_f32_kernel<8, true>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
@@ -167,23 +166,15 @@ int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n
 namespace {
 template <int D>
 void launch_enc_eg_t(const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
-    const uint32_t groups = (P.n_cubes + kCubesPerWave - 1) / kCubesPerWave;
-    const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL((encode_eg_kernel<D>), dim3(blocks), dim3(kBlock), 0, st, P, E);
+    hipLaunchKernelGGL((encode_eg_kernel<D>), dim3(grid_blocks(P.n_cubes, kCubesPerWave)), dim3(kBlock), 0, st, P, E);
 }
 }  // namespace
 
 int launch_encode(int D, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
-    if (D == 8) {
-        const uint32_t groups = (P.n_cubes - P.g_base + kE16CPW - 1) / kE16CPW;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL((encode16_kernel<true, 0>), dim3(blocks), dim3(kBlock), 0, st, P);
-    } else {
-        const uint32_t groups = (P.n_cubes - P.g_base + kCubesPerWave - 1) / kCubesPerWave;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL((encode_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, st, P);
-    }
+    const dim3 grid(enc_grid(D, P));
+    if (D == 8) hipLaunchKernelGGL((encode16_kernel<true, 0>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((encode_kernel<4, true>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -198,20 +189,17 @@ int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipSt
 // output stores were 26 % slower: profiles/r01/decode_variant_sweep.txt).
 int launch_decode(int D, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
-    const uint32_t per = (D == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * kWavesPerBlock;
-    const uint32_t groups = (uint32_t)((P.n_cubes + per - 1) / per);
-    if (D == 8) hipLaunchKernelGGL((decode_kernel<8, 1>), dim3(groups), dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((decode_kernel<4, 1>), dim3(groups), dim3(kBlock), 0, st, P);
+    const dim3 grid(dec_grid(D, P.n_cubes));
+    if (D == 8) hipLaunchKernelGGL((decode_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((decode_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 namespace {
 template <int D, int NG>
 void launch_dec_eg_t(const DecodeParams& P, const EgDecParams& E, hipStream_t st) {
-    constexpr uint32_t cpw = DecGeom<D>::CPW;
-    const uint32_t groups = (P.n_cubes - P.cube_base + cpw - 1) / cpw;  // cube_base: a multiple of cpw
-    const uint32_t blocks = (groups + kWavesPerBlock * NG - 1) / (kWavesPerBlock * NG);
-    hipLaunchKernelGGL((decode_eg_kernel<D, NG>), dim3(blocks), dim3(kBlock), 0, st, P, E);
+    const dim3 grid(dec_grid(D, P.n_cubes - P.cube_base, NG));  // cube_base: a multiple of the cubes per wave
+    hipLaunchKernelGGL((decode_eg_kernel<D, NG>), grid, dim3(kBlock), 0, st, P, E);
 }
 template <int D>
 void launch_dec_eg_d(const DecodeParams& P, const EgDecParams& E, int ng, hipStream_t st) {

@@ -14,25 +14,18 @@ namespace dct3d {
 // channels of its tile (encode16_rgb_kernel / encode_rgb_kernel).
 int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
-    if (D == 8) {
-        const uint32_t groups = (P.n_cubes - P.g_base + kE16CPW - 1) / kE16CPW;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL((encode16_rgb_kernel<true>), dim3(blocks), dim3(kBlock), 0, st, P);
-    } else {
-        const uint32_t groups = (P.n_cubes - P.g_base + kCubesPerWave - 1) / kCubesPerWave;
-        const uint32_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL((encode_rgb_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, st, P);
-    }
+    const dim3 grid(enc_grid(D, P));
+    if (D == 8) hipLaunchKernelGGL((encode16_rgb_kernel<true>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((encode_rgb_kernel<4, true>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // Packed RGB24: one wave per tile of RGB cubes, its three channels in turn (decode_rgb_kernel)
 int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
-    const uint32_t per = (D == 8 ? DecGeom<8>::CPW : DecGeom<4>::CPW) * kWavesPerBlock;
-    const uint32_t groups = (uint32_t)((P.n_cubes + per - 1) / per);
-    if (D == 8) hipLaunchKernelGGL((decode_rgb_kernel<8, 1>), dim3(groups), dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((decode_rgb_kernel<4, 1>), dim3(groups), dim3(kBlock), 0, st, P);
+    const dim3 grid(dec_grid(D, P.n_cubes));
+    if (D == 8) hipLaunchKernelGGL((decode_rgb_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((decode_rgb_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -136,21 +136,6 @@ static int diagonal_order(int bw, int bh, int bd, uint16_t* out) {
     return n;
 }
 
-// FastDiv of the kernel params (dct3d_kernels.h): s = 31 + ceil(log2 d), m = ceil(2^s / d)
-static FastDiv fast_div(uint32_t d) {
-    uint32_t l = 0;
-    while ((1ull << l) < d) l++;
-    FastDiv f;
-    f.s = 31 + l;
-    f.m = (uint32_t)(((1ull << f.s) + d - 1) / d);
-    return f;
-}
-template <class T>
-static void set_fast_div(T& P) {
-    P.div_cps = fast_div(P.cubes_per_stack);
-    P.div_nbx = fast_div(P.nbx);
-}
-
 extern "C" {
 
 int dct3d_abi_version(void) { return DCT3D_ABI_VERSION; }
@@ -449,6 +434,16 @@ static hipEvent_t* timing_slot(dct3d_ctx* c) {
     c->ring_pending++;
     return e;
 }
+// A call of one launch: events 0-1 bracket it, the second pair brackets nothing.
+static hipEvent_t* timer_begin(dct3d_ctx* c) {
+    hipEvent_t* ev = timing_slot(c);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    return ev;
+}
+static void timer_end(dct3d_ctx* c, hipEvent_t* ev) {
+    if (!ev) return;
+    for (int i = 1; i < 4; i++) (void)hipEventRecord(ev[i], c->stream);
+}
 
 int dct3d_reset_timers(dct3d_ctx* c) {
     if (!c) return DCT3D_EINVAL;
@@ -483,16 +478,6 @@ int dct3d_get_stats(dct3d_ctx* c, dct3d_stats* st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-static int check_geometry(const dct3d_ctx* c, int w, int h, int n_stacks, uint64_t* n_cubes) {
-    if (w <= 0 || h <= 0 || n_stacks < 0) return DCT3D_EINVAL;
-    if (w % c->bw || h % c->bh) return DCT3D_EINVAL;  // the reference overruns silently here
-    const uint64_t cps = (uint64_t)(w / c->bw) * (uint64_t)(h / c->bh);
-    const uint64_t n = cps * (uint64_t)n_stacks;
-    if (n >= (1ull << 31) / 8) return DCT3D_EINVAL;   // 32-bit cube indices in the kernels
-    *n_cubes = n;
-    return DCT3D_OK;
-}
-
 // Decode: uncertified cubes are replayed inside the wave; the replay count goes to the ctx's current
 // counter slot, and the launch zeroes the other one for the next call (see d_enc_counts).
 static void set_count_slot(dct3d_ctx* c, unsigned int*& count, unsigned int*& clear) {
@@ -518,6 +503,14 @@ static void count_slot_used(dct3d_ctx* c, uint64_t units) {
     c->slot_used = false;
     c->last_units = units;
     c->last_valid = true;
+}
+// The start of a call on the device: the last call's statistics no longer stand (inside a host entry point's
+// pipeline the call is one chunk of many: batch_begin did it).
+static void call_begin(dct3d_ctx* c) {
+    if (c->batch) return;
+    c->last_valid = false;
+    c->last_count_slot = -1;
+    c->slot_used = false;
 }
 static void batch_begin(dct3d_ctx* c) {
     c->batch = true;
@@ -549,22 +542,14 @@ static int forward_f64_raster(dct3d_ctx* c, const uint8_t* d_raster, int w, int 
     return launch_fwd64_raster(c->bd, P, c->stream) ? DCT3D_EKERNEL : DCT3D_OK;
 }
 
-// The encode and decode kernels' parameters for n_cubes cubes of a w x h raster with px bytes per pixel (1:
-// grey; 3: packed RGB24, n_cubes counting RGB cubes): plane and stack_stride in bytes, width in pixels.
-static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_raster, int32_t* d_q, int w, int h,
-                               uint64_t n_cubes, int px) {
-    const uint64_t plane = (uint64_t)px * w * h;
+// The encode and decode kernels' parameters for the cubes [0, n_cubes) of geometry g (packed RGB24: n_cubes
+// counts RGB cubes); the address fields: set_address_fields (dct3d_geom.h).
+static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_raster, int32_t* d_q, const Geom& g,
+                               uint64_t n_cubes) {
     memset(&P, 0, sizeof(P));
     P.raster = d_raster;
     P.out = d_q;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.g_base = 0;
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)w;
-    P.plane = plane;
-    P.stack_stride = plane * c->bd;
+    set_address_fields(P, g, c->bd, n_cubes);
     P.coef_dc = c->plan.coef_dc;
     const float* tabs = (const float*)c->d_tabs.p;
     P.tab_rstep = tabs;
@@ -577,228 +562,117 @@ static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_r
     P.tab64 = (const double*)c->d_tabs64.p;
     P.recheck = c->opt_enc_no_recheck ? 0u : 1u;
 }
-static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q, uint8_t* d_raster, int w, int h,
-                               uint64_t n_cubes, int px) {
-    const uint64_t plane = (uint64_t)px * w * h;
+static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q, uint8_t* d_raster, const Geom& g,
+                               uint64_t n_cubes) {
     P.in = d_q;
     P.out = d_raster;
-    P.n_cubes = (uint32_t)n_cubes;
+    set_address_fields(P, g, c->bd, n_cubes);
     P.cube_base = 0;
-    P.height = 0;  // (dct3d_decode_frames_dev sets it)
-    P.cubes_per_stack = (uint32_t)((w / 8) * (h / 8));
-    P.nbx = (uint32_t)(w / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)w;
-    P.plane = plane;
-    P.stack_stride = plane * c->bd;
     P.dec_G = c->plan.dec_G;
     P.dec_E = c->plan.dec_E;
     P.dec_l1_max = c->plan.dec_l1_max;
-    // dec_store_tile's conditions: nbx even (a 16-byte chunk -- two grey cubes, or part of a 48-byte pair of
-    // RGB cubes -- never straddles a block-row), 32-bit byte offsets within a stack
-    P.blk_store = (w / 8) % 2 == 0 && plane * c->bd < (1ull << 32) ? 1u : 0u;
+    P.blk_store = blk_store(g, c->bd);
     // test option: widen the certification margin so that most pixels are uncertified and their cubes
     // take the whole-cube replay path (tests/test_gpu_parity.py); a wider margin is never unsafe
     P.dec_E += c->opt_dec_margin;
     set_dec_replay(c, P);
 }
 
-int dct3d_encode_stacks_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, int32_t* d_q,
-                            double* d_dct) {
-    if (!c || (!d_raster && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
-    uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+// ---- int32 cubes <-> raster on the device: grey or packed RGB24 (dct3d.h, ABI 9: over the RGB cubes, each
+//      three cubes of the int32 side [stack][channel][cube]), multiples of 8 or frames of any size (Geom) ----
+// the arguments every raster call shares, and its geometry
+static int check_args(const dct3d_ctx* c, const void* a, const void* b, int w, int h, int px, int n_stacks, bool any_size,
+                      Geom* g, uint64_t* n_cubes) {
+    if (!c || ((!a || !b) && n_stacks)) return DCT3D_EINVAL;
+    return make_geom(w, h, px, n_stacks, any_size, g, n_cubes) ? DCT3D_OK : DCT3D_EINVAL;
+}
+
+// One launch; uncertified coefficients are replayed inside the wave (exact Java fold).
+static int encode_dev(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g, uint64_t n_cubes, int32_t* d_q, double* d_dct) {
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
+    call_begin(c);
     if (n_cubes == 0) return DCT3D_OK;
     const int D = c->bd;
-    // one launch: uncertified coefficients are replayed inside the wave (exact Java fold)
     EncodeParams P;
-    fill_encode_params(c, P, d_raster, d_q, w, h, n_cubes, 1);
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_encode(D, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // single launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
+    fill_encode_params(c, P, d_raster, d_q, g, n_cubes);
+    hipEvent_t* ev = timer_begin(c);
+    int lrc;
+    switch (2 * g.px + (g.edge() ? 1 : 0)) {
+        case 2: lrc = launch_encode(D, P, c->stream); break;
+        case 6: lrc = launch_encode_rgb(D, P, c->stream); break;
+        default: lrc = launch_encode_edge(D, g.px, P, c->stream);  // (the row loads clamped to the frame)
     }
-    count_slot_used(c, n_cubes * (uint64_t)c->plan.cs);
-    if (d_dct) return forward_f64_raster(c, d_raster, w, h, n_cubes, d_dct);
+    if (lrc) return DCT3D_EKERNEL;
+    timer_end(c, ev);
+    count_slot_used(c, (uint64_t)g.px * n_cubes * (uint64_t)c->plan.cs);
+    if (d_dct) return forward_f64_raster(c, d_raster, g.w, g.h, n_cubes, d_dct);
     return DCT3D_OK;
 }
 
-int dct3d_decode_stacks_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int n_stacks, uint8_t* d_raster) {
-    if (!c || (!d_raster && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
-    uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+static int decode_dev(dct3d_ctx* c, const int32_t* d_q, const Geom& g, uint64_t n_cubes, uint8_t* d_raster) {
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
+    call_begin(c);
     if (n_cubes == 0) return DCT3D_OK;
     const int D = c->bd;
     DecodeParams P;
-    fill_decode_params(c, P, d_q, d_raster, w, h, n_cubes, 1);
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_decode(D, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // one launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
+    fill_decode_params(c, P, d_q, d_raster, g, n_cubes);
+    hipEvent_t* ev = timer_begin(c);
+    int lrc;
+    switch (2 * g.px + (g.edge() ? 1 : 0)) {
+        case 2: lrc = launch_decode(D, P, c->stream); break;
+        case 6: lrc = launch_decode_rgb(D, P, c->stream); break;
+        default: lrc = launch_decode_edge(D, g.px, P, c->stream);  // (the stores cropped to the frame)
     }
-    count_slot_used(c, n_cubes * (uint64_t)c->plan.cs);
+    if (lrc) return DCT3D_EKERNEL;
+    timer_end(c, ev);
+    count_slot_used(c, (uint64_t)g.px * n_cubes * (uint64_t)c->plan.cs);
     return DCT3D_OK;
 }
 
-// ---- packed RGB24 (dct3d.h, ABI 9): the grey calls' parameters over the RGB cubes, strides in bytes ----
-// 3 x cubes must satisfy the grey calls' limit (the int32 side's cube indices)
-static int check_geometry_rgb(const dct3d_ctx* c, int w, int h, int n_stacks, uint64_t* n_cubes) {
-    int rc = check_geometry(c, w, h, n_stacks, n_cubes);
-    if (rc) return rc;
-    return 3 * *n_cubes >= (1ull << 31) / 8 ? DCT3D_EINVAL : DCT3D_OK;
+int dct3d_encode_stacks_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, int32_t* d_q,
+                            double* d_dct) {
+    Geom g;
+    uint64_t n_cubes;
+    int rc = check_args(c, d_raster, d_q, w, h, 1, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : encode_dev(c, d_raster, g, n_cubes, d_q, d_dct);
+}
+
+int dct3d_decode_stacks_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int n_stacks, uint8_t* d_raster) {
+    Geom g;
+    uint64_t n_cubes;
+    int rc = check_args(c, d_q, d_raster, w, h, 1, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : decode_dev(c, d_q, g, n_cubes, d_raster);
 }
 
 int dct3d_encode_stacks_rgb_dev(dct3d_ctx* c, const uint8_t* d_rgb, int w, int h, int n_stacks, int32_t* d_q) {
-    if (!c || (!d_rgb && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
-    if (n_cubes == 0) return DCT3D_OK;
-    const int D = c->bd;
-    EncodeParams P;  // over the RGB cubes: each is three cubes of the output
-    fill_encode_params(c, P, d_rgb, d_q, w, h, n_cubes, 3);
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_encode_rgb(D, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // single launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
-    count_slot_used(c, 3 * n_cubes * (uint64_t)c->plan.cs);
-    return DCT3D_OK;
+    int rc = check_args(c, d_rgb, d_q, w, h, 3, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : encode_dev(c, d_rgb, g, n_cubes, d_q, nullptr);
 }
 
 int dct3d_decode_stacks_rgb_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int n_stacks, uint8_t* d_rgb) {
-    if (!c || (!d_rgb && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
-    if (n_cubes == 0) return DCT3D_OK;
-    const int D = c->bd;
-    DecodeParams P;  // over the RGB cubes: each is three cubes of the input
-    fill_decode_params(c, P, d_q, d_rgb, w, h, n_cubes, 3);
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_decode_rgb(D, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // one launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
-    count_slot_used(c, 3 * n_cubes * (uint64_t)c->plan.cs);
-    return DCT3D_OK;
+    int rc = check_args(c, d_q, d_rgb, w, h, 3, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : decode_dev(c, d_q, g, n_cubes, d_rgb);
 }
 
-// ---- frames of any size (dct3d.h: dct3d_encode_frames* / dct3d_decode_frames*) ----
-// The cubes tile the padded raster (wp x hp = the next multiples of 8), which repeats each frame's last
-// column and last row and exists nowhere in memory: the kernels of dct3d_edge.hip clamp their row loads
-// (encode) and crop their stores (decode).  A geometry that is a multiple of 8 both ways is the *_stacks*
-// call's: the very same kernels.
-static int check_geometry_frames(const dct3d_ctx* c, int w, int h, int channels, int n_stacks, int* wp, int* hp,
-                                 uint64_t* n_cubes) {
-    if (channels != 1 && channels != 3) return DCT3D_EINVAL;
-    if (w <= 0 || h <= 0 || w > INT32_MAX - 7 || h > INT32_MAX - 7) return DCT3D_EINVAL;
-    *wp = (w + 7) / 8 * 8;
-    *hp = (h + 7) / 8 * 8;
-    return channels == 3 ? check_geometry_rgb(c, *wp, *hp, n_stacks, n_cubes) : check_geometry(c, *wp, *hp, n_stacks, n_cubes);
-}
-
+// frames of any size: a geometry that is a multiple of 8 both ways is the *_stacks* call's, the very same kernels
 int dct3d_encode_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
                             int32_t* d_q) {
-    if (!c || (!d_frames && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
-    int wp, hp;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
-    if (rc) return rc;
-    if (wp == w && hp == h)
-        return channels == 3 ? dct3d_encode_stacks_rgb_dev(c, d_frames, w, h, n_stacks, d_q)
-                             : dct3d_encode_stacks_dev(c, d_frames, w, h, n_stacks, d_q, nullptr);
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
-    if (n_cubes == 0) return DCT3D_OK;
-    EncodeParams P;  // the padded raster's cubes over the unpadded frames' bytes
-    fill_encode_params(c, P, d_frames, d_q, wp, hp, n_cubes, channels);
-    P.width = (uint32_t)w;
-    P.height = (uint32_t)h;
-    P.plane = (uint64_t)channels * w * h;
-    P.stack_stride = P.plane * c->bd;
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_encode_edge(c->bd, channels, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // single launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
-    count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
-    return DCT3D_OK;
+    int rc = check_args(c, d_frames, d_q, w, h, channels, n_stacks, true, &g, &n_cubes);
+    return rc ? rc : encode_dev(c, d_frames, g, n_cubes, d_q, nullptr);
 }
 
 int dct3d_decode_frames_dev(dct3d_ctx* c, const int32_t* d_q, int w, int h, int channels, int n_stacks,
                             uint8_t* d_frames) {
-    if (!c || (!d_frames && n_stacks) || (!d_q && n_stacks)) return DCT3D_EINVAL;
-    int wp, hp;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
-    if (rc) return rc;
-    if (wp == w && hp == h)
-        return channels == 3 ? dct3d_decode_stacks_rgb_dev(c, d_q, w, h, n_stacks, d_frames)
-                             : dct3d_decode_stacks_dev(c, d_q, w, h, n_stacks, d_frames);
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (!c->batch) {
-        c->last_valid = false;
-        c->last_count_slot = -1;
-    }
-    if (n_cubes == 0) return DCT3D_OK;
-    DecodeParams P;  // the padded raster's cubes, stored cropped into the unpadded frames
-    fill_decode_params(c, P, d_q, d_frames, wp, hp, n_cubes, channels);
-    P.width = (uint32_t)w;
-    P.height = (uint32_t)h;
-    P.plane = (uint64_t)channels * w * h;
-    P.stack_stride = P.plane * c->bd;
-    P.blk_store = 0;  // (the 16-byte block stores need 16-byte aligned rows)
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
-    if (launch_decode_edge(c->bd, channels, P, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {  // one launch: the second event pair brackets nothing
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
-    count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
-    return DCT3D_OK;
+    int rc = check_args(c, d_q, d_frames, w, h, channels, n_stacks, true, &g, &n_cubes);
+    return rc ? rc : decode_dev(c, d_q, g, n_cubes, d_frames);
 }
 
 // ---- host-pointer pipeline ------------------------------------------------------
@@ -911,121 +785,77 @@ static int run_pipeline(dct3d_ctx* c, int n_stacks, size_t in_per_stack, size_t 
 
 extern "C" {
 // ---- host-pointer entry points (synchronous; the reference's blocking transfers) ----------------
+// Chunks of whole stacks (contiguous on both sides) through the pipeline; the copies of the raster side move
+// the unpadded frames' bytes only.  Every chunk counts into one slot: dct3d_get_stats reports the whole call.
+static int host_stacks(dct3d_ctx* c, bool encode, const void* in, void* out, const Geom& g, int n_stacks, uint64_t n_cubes) {
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    if (n_cubes == 0) return DCT3D_OK;
+    const size_t raster_ps = (size_t)g.plane() * c->bd;                                     // bytes per stack
+    const size_t q_ps = (size_t)g.px * g.cps() * c->plan.cs * sizeof(int32_t);
+    batch_begin(c);
+    const int rc = run_pipeline(c, n_stacks, encode ? raster_ps : q_ps, encode ? q_ps : raster_ps, in, out,
+                                [&](const void* din, void* dout, int, int ns) {
+                                    const uint64_t n = g.cps() * (uint64_t)ns;
+                                    return encode ? encode_dev(c, (const uint8_t*)din, g, n, (int32_t*)dout, nullptr)
+                                                  : decode_dev(c, (const int32_t*)din, g, n, (uint8_t*)dout);
+                                });
+    batch_end(c);
+    return rc;
+}
+
 int dct3d_encode_stacks(dct3d_ctx* c, const uint8_t* raster, int w, int h, int n_stacks, int32_t* q, double* dct) {
-    if (!c || (!raster && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
+    int rc = check_args(c, raster, q, w, h, 1, n_stacks, false, &g, &n_cubes);
     if (rc) return rc;
+    if (!dct) return host_stacks(c, true, raster, q, g, n_stacks, n_cubes);
+    // with the fp64 coefficients: unpipelined, whole buffers
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     if (n_cubes == 0) return DCT3D_OK;
     const size_t in_bytes = n_cubes * c->plan.cs, out_bytes = in_bytes * sizeof(int32_t);
-    if (!dct) {  // pipelined
-        const size_t px = in_bytes / n_stacks;
-        batch_begin(c);  // every chunk counts into one slot: dct3d_get_stats reports the whole call
-        rc = run_pipeline(c, n_stacks, px, px * sizeof(int32_t), raster, q,
-                          [&](const void* din, void* dout, int, int ns) {
-                              return dct3d_encode_stacks_dev(c, (const uint8_t*)din, w, h, ns, (int32_t*)dout, nullptr);
-                          });
-        batch_end(c);
-        return rc;
-    }
     if ((rc = c->h_in.grow(in_bytes)) || (rc = c->h_out.grow(out_bytes))) return rc;
     if (hipMemcpyAsync(c->h_in.p, raster, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return DCT3D_EDEVICE;
-    if (dct && (rc = c->h_aux.grow(in_bytes * sizeof(double)))) return rc;
-    rc = dct3d_encode_stacks_dev(c, (const uint8_t*)c->h_in.p, w, h, n_stacks, (int32_t*)c->h_out.p,
-                                 dct ? (double*)c->h_aux.p : nullptr);
-    if (rc) return rc;
-    if (dct && hipMemcpyAsync(dct, c->h_aux.p, in_bytes * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    if ((rc = c->h_aux.grow(in_bytes * sizeof(double)))) return rc;
+    if ((rc = encode_dev(c, (const uint8_t*)c->h_in.p, g, n_cubes, (int32_t*)c->h_out.p, (double*)c->h_aux.p))) return rc;
+    if (hipMemcpyAsync(dct, c->h_aux.p, in_bytes * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         return DCT3D_EDEVICE;
     if (hipMemcpyAsync(q, c->h_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return DCT3D_EDEVICE;
     return hipStreamSynchronize(c->stream) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
 }
 
 int dct3d_decode_stacks(dct3d_ctx* c, const int32_t* q, int w, int h, int n_stacks, uint8_t* raster) {
-    if (!c || (!raster && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (n_cubes == 0) return DCT3D_OK;
-    const size_t px = n_cubes * c->plan.cs / n_stacks;
-    batch_begin(c);
-    rc = run_pipeline(c, n_stacks, px * sizeof(int32_t), px, q, raster, [&](const void* din, void* dout, int, int ns) {
-        return dct3d_decode_stacks_dev(c, (const int32_t*)din, w, h, ns, (uint8_t*)dout);
-    });
-    batch_end(c);
-    return rc;
+    int rc = check_args(c, q, raster, w, h, 1, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : host_stacks(c, false, q, raster, g, n_stacks, n_cubes);
 }
 
-// ---- packed RGB24, host pointers: chunks of whole stacks (contiguous on both sides) through the pipeline ----
 int dct3d_encode_stacks_rgb(dct3d_ctx* c, const uint8_t* rgb, int w, int h, int n_stacks, int32_t* q) {
-    if (!c || (!rgb && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (n_cubes == 0) return DCT3D_OK;
-    const size_t px = 3 * n_cubes * c->plan.cs / n_stacks;  // bytes of a packed stack
-    batch_begin(c);  // every chunk counts into one slot: dct3d_get_stats reports the whole call
-    rc = run_pipeline(c, n_stacks, px, px * sizeof(int32_t), rgb, q, [&](const void* din, void* dout, int, int ns) {
-        return dct3d_encode_stacks_rgb_dev(c, (const uint8_t*)din, w, h, ns, (int32_t*)dout);
-    });
-    batch_end(c);
-    return rc;
+    int rc = check_args(c, rgb, q, w, h, 3, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : host_stacks(c, true, rgb, q, g, n_stacks, n_cubes);
 }
 
 int dct3d_decode_stacks_rgb(dct3d_ctx* c, const int32_t* q, int w, int h, int n_stacks, uint8_t* rgb) {
-    if (!c || (!rgb && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_rgb(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (n_cubes == 0) return DCT3D_OK;
-    const size_t px = 3 * n_cubes * c->plan.cs / n_stacks;
-    batch_begin(c);
-    rc = run_pipeline(c, n_stacks, px * sizeof(int32_t), px, q, rgb, [&](const void* din, void* dout, int, int ns) {
-        return dct3d_decode_stacks_rgb_dev(c, (const int32_t*)din, w, h, ns, (uint8_t*)dout);
-    });
-    batch_end(c);
-    return rc;
+    int rc = check_args(c, q, rgb, w, h, 3, n_stacks, false, &g, &n_cubes);
+    return rc ? rc : host_stacks(c, false, q, rgb, g, n_stacks, n_cubes);
 }
 
-// ---- frames of any size, host pointers: chunks of whole stacks through the pipeline; the copies move the
-//      unpadded frames' bytes only ----
 int dct3d_encode_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks, int32_t* q) {
-    if (!c || (!frames && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
-    int wp, hp;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (n_cubes == 0) return DCT3D_OK;
-    const size_t in_ps = (size_t)channels * w * h * c->bd;
-    const size_t out_ps = (size_t)channels * wp * hp * c->bd * sizeof(int32_t);
-    batch_begin(c);  // every chunk counts into one slot: dct3d_get_stats reports the whole call
-    rc = run_pipeline(c, n_stacks, in_ps, out_ps, frames, q, [&](const void* din, void* dout, int, int ns) {
-        return dct3d_encode_frames_dev(c, (const uint8_t*)din, w, h, channels, ns, (int32_t*)dout);
-    });
-    batch_end(c);
-    return rc;
+    int rc = check_args(c, frames, q, w, h, channels, n_stacks, true, &g, &n_cubes);
+    return rc ? rc : host_stacks(c, true, frames, q, g, n_stacks, n_cubes);
 }
 
 int dct3d_decode_frames(dct3d_ctx* c, const int32_t* q, int w, int h, int channels, int n_stacks, uint8_t* frames) {
-    if (!c || (!frames && n_stacks) || (!q && n_stacks)) return DCT3D_EINVAL;
-    int wp, hp;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, &n_cubes);
-    if (rc) return rc;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (n_cubes == 0) return DCT3D_OK;
-    const size_t out_ps = (size_t)channels * w * h * c->bd;
-    const size_t in_ps = (size_t)channels * wp * hp * c->bd * sizeof(int32_t);
-    batch_begin(c);
-    rc = run_pipeline(c, n_stacks, in_ps, out_ps, q, frames, [&](const void* din, void* dout, int, int ns) {
-        return dct3d_decode_frames_dev(c, (const int32_t*)din, w, h, channels, ns, (uint8_t*)dout);
-    });
-    batch_end(c);
-    return rc;
+    int rc = check_args(c, q, frames, w, h, channels, n_stacks, true, &g, &n_cubes);
+    return rc ? rc : host_stacks(c, false, q, frames, g, n_stacks, n_cubes);
 }
 
 // ---- drop-in (A): float cube-major <-> float cube-major --------------------------------------
@@ -1035,14 +865,9 @@ static int cube_f32_dev(dct3d_ctx* c, const float* d_in, size_t n_cubes, float* 
     if (!c || (n_cubes && (!d_in || !d_out)) || n_cubes >= (1ull << 31) / 8) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     if (!n_cubes) return DCT3D_OK;
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    hipEvent_t* ev = timer_begin(c);
     if (launch_cube_f32(c->bd, inverse, d_in, d_out, (uint32_t)n_cubes, c->stream)) return DCT3D_EKERNEL;
-    if (ev) {
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
+    timer_end(c, ev);
     c->last_units = n_cubes * (uint64_t)c->plan.cs;
     c->last_valid = false;  // no flag counters for the float path
     c->last_count_slot = -1;
@@ -1135,22 +960,12 @@ int dct3d_eg_encode_dev(dct3d_ctx* c, const int32_t* d_q, uint64_t n_cubes, uint
     return eg_run(c, d_q, n_cubes, carry_byte, carry_bits, (uint32_t*)d_out, out_cap, total_bits);
 }
 
-// The geometry of a fused Exp-Golomb call: w x h frames of px bytes per pixel (1 grey, 3 packed RGB24), dense;
-// the cubes tile the padded wp x hp raster (wp = w, hp = h for the calls that need multiples of 8).
-struct EgGeom {
-    int w, h, wp, hp, px;
-    bool edge() const { return wp != w || hp != h; }
-    uint64_t cps() const { return (uint64_t)(wp / 8) * (uint64_t)(hp / 8); }  // cubes per stack and channel
-    uint64_t plane() const { return (uint64_t)px * w * h; }                   // bytes of a frame
-};
-
 // One fused launch chain on the context stream: encode_eg_kernel (transform, quantise, in-wave exact replay,
 // lane-level Exp-Golomb into slots) -> scan over segments -> eg_compact_kernel -> eg_stitch_kernel, for
 // channel ch of the n_cubes cubes of d_raster.  Returns once *total_bits is known.  A packed RGB24 call runs
 // one chain per channel back to back, reusing the slot, bits, offset and head / tail buffers.
-static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const EgGeom& g, int ch, uint64_t n_cubes,
+static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g, int ch, uint64_t n_cubes,
                            uint8_t carry_byte, int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
-    const int w = g.w, h = g.h;
     const bool plain = g.px == 1 && !g.edge();  // dct3d_encode_eg_dev's geometry: its kernel
     int rc;
     const int D = c->bd;
@@ -1166,26 +981,10 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const EgGeom& 
         return rc;
     uint64_t* const sw = eg_status_begin(c, &rc);
     if (rc) return rc;
-    const uint64_t plane = g.plane();
-    EncodeParams P{};
-    P.raster = d_raster;
-    P.out = nullptr;
-    P.n_cubes = (uint32_t)n_cubes;
-    P.g_base = 0;
-    P.cubes_per_stack = (uint32_t)g.cps();
-    P.nbx = (uint32_t)(g.wp / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)w;
-    P.height = g.edge() ? (uint32_t)h : 0u;
-    P.plane = plane;
-    P.stack_stride = plane * D;
-    P.coef_dc = c->plan.coef_dc;
-    const float* tabs = (const float*)c->d_tabs.p;
-    P.tab_rstep = tabs;
-    P.tab_G = tabs + kMaxS;
-    P.tab_E = tabs + 2 * kMaxS;
+    EncodeParams P;  // no int32 output; the replay tables travel in E
+    fill_encode_params(c, P, d_raster, nullptr, g, n_cubes);
     // (the new geometries' kernels count their exact replays; dct3d_encode_eg_dev's reports none)
-    if (!plain) set_count_slot(c, P.replay_count, P.replay_clear);
+    if (plain) P.replay_count = P.replay_clear = nullptr;
     EgFusedParams E;
     E.ch = ch;
     E.ngroups = (const int32_t*)c->d_ngroups.p;
@@ -1214,8 +1013,7 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const EgGeom& 
     G.carry_bits = (uint32_t)carry_bits;
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
     if (plain ? launch_encode_eg(D, P, E, c->stream) : launch_encode_eg_frames(D, g.px, g.edge() ? 1 : 0, P, E, c->stream))
         return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
@@ -1234,106 +1032,104 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const EgGeom& 
 int dct3d_encode_eg_dev(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int n_stacks, uint8_t carry_byte,
                         int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
     if (!c || (!d_raster && n_stacks) || carry_bits < 0 || carry_bits > 7 || ((uintptr_t)d_out & 3)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+    if (!make_geom(w, h, 1, n_stacks, false, &g, &n_cubes)) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->last_valid = false;
-    c->last_count_slot = -1;
+    call_begin(c);
     if (n_cubes == 0) return dct3d_eg_encode_dev(c, nullptr, 0, carry_byte, carry_bits, d_out, out_cap, total_bits);
     if (!d_out) return DCT3D_EINVAL;
-    return encode_eg_chain(c, d_raster, EgGeom{w, h, w, h, 1}, 0, n_cubes, carry_byte, carry_bits, d_out, out_cap, total_bits);
+    return encode_eg_chain(c, d_raster, g, 0, n_cubes, carry_byte, carry_bits, d_out, out_cap, total_bits);
 }
+
+// channel ch's host-call stream buffer on the device, and the bytes the last call left there
+static DevBuf& eg_out_buf(dct3d_ctx* c, int ch) { return ch == 0 ? c->d_eg_out : c->d_eg_out_x[ch - 1]; }
+static uint64_t& eg_last_bytes(dct3d_ctx* c, int ch) { return ch == 0 ? c->eg_last_bytes : c->eg_last_bytes_x[ch - 1]; }
+}  // extern "C"
+// run(outs, caps) codes n_ch streams into the buffers of channels ch0 .. ch0 + n_ch - 1 and sets their tb[]: first
+// with room for 8 bits per value (cap; typical content needs 1.5-4), on DCT3D_ENOSPC grown to fit and run again
+template <class Run>
+static int eg_run_to_fit(dct3d_ctx* c, int ch0, int n_ch, uint64_t first_cap, const uint64_t* tb, Run&& run) {
+    uint64_t cap[3] = {first_cap, first_cap, first_cap};
+    uint8_t* outs[3] = {nullptr, nullptr, nullptr};
+    int rc = DCT3D_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        for (int i = 0; i < n_ch; i++) {
+            DevBuf& b = eg_out_buf(c, ch0 + i);
+            if ((rc = b.grow(cap[i]))) return rc;
+            outs[i] = (uint8_t*)b.p;
+            cap[i] = b.bytes;
+        }
+        rc = run(outs, cap);
+        if (rc != DCT3D_ENOSPC) break;
+        for (int i = 0; i < n_ch; i++) cap[i] = (tb[i] + 31) / 32 * 4 + 64;
+    }
+    return rc;
+}
+extern "C" {
 
 int dct3d_encode_eg(dct3d_ctx* c, const uint8_t* raster, int w, int h, int n_stacks, uint8_t carry_byte,
                     int carry_bits, uint64_t* total_bits) {
     if (!c || (!raster && n_stacks) || carry_bits < 0 || carry_bits > 7) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+    if (!make_geom(w, h, 1, n_stacks, false, &g, &n_cubes)) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     c->eg_last_bytes = c->eg_last_bytes_x[0] = c->eg_last_bytes_x[1] = 0;
     const size_t in_bytes = n_cubes * c->plan.cs;
+    int rc;
     if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1)) || (rc = c->d_eg_q.grow((in_bytes ? in_bytes : 1) * sizeof(int32_t))))
         return rc;
     if (n_cubes && hipMemcpyAsync(c->h_in.p, raster, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return DCT3D_EDEVICE;
-    const bool two_step = c->opt_eg_two_step;  // A/B option: int32 cube-major, then the stand-alone EG stage
-    if (!two_step) {
-        uint64_t cap = in_bytes + 64, tb = 0;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            if ((rc = c->d_eg_out.grow(cap))) return rc;
-            rc = dct3d_encode_eg_dev(c, (const uint8_t*)c->h_in.p, w, h, n_stacks, carry_byte, carry_bits,
-                                     (uint8_t*)c->d_eg_out.p, c->d_eg_out.bytes, &tb);
-            if (rc != DCT3D_ENOSPC) break;
-            cap = (tb + 31) / 32 * 4 + 64;
-        }
-        if (rc) return rc;
-        if (total_bits) *total_bits = tb;
-        c->eg_last_bytes = (tb + 7) / 8;
-        return DCT3D_OK;
-    }
-    if (n_cubes && (rc = dct3d_encode_stacks_dev(c, (const uint8_t*)c->h_in.p, w, h, n_stacks, (int32_t*)c->d_eg_q.p, nullptr)))
-        return rc;
-    // first try: 1 byte per value (8 bits / value; typical content needs 1.5-4), grown to fit on ENOSPC
-    uint64_t cap = in_bytes + 64, tb = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = c->d_eg_out.grow(cap))) return rc;
-        rc = n_cubes ? eg_run(c, (const int32_t*)c->d_eg_q.p, n_cubes, carry_byte, carry_bits, (uint32_t*)c->d_eg_out.p,
-                              c->d_eg_out.bytes, &tb)
-                     : dct3d_eg_encode_dev(c, nullptr, 0, carry_byte, carry_bits, (uint8_t*)c->d_eg_out.p,
-                                           c->d_eg_out.bytes, &tb);
-        if (rc != DCT3D_ENOSPC) break;
-        cap = (tb + 31) / 32 * 4 + 64;
-    }
+    // A/B option: int32 cube-major, then the stand-alone EG stage
+    const bool two_step = c->opt_eg_two_step && n_cubes;
+    if (two_step && (rc = encode_dev(c, (const uint8_t*)c->h_in.p, g, n_cubes, (int32_t*)c->d_eg_q.p, nullptr))) return rc;
+    uint64_t tb = 0;
+    rc = eg_run_to_fit(c, 0, 1, in_bytes + 64, &tb, [&](uint8_t* const* outs, const uint64_t* caps) {
+        return two_step ? eg_run(c, (const int32_t*)c->d_eg_q.p, n_cubes, carry_byte, carry_bits, (uint32_t*)outs[0], caps[0], &tb)
+                        : dct3d_encode_eg_dev(c, (const uint8_t*)c->h_in.p, w, h, n_stacks, carry_byte, carry_bits, outs[0],
+                                              caps[0], &tb);
+    });
     if (rc) return rc;
     if (total_bits) *total_bits = tb;
     c->eg_last_bytes = (tb + 7) / 8;
     return DCT3D_OK;
 }
 
-int dct3d_eg_fetch(dct3d_ctx* c, uint8_t* out, uint64_t nbytes) {
-    if (!c || (nbytes && !out) || nbytes > c->eg_last_bytes) return DCT3D_EINVAL;
+// the bytes of channel `channel`'s stream that the last host stream encode left on the device
+int dct3d_eg_fetch_channel(dct3d_ctx* c, int channel, uint8_t* out, uint64_t nbytes) {
+    if (!c || channel < 0 || channel > 2) return DCT3D_EINVAL;
+    if ((nbytes && !out) || nbytes > eg_last_bytes(c, channel)) return DCT3D_EINVAL;
     if (nbytes == 0) return DCT3D_OK;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (hipMemcpyAsync(out, c->d_eg_out.p, nbytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    if (hipMemcpyAsync(out, eg_out_buf(c, channel).p, nbytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
         return DCT3D_EDEVICE;
     return DCT3D_OK;
 }
 
+int dct3d_eg_fetch(dct3d_ctx* c, uint8_t* out, uint64_t nbytes) { return dct3d_eg_fetch_channel(c, 0, out, nbytes); }
+
 // ---- frames of any size and packed RGB24 -> one Exp-Golomb stream per channel (dct3d.h) ----
-// the arguments the frames calls share; *aligned: grey at multiples of 8 (the call hands over to the grey one)
-static int check_eg_frames(const dct3d_ctx* c, int w, int h, int channels, int n_stacks, EgGeom* g, uint64_t* n_cubes,
-                           bool* aligned) {
-    if (!c) return DCT3D_EINVAL;
-    int wp, hp;
-    int rc = check_geometry_frames(c, w, h, channels, n_stacks, &wp, &hp, n_cubes);
-    if (rc) return rc;
-    *g = EgGeom{w, h, wp, hp, channels};
-    *aligned = channels == 1 && !g->edge();
-    return DCT3D_OK;
-}
+// (grey at multiples of 8: the call hands over to the grey one)
+static bool eg_aligned(const Geom& g) { return g.px == 1 && !g.edge(); }
 
 int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
                                const uint8_t carry_byte[], const int carry_bits[], uint8_t* const d_out[],
                                const uint64_t out_cap[], uint64_t total_bits[]) {
-    EgGeom g;
+    Geom g;
     uint64_t n_cubes;
-    bool aligned;
-    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
-    if (rc) return rc;
+    if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !d_out || !out_cap || !total_bits) return DCT3D_EINVAL;
-    if (aligned)
+    if (eg_aligned(g))
         return dct3d_encode_eg_dev(c, d_frames, w, h, n_stacks, carry_byte[0], carry_bits[0], d_out[0], out_cap[0], total_bits);
     if (!d_frames && n_stacks) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
         if (carry_bits[ch] < 0 || carry_bits[ch] > 7 || ((uintptr_t)d_out[ch] & 3) || (n_cubes && !d_out[ch])) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->last_valid = false;
-    c->last_count_slot = -1;
-    c->slot_used = false;
-    int first = DCT3D_OK;  // every channel runs (each total_bits[ch] is set); the first error is returned
+    call_begin(c);
+    int rc, first = DCT3D_OK;  // every channel runs (each total_bits[ch] is set); the first error is returned
     for (int ch = 0; ch < channels; ch++) {
         total_bits[ch] = 0;
         rc = n_cubes ? encode_eg_chain(c, d_frames, g, ch, n_cubes, carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch])
@@ -1345,18 +1141,13 @@ int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int
     return first;
 }
 
-// channel ch's host-call stream buffer on the device
-static DevBuf& eg_out_buf(dct3d_ctx* c, int ch) { return ch == 0 ? c->d_eg_out : c->d_eg_out_x[ch - 1]; }
-
 int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
                            const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]) {
-    EgGeom g;
+    Geom g;
     uint64_t n_cubes;
-    bool aligned;
-    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
-    if (rc) return rc;
+    if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !total_bits) return DCT3D_EINVAL;
-    if (aligned) return dct3d_encode_eg(c, frames, w, h, n_stacks, carry_byte[0], carry_bits[0], total_bits);
+    if (eg_aligned(g)) return dct3d_encode_eg(c, frames, w, h, n_stacks, carry_byte[0], carry_bits[0], total_bits);
     if (!frames && n_stacks) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
         if (carry_bits[ch] < 0 || carry_bits[ch] > 7) return DCT3D_EINVAL;
@@ -1364,24 +1155,16 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
     c->eg_last_bytes = c->eg_last_bytes_x[0] = c->eg_last_bytes_x[1] = 0;
     const size_t in_bytes = (size_t)g.plane() * c->bd * n_stacks;  // the unpadded frames: one copy
     const size_t ch_vals = n_cubes * c->plan.cs;                   // values of one channel
+    int rc;
     if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1))) return rc;
     if (in_bytes && hipMemcpyAsync(c->h_in.p, frames, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return DCT3D_EDEVICE;
-    uint64_t cap[3], tb[3] = {0, 0, 0};
-    uint8_t* outs[3] = {nullptr, nullptr, nullptr};
-    for (int ch = 0; ch < channels; ch++) cap[ch] = ch_vals + 64;  // 8 bits per value first, grown to fit on ENOSPC
+    uint64_t tb[3] = {0, 0, 0};
     if (!c->opt_eg_two_step || n_cubes == 0) {
-        for (int attempt = 0; attempt < 2; attempt++) {
-            for (int ch = 0; ch < channels; ch++) {
-                if ((rc = eg_out_buf(c, ch).grow(cap[ch]))) return rc;
-                outs[ch] = (uint8_t*)eg_out_buf(c, ch).p;
-                cap[ch] = eg_out_buf(c, ch).bytes;
-            }
-            rc = dct3d_encode_eg_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, carry_byte, carry_bits,
-                                            outs, cap, tb);
-            if (rc != DCT3D_ENOSPC) break;
-            for (int ch = 0; ch < channels; ch++) cap[ch] = (tb[ch] + 31) / 32 * 4 + 64;
-        }
+        rc = eg_run_to_fit(c, 0, channels, ch_vals + 64, tb, [&](uint8_t* const* outs, const uint64_t* caps) {
+            return dct3d_encode_eg_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, carry_byte, carry_bits,
+                                              outs, caps, tb);
+        });
         if (rc) return rc;
     } else {
         // A/B option: the int32 cubes ([stack][channel][cube]), then the stand-alone Exp-Golomb stage over each
@@ -1390,8 +1173,7 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
         if ((rc = c->d_eg_q.grow(channels * ch_vals * sizeof(int32_t))) ||
             (channels == 3 && (rc = c->d_eg_q_ch.grow(ch_vals * sizeof(int32_t)))))
             return rc;
-        if ((rc = dct3d_encode_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, (int32_t*)c->d_eg_q.p)))
-            return rc;
+        if ((rc = encode_dev(c, (const uint8_t*)c->h_in.p, g, n_cubes, (int32_t*)c->d_eg_q.p, nullptr))) return rc;
         for (int ch = 0; ch < channels; ch++) {
             const int32_t* q = (const int32_t*)c->d_eg_q.p;
             if (channels == 3) {
@@ -1400,32 +1182,16 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
                     return DCT3D_EDEVICE;
                 q = (const int32_t*)c->d_eg_q_ch.p;
             }
-            for (int attempt = 0; attempt < 2; attempt++) {
-                if ((rc = eg_out_buf(c, ch).grow(cap[ch]))) return rc;
-                rc = eg_run(c, q, n_cubes, carry_byte[ch], carry_bits[ch], (uint32_t*)eg_out_buf(c, ch).p,
-                            eg_out_buf(c, ch).bytes, &tb[ch]);
-                if (rc != DCT3D_ENOSPC) break;
-                cap[ch] = (tb[ch] + 31) / 32 * 4 + 64;
-            }
+            rc = eg_run_to_fit(c, ch, 1, ch_vals + 64, &tb[ch], [&](uint8_t* const* outs, const uint64_t* caps) {
+                return eg_run(c, q, n_cubes, carry_byte[ch], carry_bits[ch], (uint32_t*)outs[0], caps[0], &tb[ch]);
+            });
             if (rc) return rc;
         }
     }
     for (int ch = 0; ch < channels; ch++) {
         total_bits[ch] = tb[ch];
-        (ch == 0 ? c->eg_last_bytes : c->eg_last_bytes_x[ch - 1]) = (tb[ch] + 7) / 8;
+        eg_last_bytes(c, ch) = (tb[ch] + 7) / 8;
     }
-    return DCT3D_OK;
-}
-
-int dct3d_eg_fetch_channel(dct3d_ctx* c, int channel, uint8_t* out, uint64_t nbytes) {
-    if (!c || channel < 0 || channel > 2) return DCT3D_EINVAL;
-    if (channel == 0) return dct3d_eg_fetch(c, out, nbytes);
-    if ((nbytes && !out) || nbytes > c->eg_last_bytes_x[channel - 1]) return DCT3D_EINVAL;
-    if (nbytes == 0) return DCT3D_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    if (hipMemcpyAsync(out, c->d_eg_out_x[channel - 1].p, nbytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
     return DCT3D_OK;
 }
 
@@ -1619,8 +1385,8 @@ int dct3d_eg_decode_dev(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, u
 // put st0 * cubes-per-stack * cs on a multiple of 2,048 values.  The smallest stack count that does for a
 // w x h frame (1 at 1080p; 8 for a frame of an odd number of 8x8x8 cubes).  (Round 6: the host path's
 // chunks of stacks started anywhere, and a chunk starting inside a group parsed past its window.)
-static int eg_stack_align(const dct3d_ctx* c, int w, int h) {
-    const uint64_t per = (uint64_t)(w / c->bw) * (uint64_t)(h / c->bh) * (uint64_t)c->plan.cs;
+static int eg_stack_align(const dct3d_ctx* c, const Geom& g) {
+    const uint64_t per = g.cps() * (uint64_t)c->plan.cs;  // (the padded raster's cubes)
     const uint64_t grp = kMarkGroup * 32;
     uint64_t a = per % grp, b = grp;  // gcd(per, grp)
     while (a) {
@@ -1631,32 +1397,13 @@ static int eg_stack_align(const dct3d_ctx* c, int w, int h) {
     return (int)(grp / b);
 }
 // E: the front of each of g.px streams (packed RGB24: one per channel)
-static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const EgGeom& g, int st0, int ns, uint8_t* out_stack0) {
+static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, int st0, int ns, uint8_t* out_stack0) {
     const int D = c->bd;
-    const uint64_t plane = g.plane();
     const uint64_t cps = g.cps();
-    uint8_t* out = out_stack0 - (size_t)st0 * plane * D;  // rebased: stack st0 at out_stack0
-    DecodeParams P;
-    P.in = nullptr;
-    P.out = out;
+    DecodeParams P;  // the cubes [cube_base, n_cubes); rebased: stack st0 at out_stack0
+    fill_decode_params(c, P, nullptr, out_stack0 - (size_t)st0 * g.plane() * D, g, (st0 + ns) * cps);
     P.cube_base = (uint32_t)(st0 * cps);
-    P.n_cubes = (uint32_t)((st0 + ns) * cps);
-    P.cubes_per_stack = (uint32_t)cps;
-    P.nbx = (uint32_t)(g.wp / 8);
-    set_fast_div(P);
-    P.width = (uint32_t)g.w;
-    P.height = g.edge() ? (uint32_t)g.h : 0u;
-    P.plane = plane;
-    P.stack_stride = plane * D;
-    P.dec_G = c->plan.dec_G;
-    P.dec_E = c->plan.dec_E;
-    P.dec_l1_max = c->plan.dec_l1_max;
-    // dec_store_tile's conditions (the cropped stores of frames of any size go lane by lane)
-    P.blk_store = !g.edge() && (g.w / 8) % 2 == 0 && plane * D < (1ull << 32) ? 1u : 0u;
-    P.dec_E += c->opt_dec_margin;  // test option (see above)
-    set_dec_replay(c, P);
-    hipEvent_t* ev = timing_slot(c);
-    if (ev) (void)hipEventRecord(ev[0], c->stream);
+    hipEvent_t* ev = timer_begin(c);
     int lrc;
     if (g.px == 3) {
         EgDecRgbParams R;
@@ -1670,11 +1417,7 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const EgGeom& g, 
         lrc = launch_decode_eg(D, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
     }
     if (lrc) return DCT3D_EKERNEL;
-    if (ev) {
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventRecord(ev[2], c->stream);
-        (void)hipEventRecord(ev[3], c->stream);
-    }
+    timer_end(c, ev);
     count_slot_used(c, (uint64_t)g.px * ns * cps * (uint64_t)c->plan.cs);
     return DCT3D_OK;
 }
@@ -1685,7 +1428,7 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const EgGeom& g, 
 // every stream whose own verdict is good; the first bad verdict is returned.  One grey stream to a device
 // raster hands its verdict over from the consumer; the other cases read the status words back.
 static int decode_eg_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint64_t* nbytes, const uint64_t* start_bit,
-                         const EgGeom& g, int n_stacks, uint64_t n_cubes, uint8_t* d_out, uint8_t* host_out,
+                         const Geom& g, int n_stacks, uint64_t n_cubes, uint8_t* d_out, uint8_t* host_out,
                          uint64_t* end_bit) {
     const bool handoff = !host_out && g.px == 1;
     int rc;
@@ -1706,7 +1449,7 @@ static int decode_eg_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint
             batch_begin(c);
             rc = run_pipeline(c, n_stacks, 0, per_stack, nullptr, host_out, [&](const void*, void* dout, int st0, int ns) {
                 return decode_eg_range(c, E, g, st0, ns, (uint8_t*)dout);
-            }, eg_stack_align(c, g.wp, g.hp));  // each chunk's first cube on a consumer group
+            }, eg_stack_align(c, g));  // each chunk's first cube on a consumer group
             batch_end(c);
         } else {
             rc = decode_eg_range(c, E, g, 0, n_stacks, d_out);
@@ -1740,52 +1483,50 @@ extern "C" {
 int dct3d_decode_eg_dev(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint64_t start_bit, int w, int h,
                         int n_stacks, uint8_t* d_raster, uint64_t* end_bit) {
     if (!c || (n_stacks && (!d_bytes || !d_raster)) || ((uintptr_t)d_bytes & 3)) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+    if (!make_geom(w, h, 1, n_stacks, false, &g, &n_cubes)) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->last_valid = false;
-    c->last_count_slot = -1;
+    call_begin(c);
     if (end_bit) *end_bit = start_bit;
     if (n_cubes == 0) return DCT3D_OK;
     if (start_bit >= nbytes * 8) return DCT3D_ENODATA;
-    return decode_eg_run(c, &d_bytes, &nbytes, &start_bit, EgGeom{w, h, w, h, 1}, n_stacks, n_cubes, d_raster, nullptr, end_bit);
+    return decode_eg_run(c, &d_bytes, &nbytes, &start_bit, g, n_stacks, n_cubes, d_raster, nullptr, end_bit);
 }
 
 int dct3d_decode_eg(dct3d_ctx* c, const uint8_t* bytes, uint64_t nbytes, int start_bit, int w, int h, int n_stacks,
                     uint8_t* raster, uint64_t* end_bit) {
     if (!c || (n_stacks && (!bytes || !raster)) || start_bit < 0 || start_bit > 7) return DCT3D_EINVAL;
+    Geom g;
     uint64_t n_cubes;
-    int rc = check_geometry(c, w, h, n_stacks, &n_cubes);
-    if (rc) return rc;
+    if (!make_geom(w, h, 1, n_stacks, false, &g, &n_cubes)) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     if (end_bit) *end_bit = (uint64_t)start_bit;
     if (n_cubes == 0) return DCT3D_OK;
     if ((uint64_t)start_bit >= nbytes * 8) return DCT3D_ENODATA;
+    int rc;
     if ((rc = c->d_egd_in.grow((nbytes + 8) & ~(uint64_t)3))) return rc;
     if (hipMemcpyAsync(c->d_egd_in.p, bytes, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return DCT3D_EDEVICE;
     const uint8_t* const d_bytes = (const uint8_t*)c->d_egd_in.p;
     const uint64_t sb = (uint64_t)start_bit;
-    return decode_eg_run(c, &d_bytes, &nbytes, &sb, EgGeom{w, h, w, h, 1}, n_stacks, n_cubes, nullptr, raster, end_bit);
+    return decode_eg_run(c, &d_bytes, &nbytes, &sb, g, n_stacks, n_cubes, nullptr, raster, end_bit);
 }
 
 // ---- one Exp-Golomb stream per channel -> frames of any size, grey or packed RGB24 (dct3d.h) ----
 int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], const uint64_t nbytes[],
                                const uint64_t start_bit[], int w, int h, int channels, int n_stacks, uint8_t* d_frames,
                                uint64_t end_bit[]) {
-    EgGeom g;
+    Geom g;
     uint64_t n_cubes;
-    bool aligned;
-    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
-    if (rc) return rc;
+    if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!d_bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
-    if (aligned) return dct3d_decode_eg_dev(c, d_bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, d_frames, end_bit);
+    if (eg_aligned(g)) return dct3d_decode_eg_dev(c, d_bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, d_frames, end_bit);
     if (n_stacks && !d_frames) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
         if ((n_stacks && !d_bytes[ch]) || ((uintptr_t)d_bytes[ch] & 3)) return DCT3D_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    c->last_valid = false;
-    c->last_count_slot = -1;
+    call_begin(c);
+    int rc;
     for (int ch = 0; ch < channels; ch++) end_bit[ch] = start_bit[ch];
     if (n_cubes == 0) return DCT3D_OK;
     for (int ch = 0; ch < channels; ch++)
@@ -1808,7 +1549,7 @@ int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], con
                 return DCT3D_EDEVICE;
         }
         if (first) return first;
-        return dct3d_decode_frames_dev(c, (const int32_t*)c->d_eg_q.p, w, h, channels, n_stacks, d_frames);
+        return decode_dev(c, (const int32_t*)c->d_eg_q.p, g, n_cubes, d_frames);
     }
     return decode_eg_run(c, d_bytes, nbytes, start_bit, g, n_stacks, n_cubes, d_frames, nullptr, end_bit);
 }
@@ -1818,13 +1559,12 @@ static DevBuf& egd_in_buf(dct3d_ctx* c, int ch) { return ch == 0 ? c->d_egd_in :
 
 int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uint64_t nbytes[], const int start_bit[],
                            int w, int h, int channels, int n_stacks, uint8_t* frames, uint64_t end_bit[]) {
-    EgGeom g;
+    Geom g;
     uint64_t n_cubes;
-    bool aligned;
-    int rc = check_eg_frames(c, w, h, channels, n_stacks, &g, &n_cubes, &aligned);
-    if (rc) return rc;
+    if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
-    if (aligned) return dct3d_decode_eg(c, bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, frames, end_bit);
+    int rc;
+    if (eg_aligned(g)) return dct3d_decode_eg(c, bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, frames, end_bit);
     if (n_stacks && !frames) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
         if ((n_stacks && !bytes[ch]) || start_bit[ch] < 0 || start_bit[ch] > 7) return DCT3D_EINVAL;

@@ -1,10 +1,11 @@
 /* codec.c -- encode()/decode(): the reference codec's pipeline (encoder.c:88-293,
  * decoder.c:85-314) with the OpenCL block replaced by the libdct3d C-ABI.
  *
- * encode: per batch of stacks: fread -> dct3d_encode_stacks (fused DCT + quantisation on the GPU,
- *         Java semantics) -> per stack: diagonal order + Exp-Golomb + deflate (codec_entropy.c).
- * decode: inflate + Exp-Golomb + reorder per stack -> dct3d_decode_stacks (fused dequantisation +
- *         IDCT + clamp + truncation on the GPU) -> fwrite.
+ * encode: per batch of stacks: fread -> the device (fused DCT + quantisation, Java semantics, and by
+ *         default diagonal order + Exp-Golomb) -> per channel: deflate (codec_entropy.c).
+ * decode: inflate per channel -> the device (Exp-Golomb + reorder, fused dequantisation + IDCT + clamp +
+ *         truncation) -> fwrite.
+ * One body per direction (encode_any / decode_any) serves every frame size, grey and packed RGB24.
  * A stack is DCT_BLOCK_DEPTH frames; a short last stack is zero-filled (the reference reads
  * uninitialised bytes there, encoder.c:21-27).  Frames to encode are rounded up to whole stacks,
  * as in the reference loop (encoder.c:203).  Errors: printf + return 1 (the reference convention);
@@ -29,7 +30,7 @@
 #include "codec_entropy.h"
 #include "dct3d.h"
 
-/* DCT3D_CODEC_TIMING=1: encode_ex / decode_ex print one JSON line of per-stage wall seconds to stderr
+/* DCT3D_CODEC_TIMING=1: encode_any / decode_any print one JSON line of per-stage wall seconds to stderr
  * (tools/codec_e2e.py): which stage bounds the reference-identical .bin end to end */
 static double now_s(void) {
     struct timespec ts;
@@ -47,7 +48,7 @@ static int timing_on(void) {
         (acc) += now_s() - t_0_;      \
     } while (0)
 
-/* A frame size that is no multiple of 8 (1366 x 768, ...): see "frames of any size" below */
+/* every frame size, grey (channels = 1) or packed RGB24 (3): see "packed RGB24 and frames of any size" below */
 static int encode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels);
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
@@ -70,238 +71,13 @@ static int default_batch(void) {
 int encode_ex(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
               int depth, int batch) {
     if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
-    if (width % 8 || height % 8)
-        return encode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
-    if (batch <= 0) batch = default_batch();
-    FILE *in = fopen(inName, "rb");
-    if (!in) {
-        printf("Cannot open input file %s\n", inName);
-        return 1;
-    }
-    FILE *out = fopen(outName, "wb");
-    if (!out) {
-        printf("Cannot open output file %s\n", outName);
-        fclose(in);
-        return 1;
-    }
-    dct3d_ctx *ctx = NULL;
-    const double t_start = now_s();
-    double t_read = 0, t_dev = 0, t_fetch = 0, t_ent = 0;
-    int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
-    const double t_ctx = now_s() - t_start;
-    if (rc) {
-        printf("Error creating the device context: %s\n", dct3d_strerror(rc));
-        fclose(in);
-        fclose(out);
-        return 1;
-    }
-    const size_t frame = (size_t)width * height, stack_px = frame * depth;
-    const int n_stacks = (frames + depth - 1) / depth;
-    /* DCT3D_CODEC_HOST_EG=1: Exp-Golomb on the host from the quantised ints (A/B and tests); default:
-     * the device Exp-Golomb stage, the same bytes */
-    const char *he = getenv("DCT3D_CODEC_HOST_EG");
-    const int host_eg = he && he[0] == '1';
-    uint8_t *raster = (uint8_t *)malloc(stack_px * batch);
-    int32_t *q = host_eg ? (int32_t *)malloc(stack_px * batch * sizeof(int32_t)) : NULL;
-    size_t eg_cap = stack_px * batch / 2 + 64;
-    unsigned char *eg = host_eg ? NULL : (unsigned char *)malloc(eg_cap);
-    dct3d_entropy_enc *ent = dct3d_entropy_enc_create(width, height, depth, out);
-    /* DCT3D_CODEC_DEFLATE_THREADS=N (N > 1): parallel deflate -- the same inflated payload, a different
-     * .bin; default: one zlib stream, the reference encoder's bytes */
-    const char *dt = getenv("DCT3D_CODEC_DEFLATE_THREADS");
-    const int deflate_threads = dt ? atoi(dt) : 1;
-    int status = 0;
-    if (ent && dct3d_entropy_enc_set_threads(ent, deflate_threads, 0)) {
-        dct3d_entropy_enc_destroy(ent);
-        ent = NULL;
-    }
-    if (!raster || (host_eg ? !q : !eg) || !ent) {
-        printf("Out of memory\n");
-        status = 1;
-    }
-    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
-        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
-        size_t got = 0, r;
-        const size_t want = stack_px * nb;
-        STAGE(t_read, while (got < want && (r = fread(raster + got, 1, want - got, in)) > 0) got += r);
-        if (got < want) memset(raster + got, 0, want - got);
-        const int last = s0 + nb == n_stacks;
-        if (host_eg) {  /* quantised ints over PCIe, Exp-Golomb on the host (the reference's split) */
-            STAGE(t_dev, rc = dct3d_encode_stacks(ctx, raster, width, height, nb, q, NULL));
-            if (rc) {
-                printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
-                status = 1;
-                break;
-            }
-            const double t_e0 = now_s();
-            for (int s = 0; s < nb; s++) {
-                if (dct3d_entropy_enc_push(ent, q + stack_px * s, s0 + s == n_stacks - 1)) {
-                    printf("Error in the entropy coder\n");
-                    status = 1;
-                    break;
-                }
-            }
-            t_ent += now_s() - t_e0;
-        } else {  /* DCT + quantisation + diagonal order + Exp-Golomb on the device; the stream over PCIe */
-            uint8_t cb;
-            int cbits;
-            uint64_t tb = 0;
-            dct3d_entropy_enc_carry(ent, &cb, &cbits);
-            STAGE(t_dev, rc = dct3d_encode_eg(ctx, raster, width, height, nb, cb, cbits, &tb));
-            const size_t nbytes = (size_t)((tb + 7) / 8);
-            if (!rc && nbytes > eg_cap) {
-                free(eg);
-                eg_cap = nbytes + nbytes / 4;
-                eg = (unsigned char *)malloc(eg_cap);
-                if (!eg) rc = DCT3D_ENOMEM;
-            }
-            if (!rc) STAGE(t_fetch, rc = dct3d_eg_fetch(ctx, eg, nbytes));
-            if (rc) {
-                printf("Error running the 3D DCT: %s\n", dct3d_strerror(rc));
-                status = 1;
-                break;
-            }
-            int perr;
-            STAGE(t_ent, perr = dct3d_entropy_enc_push_stream(ent, eg, tb, last));
-            if (perr) {
-                printf("Error in the entropy coder\n");
-                status = 1;
-                break;
-            }
-        }
-        for (int s = 0; !status && s < nb; s++) printf("Frames processed: %d\n", (s0 + s + 1) * depth);
-    }
-    STAGE(t_ent, dct3d_entropy_enc_destroy(ent));  /* the last deflate output and its write */
-    free(raster);
-    free(q);
-    free(eg);
-    dct3d_ctx_destroy(ctx);
-    fclose(in);
-    if (fflush(out) || fclose(out)) status = 1;
-    if (timing_on())
-        fprintf(stderr,
-                "{\"stage_s\": {\"ctx_create\": %.6f, \"read\": %.6f, \"device\": %.6f, \"eg_fetch\": %.6f, "
-                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"deflate_threads\": %d}\n",
-                t_ctx, t_read, t_dev, t_fetch, host_eg ? "eg_deflate_write" : "deflate_write", t_ent, now_s() - t_start,
-                host_eg, deflate_threads);
-    if (!status) printf("Encoding process completed\n");
-    return status;
+    return encode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
 }
 
 int decode_ex(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
               int depth, int batch) {
     if (!geometry_ok(width, height, frames, depth)) return invalid_geometry(width, height, frames, depth);
-    if (width % 8 || height % 8)
-        return decode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
-    if (batch <= 0) batch = default_batch();
-    FILE *in = fopen(inName, "rb");
-    if (!in) {
-        printf("Cannot open input file %s\n", inName);
-        return 1;
-    }
-    FILE *out = fopen(outName, "wb");
-    if (!out) {
-        printf("Cannot open output file %s\n", outName);
-        fclose(in);
-        return 1;
-    }
-    dct3d_ctx *ctx = NULL;
-    const double t_start = now_s();
-    double t_inf = 0, t_dev = 0, t_write = 0;
-    int rc = dct3d_ctx_create(platformIndex > 0 ? platformIndex - 1 : 0, 8, 8, depth, &ctx);
-    const double t_ctx = now_s() - t_start;
-    if (rc) {
-        printf("Error creating the device context: %s\n", dct3d_strerror(rc));
-        fclose(in);
-        fclose(out);
-        return 1;
-    }
-    const size_t frame = (size_t)width * height, stack_px = frame * depth;
-    const int n_stacks = (frames + depth - 1) / depth;
-    /* DCT3D_CODEC_HOST_EG=1: Exp-Golomb decode on the host, ints over PCIe (the reference's split);
-     * default: the device decodes the inflated stream (dct3d_decode_eg), only the stream crosses PCIe */
-    const char *he = getenv("DCT3D_CODEC_HOST_EG");
-    const int host_eg = he && he[0] == '1';
-    uint8_t *raster = (uint8_t *)malloc(stack_px * batch);
-    int32_t *q = host_eg ? (int32_t *)malloc(stack_px * batch * sizeof(int32_t)) : NULL;
-    dct3d_entropy_dec *ent = dct3d_entropy_dec_create(width, height, depth, in, NULL, 0);
-    int status = 0;
-    double bits_per_value = 4.0;  /* window estimate for the first batch; then the measured rate */
-    if (!raster || (host_eg && !q) || !ent) {
-        printf("Out of memory\n");
-        status = 1;
-    }
-    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
-        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
-        if (host_eg) {
-            const double t_i0 = now_s();
-            for (int s = 0; s < nb; s++)
-                if (dct3d_entropy_dec_pull(ent, q + stack_px * s)) {
-                    printf("Truncated or corrupt input stream\n");
-                    status = 1;
-                    break;
-                }
-            t_inf += now_s() - t_i0;
-            if (status) break;
-            STAGE(t_dev, rc = dct3d_decode_stacks(ctx, q, width, height, nb, raster));
-        } else {
-            const double values = (double)stack_px * nb;
-            size_t need = (size_t)(values * bits_per_value / 8 * 1.25) + 65536;
-            for (;;) {
-                const unsigned char *p;
-                size_t len;
-                int bit;
-                uint64_t eb = 0;
-                int werr;
-                STAGE(t_inf, werr = dct3d_entropy_dec_window(ent, need, &p, &len, &bit));
-                if (werr) {
-                    rc = DCT3D_EINVAL;
-                    break;
-                }
-                STAGE(t_dev, rc = dct3d_decode_eg(ctx, p, len, bit, width, height, nb, raster, &eb));
-                if (rc == DCT3D_ENODATA && !dct3d_entropy_dec_eof(ent) && len >= need) {
-                    need *= 2;  /* the batch needs more of the stream than estimated */
-                    continue;
-                }
-                if (!rc) {
-                    dct3d_entropy_dec_consume(ent, eb);
-                    bits_per_value = (double)(eb - (uint64_t)bit) / values;
-                }
-                break;
-            }
-            if (rc == DCT3D_ENODATA || rc == DCT3D_EINVAL) {
-                printf("Truncated or corrupt input stream\n");
-                status = 1;
-                break;
-            }
-        }
-        if (rc) {
-            printf("Error running the inverse 3D DCT: %s\n", dct3d_strerror(rc));
-            status = 1;
-            break;
-        }
-        size_t wrote;
-        STAGE(t_write, wrote = fwrite(raster, 1, stack_px * nb, out));
-        if (wrote != stack_px * nb) {
-            printf("Error writing the output file\n");
-            status = 1;
-            break;
-        }
-        printf("Frames processed: %d\n", (s0 + nb) * depth);
-    }
-    dct3d_entropy_dec_destroy(ent);
-    free(raster);
-    free(q);
-    dct3d_ctx_destroy(ctx);
-    fclose(in);
-    STAGE(t_write, if (fflush(out) || fclose(out)) status = 1);
-    if (timing_on())
-        fprintf(stderr,
-                "{\"stage_s\": {\"ctx_create\": %.6f, \"%s\": %.6f, \"device\": %.6f, \"write\": %.6f}, "
-                "\"total_s\": %.6f, \"host_eg\": %d}\n",
-                t_ctx, host_eg ? "read_inflate_eg" : "read_inflate", t_inf, t_dev, t_write, now_s() - t_start, host_eg);
-    if (!status) printf("Decoding process completed\n");
-    return status;
+    return decode_any(inName, outName, width, height, frames, platformIndex, depth, batch, 1);
 }
 
 /* ---- several devices ------------------------------------------------------------------------ */
@@ -663,11 +439,11 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
  * or packed RGB24: the device pads by repeating each frame's last column and last row up to wp x hp (the
  * next multiples of 8) inside its kernels and crops on the way back; the entropy coder works on wp x hp, so
  * the streams are, byte for byte, what the same command writes for the edge-padded video at wp x hp.
- * Both go through encode_any / decode_any.  Default: the fused stream calls (dct3d_encode_eg_frames /
- * dct3d_decode_eg_frames) -- each channel's Exp-Golomb stream is built and parsed on the device, only the
- * frames and the streams cross PCIe, as in encode_ex / decode_ex.  DCT3D_CODEC_HOST_EG=1: the quantised ints
- * over PCIe (dct3d_encode_frames / dct3d_decode_frames) and the host entropy coder per stack; the same
- * files. */
+ * Both, and grey at multiples of 8 (where the frames calls are the *_stacks / grey stream calls), go through
+ * encode_any / decode_any.  Default: the fused stream calls (dct3d_encode_eg_frames / dct3d_decode_eg_frames)
+ * -- each channel's Exp-Golomb stream is built and parsed on the device, only the frames and the streams
+ * cross PCIe.  DCT3D_CODEC_HOST_EG=1: the quantised ints over PCIe (dct3d_encode_frames /
+ * dct3d_decode_frames) and the host entropy coder per stack; the same files. */
 static const char *const kRgbSuffix[3] = {".red", ".green", ".blue"};
 
 static FILE *open_plane(const char *pattern, int ch, const char *mode) {
@@ -714,7 +490,13 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         return 1;
     }
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    /* DCT3D_CODEC_HOST_EG=1: Exp-Golomb on the host from the quantised ints (A/B and tests); default: the
+     * device Exp-Golomb stage, the same bytes */
     const int host_eg = host_eg_on();
+    /* DCT3D_CODEC_DEFLATE_THREADS=N (N > 1): parallel deflate in every channel's coder -- the same inflated
+     * payload, a different .bin; default: one zlib stream, the reference encoder's bytes */
+    const char *dt = getenv("DCT3D_CODEC_DEFLATE_THREADS");
+    const int deflate_threads = dt ? atoi(dt) : 1;
     FILE *out[3] = {NULL, NULL, NULL};
     dct3d_entropy_enc *ent[3] = {NULL, NULL, NULL};
     dct3d_ctx *ctx = NULL;
@@ -745,7 +527,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         if (!host_eg) eg = (unsigned char *)malloc(eg_cap);
         int ok = fr && (host_eg ? q != NULL : eg != NULL);
         for (int ch = 0; ch < channels; ch++)
-            if (!(ent[ch] = dct3d_entropy_enc_create(wp, hp, depth, out[ch]))) ok = 0;
+            if (!(ent[ch] = dct3d_entropy_enc_create(wp, hp, depth, out[ch])) ||
+                dct3d_entropy_enc_set_threads(ent[ch], deflate_threads, 0))
+                ok = 0;
         if (!ok) {
             printf("Out of memory\n");
             status = 1;
@@ -756,7 +540,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         size_t got = 0, r;
         const size_t want = stack_bytes * nb;
         STAGE(t_read, while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r);
-        if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as encode_ex */
+        if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled */
         const int last = s0 + nb == n_stacks;
         int rc;
         if (host_eg) { /* quantised ints over PCIe, Exp-Golomb on the host */
@@ -823,9 +607,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     if (timing_on())
         fprintf(stderr,
                 "{\"stage_s\": {\"ctx_create\": %.6f, \"read\": %.6f, \"device\": %.6f, \"eg_fetch\": %.6f, "
-                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"channels\": %d}\n",
+                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"deflate_threads\": %d, \"channels\": %d}\n",
                 t_ctx, t_read, t_dev, t_fetch, host_eg ? "eg_deflate_write" : "deflate_write", t_ent, now_s() - t_start,
-                host_eg, channels);
+                host_eg, deflate_threads, channels);
     if (!status) printf("Encoding process completed\n");
     return status;
 }
@@ -888,7 +672,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
             t_inf += now_s() - t_i0;
             if (status) break;
             STAGE(t_dev, rc = dct3d_decode_frames(ctx, q, width, height, channels, nb, fr));
-        } else { /* the device parses each channel's inflated stream; the ENODATA-then-refill loop of decode_ex */
+        } else { /* the device parses each channel's inflated stream, refilled and run again on ENODATA */
             const double values = (double)stack_px * nb;
             size_t need = (size_t)(values * bits_per_value / 8 * 1.25) + 65536;
             for (;;) {

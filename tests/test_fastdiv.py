@@ -1,25 +1,20 @@
-"""CPU: the kernels' address-map division (FastDiv, dct3d_kernels.h; fast_div in dct3d_runtime.cpp):
-floor(n * m / 2^s) with s = 31 + ceil(log2 d), m = ceil(2^s / d) equals n // d for every n < 2^31.
-Restated here from the two source lines; checked at every kind of boundary (multiples of d and their
-neighbours, the top of the range) for the geometries' divisors and random ones."""
+"""CPU: the kernels' address-map division (FastDiv and fast_div, csrc/dct3d_geom.h): floor(n * m / 2^s) with
+s = 31 + ceil(log2 d), m = ceil(2^s / d) equals n // d for every n < 2^31.  The real fast_div (compiled with g++:
+tests/native/geom_check.cpp), checked at every kind of boundary (multiples of d and their neighbours, the top of
+the range) for the geometries' divisors and random ones."""
 import numpy as np
 
-
-def fast_div(d):
-    l = 0
-    while (1 << l) < d:
-        l += 1
-    s = 31 + l
-    return ((1 << s) + d - 1) // d, s
+from test_geom import fast_div_closed, fast_div_of, geom_lib  # noqa: F401  (the fixture)
 
 
-def test_fastdiv_matches_integer_division():
+def test_fastdiv_matches_integer_division(geom_lib):  # noqa: F811
     rng = np.random.default_rng(3)
     divisors = {1, 2, 3, 5, 7, 8, 60, 135, 240, 480, 1024, 32400, 129600, 2**16 + 1}
     divisors |= set(rng.integers(1, 2**20, size=100).tolist())
-    for d in sorted(divisors):
-        m, s = fast_div(d)
-        assert m < 2**32
+    divisors = sorted(divisors)
+    ms, ss = fast_div_of(geom_lib, divisors)
+    for d, m, s in zip(divisors, ms.tolist(), ss.tolist()):
+        assert (m, s) == fast_div_closed(d) and m < 2**32  # (read back from 32 bits: the closed form must fit them)
         k = rng.integers(0, (2**31 - 1) // d + 1, size=300).astype(np.uint64)
         n = np.concatenate([np.arange(0, 3 * d + 3, dtype=np.uint64)[:2000], k * d, k * d + (d - 1),
                             np.array([2**31 - 1], np.uint64)])

@@ -7,7 +7,9 @@ uniform, different seeds per channel."""
 import filecmp
 import functools
 import importlib
+import os
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -220,8 +222,8 @@ def test_rejects_bad_arguments(pkg, gpu_ctx8):
         gpu_ctx8.encode_stacks_rgb(np.zeros((8, 16, 12, 3), np.uint8))
 
 
-def _run(args):
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+def _run(args, env=None):
+    r = subprocess.run(args, capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -254,3 +256,19 @@ def test_cli_any_size(pkg, tmp_path, depth, channels):
     zfill[:frames] = fr
     _, out_ref = _oracle(depth, zfill)
     assert np.array_equal(out, out_ref)
+    # 16 frames of 13 x 11 with DCT3D_CODEC_DEFLATE_THREADS=2 and without: every channel's coder honours the
+    # option -- the same inflated payload per channel, and both decode to the same frames
+    w, h, frames = 13, 11, 16
+    fr = pkg.synthetic.frames(w, h, frames) if channels == 1 else rgb_content(pkg, w, h, frames)
+    (tmp_path / "t.raw").write_bytes(fr.tobytes())
+    tail = [str(w), str(h), str(frames), "1", str(depth)]
+    _run([pkg.CLI_PATH, enc, str(tmp_path / "t.raw"), str(tmp_path / "s")] + tail)
+    _run([pkg.CLI_PATH, enc, str(tmp_path / "t.raw"), str(tmp_path / "p")] + tail,
+         env=dict(os.environ, DCT3D_CODEC_DEFLATE_THREADS="2"))
+    for sfx in ([""] if channels == 1 else [".red", ".green", ".blue"]):
+        single, par = ((tmp_path / (n + sfx)).read_bytes() for n in "sp")
+        assert zlib.decompress(par) == zlib.decompress(single), sfx
+    _run([pkg.CLI_PATH, dec, str(tmp_path / "s"), str(tmp_path / "s.out")] + tail)
+    _run([pkg.CLI_PATH, dec, str(tmp_path / "p"), str(tmp_path / "p.out")] + tail)
+    assert len((tmp_path / "s.out").read_bytes()) == fr.size
+    assert (tmp_path / "p.out").read_bytes() == (tmp_path / "s.out").read_bytes()
