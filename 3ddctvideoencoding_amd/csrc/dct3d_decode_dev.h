@@ -366,7 +366,8 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
 // One tile (CPW cubes) from the staged input in the wave's LDS region to the raster.  after_a() runs
 // once the staged input is in registers (the persistent variant issues the next tile's loads there);
 // reload(g, cf, lane) re-reads cube g's dequantised coefficients for the rare exact replay.
-// PG: butterflies per pin group (1: one at a time, 2 / 4: that many interleaved, 0: no pins)
+// One butterfly per pin group (2 / 4 interleaved or no pins measured within 1 %:
+// profiles/r01/decode_variant_sweep.txt).
 // CODES: the staging holds Exp-Golomb codes, not values (decode_eg_kernel): v = code >> 1, negative when the
 // code is odd.  |q| * step in 32-bit integers (v_mul_u32_u24: exact while |q| < 2^15, < 2^22), the lane's
 // L1 as their exact integer sum (< 2^27), the fp64 value by one exact conversion with the sign put into its
@@ -377,7 +378,7 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
 // values from the stream.
 // KEEP (decode_rgb_kernel): no stores; the lane's words outw[z][wd] go to keep[z * NXC / 4 + wd] and the
 // lane's `valid` to *keep_valid.
-template <int D, int PG, bool LOOP = false, bool CODES = false, bool KEEP = false, int EDGE = 0, class AfterA, class Reload>
+template <int D, bool LOOP = false, bool CODES = false, bool KEEP = false, int EDGE = 0, class AfterA, class Reload>
 __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
                                             AfterA&& after_a, const Reload& reload, uint32_t* keep = nullptr,
                                             bool* keep_valid = nullptr) {
@@ -452,22 +453,16 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
     }
 
     // ---- inverse pass Y ----
-    constexpr int G1 = PG == 0 ? 4 : PG;
 #pragma unroll
-    for (int e0 = 0; e0 < 4; e0 += G1) {
-        double col[G1][8];
+    for (int e = 0; e < 4; e++) {
+        double col[8];
 #pragma unroll
-        for (int i = 0; i < G1; i++)
+        for (int y = 0; y < 8; y++) col[y] = b[y][e];
+        pin(col);
+        idct8(col);
+        pin(col);
 #pragma unroll
-            for (int y = 0; y < 8; y++) col[i][y] = b[y][e0 + i];
-        if (PG) for (int i = 0; i < G1; i++) pin(col[i]);
-#pragma unroll
-        for (int i = 0; i < G1; i++) idct8(col[i]);
-        if (PG) for (int i = 0; i < G1; i++) pin(col[i]);
-#pragma unroll
-        for (int i = 0; i < G1; i++)
-#pragma unroll
-            for (int y = 0; y < 8; y++) b[y][e0 + i] = col[i][y];
+        for (int y = 0; y < 8; y++) b[y][e] = col[y];
     }
 
     // ---- A -> B: swap the off-diagonal 4x4 blocks of the lane pair (l, l^16) ----
@@ -479,48 +474,37 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
 
     // ---- inverse pass X ----
 #pragma unroll
-    for (int r0 = 0; r0 < 4; r0 += G1) {
-        double row[G1][8];
+    for (int r = 0; r < 4; r++) {
+        double row[8];
 #pragma unroll
-        for (int i = 0; i < G1; i++)
+        for (int e = 0; e < 4; e++) {
+            row[e] = b[r][e];
+            row[4 + e] = b[4 + r][e];
+        }
+        pin(row);
+        idct8(row);
+        pin(row);
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                row[i][e] = b[r0 + i][e];
-                row[i][4 + e] = b[4 + r0 + i][e];
-            }
-        if (PG) for (int i = 0; i < G1; i++) pin(row[i]);
-#pragma unroll
-        for (int i = 0; i < G1; i++) idct8(row[i]);
-        if (PG) for (int i = 0; i < G1; i++) pin(row[i]);
-#pragma unroll
-        for (int i = 0; i < G1; i++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                b[r0 + i][e] = row[i][e];
-                b[4 + r0 + i][e] = row[i][4 + e];
-            }
+        for (int e = 0; e < 4; e++) {
+            b[r][e] = row[e];
+            b[4 + r][e] = row[4 + e];
+        }
     }
 
     double cz[D][NXC];
     dec_b_to_c<D>(b, cz, wl, c, k, h);
 
     // ---- inverse pass Z ----
-    constexpr int G3 = PG == 0 ? NXC : PG;
 #pragma unroll
-    for (int e0 = 0; e0 < NXC; e0 += G3) {
-        double col[G3][D];
+    for (int e = 0; e < NXC; e++) {
+        double col[D];
 #pragma unroll
-        for (int i = 0; i < G3; i++)
+        for (int z = 0; z < D; z++) col[z] = cz[z][e];
+        pin(col);
+        idctN_fix<D>(col, kFixMagic);  // outputs v + kFixMagic
+        pin(col);
 #pragma unroll
-            for (int z = 0; z < D; z++) col[i][z] = cz[z][e0 + i];
-        if (PG) for (int i = 0; i < G3; i++) pin(col[i]);
-#pragma unroll
-        for (int i = 0; i < G3; i++) idctN_fix<D>(col[i], kFixMagic);  // outputs v + kFixMagic
-        if (PG) for (int i = 0; i < G3; i++) pin(col[i]);
-#pragma unroll
-        for (int i = 0; i < G3; i++)
-#pragma unroll
-            for (int z = 0; z < D; z++) cz[z][e0 + i] = col[i][z];
+        for (int z = 0; z < D; z++) cz[z][e] = col[z];
     }
 
     // ---- certify, clamp + truncate, store ----
@@ -602,7 +586,7 @@ __device__ __forceinline__ void dec_clear_next_slot(const DecodeParams& P) {
     }
 }
 
-template <int D, int PG, int EDGE = 0>
+template <int D, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -615,7 +599,7 @@ __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     dec_clear_next_slot(P);
     dec_stage_tile<D>(wl, lane, v);
     wave_lds_sync();
-    decode_tile<D, PG, false, false, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
+    decode_tile<D, false, false, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -667,7 +651,7 @@ struct ReloadCubesRgb {  // ReloadCubes for cube g of channel ch (dec_rgb_cube, 
     }
 };
 
-template <int D, int PG, int EDGE = 0>
+template <int D, int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
     constexpr int NW = (D == 8) ? 1 : 2;  // words per plane and channel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
@@ -697,7 +681,7 @@ __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
         }
         wave_lds_sync();
         uint32_t outw[D][NW];
-        decode_tile<D, PG, false, false, true>(P, wl, lane, cube0, [] {}, ReloadCubesRgb<D>{P.in, P.div_cps, P.cubes_per_stack, ch}, &outw[0][0], &valid);
+        decode_tile<D, false, false, true>(P, wl, lane, cube0, [] {}, ReloadCubesRgb<D>{P.in, P.div_cps, P.cubes_per_stack, ch}, &outw[0][0], &valid);
         const uint32_t s0 = ch == 0 ? rgb_put_sel(0, 0) : ch == 1 ? rgb_put_sel(1, 0) : rgb_put_sel(2, 0);
         const uint32_t s1 = ch == 0 ? rgb_put_sel(0, 1) : ch == 1 ? rgb_put_sel(1, 1) : rgb_put_sel(2, 1);
         const uint32_t s2 = ch == 0 ? rgb_put_sel(0, 2) : ch == 1 ? rgb_put_sel(1, 2) : rgb_put_sel(2, 2);

@@ -34,14 +34,14 @@ __global__ __launch_bounds__(kBlock, 4) void encode_memonly_kernel(EncodeParams 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;  // the product's order
     uint2 raw[D];
-    load_rows<D>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);
+    load_cube_rows<D, 0, 0>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, raw);
     if (cube0 >= P.n_cubes) return;
     int32_t qv[8][NB];
 #pragma unroll
     for (int ky = 0; ky < 8; ky++)
 #pragma unroll
         for (int x = 0; x < NB; x++) qv[ky][x] = (int32_t)((ky & 1 ? raw[x % D].y : raw[x % D].x) >> (ky * 3 % 24)) & 255;
-    enc_stage_store<D, true>(P, qv, lds + wave * enc_wave_lds<D>(), lane, cube0);
+    enc_stage_store<D>(P, qv, lds + wave * enc_wave_lds<D>(), lane, cube0);
 }
 
 // dct3d_decode_diag_dev (the output is NOT a decode): MODE 1 = memory only
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kBlock, 4) void decode_kernel_diag(DecodeParams P) 
     }
     DecodeParams Q = P;
     if (MODE == 2 && P.width != 0xFFFFFFFFu) Q.n_cubes = 0;  // all stores suppressed, compute kept
-    decode_tile<D, 1>(Q, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
+    decode_tile<D>(Q, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
 }
 
 // =============================================================================================
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void ceiling_kernel(const uint8_t* __restrict_
             for (int w = 0; w < 16; w++) {
                 const long long o = it * 16 * T + w * T + g;
                 const uint4 x = v[w & 3];
-                if (o < 4 * n_in) store16<true>(out + o * 16, make_int4((int)x.x, (int)x.y, (int)x.z, (int)(x.w + w)));
+                if (o < 4 * n_in) store16(out + o * 16, make_int4((int)x.x, (int)x.y, (int)x.z, (int)(x.w + w)));
             }
         } else if (mode == 1 || mode == 4) {
 #pragma unroll
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void ceiling_kernel(const uint8_t* __restrict_
                 const long long c = it * 4 * T + u * T + g;
                 const int4 o = make_int4((int)v[u].x, (int)v[u].y, (int)v[u].z, (int)v[u].w);
                 if (c < n_in) {
-                    if (mode == 1) store16<true>(out + c * 16, o);
+                    if (mode == 1) store16(out + c * 16, o);
                     else *(int4*)(out + c * 16) = o;
                 }
             }
@@ -359,8 +359,8 @@ static int encode_diag(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int 
     const dim3 grid(enc_grid(v.bd, P));
     if (v.bd == 8) {  // the twins of encode16_kernel
         if (mode == 1 || mode == 4) {
-            if (mode == 1) hipLaunchKernelGGL((encode16_kernel<true, 1>), grid, dim3(kBlock), 0, v.stream, P);
-            else hipLaunchKernelGGL((encode16_kernel<true, 4>), grid, dim3(kBlock), 0, v.stream, P);
+            if (mode == 1) hipLaunchKernelGGL((encode16_kernel<1>), grid, dim3(kBlock), 0, v.stream, P);
+            else hipLaunchKernelGGL((encode16_kernel<4>), grid, dim3(kBlock), 0, v.stream, P);
         } else {  // compute only / the product with the strip traversal, with the product's tables
             const EncTables* t = enc8_tables(v.device);
             if (!t) return DCT3D_ENOMEM;
@@ -374,9 +374,9 @@ static int encode_diag(dct3d_ctx* c, const uint8_t* d_raster, int w, int h, int 
             P.coef = t->coef;
             P.group_of = t->group_of;
             P.trace = d_trace;
-            if (mode == 2) hipLaunchKernelGGL((encode16_kernel<true, 2>), grid, dim3(kBlock), 0, v.stream, P);
-            else if (mode == 3) hipLaunchKernelGGL((encode16_kernel<true, 3>), grid, dim3(kBlock), 0, v.stream, P);
-            else hipLaunchKernelGGL((encode16_kernel<true, 5>), grid, dim3(kBlock), 0, v.stream, P);
+            if (mode == 2) hipLaunchKernelGGL((encode16_kernel<2>), grid, dim3(kBlock), 0, v.stream, P);
+            else if (mode == 3) hipLaunchKernelGGL((encode16_kernel<3>), grid, dim3(kBlock), 0, v.stream, P);
+            else hipLaunchKernelGGL((encode16_kernel<5>), grid, dim3(kBlock), 0, v.stream, P);
         }
     } else {
         hipLaunchKernelGGL((encode_memonly_kernel<4>), grid, dim3(kBlock), 0, v.stream, P);

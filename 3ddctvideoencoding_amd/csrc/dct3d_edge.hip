@@ -15,11 +15,11 @@ int launch_encode_edge(int D, int px, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(enc_grid(D, P));
     if (D == 8) {
-        if (px == 1) hipLaunchKernelGGL((encode16_kernel<true, 0, 1>), grid, dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((encode16_rgb_kernel<true, 1>), grid, dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((encode16_kernel<0, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((encode16_rgb_kernel<1>), grid, dim3(kBlock), 0, st, P);
     } else {
-        if (px == 1) hipLaunchKernelGGL((encode_kernel<4, true, false, 1>), grid, dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((encode_rgb_kernel<4, true, 1>), grid, dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((encode_kernel<1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((encode_rgb_kernel<1>), grid, dim3(kBlock), 0, st, P);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -28,11 +28,11 @@ int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(dec_grid(D, P.n_cubes));
     if (D == 8) {
-        if (px == 1) hipLaunchKernelGGL((decode_kernel<8, 1, 1>), grid, dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((decode_rgb_kernel<8, 1, 1>), grid, dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((decode_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((decode_rgb_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
     } else {
-        if (px == 1) hipLaunchKernelGGL((decode_kernel<4, 1, 1>), grid, dim3(kBlock), 0, st, P);
-        else hipLaunchKernelGGL((decode_rgb_kernel<4, 1, 1>), grid, dim3(kBlock), 0, st, P);
+        if (px == 1) hipLaunchKernelGGL((decode_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((decode_rgb_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -671,18 +671,28 @@ __device__ __forceinline__ void copy_lut(uint8_t* s_lut) {
 }
 static_assert(kEgLutBits <= 15, "counts and widths fit 4 bits");
 
+// The table steps' shared prologue: the 64 bits at p from the column, the run of 1-bit codes n1 (at most 31;
+// BOUNDED: capped at the `room` bits left before the stop), the 32 bits after the run th, the table entry e of
+// their top B bits and th's leading zeros zz.
+template <int B, bool BOUNDED>
+__device__ __forceinline__ void table_peek(const uint32_t* col, const uint8_t* lut, uint32_t p, uint32_t room,
+                                           uint32_t& n1, uint32_t& th, uint32_t& e, uint32_t& zz) {
+    uint32_t hi, lo;
+    col_bits64(col, p, hi, lo);
+    n1 = __builtin_clz(~hi | (BOUNDED ? 0x80000000u >> min(room, 31u) : 1u));
+    th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
+    e = lut[th >> (32 - B)];
+    zz = ffbh_u32(th);
+}
+
 // A step that meets a code of >= 33 bits (or 32 zero bits) ends the interior loop with that code counted
 // and its (meaningless) width added to p; the loop's caller takes both back (pos_step_undo), so the step
 // needs no selects for the case.
 __device__ __forceinline__ uint32_t pos_step_lut(const uint32_t* col, const uint8_t* lut, uint32_t& p, bool& bad,
                                                  uint32_t& w_last) {
-    uint32_t hi, lo;
-    col_bits64(col, p, hi, lo);
-    const uint32_t n1 = __builtin_clz(~hi | 1u);  // run of 1-bit codes, at most 31
-    const uint32_t th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
-    const uint32_t e = lut[th >> (32 - kEgLutBits)];
+    uint32_t n1, th, e, zz;
+    table_peek<kEgLutBits, false>(col, lut, p, 0u, n1, th, e, zz);
     const uint32_t k = e & 15u;
-    const uint32_t zz = ffbh_u32(th);
     const bool kz = k == 0u;                 // no code complete in the table's bits: one code by clz
     bad = kz & (zz >= 16u);                  // >= 33 bits or invalid: the checked loop reads it
     w_last = kz ? 2u * zz + 1u : e >> 4;
@@ -704,13 +714,9 @@ __device__ __forceinline__ void pos_step_undo(bool bad, uint32_t w_last, uint32_
 template <int B = kEgLutBits>
 __device__ __forceinline__ uint32_t pos_step_lut_mark(const uint32_t* col, const uint8_t* lut, uint32_t& p, bool& bad,
                                                       uint32_t d0, uint32_t& w_last) {
-    uint32_t hi, lo;
-    col_bits64(col, p, hi, lo);
-    const uint32_t n1 = __builtin_clz(~hi | 1u);
-    const uint32_t th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
-    const uint32_t e = lut[th >> (32 - B)];
+    uint32_t n1, th, e, zz;
+    table_peek<B, false>(col, lut, p, 0u, n1, th, e, zz);
     const uint32_t k = e & 15u;
-    const uint32_t zz = ffbh_u32(th);
     // (bitwise, not short-circuit: the compiler made branches of &&)
     const bool full = (k != 0u) & (n1 + k <= 32u) & (d0 - n1 - 1u >= k - 1u);
     bad = !full & (zz >= 16u);  // counted and taken back by the caller (pos_step_undo), as pos_step_lut
@@ -729,13 +735,9 @@ __device__ __forceinline__ uint32_t pos_step_lut_mark(const uint32_t* col, const
 __device__ __forceinline__ uint32_t pos_step_lut_bounded(const uint32_t* col, const uint8_t* lut, uint32_t& p, bool& bad,
                                                          uint32_t stop) {
     const uint32_t room = stop - p;
-    uint32_t hi, lo;
-    col_bits64(col, p, hi, lo);
-    const uint32_t n1 = __builtin_clz(~hi | (0x80000000u >> min(room, 31u)));
-    const uint32_t th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
-    const uint32_t e = lut[th >> (32 - kEgLutBits)];
+    uint32_t n1, th, e, zz;
+    table_peek<kEgLutBits, true>(col, lut, p, room, n1, th, e, zz);
     const uint32_t k = e & 15u, wt = e >> 4;
-    const uint32_t zz = ffbh_u32(th);
     const bool has = ((th >> 31) == 0u) & (n1 < room);  // a code starts after the run, before the stop
     const bool table = has & (k != 0u) & (p + n1 + wt <= stop);
     const bool one = has & !table;
@@ -749,13 +751,9 @@ template <int B = kEgLutBits>
 __device__ __forceinline__ uint32_t pos_step_lut_mark_bounded(const uint32_t* col, const uint8_t* lut, uint32_t& p,
                                                               bool& bad, uint32_t d0, uint32_t stop) {
     const uint32_t room = stop - p;
-    uint32_t hi, lo;
-    col_bits64(col, p, hi, lo);
-    const uint32_t n1 = __builtin_clz(~hi | (0x80000000u >> min(room, 31u)));
-    const uint32_t th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
-    const uint32_t e = lut[th >> (32 - B)];
+    uint32_t n1, th, e, zz;
+    table_peek<B, true>(col, lut, p, room, n1, th, e, zz);
     const uint32_t k = e & 15u, wt = e >> 4;
-    const uint32_t zz = ffbh_u32(th);
     const bool has = ((th >> 31) == 0u) & (n1 < room);
     const bool full = has & (k != 0u) & (n1 + k <= 32u) & (d0 - n1 - 1u >= k - 1u) & (p + n1 + wt <= stop);
     const bool one = has & !full;
@@ -813,13 +811,9 @@ __device__ __forceinline__ bool walk(const uint32_t* col, const uint8_t* lut, ui
     for (uint32_t i = 0; i < steps && !walk_done(w, limit); i++) {
         const bool a_behind = w.pa < w.pq;
         const uint32_t behind = min(w.pa, w.pq), ahead = max(w.pa, w.pq);
-        uint32_t hi, lo;
-        col_bits64(col, behind, hi, lo);
-        const uint32_t n1 = __builtin_clz(~hi | 1u);  // <= 31
-        const uint32_t th = (uint32_t)(((((uint64_t)hi << 32) | lo) << n1) >> 32);
-        const uint32_t ent = lut[th >> (32 - kEgLutBits)];
+        uint32_t n1, th, ent, zz;
+        table_peek<kEgLutBits, false>(col, lut, behind, 0u, n1, th, ent, zz);
         const uint32_t k = ent & 15u, wt = ent >> 4;
-        const uint32_t zz = ffbh_u32(th);
         const bool run_meet = behind + n1 >= ahead;
         const bool code = (th >> 31) == 0u;  // a code follows the run (not a capped run)
         const bool table = (k != 0u) & (behind + n1 + wt <= ahead);

@@ -197,11 +197,10 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     // the rows in flight first, issued at the top priority (as encode16_kernel's: under oldest-first issue
     // they queue behind the computing waves' VALU work; c7 -0.4 %, profiles/r05/c7_ab/7_prio)
     __builtin_amdgcn_s_setprio(3);
-    if constexpr (PX == 1 && EDGE == 0) load_rows<D>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);
-    else if constexpr (PX == 1) load_rows<D, false, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);
-    else load_rows_rgb_ch<D, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, E.ch, raw);
+    load_channel_rows<D, 0, PX, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, E.ch, raw);
     __builtin_amdgcn_s_setprio(0);
     if constexpr (PX != 1 || EDGE != 0) {
+        // (written out, not enc_clear_next_slot: through the call the 8x8x8 instantiations' text changes)
         if (blockIdx.x == 0 && P.replay_clear) {
 #pragma unroll
             for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
@@ -549,7 +548,7 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(DecodeParams P, Eg
         }
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
-        decode_tile<D, 1, (NG > 1), true, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadStream<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag});
+        decode_tile<D, (NG > 1), true, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadStream<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag});
         // the region receives the next group's window: after a block store (its rows are read by every
         // wave of the block) the whole block must be past it (block-uniform condition, as dec_store_tile's)
         if (i + 1 < NG) {
@@ -665,7 +664,7 @@ __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(DecodeParams P
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
         uint32_t outw[D][NW];
-        decode_tile<D, 1, false, true, true>(P, wl, lane, cube0, [] {},
+        decode_tile<D, false, true, true>(P, wl, lane, cube0, [] {},
                                              ReloadStream<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag},
                                              &outw[0][0], &valid);
         const uint32_t s0 = ch == 0 ? rgb_put_sel(0, 0) : ch == 1 ? rgb_put_sel(1, 0) : rgb_put_sel(2, 0);

@@ -9,7 +9,6 @@ namespace dct3d {
 // =============================================================================================
 // Fused encode
 // =============================================================================================
-// Loads row y = j of frames 0..D-1 of cube g (row layout).
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
@@ -18,30 +17,50 @@ typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 // and last row and exists nowhere in memory: row y of a cube is frame row min(y, h - 1), and the cube of
 // the last column, when w % 8 = n != 0, holds its n pixels and then pixel w - 1 again.  The frames are
 // dense (row stride w pixels), so a row is byte aligned: the 8-byte accesses carry that alignment in their
-// type.  When w >= 8 the ragged cube loads the 8 pixels that end at w - 1 (edge_src moves the address back
+// type.  When w >= 8 the ragged cube loads the 8 pixels that end at w - 1 (row_src moves the address back
 // by sh = 8 - n pixels) and edge_fix shifts them down and fills the tail; when w < 8 (one cube column) the
 // pixels are loaded one byte at a time, clamped.  No access leaves the frames.
 // ---------------------------------------------------------------------------------------------
 typedef u32x2_t u32x2_u_t __attribute__((aligned(1)));
-struct EdgeSrc {
-    const uint8_t* p;  // PX bytes per pixel: the row's first loaded pixel, frame 0 of the stack
-    uint32_t sh;       // pixels the loaded 8 lie before the cube's column (0: a cube inside the frame, or w < 8)
+// Cube g -> its stack s, its index r within the stack, its block row and column
+struct CubePos {
+    uint32_t s, r, by, bx;
 };
-template <int PX>
-__device__ __forceinline__ EdgeSrc edge_src(const uint8_t* raster, uint64_t stack_stride, uint32_t width,
-                                            uint32_t height, uint32_t s, uint32_t by, uint32_t bx, int y) {
-    const uint32_t row = min(by * 8 + (uint32_t)y, height - 1);
-    uint32_t x0 = bx * 8, sh = 0;
-    if (x0 + 8 > width && width >= 8) {
-        sh = x0 + 8 - width;
-        x0 = width - 8;
-    }
-    return EdgeSrc{raster + (size_t)s * stack_stride + (size_t)PX * ((size_t)row * width + x0), sh};
+__device__ __forceinline__ CubePos cube_pos(const EncodeParams& P, uint32_t g) {
+    const uint32_t s = fdiv(g, P.div_cps);
+    const uint32_t r = g - s * P.cubes_per_stack;
+    const uint32_t by = fdiv(r, P.div_nbx);
+    return CubePos{s, r, by, r - by * P.nbx};
 }
-// the 8 PX bytes of 8 pixels from p (width >= 8), or of pixels min(i, width - 1) (width < 8: p is the row's start)
-template <int PX>
-__device__ __forceinline__ void edge_load(const uint8_t* p, uint32_t width, uint2 (&w)[PX]) {
-    if (width >= 8) {  // uniform
+// Row y of the cube at c, frame 0 of its stack (PX bytes per pixel; stack_stride in bytes, width in pixels)
+struct RowSrc {
+    const uint8_t* p;  // the row's first loaded pixel
+    uint32_t sh;       // EDGE: pixels the loaded 8 lie before the cube's column (0: a cube inside the frame, or w < 8)
+};
+template <int PX, int EDGE>
+__device__ __forceinline__ RowSrc row_src(const uint8_t* raster, uint64_t stack_stride, uint32_t width,
+                                          uint32_t height, const CubePos& c, int y) {
+    if constexpr (EDGE) {
+        const uint32_t row = min(c.by * 8 + (uint32_t)y, height - 1);
+        uint32_t x0 = c.bx * 8, sh = 0;
+        if (x0 + 8 > width && width >= 8) {
+            sh = x0 + 8 - width;
+            x0 = width - 8;
+        }
+        return RowSrc{raster + (size_t)c.s * stack_stride + (size_t)PX * ((size_t)row * width + x0), sh};
+    } else {
+        if constexpr (PX == 1) return RowSrc{raster + (size_t)c.s * stack_stride + (size_t)(c.by * 8 + y) * width + c.bx * 8, 0u};
+        else return RowSrc{raster + (size_t)c.s * stack_stride + PX * ((size_t)(c.by * 8 + y) * width + c.bx * 8), 0u};
+    }
+}
+// The PX * 8 bytes of a row's 8 pixels from p (8-byte aligned: the width is a multiple of 8).  EDGE: byte
+// aligned (width >= 8), or pixels min(i, width - 1) one byte at a time (width < 8: p is the row's start)
+template <int PX, int EDGE>
+__device__ __forceinline__ void row_load(const uint8_t* p, uint32_t width, uint2 (&w)[PX]) {
+    if constexpr (!EDGE) {
+#pragma unroll
+        for (int i = 0; i < PX; i++) w[i] = *(const uint2*)(p + 8 * i);
+    } else if (width >= 8) {  // uniform
 #pragma unroll
         for (int i = 0; i < PX; i++) {
             const u32x2_t t = *(const u32x2_u_t*)(p + 8 * i);
@@ -71,41 +90,8 @@ __device__ __forceinline__ uint2 edge_fix(uint2 v, uint32_t sh) {
 }
 // sh of cube g (the RGB kernels apply edge_fix after the channel pick)
 __device__ __forceinline__ uint32_t edge_sh(const EncodeParams& P, uint32_t g) {
-    const uint32_t r = g - fdiv(g, P.div_cps) * P.cubes_per_stack;
-    const uint32_t bx = r - fdiv(r, P.div_nbx) * P.nbx;
+    const uint32_t bx = cube_pos(P, g).bx;
     return (bx * 8 + 8 > P.width && P.width >= 8) ? bx * 8 + 8 - P.width : 0u;
-}
-
-template <int D, bool NTL = false, int EDGE = 0>
-__device__ __forceinline__ void load_rows(const EncodeParams& P, uint32_t g, bool valid, int j, uint2 (&raw)[D]) {
-    if (valid) {
-        const uint32_t s = fdiv(g, P.div_cps);
-        const uint32_t r = g - s * P.cubes_per_stack;
-        const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<1>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
-#pragma unroll
-            for (int z = 0; z < D; z++) {
-                uint2 w[1];
-                edge_load<1>(e.p + (size_t)z * P.plane, P.width, w);
-                raw[z] = edge_fix(w[0], e.sh);
-            }
-            return;
-        }
-        const uint8_t* src = P.raster + (size_t)s * P.stack_stride + (size_t)(by * 8 + j) * P.width + bx * 8;
-#pragma unroll
-        for (int z = 0; z < D; z++) {
-            if constexpr (NTL) {
-                const u32x2_t t = __builtin_nontemporal_load((const u32x2_t*)(src + (size_t)z * P.plane));
-                raw[z] = make_uint2(t.x, t.y);
-            } else {
-                raw[z] = *(const uint2*)(src + (size_t)z * P.plane);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int z = 0; z < D; z++) raw[z] = make_uint2(0u, 0u);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -130,10 +116,6 @@ constexpr uint32_t rgb_pick_sel2(int ch) {  // perm(w2, t, .): the bytes of w2 a
     }
     return s;
 }
-__device__ __forceinline__ void rgb_load24(const uint8_t* src, uint2 (&w)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) w[i] = *(const uint2*)(src + 8 * i);
-}
 __device__ __forceinline__ uint2 rgb_pick8(const uint2 (&w)[3], int ch) {
     const uint32_t s1 = ch == 0 ? rgb_pick_sel1(0) : ch == 1 ? rgb_pick_sel1(1) : rgb_pick_sel1(2);
     const uint32_t s2 = ch == 0 ? rgb_pick_sel2(0) : ch == 1 ? rgb_pick_sel2(1) : rgb_pick_sel2(2);
@@ -147,59 +129,70 @@ __device__ __forceinline__ uint32_t enc_out_cube(const EncodeParams& P, uint32_t
     if constexpr (PX == 1) return g;
     else return g + (2u * fdiv(g, P.div_cps) + (uint32_t)ch) * P.cubes_per_stack;
 }
-// load_rows for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
-// (EDGE: the ragged cube's 8 pixels end at w - 1; the caller applies edge_fix to each picked channel)
-template <int D, int EDGE = 0>
-__device__ __forceinline__ void load_rows_rgb(const EncodeParams& P, uint32_t g, bool valid, int j, uint2 (&raw)[D][3]) {
+
+// ---------------------------------------------------------------------------------------------
+// Row loaders.  Row y of N frames of cube g, the first one frame ZM * h: the 8-lane kernels load frames
+// 0 .. D - 1 (N = D, ZM = 0), a lane (k, h) of the 16-lane kernels row k of frames 4h .. 4h + 3 (N = 4, ZM = 4).
+// Zero past the last cube.  (Non-temporal row loads lost: profiles/r01/encode_variant_sweep.txt.)
+// ---------------------------------------------------------------------------------------------
+// Frame ZM * h + z from frame 0's address p.  (Each path keeps the order its sum had in the separate loaders:
+// the other order changes the register allocation of the 16-lane kernels.)
+template <int ZM, int EDGE>
+__device__ __forceinline__ const uint8_t* frame_src(const uint8_t* p, int h, int z, uint64_t plane) {
+    if constexpr (EDGE) return p + (size_t)(ZM * h + z) * plane;
+    else return p + (size_t)(ZM * h) * plane + (size_t)z * plane;
+}
+// The rows' full PX * 8 bytes (Row = uint2: grey; uint2[3]: packed RGB24, P.plane and P.stack_stride in bytes,
+// P.width in pixels).  EDGE: the grey rows as the padded raster's; the RGB callers apply edge_fix to each
+// picked channel (edge_sh).
+template <int N, int ZM, int EDGE, class Row>
+__device__ __forceinline__ void load_cube_rows(const EncodeParams& P, uint32_t g, bool valid, int y, int h,
+                                               Row (&raw)[N]) {
+    constexpr int PX = sizeof(Row) / sizeof(uint2);
     if (valid) {
-        const uint32_t s = fdiv(g, P.div_cps);
-        const uint32_t r = g - s * P.cubes_per_stack;
-        const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
+        const RowSrc e = row_src<PX, EDGE>(P.raster, P.stack_stride, P.width, P.height, cube_pos(P, g), y);
 #pragma unroll
-            for (int z = 0; z < D; z++) edge_load<3>(e.p + (size_t)z * P.plane, P.width, raw[z]);
-            return;
+        for (int z = 0; z < N; z++) {
+            const uint8_t* src = frame_src<ZM, EDGE>(e.p, h, z, P.plane);
+            if constexpr (PX == 1) {
+                uint2 w[1];
+                row_load<1, EDGE>(src, P.width, w);
+                raw[z] = edge_fix(w[0], e.sh);
+            } else {
+                row_load<PX, EDGE>(src, P.width, raw[z]);
+            }
         }
-        const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
-#pragma unroll
-        for (int z = 0; z < D; z++) rgb_load24(src + (size_t)z * P.plane, raw[z]);
     } else {
 #pragma unroll
-        for (int z = 0; z < D; z++)
+        for (int z = 0; z < N; z++) {
+            if constexpr (PX == 1) {
+                raw[z] = make_uint2(0u, 0u);
+            } else {
 #pragma unroll
-            for (int i = 0; i < 3; i++) raw[z][i] = make_uint2(0u, 0u);
+                for (int i = 0; i < PX; i++) raw[z][i] = make_uint2(0u, 0u);
+            }
+        }
     }
 }
-
-// the rows of channel ch alone (the rare path's reload), one row's 24 bytes in registers at a time
-template <int D, int EDGE = 0>
-__device__ __forceinline__ void load_rows_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int j, int ch,
-                                                 uint2 (&raw)[D]) {
+// The rows of channel ch alone (the rare paths' reloads, the fused encode's one channel per launch): one
+// row's 24 bytes in registers at a time.  Grey: the rows themselves.
+template <int N, int ZM, int PX, int EDGE>
+__device__ __forceinline__ void load_channel_rows(const EncodeParams& P, uint32_t g, bool valid, int y, int h, int ch,
+                                                  uint2 (&raw)[N]) {
+    if constexpr (PX == 1) {
+        load_cube_rows<N, ZM, EDGE>(P, g, valid, y, h, raw);
+    } else {
 #pragma unroll
-    for (int z = 0; z < D; z++) raw[z] = make_uint2(0u, 0u);
-    if (valid) {
-        const uint32_t s = fdiv(g, P.div_cps);
-        const uint32_t r = g - s * P.cubes_per_stack;
-        const uint32_t by = fdiv(r, P.div_nbx), bx = r - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, s, by, bx, j);
+        for (int z = 0; z < N; z++) raw[z] = make_uint2(0u, 0u);
+        if (valid) {
+            const RowSrc e = row_src<PX, EDGE>(P.raster, P.stack_stride, P.width, P.height, cube_pos(P, g), y);
 #pragma unroll
-            for (int z = 0; z < D; z++) {
-                uint2 w[3];
-                edge_load<3>(e.p + (size_t)z * P.plane, P.width, w);
+            for (int z = 0; z < N; z++) {
+                uint2 w[PX];
+                row_load<PX, EDGE>(frame_src<ZM, EDGE>(e.p, h, z, P.plane), P.width, w);
                 raw[z] = edge_fix(rgb_pick8(w, ch), e.sh);
                 asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
             }
-            return;
-        }
-        const uint8_t* src = P.raster + (size_t)s * P.stack_stride + 3 * ((size_t)(by * 8 + j) * P.width + bx * 8);
-#pragma unroll
-        for (int z = 0; z < D; z++) {
-            uint2 w[3];
-            rgb_load24(src + (size_t)z * P.plane, w);
-            raw[z] = rgb_pick8(w, ch);
-            asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
         }
     }
 }
@@ -331,20 +324,16 @@ __device__ __forceinline__ void forward_cube(float (&a)[D][8], int m, int c, int
     }
 }
 
-template <bool NT>
+// The int32 output goes out non-temporally (plain stores lost: profiles/r01/encode_variant_sweep.txt)
 __device__ __forceinline__ void store16(void* p, const int4& v) {
-    if constexpr (NT) {
-        i32x4_t t = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(t, (i32x4_t*)p);
-    } else {
-        *(int4*)p = v;
-    }
+    i32x4_t t = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(t, (i32x4_t*)p);
 }
 
 // Stage the wave's 8 quantised cubes through LDS (face-padded cube-major) and store them 1 KiB per
 // instruction (lane (c, j) holds qv[ky][kx'] of cube c, kz = j (8x8x8) / j >> 1 (8x8x4)).
 // PX = 3 (packed RGB24): the cubes of channel ch, each to its place in the [stack][channel] blocks.
-template <int D, bool NT, int PX = 1>
+template <int D, int PX = 1>
 __device__ __forceinline__ void enc_stage_store(const EncodeParams& P, const int32_t (&qv)[8][(D == 8) ? 8 : 4],
                                                 char* wl, int lane, uint32_t cube0, int ch = 0) {
     constexpr int CS = 64 * D;
@@ -383,11 +372,11 @@ __device__ __forceinline__ void enc_stage_store(const EncodeParams& P, const int
             if (rcube0 + cc < P.n_cubes) {
                 const int4 v = *(const int4*)(wl + (cc * D + face) * kFace + w * 16);
                 if constexpr (PX == 1) {
-                    store16<NT>(outb + (size_t)q * 16, v);
+                    store16(outb + (size_t)q * 16, v);
                 } else {  // a store instruction lies within one cube: its cube is wave-uniform
                     static_assert((CS / 4) % 64 == 0, "whole store instructions per cube");
                     char* ob = (char*)(P.out + (size_t)enc_out_cube<PX>(P, rcube0 + t * 64 / (CS / 4), ch) * CS);
-                    store16<NT>(ob + (size_t)(q % (CS / 4)) * 16, v);
+                    store16(ob + (size_t)(q % (CS / 4)) * 16, v);
                 }
             }
         }
@@ -514,15 +503,15 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
 // Everything after the row loads, for the 8 cubes from cube0 (8x8x4): statistics, transform, quantise +
 // certify, staged 1 KiB stores, the exact fold of the uncertified coefficients (enc4_replay).
 // PX = 3 (packed RGB24): raw = the rows of channel ch, whose cubes go to its [stack][channel] blocks.
-template <int D, bool NT, int PX = 1, int EDGE = 0>
-__device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (&raw)[D], char* wl,
+template <int PX = 1, int EDGE = 0>
+__device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (&raw)[4], char* wl,
                                             const float4* tab, int lane, uint32_t cube0, int ch = 0) {
-    static_assert(D == 4, "8x8x8 encodes in encode16_kernel");
-    constexpr int NB = (D == 8) ? 8 : 4;      // kx values per lane in the face layout
+    constexpr int D = 4;  // 8x8x8 encodes in encode16_kernel
+    constexpr int NB = 4;                     // kx values per lane in the face layout
     constexpr int NI = 7 + NB;                // distinct (ky + kx') sums per lane
     const int c = lane >> 3, j = lane & 7;
-    const int kz = (D == 8) ? j : (j >> 1);
-    const int kx0 = (D == 8) ? 0 : (j & 1) * 4;
+    const int kz = j >> 1;
+    const int kx0 = (j & 1) * 4;
     const int so = kz + kx0;
     const uint32_t g = cube0 + c;
     const bool valid = g < P.n_cubes;
@@ -574,59 +563,59 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
     }
     if (!valid) fm = 0u;
 
-    enc_stage_store<D, NT, PX>(P, qv, wl, lane, cube0, ch);
+    enc_stage_store<D, PX>(P, qv, wl, lane, cube0, ch);
 
     // rare path: the rows again (after the stores: held across them they cost occupancy), the fold
     if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {  // wave-uniform
         uint2 px[D];
-        if constexpr (PX == 1) {
-            load_rows<D, false, EDGE>(P, g, valid, j, px);
-        } else {
-            load_rows_rgb_ch<D, EDGE>(P, g, valid, j, ch, px);
-        }
+        load_channel_rows<D, 0, PX, EDGE>(P, g, valid, j, 0, ch, px);
         enc4_replay<PX>(P, px, fm, wl, lane, cube0, ch);
     }
 }
 
+// The next call's counter slot zeroed, both halves (the two slots alternate between calls; as
+// dec_clear_next_slot).  Block 0 calls it when P.replay_clear is set; the test stays with the caller (inside
+// this function the compiler inverts it, and the kernels' text changes).
+__device__ __forceinline__ void enc_clear_next_slot(const EncodeParams& P) {
+#pragma unroll
+    for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
+}
+
 // One wave = one group of 8 consecutive cubes (register-prefetch loops over several groups spill
 // and were 25-40 % slower: profiles/r01/encode_variant_sweep.txt).
-template <int D, bool NT, bool NTL = false, int EDGE = 0>
+template <int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
+    constexpr int D = 4;  // 8x8x8 encodes in encode16_kernel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
     __shared__ float4 s_tab[kTabN];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;
     uint2 raw[D];
     __builtin_amdgcn_s_setprio(3);
-    load_rows<D, NTL, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw);  // in flight first
+    load_cube_rows<D, 0, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, raw);  // in flight first
     __builtin_amdgcn_s_setprio(0);
-    if (blockIdx.x == 0 && P.replay_clear) {
-#pragma unroll
-        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
-    }
+    if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     enc_tables(P, s_tab, lane);
-    encode_body<D, NT, 1, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
+    encode_body<1, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
 }
 
 // Packed RGB24 (dct3d_encode_stacks_rgb_dev, 8x8x4): the wave owns the three channels of its 8 cubes'
 // tile.  Each lane loads its rows' 24 bytes once and keeps them packed (24 registers); per channel the
 // rows are picked out of them (rgb_pick8) and encode_body runs as for a grey plane, its cubes going to
 // the channel's [stack][channel] block.  P.n_cubes counts RGB cubes (a third of the output's).
-template <int D, bool NT, int EDGE = 0>
+template <int EDGE = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
+    constexpr int D = 4;  // 8x8x8 encodes in encode16_rgb_kernel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
     __shared__ float4 s_tab[kTabN];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t cube0 = P.g_base + (xcd_tile<64>() * kWavesPerBlock + wave) * kCubesPerWave;
     uint2 raw3[D][3];
     __builtin_amdgcn_s_setprio(3);
-    load_rows_rgb<D, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, raw3);
+    load_cube_rows<D, 0, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, raw3);
     __builtin_amdgcn_s_setprio(0);
-    if (blockIdx.x == 0 && P.replay_clear) {
-#pragma unroll
-        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
-    }
+    if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     enc_tables(P, s_tab, lane);
 #pragma unroll 1
@@ -643,7 +632,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
 #pragma unroll
             for (int z = 0; z < D; z++) raw[z] = edge_fix(raw[z], sh);
         }
-        encode_body<D, NT, 3, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
+        encode_body<3, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
         wave_lds_sync();  // the next channel reuses the wave's region
     }
 }
@@ -686,10 +675,10 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
         const uint32_t s = g / R.cubes_per_stack;
         const uint32_t r = g - s * R.cubes_per_stack;
         const uint32_t by = r / R.nbx, bx = r - by * R.nbx;
-        if constexpr (EDGE) {  // the main path's padded values (edge_src, edge_load, edge_fix)
-            const EdgeSrc e = edge_src<PX>(R.raster, R.stack_stride, R.width, R.height, s, by, bx, y);
+        if constexpr (EDGE) {  // the main path's padded values (row_src, row_load, edge_fix)
+            const RowSrc e = row_src<PX, 1>(R.raster, R.stack_stride, R.width, R.height, CubePos{s, r, by, bx}, y);
             uint2 w[PX];
-            edge_load<PX>(e.p + (size_t)z * R.plane, R.width, w);
+            row_load<PX, 1>(e.p + (size_t)z * R.plane, R.width, w);
             if constexpr (PX == 1) in.px = edge_fix(w[0], e.sh);
             else in.px = edge_fix(rgb_pick8(w, R.ch), e.sh);
         } else if constexpr (PX == 1) {
@@ -698,8 +687,8 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
             in.px = *(const uint2*)src;
         } else {  // (R.plane, R.stack_stride: bytes, R.width: pixels)
             uint2 w[3];
-            rgb_load24(R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
-                           3 * ((size_t)(by * 8 + y) * R.width + bx * 8), w);
+            row_load<3, 0>(R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
+                               3 * ((size_t)(by * 8 + y) * R.width + bx * 8), R.width, w);
             in.px = rgb_pick8(w, R.ch);
         }
         in.gr = *(const uint2*)(R.group_of + (size_t)k * CS + lane * 8);
@@ -782,93 +771,6 @@ constexpr int kE16Lds = 4 * kE16TC;
 constexpr int kE16S16F = 144;
 constexpr int kE16S16C = 8 * kE16S16F;
 static_assert(4 * kE16S16C <= kE16Lds, "int16 staging of the wave's 4 cubes fits its region");
-
-// rows of the lane's cube (row y = k of frames 4h .. 4h + 3), zero past the end
-template <int EDGE = 0>
-__device__ __forceinline__ void e16_load(const EncodeParams& P, uint32_t g, bool valid, int k, int h, uint2 (&raw)[4]) {
-    if (valid) {
-        const uint32_t st = fdiv(g, P.div_cps);
-        const uint32_t rr = g - st * P.cubes_per_stack;
-        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<1>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                uint2 w[1];
-                edge_load<1>(e.p + (size_t)(4 * h + r) * P.plane, P.width, w);
-                raw[r] = edge_fix(w[0], e.sh);
-            }
-            return;
-        }
-        const uint8_t* src = P.raster + (size_t)st * P.stack_stride + (size_t)(by * 8 + k) * P.width + bx * 8 +
-                             (size_t)(4 * h) * P.plane;
-#pragma unroll
-        for (int r = 0; r < 4; r++) raw[r] = *(const uint2*)(src + (size_t)r * P.plane);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; r++) raw[r] = make_uint2(0u, 0u);
-    }
-}
-
-// e16_load for a packed RGB24 raster: the rows' 24 bytes (P.plane, P.stack_stride: bytes, P.width: pixels)
-// (EDGE: as load_rows_rgb)
-template <int EDGE = 0>
-__device__ __forceinline__ void e16_load_rgb(const EncodeParams& P, uint32_t g, bool valid, int k, int h,
-                                             uint2 (&raw)[4][3]) {
-    if (valid) {
-        const uint32_t st = fdiv(g, P.div_cps);
-        const uint32_t rr = g - st * P.cubes_per_stack;
-        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
-#pragma unroll
-            for (int r = 0; r < 4; r++) edge_load<3>(e.p + (size_t)(4 * h + r) * P.plane, P.width, raw[r]);
-            return;
-        }
-        const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
-                             (size_t)(4 * h) * P.plane;
-#pragma unroll
-        for (int r = 0; r < 4; r++) rgb_load24(src + (size_t)r * P.plane, raw[r]);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int i = 0; i < 3; i++) raw[r][i] = make_uint2(0u, 0u);
-    }
-}
-
-// the rows of channel ch alone (the rare paths' reload), one row's 24 bytes in registers at a time
-template <int EDGE = 0>
-__device__ __forceinline__ void e16_load_rgb_ch(const EncodeParams& P, uint32_t g, bool valid, int k, int h, int ch,
-                                                uint2 (&raw)[4]) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) raw[r] = make_uint2(0u, 0u);
-    if (valid) {
-        const uint32_t st = fdiv(g, P.div_cps);
-        const uint32_t rr = g - st * P.cubes_per_stack;
-        const uint32_t by = fdiv(rr, P.div_nbx), bx = rr - by * P.nbx;
-        if constexpr (EDGE) {
-            const EdgeSrc e = edge_src<3>(P.raster, P.stack_stride, P.width, P.height, st, by, bx, k);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                uint2 w[3];
-                edge_load<3>(e.p + (size_t)(4 * h + r) * P.plane, P.width, w);
-                raw[r] = edge_fix(rgb_pick8(w, ch), e.sh);
-                asm volatile("" : "+v"(raw[r].x), "+v"(raw[r].y));
-            }
-            return;
-        }
-        const uint8_t* src = P.raster + (size_t)st * P.stack_stride + 3 * ((size_t)(by * 8 + k) * P.width + bx * 8) +
-                             (size_t)(4 * h) * P.plane;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            uint2 w[3];
-            rgb_load24(src + (size_t)r * P.plane, w);
-            raw[r] = rgb_pick8(w, ch);
-            asm volatile("" : "+v"(raw[r].x), "+v"(raw[r].y));
-        }
-    }
-}
 
 // Statistics, passes X / Z / Y, quantise + certify, exact DC.  Uncertified coefficients are returned
 // as the lane's mask fm (bit 4 ky + e: coefficient (kz = k, ky, kx = 4h + e)); the caller replays them.
@@ -1110,14 +1012,13 @@ static_assert(kMaxGroupsDev * (4 + 8) <= kE16Lds, "exact-replay scratch fits the
 // Diagnostic traversal (MODES 4 / 5): wave slot s, counted strip-major (stack, strip, block row, column in
 // the strip), -> the cube it encodes (the reference's cube-major index, so the output is unchanged)
 __device__ __forceinline__ uint32_t strip_cube(const EncodeParams& P, uint32_t s) {
-    const uint32_t st = fdiv(s, P.div_cps);
-    const uint32_t r = s - st * P.cubes_per_stack;
-    const uint32_t strip = fdiv(r, P.div_strip_cubes);
-    const uint32_t rr = r - strip * P.strip_cubes;
+    const CubePos c = cube_pos(P, s);
+    const uint32_t strip = fdiv(c.r, P.div_strip_cubes);
+    const uint32_t rr = c.r - strip * P.strip_cubes;
     const uint32_t by = fdiv(rr, P.div_strip_w);
-    return st * P.cubes_per_stack + by * P.nbx + strip * P.strip_w + (rr - by * P.strip_w);
+    return c.s * P.cubes_per_stack + by * P.nbx + strip * P.strip_w + (rr - by * P.strip_w);
 }
-template <bool NT, int MODE = 0, int EDGE = 0>
+template <int MODE = 0, int EDGE = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) void encode16_kernel(EncodeParams P) {
     constexpr int CS = 512;
     // MODE 4 / 5: MODE 1 / 0 with the strip traversal (diagnostic sweep)
@@ -1150,13 +1051,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
         // default oldest-first issue they queue behind the computing waves' VALU work, and a box whose
         // encode loses the overlap of memory and compute that way runs 10 % slower (variant_sweep.txt)
         if constexpr (!MEM) __builtin_amdgcn_s_setprio(3);
-        e16_load<EDGE>(P, g, valid, k, h, raw);
+        load_cube_rows<4, 4, EDGE>(P, g, valid, k, h, raw);
         if constexpr (!MEM) __builtin_amdgcn_s_setprio(0);
     }
-    if (!MEM && !COMP && blockIdx.x == 0 && P.replay_clear) {
-#pragma unroll
-        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
-    }
+    if (!MEM && !COMP && blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     char* wl = lds + wave * kE16Lds;
     int32_t qv[8][4];
@@ -1190,7 +1088,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
         wave_lds_sync();
         if (rare) {
             uint2 raw2[4];
-            e16_load<EDGE>(P, g, valid, k, h, raw2);
+            load_cube_rows<4, 4, EDGE>(P, g, valid, k, h, raw2);
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
@@ -1206,7 +1104,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
             const int cc = q >> 7, face = (q >> 4) & 7, w = q & 15;
             if (cube0 + cc < P.n_cubes && (!COMP || P.width == 0u)) {
                 const uint2 v = *(const uint2*)(wl + cc * kE16S16C + face * kE16S16F + w * 8);
-                store16<NT>(outb + (size_t)q * 16, make_int4((int)(int16_t)v.x, (int)v.x >> 16, (int)(int16_t)v.y,
+                store16(outb + (size_t)q * 16, make_int4((int)(int16_t)v.x, (int)v.x >> 16, (int)(int16_t)v.y,
                                                              (int)v.y >> 16));
             }
         }
@@ -1257,11 +1155,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
 // (24 registers) across three passes, one per channel: the channel's rows are picked out of them
 // (rgb_pick8), e16_body, the int16 staging, the second certificate, the stores and the exact fold run as
 // for a grey plane, and the cubes go to the channel's [stack][channel] block.  The replay paths reload
-// their rows through the same pick (e16_load_rgb_ch, replay_load<8, 3>).  P.n_cubes counts RGB cubes (a
+// their rows through the same pick (load_channel_rows, replay_load<8, 3>).  P.n_cubes counts RGB cubes (a
 // third of the output's).  Occupancy: the packed rows on top of the main path's 72 registers do not fit 7
 // waves per SIMD (73 registers); the kernel takes what it needs up to 4 waves per SIMD (128).
 // ---------------------------------------------------------------------------------------------
-template <bool NT, int EDGE = 0>
+template <int EDGE = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void encode16_rgb_kernel(EncodeParams P) {
     constexpr int CS = 512;
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kE16Lds];
@@ -1274,13 +1172,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         const int lane = threadIdx.x & 63;
         const uint32_t g = cube0 + (lane >> 5) * 2 + ((lane & 15) >> 3);
         __builtin_amdgcn_s_setprio(3);
-        e16_load_rgb<EDGE>(P, g, g < P.n_cubes, lane & 7, (lane >> 4) & 1, raw3);
+        load_cube_rows<4, 4, EDGE>(P, g, g < P.n_cubes, lane & 7, (lane >> 4) & 1, raw3);
         __builtin_amdgcn_s_setprio(0);
     }
-    if (blockIdx.x == 0 && P.replay_clear) {
-#pragma unroll
-        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
-    }
+    if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     enc_tables(P, s_tab, threadIdx.x & 63);
 #pragma unroll 1
@@ -1316,7 +1211,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         wave_lds_sync();
         if (rare) {
             uint2 raw2[4];
-            e16_load_rgb_ch<EDGE>(P, g, valid, k, h, ch, raw2);
+            load_channel_rows<4, 4, 3, EDGE>(P, g, valid, k, h, ch, raw2);
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
@@ -1333,7 +1228,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
             if (cube0 + cc < P.n_cubes) {
                 const uint2 v = *(const uint2*)(wl + cc * kE16S16C + face * kE16S16F + w * 8);
                 char* ob = (char*)(P.out + (size_t)enc_out_cube<3>(P, cube0 + cc, ch) * CS);
-                store16<NT>(ob + (q & 127) * 16, make_int4((int)(int16_t)v.x, (int)v.x >> 16, (int)(int16_t)v.y,
+                store16(ob + (q & 127) * 16, make_int4((int)(int16_t)v.x, (int)v.x >> 16, (int)(int16_t)v.y,
                                                            (int)v.y >> 16));
             }
         }

@@ -160,7 +160,7 @@ int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n
 // Launchers
 // =============================================================================================
 // Encode: 8x8x8 = encode16_kernel (16 lanes per cube, in-wave exact replay, one launch per call);
-// 8x8x4 = encode_kernel<4> (8 lanes per cube, in-wave exact replay, one launch).  Both store the int32
+// 8x8x4 = encode_kernel (8 lanes per cube, in-wave exact replay, one launch).  Both store the int32
 // output non-temporally.  The variants that lost (8 lanes per cube at 8x8x8, plain stores, NT loads,
 // LDS-padded occupancy) are recorded in profiles/r01/encode_variant_sweep.txt, not built.
 namespace {
@@ -173,8 +173,8 @@ void launch_enc_eg_t(const EncodeParams& P, const EgFusedParams& E, hipStream_t 
 int launch_encode(int D, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(enc_grid(D, P));
-    if (D == 8) hipLaunchKernelGGL((encode16_kernel<true, 0>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((encode_kernel<4, true>), grid, dim3(kBlock), 0, st, P);
+    if (D == 8) hipLaunchKernelGGL((encode16_kernel<>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((encode_kernel<>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -190,8 +190,8 @@ int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipSt
 int launch_decode(int D, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(dec_grid(D, P.n_cubes));
-    if (D == 8) hipLaunchKernelGGL((decode_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((decode_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
+    if (D == 8) hipLaunchKernelGGL((decode_kernel<8>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((decode_kernel<4>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

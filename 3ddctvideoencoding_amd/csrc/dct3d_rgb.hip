@@ -15,8 +15,8 @@ namespace dct3d {
 int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(enc_grid(D, P));
-    if (D == 8) hipLaunchKernelGGL((encode16_rgb_kernel<true>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((encode_rgb_kernel<4, true>), grid, dim3(kBlock), 0, st, P);
+    if (D == 8) hipLaunchKernelGGL((encode16_rgb_kernel<>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((encode_rgb_kernel<>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -24,8 +24,8 @@ int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st) {
 int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     const dim3 grid(dec_grid(D, P.n_cubes));
-    if (D == 8) hipLaunchKernelGGL((decode_rgb_kernel<8, 1>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((decode_rgb_kernel<4, 1>), grid, dim3(kBlock), 0, st, P);
+    if (D == 8) hipLaunchKernelGGL((decode_rgb_kernel<8>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((decode_rgb_kernel<4>), grid, dim3(kBlock), 0, st, P);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
