@@ -33,6 +33,7 @@ DCT3D_OPT_DEC_MARGIN, DCT3D_OPT_ENC_NO_RECHECK, DCT3D_OPT_EG_TWO_STEP, DCT3D_OPT
 DCT3D_OPT_EG_FORCE_RETRY = 8
 DCT3D_OPT_EG_DEC_GROUPS = 9
 DCT3D_OPT_EG_FUSED_FRONT = 10
+DCT3D_OPT_QUANT_FORCE_TABLE = 11
 
 # Every symbol include/dct3d.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -48,6 +49,7 @@ ABI_SYMBOLS = (
     "dct3d_encode_frames", "dct3d_encode_frames_dev", "dct3d_decode_frames", "dct3d_decode_frames_dev",
     "dct3d_encode_eg_frames", "dct3d_encode_eg_frames_dev", "dct3d_eg_fetch_channel",
     "dct3d_decode_eg_frames", "dct3d_decode_eg_frames_dev",
+    "dct3d_ctx_set_quant", "dct3d_ctx_get_quant", "dct3d_plan_query_quant",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -119,6 +121,9 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [vp, vp, sz, vp]
         L.dct3d_ctx_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
         L.dct3d_plan_query.argtypes = [i32, i32, i32, C.POINTER(PlanInfo), vp, vp, vp, vp]
+        L.dct3d_plan_query_quant.argtypes = [i32, i32, i32, vp, i32, C.POINTER(PlanInfo), vp, vp, vp, vp]
+        L.dct3d_ctx_set_quant.argtypes = [vp, vp, i32]
+        L.dct3d_ctx_get_quant.argtypes = [vp, vp, i32]
         L.dct3d_eg_encode_dev.argtypes = [vp, vp, u64, C.c_uint8, i32, vp, u64, C.POINTER(u64)]
         L.dct3d_encode_eg.argtypes = [vp, vp, i32, i32, i32, C.c_uint8, i32, C.POINTER(u64)]
         L.dct3d_encode_eg_dev.argtypes = [vp, vp, i32, i32, i32, C.c_uint8, i32, vp, u64, C.POINTER(u64)]
@@ -187,16 +192,63 @@ def _tptr(t) -> int:
     return t.data_ptr()
 
 
-def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8) -> dict:
-    """Host-side transform plan (no device): Java fold tables + certification tables."""
+def _steps_array(steps) -> np.ndarray:
+    """A quantiser table as the C-ABI takes it (int32, contiguous); values must be whole numbers."""
+    a = np.asarray(steps)
+    if a.ndim != 1 or not np.all(a == np.floor(a)):
+        raise ValueError("a quantiser table is a 1-D array of integer steps")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def quant_table(quality: int, block_d: int = 8) -> np.ndarray:
+    """The scalar family of quantiser tables: step[s] = max(1, quality * s) clipped to 255, s = kx + ky + kz,
+    8 + 8 + block_d - 2 entries.  quant_table(5) is the reference codec's quantiser."""
+    s = np.arange(8 + 8 + block_d - 2, dtype=np.int64)
+    return np.clip(int(quality) * s, 1, 255).astype(np.int32)
+
+
+def _step_cube(steps, shape) -> np.ndarray:
+    """step[kx + ky + kz] over a cube array's last three axes [.., bd, bh, bw], as fp64."""
+    st = _steps_array(steps)
+    bd, bh, bw = shape[-3:]
+    if st.size != bw + bh + bd - 2:
+        raise ValueError(f"the table of a {bw}x{bh}x{bd} block has {bw + bh + bd - 2} steps")
+    z, y, x = np.ogrid[:bd, :bh, :bw]
+    return st[x + y + z].astype(np.float64)
+
+
+def quantize_ref(dct_cubes: np.ndarray, steps) -> np.ndarray:
+    """The definition of the quantiser in numpy (Encoder.java:75-89 with step[x + y + z]): fp64 DCT coefficients
+    [.., bd, bh, bw] -> int32 Math.round(c / step): an IEEE double division, then exact half-up rounding
+    (floor(x + 0.5) misrounds the double below 0.5; Math.round does not)."""
+    d = np.asarray(dct_cubes, np.float64)
+    v = d / _step_cube(steps, d.shape)
+    f = np.floor(v)
+    return (f + (v - f >= 0.5)).astype(np.int32)  # v - f is exact: Math.round's floor(v + 1/2) in exact arithmetic
+
+
+def dequantize_ref(q_cubes: np.ndarray, steps) -> np.ndarray:
+    """Decoder.java:78-96 with step[x + y + z]: int32 [.., bd, bh, bw] -> fp64 (double) q * step (exact)."""
+    q = np.asarray(q_cubes)
+    return q.astype(np.float64) * _step_cube(steps, q.shape)
+
+
+def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8, steps=None) -> dict:
+    """Host-side transform plan (no device): Java fold tables + certification tables, for the quantiser
+    table `steps` (None: the reference's)."""
     cs = block_w * block_h * block_d
     info = PlanInfo()
     ng = np.empty(cs, np.int32)
     coef = np.empty(cs * 64, np.float64)
     gof = np.empty(cs * cs, np.uint8)
     K = np.empty(cs, np.float64)
-    _check(lib().dct3d_plan_query(block_w, block_h, block_d, C.byref(info), _ptr(ng), _ptr(coef), _ptr(gof), _ptr(K)),
-           "dct3d_plan_query")
+    if steps is None:
+        _check(lib().dct3d_plan_query(block_w, block_h, block_d, C.byref(info), _ptr(ng), _ptr(coef), _ptr(gof), _ptr(K)),
+               "dct3d_plan_query")
+    else:
+        st = _steps_array(steps)
+        _check(lib().dct3d_plan_query_quant(block_w, block_h, block_d, _ptr(st), st.size, C.byref(info), _ptr(ng),
+                                            _ptr(coef), _ptr(gof), _ptr(K)), "dct3d_plan_query_quant")
     return {"cube_size": info.cube_size, "n_mults": info.n_mults, "treeified": bool(info.treeified),
             "coef_dc": info.coef_dc, "dec_G": info.dec_G, "dec_E": info.dec_E, "dec_l1_max": info.dec_l1_max,
             "enc_rstep": np.array(info.enc_rstep[:]), "enc_G": np.array(info.enc_G[:]),
@@ -273,6 +325,22 @@ class Context:
         """Test / diagnostic option (DCT3D_OPT_*): changes how later calls reach their (identical)
         results, e.g. to drive a rare path.  0 restores the default."""
         _check(lib().dct3d_ctx_set_option(self._h, option, float(value)), "dct3d_ctx_set_option")
+
+    def set_quant(self, steps) -> None:
+        """The context's quantiser table: one integer step in [1, 255] per s = kx + ky + kz (bw + bh + bd - 2
+        entries; quant_table()), or None for the reference table.  Every later raster call encodes and decodes
+        with it.  Waits for the context's stream; not to be called while another thread has a call in flight."""
+        if steps is None:
+            _check(lib().dct3d_ctx_set_quant(self._h, None, 0), "dct3d_ctx_set_quant")
+        else:
+            st = _steps_array(steps)
+            _check(lib().dct3d_ctx_set_quant(self._h, _ptr(st), st.size), "dct3d_ctx_set_quant")
+
+    def quant(self) -> np.ndarray:
+        """The context's quantiser table (int32 [bw + bh + bd - 2])."""
+        st = np.empty(self.bw + self.bh + self.bd - 2, np.int32)
+        _check(lib().dct3d_ctx_get_quant(self._h, _ptr(st), st.size), "dct3d_ctx_get_quant")
+        return st
 
     def set_profiling(self, on: bool) -> None:
         _check(lib().dct3d_ctx_set_profiling(self._h, 1 if on else 0), "dct3d_ctx_set_profiling")

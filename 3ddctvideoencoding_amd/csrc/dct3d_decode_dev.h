@@ -179,6 +179,21 @@ struct ReloadCubes {  // from the int32 cube-major input
     }
 };
 
+template <int D>
+struct ReloadCubesQ {  // ReloadCubes with the quantiser's table (QT = 1): steps[s], s = kx + ky + kz
+    const int32_t* in;
+    const double* steps;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        constexpr int CS = 64 * D;
+#pragma unroll
+        for (int i = 0; i < CS / 64; i++) {
+            const int k = lane + 64 * i;
+            const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
+            cf[k] = (double)in[(size_t)g * CS + k] * steps[kx + ky + kz];
+        }
+    }
+};
+
 template <int D, class Reload>
 __device__ __attribute__((noinline)) const uint8_t* decode_replay_lane(const double* inv_coef_t, Reload reload,
                                                                        char* wl, int lane, uint32_t g, int src) {
@@ -378,10 +393,14 @@ __device__ __forceinline__ void dec_store_tile(const DecodeParams& P, char* wl, 
 // values from the stream.
 // KEEP (decode_rgb_kernel): no stores; the lane's words outw[z][wd] go to keep[z * NXC / 4 + wd] and the
 // lane's `valid` to *keep_valid.
-template <int D, bool LOOP = false, bool CODES = false, bool KEEP = false, int EDGE = 0, class AfterA, class Reload>
+// QT = 1 (dct3d_quant.hip): the lane's 11 steps, sums s = 4h + k + j, come from the quantiser's table qsteps
+// (fp64, [32]) by plain global loads: 256 bytes that every wave of the grid reads, so they stay in the
+// L1 / L2, and the wave's LDS region -- sized for 4 blocks per CU -- is untouched.
+template <int D, bool LOOP = false, bool CODES = false, bool KEEP = false, int EDGE = 0, int QT = 0, class AfterA,
+          class Reload>
 __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int lane, uint32_t cube0,
                                             AfterA&& after_a, const Reload& reload, uint32_t* keep = nullptr,
-                                            bool* keep_valid = nullptr) {
+                                            bool* keep_valid = nullptr, const double* qsteps = nullptr) {
     using G = DecGeom<D>;
     constexpr int CPW = G::CPW;
     constexpr int NXC = (D == 8) ? 4 : 8;  // x values per lane in layout C
@@ -408,13 +427,21 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
         for (int ky = 0; ky < 8; ky++) raw[ky] = *(const int4*)(src + ky * 32);
         if constexpr (CODES) {
             uint32_t l1 = 0, any = 0;
+            uint32_t sti[11];  // QT: the lane's steps as integers (<= 255: |q| * step < 2^23, dct3d_plan.h)
+            if constexpr (QT) {
+                const double* ts = qsteps + (4 * h + k);
+#pragma unroll
+                for (int j = 0; j < 11; j++) sti[j] = (uint32_t)ts[j];
+            }
 #pragma unroll
             for (int ky = 0; ky < 8; ky++) {
                 const uint32_t vv[4] = {(uint32_t)raw[ky].x, (uint32_t)raw[ky].y, (uint32_t)raw[ky].z, (uint32_t)raw[ky].w};
                 any |= vv[0] | vv[1] | vv[2] | vv[3];
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const uint32_t st = (e + ky) ? (uint32_t)(sb + 5 * (e + ky)) : (uint32_t)max(sb, 1);
+                    uint32_t st;
+                    if constexpr (QT) st = sti[e + ky];
+                    else st = (e + ky) ? (uint32_t)(sb + 5 * (e + ky)) : (uint32_t)max(sb, 1);
                     const uint32_t ms = __umul24(vv[e] >> 1, st);  // |q| * step
                     l1 += ms;
                     uint2 m = __builtin_bit_cast(uint2, (double)ms);
@@ -425,9 +452,15 @@ __device__ __forceinline__ void decode_tile(const DecodeParams& P, char* wl, int
             l1_f = any < 0x10000u ? (float)l1 : __builtin_inff();
         } else {
             double stp[11];
-            stp[0] = (double)max(sb, 1);
+            if constexpr (QT) {
+                const double* ts = qsteps + (4 * h + k);  // 4h + k + 10 <= 21 < 32
 #pragma unroll
-            for (int j = 1; j < 11; j++) stp[j] = (double)(sb + 5 * j);
+                for (int j = 0; j < 11; j++) stp[j] = ts[j];
+            } else {
+                stp[0] = (double)max(sb, 1);
+#pragma unroll
+                for (int j = 1; j < 11; j++) stp[j] = (double)(sb + 5 * j);
+            }
             double l1 = 0.0;
 #pragma unroll
             for (int ky = 0; ky < 8; ky++) {
@@ -586,8 +619,8 @@ __device__ __forceinline__ void dec_clear_next_slot(const DecodeParams& P) {
     }
 }
 
-template <int D, int EDGE = 0>
-__global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
+template <int D, int EDGE = 0, int QT = 0>
+__global__ __launch_bounds__(kBlock, 4) void decode_kernel(typename DecodeArgs<QT>::type P) {
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     char* wl = lds + wave * kDecWaveLds;
@@ -599,7 +632,11 @@ __global__ __launch_bounds__(kBlock, 4) void decode_kernel(DecodeParams P) {
     dec_clear_next_slot(P);
     dec_stage_tile<D>(wl, lane, v);
     wave_lds_sync();
-    decode_tile<D, false, false, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
+    if constexpr (QT)
+        decode_tile<D, false, false, false, EDGE, 1>(P, wl, lane, cube0, [] {}, ReloadCubesQ<D>{P.in, dec_steps(P)},
+                                                     nullptr, nullptr, dec_steps(P));
+    else
+        decode_tile<D, false, false, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadCubes<D>{P.in});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -651,8 +688,20 @@ struct ReloadCubesRgb {  // ReloadCubes for cube g of channel ch (dec_rgb_cube, 
     }
 };
 
-template <int D, int EDGE = 0>
-__global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
+template <int D>
+struct ReloadCubesRgbQ {  // ReloadCubesRgb with the quantiser's table (QT = 1)
+    const int32_t* in;
+    const double* steps;
+    FastDiv div_cps;
+    uint32_t cubes_per_stack;
+    int ch;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        ReloadCubesQ<D>{in, steps}(g + (2u * fdiv(g, div_cps) + (uint32_t)ch) * cubes_per_stack, cf, lane);
+    }
+};
+
+template <int D, int EDGE = 0, int QT = 0>
+__global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(typename DecodeArgs<QT>::type P) {
     constexpr int NW = (D == 8) ? 1 : 2;  // words per plane and channel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kDecWaveLds];
     const int wave = threadIdx.x >> 6;
@@ -681,7 +730,12 @@ __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(DecodeParams P) {
         }
         wave_lds_sync();
         uint32_t outw[D][NW];
-        decode_tile<D, false, false, true>(P, wl, lane, cube0, [] {}, ReloadCubesRgb<D>{P.in, P.div_cps, P.cubes_per_stack, ch}, &outw[0][0], &valid);
+        if constexpr (QT)
+            decode_tile<D, false, false, true, 0, 1>(P, wl, lane, cube0, [] {},
+                                                     ReloadCubesRgbQ<D>{P.in, dec_steps(P), P.div_cps, P.cubes_per_stack, ch},
+                                                     &outw[0][0], &valid, dec_steps(P));
+        else
+            decode_tile<D, false, false, true>(P, wl, lane, cube0, [] {}, ReloadCubesRgb<D>{P.in, P.div_cps, P.cubes_per_stack, ch}, &outw[0][0], &valid);
         const uint32_t s0 = ch == 0 ? rgb_put_sel(0, 0) : ch == 1 ? rgb_put_sel(1, 0) : rgb_put_sel(2, 0);
         const uint32_t s1 = ch == 0 ? rgb_put_sel(0, 1) : ch == 1 ? rgb_put_sel(1, 1) : rgb_put_sel(2, 1);
         const uint32_t s2 = ch == 0 ? rgb_put_sel(0, 2) : ch == 1 ? rgb_put_sel(1, 2) : rgb_put_sel(2, 2);

@@ -168,7 +168,7 @@ __device__ __forceinline__ uint32_t k1_code_off(uint32_t k) {
 // stream per channel: a launch chain each).  EDGE = 1: frames of any size, P as launch_encode_edge's.  Both
 // only change the row loads and the replay's reloads; these instantiations also count their exact replays
 // (P.replay_count) and zero the next call's counter slot, as the int32 encode kernels do.
-template <int D, int PX = 1, int EDGE = 0>
+template <int D, int PX = 1, int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, EgFusedParams E) {
     constexpr int CS = 64 * D;
     constexpr int NB = (D == 8) ? 8 : 4;
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     }
     __syncthreads();
     if (cube0 >= P.n_cubes) return;  // wave-uniform, after the barrier
-    enc_tables(P, s_tab, lane);
+    enc_tables<QT>(P, s_tab, lane);
     char* wl = lds + wave * enc_wave_lds<D>();
     char* rs = RS_TAIL ? wl + 8 * CUBE_B : rs_extra + wave * RS_B;
     static_assert((8 * CUBE_B) % 8 == 0 && RS_B % 8 == 0, "replay scratch alignment");
@@ -266,7 +266,8 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
         asm volatile("" : "+v"(fm_lo), "+v"(fm_hi));
     }
     if (j == 0) {
-        qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (single Java group)
+        if constexpr (QT) qv[0][0] = java_round_dev(__ddiv_rn((double)S * P.coef_dc, enc_step<1>(s_tab, 0)));
+        else qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (single Java group)
         fm_lo &= ~1u;
     }
     if (!valid) fm_lo = fm_hi = 0;
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
             const int sj = src & 7, sc = src >> 3;
             const int skz = (D == 8) ? sj : (sj >> 1), skx0 = (D == 8) ? 0 : (sj & 1) * 4;
             const uint32_t k = (uint32_t)((skz * 8 + bit / NB) * 8 + skx0 + bit % NB);
-            const int q = exact_coef<D, PX, EDGE>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4));
+            const int q = exact_coef<D, PX, EDGE, QT>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4), s_tab);
             if constexpr (PX != 1 || EDGE != 0) nrep++;
             if (lane == 0) *(uint16_t*)(wl + sc * CUBE_B + k1_code_off<D>(k)) = (uint16_t)(q > 0 ? 2 * q : 1 - 2 * q);
             if (lane == src) {
@@ -380,6 +381,30 @@ struct ReloadStream {
     }
 };
 
+template <int D>
+struct ReloadStreamQ {  // ReloadStream with the quantiser's table (QT = 1): steps[s], s = kx + ky + kz
+    const uint32_t* words;
+    uint64_t n_words;
+    const uint16_t* mark;
+    const uint64_t* mark_base;
+    const uint16_t* diag;
+    const double* steps;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        constexpr int PARTS = 64 * D / 32;
+        if (lane < PARTS) {
+            BitReader<GlobalBits> r{GlobalBits{words, n_words}, 0, 0, 0, 0};
+            r.seek(mark_serial(mark, mark_base, (uint64_t)g * PARTS + lane));
+            for (int i = 0; i < 32; i++) {
+                uint32_t code = 1u;
+                (void)r.get(code);
+                const int k = diag[lane * 32 + i];
+                const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
+                cf[k] = (double)eg_value(code) * steps[kx + ky + kz];
+            }
+        }
+    }
+};
+
 // lane 0's 64-bit value in scalar registers (readfirstlane returns int: widened from uint32_t, unsigned)
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)x);
@@ -395,8 +420,8 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
 // (32 bits) and two wave-uniform 64-bit values (scalar registers).  NG = 1: no look-ahead.
 // EDGE = 1 (dct3d_eg_frames.hip): frames of any size, P as launch_decode_edge's (blk_store off): the stores
 // are cropped, nothing else differs.
-template <int D, int NG, int EDGE = 0>
-__global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(DecodeParams P, EgDecParams E) {
+template <int D, int NG, int EDGE = 0, int QT = 0>
+__global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArgs<QT>::type P, EgDecParams E) {
     using G = DecGeom<D>;
     constexpr uint32_t CS = G::CS, PARTS = CS / 32, CPW = G::CPW;
     static_assert(CPW * CS == 2048 && PARTS * CPW == 64, "one wave = 64 marks");
@@ -548,7 +573,12 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(DecodeParams P, Eg
         }
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
-        decode_tile<D, (NG > 1), true, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadStream<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag});
+        if constexpr (QT)
+            decode_tile<D, (NG > 1), true, false, EDGE, 1>(P, wl, lane, cube0, [] {},
+                                                           ReloadStreamQ<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag, dec_steps(P)},
+                                                           nullptr, nullptr, dec_steps(P));
+        else
+            decode_tile<D, (NG > 1), true, false, EDGE>(P, wl, lane, cube0, [] {}, ReloadStream<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag});
         // the region receives the next group's window: after a block store (its rows are read by every
         // wave of the block) the whole block must be past it (block-uniform condition, as dec_store_tile's)
         if (i + 1 < NG) {
@@ -565,8 +595,8 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(DecodeParams P, Eg
 // replay re-parses its cube from stream ch.  The channels' bytes are merged in registers and dec_store_tile<PX
 // = 3> writes every packed byte once.  One group per wave (no look-ahead across groups).  A launch whose
 // streams are not all valid (any front's verdict) writes nothing.
-template <int D, int EDGE = 0>
-__global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(DecodeParams P, EgDecRgbParams E) {
+template <int D, int EDGE = 0, int QT = 0>
+__global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename DecodeArgs<QT>::type P, EgDecRgbParams E) {
     using G = DecGeom<D>;
     constexpr uint32_t CS = G::CS, PARTS = CS / 32, CPW = G::CPW;
     static_assert(CPW * CS == 2048 && PARTS * CPW == 64, "one wave = 64 marks");
@@ -664,9 +694,14 @@ __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(DecodeParams P
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
         uint32_t outw[D][NW];
-        decode_tile<D, false, true, true>(P, wl, lane, cube0, [] {},
-                                             ReloadStream<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag},
-                                             &outw[0][0], &valid);
+        if constexpr (QT)
+            decode_tile<D, false, true, true, 0, 1>(P, wl, lane, cube0, [] {},
+                                                    ReloadStreamQ<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag, dec_steps(P)},
+                                                    &outw[0][0], &valid, dec_steps(P));
+        else
+            decode_tile<D, false, true, true>(P, wl, lane, cube0, [] {},
+                                              ReloadStream<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag},
+                                              &outw[0][0], &valid);
         const uint32_t s0 = ch == 0 ? rgb_put_sel(0, 0) : ch == 1 ? rgb_put_sel(1, 0) : rgb_put_sel(2, 0);
         const uint32_t s1 = ch == 0 ? rgb_put_sel(0, 1) : ch == 1 ? rgb_put_sel(1, 1) : rgb_put_sel(2, 1);
         const uint32_t s2 = ch == 0 ? rgb_put_sel(0, 2) : ch == 1 ? rgb_put_sel(1, 2) : rgb_put_sel(2, 2);

@@ -390,9 +390,24 @@ __device__ __forceinline__ void enc_stage_store(const EncodeParams& P, const int
 // instead of three global loads per sum waited on after the transform.  EVERY wave writes the whole
 // table right after its row loads (identical bits, so the other waves' writes change nothing) and
 // reads only after its own writes (one wave's LDS operations complete in order).
+// QT = 1 (the quantiser's table, dct3d_quant.hip): the fourth component is step_s itself (an integer <= 255,
+// exact in fp32), which the DC and the rare paths divide by (enc_step) where the product kernels have
+// max(1, 5 s) in their text; the main path reads the same three components either way.
 constexpr int kTabN = 24;
+template <int QT = 0>
 __device__ __forceinline__ void enc_tables(const EncodeParams& P, float4* tab, int lane) {
-    if (lane < kTabN) tab[lane] = make_float4(P.tab_rstep[lane], P.tab_G[lane], 0.5f - P.tab_E[lane], 0.f);
+    if constexpr (QT) {
+        if (lane < kTabN)
+            tab[lane] = make_float4(P.tab_rstep[lane], P.tab_G[lane], 0.5f - P.tab_E[lane], (float)P.tab64[kQtStepOff + lane]);
+    } else {
+        if (lane < kTabN) tab[lane] = make_float4(P.tab_rstep[lane], P.tab_G[lane], 0.5f - P.tab_E[lane], 0.f);
+    }
+}
+// the step of sum s: the reference's, or the table's (tab: the block's enc_tables<1> copy)
+template <int QT>
+__device__ __forceinline__ double enc_step(const float4* tab, int s) {
+    if constexpr (QT) return (double)tab[s].w;
+    else return (double)max(1, 5 * s);
 }
 // Descending rows (ky = 7 .. 0; e16_body): the first row reads its NB entries, each later row the one
 // entry that enters the window.
@@ -436,9 +451,9 @@ __device__ __forceinline__ void tab_window(const float4* tab, int& sz, int ky, f
 // after the stores: kGM4 int sums + kGM4 fp64 products per cube.
 constexpr int kGM4 = kGM4Dev;  // >= the most Java groups of any 8x8x4 coefficient (40; the plan checks it)
 static_assert(8 * kGM4 * (4 + 8) <= enc_wave_lds<4>(), "8x8x4 replay scratch fits the wave's region");
-template <int PX = 1>
+template <int PX = 1, int QT = 0>
 __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (&px)[4], uint32_t fm, char* wl,
-                                            int lane, uint32_t cube0, int ch = 0) {
+                                            int lane, uint32_t cube0, int ch = 0, const float4* tab = nullptr) {
     constexpr int CS = 256;
     const int c = lane >> 3, j = lane & 7;
     int* const ssum = (int*)wl + c * kGM4;
@@ -489,7 +504,7 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
             double acc = 0.0;
 #pragma unroll 1
             for (int gi = 0; gi < ng; gi++) acc = __dadd_rn(acc, prod[gi]);  // DCT.java:50, in order
-            const int q = java_round_dev(__ddiv_rn(acc, (double)max(1, 5 * (kx + ky + kz))));
+            const int q = java_round_dev(__ddiv_rn(acc, enc_step<QT>(tab, kx + ky + kz)));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // after the wave's staged stores (one in-order count)
             P.out[(size_t)enc_out_cube<PX>(P, cube0 + c, ch) * CS + k] = q;
         }
@@ -503,7 +518,7 @@ __device__ __forceinline__ void enc4_replay(const EncodeParams& P, const uint2 (
 // Everything after the row loads, for the 8 cubes from cube0 (8x8x4): statistics, transform, quantise +
 // certify, staged 1 KiB stores, the exact fold of the uncertified coefficients (enc4_replay).
 // PX = 3 (packed RGB24): raw = the rows of channel ch, whose cubes go to its [stack][channel] blocks.
-template <int PX = 1, int EDGE = 0>
+template <int PX = 1, int EDGE = 0, int QT = 0>
 __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (&raw)[4], char* wl,
                                             const float4* tab, int lane, uint32_t cube0, int ch = 0) {
     constexpr int D = 4;  // 8x8x8 encodes in encode16_kernel
@@ -558,7 +573,8 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
         asm volatile("" : "+v"(fm));  // the row's checks complete here (q, n die)
     }
     if (j == 0) {
-        qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (single Java group)
+        if constexpr (QT) qv[0][0] = java_round_dev(__ddiv_rn((double)S * P.coef_dc, enc_step<1>(tab, 0)));
+        else qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (single Java group)
         fm &= ~1u;
     }
     if (!valid) fm = 0u;
@@ -569,7 +585,7 @@ __device__ __forceinline__ void encode_body(const EncodeParams& P, const uint2 (
     if (__builtin_expect(__ballot(fm != 0u) != 0ull, 0)) {  // wave-uniform
         uint2 px[D];
         load_channel_rows<D, 0, PX, EDGE>(P, g, valid, j, 0, ch, px);
-        enc4_replay<PX>(P, px, fm, wl, lane, cube0, ch);
+        enc4_replay<PX, QT>(P, px, fm, wl, lane, cube0, ch, tab);
     }
 }
 
@@ -583,7 +599,7 @@ __device__ __forceinline__ void enc_clear_next_slot(const EncodeParams& P) {
 
 // One wave = one group of 8 consecutive cubes (register-prefetch loops over several groups spill
 // and were 25-40 % slower: profiles/r01/encode_variant_sweep.txt).
-template <int EDGE = 0>
+template <int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     constexpr int D = 4;  // 8x8x8 encodes in encode16_kernel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
@@ -596,15 +612,15 @@ __global__ __launch_bounds__(kBlock, 4) void encode_kernel(EncodeParams P) {
     __builtin_amdgcn_s_setprio(0);
     if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
-    enc_tables(P, s_tab, lane);
-    encode_body<1, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
+    enc_tables<QT>(P, s_tab, lane);
+    encode_body<1, EDGE, QT>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, lane, cube0);
 }
 
 // Packed RGB24 (dct3d_encode_stacks_rgb_dev, 8x8x4): the wave owns the three channels of its 8 cubes'
 // tile.  Each lane loads its rows' 24 bytes once and keeps them packed (24 registers); per channel the
 // rows are picked out of them (rgb_pick8) and encode_body runs as for a grey plane, its cubes going to
 // the channel's [stack][channel] block.  P.n_cubes counts RGB cubes (a third of the output's).
-template <int EDGE = 0>
+template <int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
     constexpr int D = 4;  // 8x8x8 encodes in encode16_rgb_kernel
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
@@ -617,7 +633,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
     __builtin_amdgcn_s_setprio(0);
     if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
-    enc_tables(P, s_tab, lane);
+    enc_tables<QT>(P, s_tab, lane);
 #pragma unroll 1
     for (int ch = 0; ch < 3; ch++) {
         uint2 raw[D];
@@ -632,7 +648,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_rgb_kernel(EncodeParams P) {
 #pragma unroll
             for (int z = 0; z < D; z++) raw[z] = edge_fix(raw[z], sh);
         }
-        encode_body<3, EDGE>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
+        encode_body<3, EDGE, QT>(P, raw, lds + wave * enc_wave_lds<D>(), s_tab, ln, cube0, ch);
         wave_lds_sync();  // the next channel reuses the wave's region
     }
 }
@@ -696,8 +712,9 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
     return in;
 }
 // LEAN: the fold loop is not unrolled (in-wave replay: its registers would count against the main path)
-template <int D, bool LEAN = false>
-__device__ __forceinline__ int replay_fold(const ReplayIn& in, uint32_t k, int lane, int* ssum, double* prod) {
+template <int D, bool LEAN = false, int QT = 0>
+__device__ __forceinline__ int replay_fold(const ReplayIn& in, uint32_t k, int lane, int* ssum, double* prod,
+                                           const float4* tab = nullptr) {
     constexpr int CS = 64 * D;
     ssum[lane] = 0;
     wave_lds_sync();
@@ -732,16 +749,20 @@ __device__ __forceinline__ int replay_fold(const ReplayIn& in, uint32_t k, int l
 #pragma unroll 1
         for (; gi < ng; gi++) acc = __dadd_rn(acc, prod[gi]);
         const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
-        const int st = max(1, 5 * (kx + ky + kz));
-        q = java_round_dev(__ddiv_rn(acc, (double)st));
+        if constexpr (QT) {
+            q = java_round_dev(__ddiv_rn(acc, enc_step<1>(tab, kx + ky + kz)));
+        } else {
+            const int st = max(1, 5 * (kx + ky + kz));
+            q = java_round_dev(__ddiv_rn(acc, (double)st));
+        }
     }
     wave_lds_sync();
     return q;
 }
-template <int D, int PX = 1, int EDGE = 0>
+template <int D, int PX = 1, int EDGE = 0, int QT = 0>
 __device__ __forceinline__ int exact_coef(const ReplayGeom& R, uint32_t g, uint32_t k, int lane, int* ssum,
-                                          double* prod) {
-    return replay_fold<D>(replay_load<D, PX, EDGE>(R, g, k, lane), k, lane, ssum, prod);
+                                          double* prod, const float4* tab = nullptr) {
+    return replay_fold<D, false, QT>(replay_load<D, PX, EDGE>(R, g, k, lane), k, lane, ssum, prod, tab);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -774,6 +795,7 @@ static_assert(4 * kE16S16C <= kE16Lds, "int16 staging of the wave's 4 cubes fits
 
 // Statistics, passes X / Z / Y, quantise + certify, exact DC.  Uncertified coefficients are returned
 // as the lane's mask fm (bit 4 ky + e: coefficient (kz = k, ky, kx = 4h + e)); the caller replays them.
+template <int QT = 0>
 __device__ __forceinline__ void e16_body(const EncodeParams& P, const uint2 (&raw)[4], char* wl, const float4* tab,
                                          int lane, bool valid, int32_t (&qv)[8][4], uint32_t& fm) {
     constexpr int CS = 512;
@@ -907,7 +929,8 @@ __device__ __forceinline__ void e16_body(const EncodeParams& P, const uint2 (&ra
         asm volatile("" : "+v"(fm));
     }
     if (k == 0 && h == 0) {
-        qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (the single Java group)
+        if constexpr (QT) qv[0][0] = java_round_dev(__ddiv_rn((double)S * P.coef_dc, enc_step<1>(tab, 0)));
+        else qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (the single Java group)
         fm &= ~1u;
     }
     if (!valid) fm = 0u;
@@ -936,8 +959,9 @@ __device__ __forceinline__ void e16_flag_pos(uint32_t fm, int src, uint32_t cube
 // staged values are out of the registers by then).  s_b: the block's copy of the tables ([64] basis,
 // [32] thresholds), written by every wave that takes this path (identical bits) and read only after its
 // own writes.
+template <int QT = 0>
 __device__ __forceinline__ void e16_recheck64(const uint2 (&raw)[4], double bv, double tv, double* s_b, char* wl,
-                                              int lane, uint32_t& fm, uint32_t& nset) {
+                                              int lane, uint32_t& fm, uint32_t& nset, const float4* tab = nullptr) {
     const int k = lane & 7, h = (lane >> 4) & 1;
     s_b[lane] = bv;
     if (lane < 32) s_b[64 + lane] = tv;
@@ -982,7 +1006,9 @@ __device__ __forceinline__ void e16_recheck64(const uint2 (&raw)[4], double bv, 
         }
         if (mine != 0ull && lane == src) {
             const int s = kz + ky + kx;
-            const double q = __ddiv_rn(t, (double)(5 * s));  // s >= 1: the DC is never open
+            double q;
+            if constexpr (QT) q = __ddiv_rn(t, enc_step<1>(tab, s));
+            else q = __ddiv_rn(t, (double)(5 * s));  // s >= 1: the DC is never open
             const double n = __builtin_rint(q);
             if (__builtin_fabs(q - n) < s_b[64 + s]) {
                 const uint32_t cl = (lane >> 5) * 2 + ((lane & 15) >> 3);  // the cube within the wave
@@ -1018,7 +1044,7 @@ __device__ __forceinline__ uint32_t strip_cube(const EncodeParams& P, uint32_t s
     const uint32_t by = fdiv(rr, P.div_strip_w);
     return c.s * P.cubes_per_stack + by * P.nbx + strip * P.strip_w + (rr - by * P.strip_w);
 }
-template <int MODE = 0, int EDGE = 0>
+template <int MODE = 0, int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) void encode16_kernel(EncodeParams P) {
     constexpr int CS = 512;
     // MODE 4 / 5: MODE 1 / 0 with the strip traversal (diagnostic sweep)
@@ -1065,8 +1091,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
 #pragma unroll
             for (int e = 0; e < 4; e++) qv[ky][e] = (int32_t)(((ky & 1) ? raw[e].y : raw[e].x) >> (ky * 3 % 24)) & 255;
     } else {
-        enc_tables(P, s_tab, lane);
-        e16_body(P, raw, wl, s_tab, lane, valid, qv, fm);
+        enc_tables<QT>(P, s_tab, lane);
+        e16_body<QT>(P, raw, wl, s_tab, lane, valid, qv, fm);
     }
     if constexpr (TRACE) t_comp = __builtin_amdgcn_s_memrealtime();
     const bool rare = !MEM && !COMP && P.recheck && __builtin_expect(__ballot(fm != 0u) != 0ull, 0);  // wave-uniform
@@ -1092,7 +1118,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
-            e16_recheck64(raw2, bv, tv, s_b64, wl, lane, fm, nset);
+            e16_recheck64<QT>(raw2, bv, tv, s_b64, wl, lane, fm, nset, s_tab);
             for (int o = 1; o < 64; o <<= 1) nset += __shfl_xor(nset, o, 64);
             if (lane == 0 && nset && P.replay_count)
                 atomicAdd(P.replay_count + kCountSpread + (blockIdx.x & (kCountSpread - 1)), nset);
@@ -1136,8 +1162,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
             const int src = (int)__builtin_ctzll(who);
             uint32_t rg, rk;
             e16_flag_pos(fm, src, cube0, rg, rk);
-            const int q = replay_fold<8, true>(replay_load<8, 1, EDGE>(R, rg, rk, lane), rk, lane, (int*)rs,
-                                               (double*)(rs + kMaxGroupsDev * 4));
+            const int q = replay_fold<8, true, QT>(replay_load<8, 1, EDGE>(R, rg, rk, lane), rk, lane, (int*)rs,
+                                                   (double*)(rs + kMaxGroupsDev * 4), s_tab);
             if (lane == 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 P.out[(size_t)rg * CS + rk] = q;
@@ -1159,7 +1185,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) voi
 // third of the output's).  Occupancy: the packed rows on top of the main path's 72 registers do not fit 7
 // waves per SIMD (73 registers); the kernel takes what it needs up to 4 waves per SIMD (128).
 // ---------------------------------------------------------------------------------------------
-template <int EDGE = 0>
+template <int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void encode16_rgb_kernel(EncodeParams P) {
     constexpr int CS = 512;
     __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * kE16Lds];
@@ -1177,7 +1203,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
     if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);
     if (cube0 >= P.n_cubes) return;  // wave-uniform
-    enc_tables(P, s_tab, threadIdx.x & 63);
+    enc_tables<QT>(P, s_tab, threadIdx.x & 63);
 #pragma unroll 1
     for (int ch = 0; ch < 3; ch++) {
         // the lane's indices and addresses are made again for each channel (an opaque lane index), not
@@ -1199,7 +1225,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         }
         int32_t qv[8][4];
         uint32_t fm = 0u;
-        e16_body(P, raw, wl, s_tab, lane, valid, qv, fm);
+        e16_body<QT>(P, raw, wl, s_tab, lane, valid, qv, fm);
         const bool rare = P.recheck && __builtin_expect(__ballot(fm != 0u) != 0ull, 0);  // wave-uniform
         {  // int16 staging of the 4 cubes, the second certificate in it, 8 stores of 1 KiB (as encode16_kernel)
             char* dst = wl + c * kE16S16C + k * kE16S16F + h * 8;
@@ -1215,7 +1241,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
             const double bv = P.tab64[lane];
             const double tv = lane < 32 ? P.tab64[64 + lane] : 0.0;
             uint32_t nset;
-            e16_recheck64(raw2, bv, tv, s_b64, wl, lane, fm, nset);
+            e16_recheck64<QT>(raw2, bv, tv, s_b64, wl, lane, fm, nset, s_tab);
             for (int o = 1; o < 64; o <<= 1) nset += __shfl_xor(nset, o, 64);
             if (lane == 0 && nset && P.replay_count)
                 atomicAdd(P.replay_count + kCountSpread + (blockIdx.x & (kCountSpread - 1)), nset);
@@ -1244,8 +1270,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
                 const int src = (int)__builtin_ctzll(who);
                 uint32_t rg, rk;
                 e16_flag_pos(fm, src, cube0, rg, rk);
-                const int q = replay_fold<8, true>(replay_load<8, 3, EDGE>(R, rg, rk, lane), rk, lane, (int*)wl,
-                                                   (double*)(wl + kMaxGroupsDev * 4));
+                const int q = replay_fold<8, true, QT>(replay_load<8, 3, EDGE>(R, rg, rk, lane), rk, lane, (int*)wl,
+                                                       (double*)(wl + kMaxGroupsDev * 4), s_tab);
                 if (lane == 0) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     P.out[(size_t)enc_out_cube<3>(P, rg, ch) * CS + rk] = q;

@@ -43,7 +43,8 @@ struct EncodeParams {
     unsigned int* replay_count;  // this call's counter slot: [0, S) Java-fold replays, [S, 2S) fp64
                                  // settlements (S = kCountSpread words each), or nullptr
     unsigned int* replay_clear;  // the other slot (2S words): zeroed by block 0 for the next call
-    const double* tab64;       // 8x8x8 second certificate: [64] fp64 basis [k][n], [32] thresholds per s
+    const double* tab64;       // 8x8x8 second certificate: [64] fp64 basis [k][n], [32] thresholds per s;
+                               // then (both depths; read by the QT = 1 kernels only) [32] steps per s, fp64
     uint32_t recheck;          // 1: run the second certificate (0: test option, all open -> Java fold)
     uint64_t* trace;           // MODE 3 (diagnostic timeline): per wave {start, transform done, stored, hw id}
     // MODES 4 / 5 (diagnostic traversal sweep): the waves walk the cubes in vertical strips of strip_w
@@ -70,6 +71,20 @@ struct DecodeParams {
 };
 
 static_assert(sizeof(EncodeParams) == 192 && sizeof(DecodeParams) == 120, "the kernels' argument layout");
+
+// Quantiser tables (dct3d_quant.hip).  The kernels' QT = 1 instantiations take the step of sum
+// s = kx + ky + kz from a table where the product kernels have max(1, 5 s) in their text.  Encode: the table
+// is the tail of tab64 (kQtStepOff; EncodeParams does not change).  Decode: DecodeParams has no room and no
+// such table, so the QT kernels' argument wraps it.
+constexpr int kQtStepOff = 96;  // tab64[kQtStepOff + s] = step[s], s < 32
+struct DecodeParamsQ : DecodeParams {
+    const double* steps;  // [32] fp64 steps per s
+};
+template <int QT> struct DecodeArgs { using type = DecodeParams; };
+template <> struct DecodeArgs<1> { using type = DecodeParamsQ; };
+// a decode kernel's step table: nullptr for the product kernels (QT = 0: the steps are in their text)
+__host__ __device__ inline const double* dec_steps(const DecodeParams&) { return nullptr; }
+__host__ __device__ inline const double* dec_steps(const DecodeParamsQ& P) { return P.steps; }
 
 struct Fwd64Params {
     const uint8_t* raster;
@@ -226,6 +241,10 @@ int launch_decode(int D, const DecodeParams& P, hipStream_t st);
 int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st);
 int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st);
 int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+// The int32 raster kernels with the quantiser's table (dct3d_quant.hip): px = 1 grey | 3 packed RGB24, edge =
+// 0 | 1 (frames of any size); P as the launcher's of the same geometry above, P.tab64 with the steps' tail
+int launch_encode_qt(int D, int px, int edge, const EncodeParams& P, hipStream_t st);
+int launch_decode_qt(int D, int px, int edge, const DecodeParamsQ& P, hipStream_t st);
 // Frames of any size and packed RGB24 through the fused Exp-Golomb kernels (dct3d_eg_frames.hip).  Encode: px =
 // 1 grey (edge = 1 only), 3 packed RGB24 (edge = 0 or 1), channel E.ch of the RGB cubes per launch; P as
 // launch_encode_rgb's / launch_encode_edge's.  Decode: grey with the crop (P as launch_decode_edge's, 8 groups
@@ -234,6 +253,11 @@ int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipSt
 int launch_encode_eg_frames(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
 int launch_decode_eg_edge(int D, const DecodeParams& P, const EgDecParams& E, hipStream_t st);
 int launch_decode_eg_rgb(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, hipStream_t st);
+// The fused Exp-Golomb kernels with the quantiser's table (dct3d_quant_eg.hip), every geometry: px, edge and P
+// as launch_encode_eg / launch_encode_eg_frames and launch_decode_eg (8 groups per wave) / _eg_edge / _eg_rgb
+int launch_encode_eg_qt(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+int launch_decode_eg_qt(int D, int edge, const DecodeParamsQ& P, const EgDecParams& E, hipStream_t st);
+int launch_decode_eg_rgb_qt(int D, int edge, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =
 // segments, P.bits = seg_bits)

@@ -354,9 +354,23 @@ void analyse_decoder(Plan& p, std::vector<double>& K, std::vector<double>& L1, d
 // =============================================================================================
 // Plan construction
 // =============================================================================================
-bool build_plan(int cw, int ch, int cd, Plan& p) {
+bool build_plan(int cw, int ch, int cd, Plan& p) { return build_plan(cw, ch, cd, nullptr, p); }
+
+bool build_plan(int cw, int ch, int cd, const int32_t* steps, Plan& p) {
     if (cw != 8 || ch != 8 || (cd != 8 && cd != 4)) return false;
+    const int n_steps = cw + ch + cd - 2;
+    if (steps)
+        for (int s = 0; s < n_steps; s++)
+            if (steps[s] < kMinStep || steps[s] > kMaxStep) return false;
     p = Plan();
+    p.steps.resize(n_steps);
+    for (int s = 0; s < n_steps; s++) {
+        p.steps[s] = steps ? steps[s] : reference_step(s);
+        if (p.steps[s] != reference_step(s)) p.reference_quant = false;
+    }
+    // the step of sum s (table entries past the cube's largest sum are never read by a kernel: the
+    // reference's value there, as before)
+    const auto step_of = [&](int s) { return (double)(s < n_steps ? p.steps[s] : reference_step(s)); };
     p.cw = cw;
     p.ch = ch;
     p.cd = cd;
@@ -446,17 +460,21 @@ bool build_plan(int cw, int ch, int cd, Plan& p) {
                 const int k = (kz * 8 + ky) * 8 + kx;
                 const int s = kx + ky + kz;
                 if (s == 0) continue;  // DC is produced exactly from the integer cube sum
-                const double step = std::max(1, 5 * s);
+                const double step = step_of(s);
                 const double K = p.enc_K[k], L1 = p.enc_L1[k];
                 // |q_f - q_java| <= A*[K + 2.02u(L1+K) + 2^-50 L1]/step
                 //                   + [255*dev + (ng+16) 2^-52 255 L1]/step + 1e-12
+                // (every term but the last scales with 1/step, so a smaller step certifies less: at
+                // A G_s + E_s >= 0.5 the kernels' threshold is <= 0 and every coefficient of that s is
+                // open -- |qq - n| >= thr holds for any thr <= 0 -- never certified.  1e-12 covers the
+                // rounding of Java's quotient, <= 2^-41 for |q| < 2^13, whatever the step.)
                 const double gk = (K + 2.02 * u32 * (L1 + K) + std::ldexp(L1, -50)) / step;
                 const double ek = (255.0 * p.enc_dev[k] + (p.fwd_ngroups[k] + 16) * std::ldexp(255.0 * L1, -52)) / step + 1e-12;
                 G[s] = std::max(G[s], gk);
                 E[s] = std::max(E[s], ek);
             }
     for (int s = 0; s < kMaxS; s++) {
-        const double step = std::max(1, 5 * s);
+        const double step = step_of(s);
         p.enc_rstep[s] = (float)(1.0 / step);
         if (s == 0) {
             p.enc_G[s] = 0.0f;
@@ -478,7 +496,7 @@ bool build_plan(int cw, int ch, int cd, Plan& p) {
     //   |v_java - V| <= 255 * devx + (ng + 2) u * 255 * L1j
     //        devx = sum_n |cj_n - c_n|, cj_n = Java's group coefficient of input n (0 if dropped:
     //        DCT.java:84), L1j = sum_n |cj_n| (the fold's ng products and additions, DCT.java:49-52)
-    // Both quotients by the step round once more (|q| < 2^12: 2^-40 each).  So with
+    // Both quotients by the step round once more (|q| < 2^13 for any step >= 1: 2^-40 each).  So with
     //   E64 = (255 devx + (ng + 2) u 255 L1j + 72 u 255 L1x) / step + 2^-38,
     // |q64 - rint(q64)| < 0.5 - E64 implies Math.round(v_java / step) = rint(q64).  The table holds
     // 0.5 - 2 max_k E64 per s (a further factor 2).  Exact values: long double (64-bit mantissa).
@@ -510,7 +528,7 @@ bool build_plan(int cw, int ch, int cd, Plan& p) {
                                 L1j += fabsl(cj);
                             }
                     const long double e = (255.0L * devx + (p.fwd_ngroups[k] + 2) * u * 255.0L * L1j +
-                                           72.0L * u * 255.0L * L1x) / (long double)(5 * s) +
+                                           72.0L * u * 255.0L * L1x) / (long double)step_of(s) +
                                           ldexpl(1.0L, -38);
                     E64[s] = std::max(E64[s], e);
                 }
@@ -522,6 +540,10 @@ bool build_plan(int cw, int ch, int cd, Plan& p) {
     // a few ulps of the exact basis: |v_java - v_exact| <= J sum_k |x_k B_nk| with J = (cs + 16) 2^-52.
     // The kernel: |v_gpu - v_exact| <= sum_k ev[n][k] |x_k| (analyse_decoder).  So with
     // L1x = sum_k |x_k| (the kernel's upper bound of it), |v_gpu - v_java| <= G1 L1x (+ dec_E).
+    // None of dec_G, dec_E, dec_l1_max depends on the quantiser: the bound is stated per unit of the
+    // DEQUANTISED coefficients' L1 norm, which the kernel sums from the products q * step themselves, and
+    // those products are exact in fp64 for every step <= 255 (dct3d_plan.h).  A coarser table only makes
+    // L1, and with it the margin, larger on the same q.
     std::vector<double> Kd, L1d;
     double G1 = 0.0, Bmax = 0.0;
     const double J = (cs + 16) * std::ldexp(1.0, -52);

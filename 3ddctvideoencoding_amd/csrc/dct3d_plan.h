@@ -11,8 +11,27 @@ constexpr int kMaxGroups = 64;   // per-coefficient group slots in the device fo
 constexpr int kMaxGroups4 = 48;  // 8x8x4: group sums per cube of the encode's in-wave fold (kGM4Dev)
 constexpr int kMaxS = 32;        // s = kx + ky + kz table size (max 21 for 8x8x8)
 
+// ---- the quantiser: one integer step per s = kx + ky + kz (0 <= s <= cw + ch + cd - 3), each in
+//      [kMinStep, kMaxStep].  The reference codec's is step[s] = max(1, 5 s) (Encoder.java:75-89,
+//      Decoder.java:78-96); any other table keeps those lines' arithmetic with step[x + y + z] in place
+//      of Math.max(1, 5 * (x + y + z)).  Range facts the kernels rely on, for every step in [1, 255]:
+//        |c| <= 255 sqrt(cs) <= 255 * 22.63 = 5,771 for every coefficient c of 8-bit frames (Parseval;
+//          the DC c = S coef_dc with S <= 255 cs), so |q| = |round(c / step)| <= 5,771 < 2^13 for any
+//          step >= 1: the encode's int16 staging and the 16-bit Exp-Golomb codes (2 |q| + 1 < 2^14) hold
+//          whatever the table;
+//        stream decode: |q| < 2^15 (a code < 2^16) times step <= 255 < 2^8 is < 2^23 < 2^24, exact in
+//          v_mul_u32_u24 and in its 32-bit result; a lane's integer L1 over its 32 values is
+//          < 32 * 2^23 = 2^28 < 2^32;
+//        int32 decode: |q step| <= 2^31 * 255 < 2^39, a 39-bit integer: the fp64 product is exact. ----
+constexpr int kMinStep = 1, kMaxStep = 255;
+inline int reference_step(int s) { return s < 1 ? 1 : 5 * s; }  // <= 105 (s <= 21)
+
 struct Plan {
     int cw = 8, ch = 8, cd = 8, cs = 512;
+
+    // the quantiser's table, [cw + ch + cd - 2] entries, and whether it is the reference codec's
+    std::vector<int32_t> steps;
+    bool reference_quant = true;
 
     // ---- Java forward fold (DCT.java:77-112 + HashMap<Long,..> iteration order) ----
     std::vector<int32_t> fwd_ngroups;     // [cs]
@@ -27,7 +46,7 @@ struct Plan {
 
     // ---- fused-encode certification (fp32 kernel), per s = kx+ky+kz ----
     // |q_fp32 - q_java| <= A * enc_G[s] + enc_E[s], A = max |x - m| over the cube.
-    float enc_rstep[kMaxS] = {};          // fp32(1/max(1,5s))
+    float enc_rstep[kMaxS] = {};          // fp32(1/step[s])
     float enc_G[kMaxS] = {};
     float enc_E[kMaxS] = {};
     // per-coefficient raw analysis results (exposed for tests)
@@ -52,7 +71,10 @@ struct Plan {
 };
 
 // Builds the plan for cube dims (cw, ch, cd).  Supported: cw = ch = 8, cd in {4, 8}.
-// Returns false on unsupported dims.
+// Returns false on unsupported dims.  The quantiser is the reference codec's.
 bool build_plan(int cw, int ch, int cd, Plan& p);
+// The same for the quantiser steps[0 .. cw + ch + cd - 3] (nullptr: the reference's).  Also false when a
+// step lies outside [kMinStep, kMaxStep].
+bool build_plan(int cw, int ch, int cd, const int32_t* steps, Plan& p);
 
 }  // namespace dct3d

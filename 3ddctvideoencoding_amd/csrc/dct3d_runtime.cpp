@@ -76,6 +76,7 @@ struct dct3d_ctx {
     bool opt_eg_force_retry = false;
     bool opt_eg_fused_front = false;
     int opt_eg_dec_groups = 0;  // fused stream decode: groups per wave (0: the default, 8)
+    bool opt_quant_force = false;  // the table kernels even for the reference table (DCT3D_OPT_QUANT_FORCE_TABLE)
     // certify-or-replay state
     uint64_t last_units = 0;
     bool last_valid = false;
@@ -219,10 +220,20 @@ static int upload(DevBuf& b, const void* src, size_t bytes) {
     return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
 }
 
+// a caller's quantiser table for block dims (bw, bh, bd): its length (the steps' range: build_plan)
+static bool quant_len_ok(int bw, int bh, int bd, const int32_t* steps, int n) {
+    return !steps || (bw > 0 && bh > 0 && bd > 0 && n == bw + bh + bd - 2);
+}
+
 int dct3d_plan_query(int bw, int bh, int bd, dct3d_plan_info* info, int32_t* ngroups, double* coef,
                      uint8_t* group_of, double* enc_K) {
+    return dct3d_plan_query_quant(bw, bh, bd, nullptr, 0, info, ngroups, coef, group_of, enc_K);
+}
+
+int dct3d_plan_query_quant(int bw, int bh, int bd, const int32_t* steps, int n, dct3d_plan_info* info, int32_t* ngroups,
+                           double* coef, uint8_t* group_of, double* enc_K) {
     Plan p;
-    if (!build_plan(bw, bh, bd, p)) return DCT3D_EINVAL;
+    if (!quant_len_ok(bw, bh, bd, steps, n) || !build_plan(bw, bh, bd, steps, p)) return DCT3D_EINVAL;
     if (info) {
         memset(info, 0, sizeof(*info));
         info->cube_size = p.cs;
@@ -241,6 +252,45 @@ int dct3d_plan_query(int bw, int bh, int bd, dct3d_plan_info* info, int32_t* ngr
     if (coef) memcpy(coef, p.fwd_coef.data(), sizeof(double) * p.fwd_coef.size());
     if (group_of) memcpy(group_of, p.fwd_group_of.data(), p.fwd_group_of.size());
     if (enc_K) memcpy(enc_K, p.enc_K.data(), sizeof(double) * p.cs);
+    return DCT3D_OK;
+}
+
+// The plan's tables that depend on the quantiser, to the device (context creation, dct3d_ctx_set_quant):
+// the encode's {1 / step, G, E} per s, and the fp64 table [64] basis, [32] second-certificate thresholds,
+// [32] steps (kQtStepOff; entries past the cube's largest s: the reference's, never read)
+static int upload_quant_tables(dct3d_ctx* c) {
+    const Plan& p = c->plan;
+    float tabs[3 * kMaxS];
+    memcpy(tabs, p.enc_rstep, sizeof(float) * kMaxS);
+    memcpy(tabs + kMaxS, p.enc_G, sizeof(float) * kMaxS);
+    memcpy(tabs + 2 * kMaxS, p.enc_E, sizeof(float) * kMaxS);
+    int rc = upload(c->d_tabs, tabs, sizeof(tabs));
+    if (rc) return rc;
+    static_assert(kQtStepOff == 64 + kMaxS, "the steps follow the thresholds");
+    double t64[kQtStepOff + kMaxS];
+    memcpy(t64, p.basis64, sizeof(p.basis64));
+    memcpy(t64 + 64, p.enc_thr64, sizeof(p.enc_thr64));
+    for (int s = 0; s < kMaxS; s++) t64[kQtStepOff + s] = s < (int)p.steps.size() ? p.steps[s] : reference_step(s);
+    return upload(c->d_tabs64, t64, sizeof(t64));
+}
+// the context's calls run the table kernels (else: the product kernels, the reference steps in their text)
+static bool use_qt(const dct3d_ctx* c) { return !c->plan.reference_quant || c->opt_quant_force; }
+static const double* qt_steps(const dct3d_ctx* c) { return (const double*)c->d_tabs64.p + kQtStepOff; }
+
+int dct3d_ctx_set_quant(dct3d_ctx* c, const int32_t* steps, int n) {
+    if (!c || !quant_len_ok(c->bw, c->bh, c->bd, steps, n)) return DCT3D_EINVAL;
+    Plan p;
+    if (!build_plan(c->bw, c->bh, c->bd, steps, p)) return DCT3D_EINVAL;  // (a step outside [1, 255])
+    if (p.steps == c->plan.steps) return DCT3D_OK;
+    // a call enqueued earlier still reads the tables that are rewritten below
+    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return DCT3D_EDEVICE;
+    c->plan = std::move(p);
+    return upload_quant_tables(c);
+}
+
+int dct3d_ctx_get_quant(const dct3d_ctx* c, int32_t* steps, int n) {
+    if (!c || !steps || n != (int)c->plan.steps.size()) return DCT3D_EINVAL;
+    memcpy(steps, c->plan.steps.data(), sizeof(int32_t) * n);
     return DCT3D_OK;
 }
 
@@ -273,10 +323,6 @@ int dct3d_ctx_create(int device, int block_w, int block_h, int block_d, dct3d_ct
                 return DCT3D_EDEVICE;
             }
     const Plan& p = c->plan;
-    float tabs[3 * kMaxS];
-    memcpy(tabs, p.enc_rstep, sizeof(float) * kMaxS);
-    memcpy(tabs + kMaxS, p.enc_G, sizeof(float) * kMaxS);
-    memcpy(tabs + 2 * kMaxS, p.enc_E, sizeof(float) * kMaxS);
     int rc = upload(c->d_ngroups, p.fwd_ngroups.data(), p.fwd_ngroups.size() * sizeof(int32_t));
     if (!rc) rc = upload(c->d_coef, p.fwd_coef.data(), p.fwd_coef.size() * sizeof(double));
     if (!rc) rc = upload(c->d_group_of, p.fwd_group_of.data(), p.fwd_group_of.size());
@@ -286,13 +332,7 @@ int dct3d_ctx_create(int device, int block_w, int block_h, int block_d, dct3d_ct
             for (int k = 0; k < p.cs; k++) t[(size_t)k * p.cs + n] = p.inv_coef[(size_t)n * p.cs + k];
         rc = upload(c->d_inv_coef, t.data(), t.size() * sizeof(double));
     }
-    if (!rc) rc = upload(c->d_tabs, tabs, sizeof(tabs));
-    if (!rc) {  // second certificate (8x8x8): [64] fp64 basis, [32] thresholds
-        double t64[64 + kMaxS];
-        memcpy(t64, p.basis64, sizeof(p.basis64));
-        memcpy(t64 + 64, p.enc_thr64, sizeof(p.enc_thr64));
-        rc = upload(c->d_tabs64, t64, sizeof(t64));
-    }
+    if (!rc) rc = upload_quant_tables(c);
     if (!rc) rc = c->d_enc_counts.grow(4 * kCountSpread * sizeof(uint32_t));
     if (!rc && hipMemset(c->d_enc_counts.p, 0, 4 * kCountSpread * sizeof(uint32_t)) != hipSuccess) rc = DCT3D_EDEVICE;
     if (!rc) {
@@ -388,6 +428,7 @@ int dct3d_ctx_set_option(dct3d_ctx* c, int option, double value) {
         case DCT3D_OPT_EG_NO_RESOLVE: c->opt_eg_no_resolve = value != 0.0; return DCT3D_OK;
         case DCT3D_OPT_EG_FORCE_RETRY: c->opt_eg_force_retry = value != 0.0; return DCT3D_OK;
         case DCT3D_OPT_EG_FUSED_FRONT: c->opt_eg_fused_front = value != 0.0; return DCT3D_OK;
+        case DCT3D_OPT_QUANT_FORCE_TABLE: c->opt_quant_force = value != 0.0; return DCT3D_OK;
         case DCT3D_OPT_EG_DEC_GROUPS:
             if (value != 0.0 && value != 1.0 && value != 2.0 && value != 4.0 && value != 8.0) return DCT3D_EINVAL;
             c->opt_eg_dec_groups = (int)value;
@@ -597,7 +638,8 @@ static int encode_dev(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g, uint
     fill_encode_params(c, P, d_raster, d_q, g, n_cubes);
     hipEvent_t* ev = timer_begin(c);
     int lrc;
-    switch (2 * g.px + (g.edge() ? 1 : 0)) {
+    if (use_qt(c)) lrc = launch_encode_qt(D, g.px, g.edge() ? 1 : 0, P, c->stream);
+    else switch (2 * g.px + (g.edge() ? 1 : 0)) {
         case 2: lrc = launch_encode(D, P, c->stream); break;
         case 6: lrc = launch_encode_rgb(D, P, c->stream); break;
         default: lrc = launch_encode_edge(D, g.px, P, c->stream);  // (the row loads clamped to the frame)
@@ -614,11 +656,13 @@ static int decode_dev(dct3d_ctx* c, const int32_t* d_q, const Geom& g, uint64_t 
     call_begin(c);
     if (n_cubes == 0) return DCT3D_OK;
     const int D = c->bd;
-    DecodeParams P;
+    DecodeParamsQ P;  // (the product kernels take its DecodeParams part)
     fill_decode_params(c, P, d_q, d_raster, g, n_cubes);
+    P.steps = qt_steps(c);
     hipEvent_t* ev = timer_begin(c);
     int lrc;
-    switch (2 * g.px + (g.edge() ? 1 : 0)) {
+    if (use_qt(c)) lrc = launch_decode_qt(D, g.px, g.edge() ? 1 : 0, P, c->stream);
+    else switch (2 * g.px + (g.edge() ? 1 : 0)) {
         case 2: lrc = launch_decode(D, P, c->stream); break;
         case 6: lrc = launch_decode_rgb(D, P, c->stream); break;
         default: lrc = launch_decode_edge(D, g.px, P, c->stream);  // (the stores cropped to the frame)
@@ -1014,7 +1058,9 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    if (plain ? launch_encode_eg(D, P, E, c->stream) : launch_encode_eg_frames(D, g.px, g.edge() ? 1 : 0, P, E, c->stream))
+    if (use_qt(c) ? launch_encode_eg_qt(D, g.px, g.edge() ? 1 : 0, P, E, c->stream)
+        : plain   ? launch_encode_eg(D, P, E, c->stream)
+                  : launch_encode_eg_frames(D, g.px, g.edge() ? 1 : 0, P, E, c->stream))
         return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
@@ -1400,9 +1446,11 @@ static int eg_stack_align(const dct3d_ctx* c, const Geom& g) {
 static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, int st0, int ns, uint8_t* out_stack0) {
     const int D = c->bd;
     const uint64_t cps = g.cps();
-    DecodeParams P;  // the cubes [cube_base, n_cubes); rebased: stack st0 at out_stack0
+    DecodeParamsQ P;  // the cubes [cube_base, n_cubes); rebased: stack st0 at out_stack0
     fill_decode_params(c, P, nullptr, out_stack0 - (size_t)st0 * g.plane() * D, g, (st0 + ns) * cps);
     P.cube_base = (uint32_t)(st0 * cps);
+    P.steps = qt_steps(c);
+    const bool qt = use_qt(c);
     hipEvent_t* ev = timer_begin(c);
     int lrc;
     if (g.px == 3) {
@@ -1410,7 +1458,10 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = launch_decode_eg_rgb(D, g.edge() ? 1 : 0, P, R, c->stream);
+        lrc = qt ? launch_decode_eg_rgb_qt(D, g.edge() ? 1 : 0, P, R, c->stream)
+                 : launch_decode_eg_rgb(D, g.edge() ? 1 : 0, P, R, c->stream);
+    } else if (qt) {
+        lrc = launch_decode_eg_qt(D, g.edge() ? 1 : 0, P, E[0], c->stream);
     } else if (g.edge()) {
         lrc = launch_decode_eg_edge(D, P, E[0], c->stream);
     } else {

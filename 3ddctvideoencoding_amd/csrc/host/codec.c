@@ -62,6 +62,77 @@ static int invalid_geometry(int width, int height, int frames, int depth) {
     return 1;
 }
 
+/* ---- the quantiser (codec.h) ------------------------------------------------------------------- */
+#define QUANT_MAX_STEPS 22 /* block depth 8: 8 + 8 + 8 - 2 */
+
+int codec_parse_quant(const char *text, int depth, int32_t *steps) {
+    if (!text || !steps || (depth != 8 && depth != 4)) return 1;
+    const int n = depth + 14;
+    int32_t t[QUANT_MAX_STEPS];
+    char *end = NULL;
+    if (!strncmp(text, "q=", 2)) {
+        if (text[2] < '0' || text[2] > '9') return 1; /* (strtol would take a sign or blanks) */
+        const long q = strtol(text + 2, &end, 10);
+        if (*end != '\0' || q > 255) return 1;
+        for (int s = 0; s < n; s++) t[s] = q * s < 1 ? 1 : q * s > 255 ? 255 : (int32_t)(q * s);
+    } else {
+        const char *p = text;
+        for (int s = 0; s < n; s++) {
+            if (*p < '0' || *p > '9') return 1;
+            const long v = strtol(p, &end, 10);
+            if (v < 1 || v > 255 || *end != (s == n - 1 ? '\0' : ',')) return 1;
+            t[s] = (int32_t)v;
+            p = end + 1;
+        }
+    }
+    memcpy(steps, t, sizeof(int32_t) * (size_t)n);
+    return 0;
+}
+
+static char g_quant_text[QUANT_MAX_STEPS * 4 + 8]; /* codec_set_quant's text; "": none */
+
+int codec_set_quant(const char *text) {
+    if (text && strlen(text) >= sizeof(g_quant_text)) return 1;
+    snprintf(g_quant_text, sizeof(g_quant_text), "%s", text ? text : "");
+    return 0;
+}
+
+/* The quantiser of a call at block depth `depth`: codec_set_quant's text, else DCT3D_CODEC_QUANT.  *set = 0:
+ * none given (the context keeps the reference table).  1 after printing when the text does not parse. */
+static int call_quant(int depth, int32_t *steps, int *set) {
+    const char *text = g_quant_text[0] ? g_quant_text : getenv("DCT3D_CODEC_QUANT");
+    *set = text && text[0];
+    if (*set && codec_parse_quant(text, depth, steps)) {
+        printf("Invalid quantiser '%s': q=<0..255>, or %d comma-separated steps in 1..255\n", text, depth + 14);
+        return 1;
+    }
+    return 0;
+}
+
+/* ... and set on a context right after its creation; 1 after printing on an error */
+static int ctx_apply_quant(dct3d_ctx *ctx, int depth) {
+    int32_t steps[QUANT_MAX_STEPS];
+    int set;
+    if (call_quant(depth, steps, &set)) return 1;
+    const int rc = set ? dct3d_ctx_set_quant(ctx, steps, depth + 14) : DCT3D_OK;
+    if (rc) printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
+    return rc != DCT3D_OK;
+}
+
+/* the table of a context as text for the DCT3D_CODEC_TIMING line: "[1, 5, 10, ...]" */
+static void quant_json(const dct3d_ctx *ctx, int depth, char *buf, size_t cap) {
+    int32_t steps[QUANT_MAX_STEPS];
+    size_t o = 0;
+    buf[0] = '\0';
+    if (!ctx || dct3d_ctx_get_quant(ctx, steps, depth + 14)) {
+        snprintf(buf, cap, "null");
+        return;
+    }
+    for (int s = 0; s < depth + 14 && o + 8 < cap; s++)
+        o += (size_t)snprintf(buf + o, cap - o, "%s%d", s ? ", " : "[", (int)steps[s]);
+    snprintf(buf + o, cap - o, "]");
+}
+
 static int default_batch(void) {
     const char *e = getenv("DCT3D_CODEC_BATCH");
     int b = e ? atoi(e) : 16;
@@ -189,6 +260,10 @@ static dev_worker *dev_workers_create(const int *platformIndices, int n, int wid
         int rc = dct3d_ctx_create(idx > 0 ? idx - 1 : 0, 8, 8, depth, &w->ctx);
         if (rc) {
             printf("Error creating the device context (device %d): %s\n", idx, dct3d_strerror(rc));
+            dev_workers_destroy(ws, n);
+            return NULL;
+        }
+        if (ctx_apply_quant(w->ctx, depth)) {
             dev_workers_destroy(ws, n);
             return NULL;
         }
@@ -515,6 +590,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         if (rc) {
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
+        } else {
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth; /* of the frames as they are */
@@ -602,14 +679,17 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     free(fr);
     free(q);
     free(eg);
+    char qtext[QUANT_MAX_STEPS * 5 + 8];
+    quant_json(ctx, depth, qtext, sizeof(qtext));
     if (ctx) dct3d_ctx_destroy(ctx);
     fclose(in);
     if (timing_on())
         fprintf(stderr,
                 "{\"stage_s\": {\"ctx_create\": %.6f, \"read\": %.6f, \"device\": %.6f, \"eg_fetch\": %.6f, "
-                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"deflate_threads\": %d, \"channels\": %d}\n",
+                "\"%s\": %.6f}, \"total_s\": %.6f, \"host_eg\": %d, \"deflate_threads\": %d, \"channels\": %d, "
+                "\"quant\": %s}\n",
                 t_ctx, t_read, t_dev, t_fetch, host_eg ? "eg_deflate_write" : "deflate_write", t_ent, now_s() - t_start,
-                host_eg, deflate_threads, channels);
+                host_eg, deflate_threads, channels, qtext);
     if (!status) printf("Encoding process completed\n");
     return status;
 }
@@ -640,6 +720,8 @@ static int decode_any(const char *inName, const char *outName, int width, int he
         if (rc) {
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
+        } else {
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth;
@@ -735,14 +817,16 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     }
     free(fr);
     free(q);
+    char qtext[QUANT_MAX_STEPS * 5 + 8];
+    quant_json(ctx, depth, qtext, sizeof(qtext));
     if (ctx) dct3d_ctx_destroy(ctx);
     STAGE(t_write, if (out && (fflush(out) || fclose(out))) status = 1);
     if (timing_on())
         fprintf(stderr,
                 "{\"stage_s\": {\"ctx_create\": %.6f, \"%s\": %.6f, \"device\": %.6f, \"write\": %.6f}, "
-                "\"total_s\": %.6f, \"host_eg\": %d, \"channels\": %d}\n",
+                "\"total_s\": %.6f, \"host_eg\": %d, \"channels\": %d, \"quant\": %s}\n",
                 t_ctx, host_eg ? "read_inflate_eg" : "read_inflate", t_inf, t_dev, t_write, now_s() - t_start, host_eg,
-                channels);
+                channels, qtext);
     if (!status) printf("Decoding process completed\n");
     return status;
 }

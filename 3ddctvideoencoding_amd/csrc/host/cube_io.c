@@ -62,6 +62,28 @@ void applyDequantization_d(float *c, size_t n, int depth) {
                 }
 }
 
+void applyQuantization_steps(float *c, size_t n, int depth, const int32_t *steps) {
+    const size_t cs = (size_t)64 * depth;
+    for (size_t off = 0; off + cs <= n; off += cs)
+        for (int z = 0; z < depth; z++)
+            for (int y = 0; y < 8; y++)
+                for (int x = 0; x < 8; x++) {
+                    float *p = c + off + z * 64 + y * 8 + x;
+                    *p = (float)round(*p / (double)steps[x + y + z]);
+                }
+}
+
+void applyDequantization_steps(float *c, size_t n, int depth, const int32_t *steps) {
+    const size_t cs = (size_t)64 * depth;
+    for (size_t off = 0; off + cs <= n; off += cs)
+        for (int z = 0; z < depth; z++)
+            for (int y = 0; y < 8; y++)
+                for (int x = 0; x < 8; x++) {
+                    float *p = c + off + z * 64 + y * 8 + x;
+                    *p = (float)round(*p * (double)steps[x + y + z]);
+                }
+}
+
 void reorderDctCoeffs_d(float *c, size_t n, float *eg, struct SlicesPositions *sp, int depth) {
     const size_t cs = (size_t)64 * depth;
     size_t k = 0;

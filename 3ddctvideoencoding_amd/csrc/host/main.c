@@ -4,6 +4,9 @@
  *   dct3d_codec encode_rgb <rgb24 file> <name pattern> <width> <height> <frames> [device_index] [block_depth 8|4]
  *   dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <frames> [device_index] [block_depth 8|4]
  *     (packed RGB24 <-> <name pattern>.red / .green / .blue, the RGBUtils plane names; one device)
+ *   every command takes a quantiser after the block depth (codec.h, codec_parse_quant): q=<int>, i.e. step
+ *   max(1, <int> s) clipped to 255 (q=5: the reference's), or block_depth + 14 comma-separated steps in 1..255;
+ *   the file does not record it: decode with the quantiser of the encode
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -28,6 +31,9 @@ static void usage(void) {
     printf("dct3d_codec decode_rgb <name pattern> <rgb24 file> <width> <height> <nr of frames> "
            "<device_index (optional)> <block depth 8|4 (optional)> -> Decode <name pattern>.red/.green/.blue "
            "into packed RGB24\n");
+    printf("Every command takes a quantiser after the block depth: q=<int> (steps max(1, <int> * (x+y+z)), at most "
+           "255; q=5 is the reference's) or <block depth + 14> comma-separated steps in 1..255.  The file does not "
+           "record it: decode with the quantiser of the encode\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -81,6 +87,14 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
+    if (argc > 9 && (depth == 8 || depth == 4)) { /* (any other depth: the entry point reports the geometry) */
+        int32_t steps[32];
+        if (codec_parse_quant(argv[9], depth, steps) || codec_set_quant(argv[9])) {
+            printf("Invalid quantiser '%s': q=<0..255>, or block depth + 14 comma-separated steps in 1..255\n", argv[9]);
+            usage();
+            return 1;
+        }
+    }
     if (!strcmp(argv[1], "encode"))
         return n_dev > 1 ? encode_multi(argv[2], argv[3], width, height, frames, devs, n_dev, depth, 0)
                          : encode_ex(argv[2], argv[3], width, height, frames, devs[0], depth, 0);

@@ -62,6 +62,25 @@ int encode_rgb_ex(const char *inputFileName, const char *outputNamePattern, int 
 int decode_rgb_ex(const char *inputNamePattern, const char *outputFileName, int width, int height, int framesToDecode,
                   int platformIndex, int blockDepth, int stacksPerBatch);
 
+/* The quantiser (dct3d.h, dct3d_ctx_set_quant): one integer step in [1, 255] per s = x + y + z of a
+ * coefficient's position in its cube, blockDepth + 14 of them; the reference's is max(1, 5 s).  The .bin has no
+ * header -- width, height, frame count and block depth are already the caller's to repeat at decode -- and the
+ * quantiser joins them: the file format stays the reference's, and a file is decoded with the quantiser it was
+ * encoded with.  With none given, every file is byte for byte what it was before quantisers existed.
+ *
+ * codec_parse_quant: the one parser of a quantiser given as text: "q=<int>" is step[s] = max(1, <int> * s)
+ *   clipped to 255 (q=5: the reference's; <int> in [0, 255]), or a comma-separated list of exactly
+ *   blockDepth + 14 steps, each in [1, 255].  Returns 0 and fills steps[0 .. blockDepth + 13], or 1 (steps
+ *   untouched) on anything else.
+ * codec_set_quant: the quantiser of every later encode / decode call of this process (every entry point above,
+ *   on every device), as such a text; NULL or "": none.  It overrides the environment variable
+ *   DCT3D_CODEC_QUANT, which holds the same text for callers that cannot add a call.  The text is parsed when
+ *   a call starts, against that call's block depth: a call whose quantiser does not parse prints the reason
+ *   and returns 1.  Returns 1 if the text is too long to keep (nothing changes then). */
+#include <stdint.h>
+int codec_parse_quant(const char *text, int blockDepth, int32_t *steps);
+int codec_set_quant(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
 #define DCT3D_CUBE_IO_H_
 
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "cube_utils.h"
@@ -42,6 +43,10 @@ void applyQuantization_d(float *dctCoeff, size_t bufferSize, int depth);
 void applyDequantization_d(float *dctCoeff, size_t bufferSize, int depth);
 void reorderDctCoeffs_d(float *dctCoeff, size_t bufferSize, float *expGolombDecodedData,
                         struct SlicesPositions *slicesPositions, int depth);
+/* applyQuantization_d / applyDequantization_d with a quantiser table (codec.h): steps[x + y + z], depth + 14
+ * entries, in place of fmax(1, 5 (x + y + z)); the reference's table gives the same values */
+void applyQuantization_steps(float *dctCoeff, size_t bufferSize, int depth, const int32_t *steps);
+void applyDequantization_steps(float *dctCoeff, size_t bufferSize, int depth, const int32_t *steps);
 
 #ifdef __cplusplus
 }

@@ -88,7 +88,7 @@ typedef struct {
     int treeified;        /* 1 if Java's HashMap would have treeified a bin (fold order then unverified) */
     double coef_dc;       /* the single DC group coefficient (DCT.java:110 with k = 0) */
     double dec_G, dec_E;  /* decode certification: margin = L1 * dec_G + dec_E, L1 = sum |q * step| of the cube */
-    float enc_rstep[32];  /* encode certification per s = kx+ky+kz: fp32(1/max(1,5s)) */
+    float enc_rstep[32];  /* encode certification per s = kx+ky+kz: fp32(1/step[s]) (reference: max(1,5s)) */
     float enc_G[32];      /*   threshold_s = 0.5 - (A * G_s + E_s), A = max|x - mean| of the cube */
     float enc_E[32];
     double enc_thr64[32]; /* 8x8x8 second certificate: settled iff |q64 - rint(q64)| < enc_thr64[s] */
@@ -146,7 +146,45 @@ int dct3d_ctx_info(const dct3d_ctx *ctx, int *device, int *block_d, void **hip_s
                                          resolving sync pass, the chunk scan and the mark pass fused, a
                                          decoupled look-back for the chunks' value indices) instead of three
                                          (A/B: measured slower) */
+#define DCT3D_OPT_QUANT_FORCE_TABLE 11 /* test: 1: a context whose quantiser is the reference table runs the
+                                         table kernels (dct3d_ctx_set_quant) too, reading max(1, 5 s) from
+                                         the table instead of having it in their text */
 int dct3d_ctx_set_option(dct3d_ctx *ctx, int option, double value);
+
+/* ---------------------------------------------------------------------------------------------
+ * Quantiser tables (additive to ABI 9).  A quantiser is one integer step per s = kx + ky + kz of a
+ * coefficient's indices, 0 <= s <= bw + bh + bd - 3 (22 entries at 8x8x8, 18 at 8x8x4), each step in
+ * [1, 255].  The reference codec's is step[s] = max(1, 5 s) (Encoder.java:75-89, Decoder.java:78-96),
+ * and a context starts with it.  With any other table the values are DEFINED as that Java code's with
+ * step[x + y + z] in place of Math.max(1, 5 * (x + y + z)):
+ *   encode  q = Math.round(c_java / step)     (IEEE double division of the Java fold's value, the DC's
+ *                                              included, then Math.round's exact half-up rounding)
+ *   decode  (double) q * step, Java's InverseDCT fold, (byte) clamp
+ * and every output is either certified equal to that definition or replayed exactly, as with the
+ * reference table: there is no approximate mode.  Small steps certify less (the bound scales with
+ * 1 / step), so more coefficients take the exact paths; dct3d_get_stats reports them.
+ *
+ * dct3d_ctx_set_quant: n must be bw + bh + bd - 2, every step in [1, 255] (else DCT3D_EINVAL, the table
+ *   unchanged); steps == NULL restores the reference table (n is then ignored).  It waits for the
+ *   context's stream, rebuilds the plan's certification tables and uploads them: it is a property of
+ *   the context, not a per-call argument, and MUST NOT race a call in flight on this context from
+ *   another thread.  A context whose table equals the reference table -- never set, or set explicitly --
+ *   runs the same kernels as before this interface existed.
+ * dct3d_ctx_get_quant: copies the table out (n as above).
+ * dct3d_plan_query_quant: dct3d_plan_query for a table (steps == NULL: the reference table).
+ *
+ * Every raster call honours the context's table, in its _dev and host-pointer forms:
+ * dct3d_encode_stacks*, dct3d_decode_stacks*, the _rgb calls, dct3d_encode_frames*, dct3d_decode_frames*,
+ * dct3d_encode_eg*, dct3d_decode_eg*, the _eg_frames* calls, with or without DCT3D_OPT_EG_TWO_STEP.
+ * (With a table other than the reference's, the grey stream decode runs 8 groups per wave whatever
+ * DCT3D_OPT_EG_DEC_GROUPS says.)  Calls with no quantiser in them are unaffected: the float drop-ins
+ * (dct3d_forward_f32*, dct3d_inverse_f32*), the dct_opt output of dct3d_encode_stacks*, and the entropy
+ * stages on int32 cubes, dct3d_eg_encode_dev and dct3d_eg_decode_dev.  libdct3d_diag.so's kernels keep
+ * the reference table. */
+int dct3d_ctx_set_quant(dct3d_ctx *ctx, const int32_t *steps, int n);
+int dct3d_ctx_get_quant(const dct3d_ctx *ctx, int32_t *steps, int n);
+int dct3d_plan_query_quant(int bw, int bh, int bd, const int32_t *steps, int n, dct3d_plan_info *info,
+                           int32_t *ngroups, double *coef, uint8_t *group_of, double *enc_K);
 /* Enable HIP-event timing of the kernels (reported by dct3d_get_stats). */
 int dct3d_ctx_set_profiling(dct3d_ctx *ctx, int on);
 int dct3d_synchronize(dct3d_ctx *ctx);
