@@ -1,4 +1,4 @@
-"""Shared by the quantiser-table tests (test_quant_*.py, test_gpu_quant.py): the tables T, and the reference the
+"""Shared by the quantiser-table tests (test_quant_*.py, test_gpu_quant*.py): the tables T, and the reference the
 tests compare with -- the oracle's Java-semantics DCT with the package's numpy definition of the quantiser
 around it:
 
@@ -84,3 +84,133 @@ def ref_frames(frames, steps, depth):
         q = ref_encode(planar(pad, depth), steps, depth)
         out = packed(ref_decode(q, wp, hp, 3 * pad.shape[0], steps, depth), depth)[:, :h, :w]
     return q, np.ascontiguousarray(out)
+
+
+# ---- decode inputs that no encoder of 8-bit frames writes (test_gpu_quant_foreign.py) -----------------------------
+
+Q15 = 2**15 - 1  # the largest |q| whose Exp-Golomb code (31 bits) the stream decode's unchecked parse steps take
+
+
+def step_cube(steps, depth):
+    """int64 [depth, 8, 8]: steps[kx + ky + kz]"""
+    z, y, x = np.ogrid[:depth, :8, :8]
+    return np.asarray(steps, np.int64)[x + y + z]
+
+
+def l1(q, steps, depth):
+    """sum |q * step| of each cube, exact (int64: < 2^31 * 255 * 512 < 2^49): what the decode compares with dec_l1_max"""
+    q = np.asarray(q, np.int64).reshape(-1, depth, 8, 8)
+    return (np.abs(q) * step_cube(steps, depth)).sum(axis=(1, 2, 3))
+
+
+@functools.lru_cache(maxsize=None)
+def l1_max(depth):
+    """the decode's guard: a cube whose L1 reaches it goes to the exact replay whole.  It does not depend on the
+    table (test_quant_plan.py), so the reference table's plan is asked"""
+    return float(pkg().plan_query(8, 8, depth)["dec_l1_max"])
+
+
+def code_bits(v):
+    """bits of each value's signed order-0 Exp-Golomb code (ExpGolombWriter.java: code = 2|v| - (v > 0) + 1, 2n - 1
+    bits for a code of n bits), in exact integer arithmetic"""
+    v = np.asarray(v, np.int64)
+    code = np.where(v <= 0, -2 * v, 2 * v - 1) + 1
+    n = np.zeros(code.shape, np.int64)
+    while (code >> n).any():
+        n += (code >> n) > 0
+    return 2 * n - 1
+
+
+@functools.lru_cache(maxsize=None)
+def widest_ac(depth):
+    """((kz, ky, kx), B): the AC coefficient whose largest basis product B = max over the pixels of
+    |b_kz(z) b_ky(y) b_kx(x)| is the largest, the orthonormal DCT-II basis b_k(n) = c_k sqrt(2 / N)
+    cos((2n + 1) k pi / 2N), c_0 = 1 / sqrt 2.  dec_l1_max is 32000 / B (dct3d_plan.cpp)."""
+    def peak(N):
+        k, n = np.ogrid[:N, :N]
+        b = np.sqrt(2.0 / N) * np.cos((2 * n + 1) * k * np.pi / (2 * N))
+        b[0] /= np.sqrt(2.0)
+        return np.abs(b).max(axis=1)
+    prod = peak(depth)[:, None, None] * peak(8)[None, :, None] * peak(8)[None, None, :]
+    prod[0, 0, 0] = 0.0
+    at = np.unravel_index(int(np.argmax(prod)), prod.shape)
+    return tuple(int(i) for i in at), float(prod[at])
+
+
+def saturation_cubes(depth, rng, n_random=1):
+    """test_decode_saturation_extremes' list: DC +-20000, DC 2^31 - 1 and -2^31, zeros, DC 2000 with an AC of 2^30,
+    DC 3000 with -2^28 at (1, 2, 3), and n_random cubes of random values in +-2000"""
+    q = np.zeros((7 + n_random, depth, 8, 8), np.int64)
+    q[0, 0, 0, 0] = 20000
+    q[1, 0, 0, 0] = -20000
+    q[2, 0, 0, 0] = 2**31 - 1
+    q[3, 0, 0, 0] = -(2**31)
+    q[5, 0, 0, 0], q[5, 0, 0, 1] = 2000, 2**30
+    q[6, 0, 0, 0], q[6, 1, 2, 3] = 3000, -2**28
+    q[7:] = rng.integers(-2000, 2000, size=(n_random, depth, 8, 8))
+    return q.astype(np.int32)
+
+
+def random_dense_cubes(depth, rng, n):
+    """test_decode_random_coefficients' cubes: AC in [-40, 40], DC in [-300, 6000]"""
+    q = rng.integers(-40, 41, size=(n, depth, 8, 8))
+    q[:, 0, 0, 0] = rng.integers(-300, 6000, size=n)
+    return q.astype(np.int32)
+
+
+def ordinary_cubes(steps, depth, rng, n):
+    """cubes as an encoder writes them under the table: a DC of a mid-grey block and sparse small AC values divided
+    by their steps; L1 far below the guard (asserted by the caller)"""
+    c = rng.integers(-30, 31, size=(n, depth, 8, 8)) * (rng.random((n, depth, 8, 8)) < 0.3)
+    c[:, 0, 0, 0] = rng.integers(200, 5000, size=n)
+    return np.rint(c / step_cube(steps, depth)).astype(np.int32)
+
+
+def guard_cube(steps, depth, rng, target):
+    """a dense cube of random signs whose L1 = sum |q * step| lies in (target - max(steps), target]: every |q| starts
+    at floor(target / sum(step)), then entries in random order gain 1 while that still fits"""
+    st = step_cube(steps, depth).reshape(-1)
+    a = np.full(st.size, int(target) // int(st.sum()), np.int64)
+    room = int(target) - int((a * st).sum())
+    assert room >= 0
+    while room >= int(st.min()):
+        for i in rng.permutation(st.size):
+            if st[i] <= room:
+                a[i] += 1
+                room -= int(st[i])
+    q = a * rng.choice([-1, 1], size=st.size)
+    return q.reshape(depth, 8, 8).astype(np.int32)
+
+
+def widest_cubes(steps, depth):
+    """four cubes on the ordinary path whose pixels come nearest the byte packing's signed 16-bit read: only the AC
+    coefficient of widest_ac, q = +-floor(0.98 dec_l1_max / step); the same over a DC of 128 sqrt(512) / step[0]"""
+    (kz, ky, kx), _ = widest_ac(depth)
+    qa = int(0.98 * l1_max(depth) / int(steps[kz + ky + kx]))
+    q = np.zeros((4, depth, 8, 8), np.int32)
+    q[0, kz, ky, kx], q[1, kz, ky, kx] = qa, -qa
+    q[2, kz, ky, kx], q[3, kz, ky, kx] = qa, -qa
+    q[2:, 0, 0, 0] = int(round(128 * np.sqrt(512.0) / int(steps[0])))
+    return q
+
+
+def ref_decode_frames(q, w, h, stacks, channels, steps, depth):
+    """decode_frames' definition on any int32 input: q [stack][channel][cube] of the padded raster -> the frames
+    [F, h, w] or [F, h, w, 3], by ref_decode (dequantize_ref, the oracle's Java fold, the (byte) clamp), cropped"""
+    wp, hp = pkg().padded_size(w, h)
+    out = ref_decode(np.ascontiguousarray(q, np.int32), wp, hp, channels * stacks * depth, steps, depth)
+    if channels == 3:
+        out = packed(out, depth)
+    return np.ascontiguousarray(out[:, :h, :w])
+
+
+def banded(torch, nbytes, fill, band=4096):
+    """a device byte buffer of band + nbytes + band bytes, all `fill`: (the buffer, its middle view)"""
+    buf = torch.full((band + nbytes + band,), fill, dtype=torch.uint8, device="cuda")
+    return buf, buf[band:band + nbytes]
+
+
+def bands_intact(buf, nbytes, fill, band=4096):
+    """(the middle as a numpy array, whether both bands still hold `fill`)"""
+    host = buf.cpu().numpy()
+    return host[band:band + nbytes], bool((host[:band] == fill).all() and (host[band + nbytes:] == fill).all())
