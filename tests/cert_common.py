@@ -1,0 +1,331 @@
+"""Shared by test_cert_common.py (CPU) and test_gpu_certificates.py (GPU): what the host emulations of the kernels'
+arithmetic predict for the counts dct3d_get_stats reports -- which coefficients the fp32 encode certificate leaves
+open, which lanes the decode certificate flags, and how the 8x8x8 second certificate splits the open ones.
+
+The emulations are tests/native/emulate_encode.cpp and emulate_decode_quant.cpp, built here as test_emulation.py
+builds them (g++ -O2 -ffp-contract=off -fno-fast-math, into a temporary directory).  With contraction off on both
+sides and the same butterfly source, IEEE fp32 / fp64 arithmetic is deterministic: the device's counts must equal
+these predictions exactly.  No GPU is needed by anything in this module."""
+import atexit
+import ctypes as C
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+
+import quant_common as qc
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "3ddctvideoencoding_amd", "csrc")
+NATIVE = os.path.join(REPO, "tests", "native")
+GXX = ["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-shared", "-fPIC", "-I", CSRC]
+
+
+@functools.lru_cache(maxsize=None)
+def _libs():
+    """(emulate_encode's library, emulate_decode_quant's), built once per process"""
+    d = tempfile.mkdtemp(prefix="cert_emu_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    out = []
+    for src in ("emulate_encode.cpp", "emulate_decode_quant.cpp"):
+        so = os.path.join(d, src.replace(".cpp", ".so"))
+        subprocess.run(GXX + [os.path.join(NATIVE, src), "-o", so], check=True)
+        out.append(C.CDLL(so))
+    out[0].emulate_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    out[1].emulate_decode_quant_w.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return tuple(out)
+
+
+def steps_of(steps, depth):
+    """the table as int32 (None: the reference's max(1, 5 s))"""
+    return qc.pkg().quant_table(5, depth) if steps is None else np.ascontiguousarray(steps, np.int32)
+
+
+def raster_of(frames, depth):
+    """frames [F, h, w] or packed [F, h, w, 3], any h, w -> the edge-padded raster the calls are defined on, RGB as
+    the planar-stacked raster of dct3d.h (per stack: its R, G, B frames): [channels F, Hp, Wp]"""
+    pad = qc.pkg().pad_frames(np.asarray(frames, np.uint8))
+    return np.ascontiguousarray(pad if pad.ndim == 3 else qc.planar(pad, depth))
+
+
+def encode_emulate(frames, depth, steps=None, channels=1, shift=0):
+    """the emulated fp32 kernel on the cubes of raster_of(frames): (q, open, cubes).  open[cube][kz][ky][kx] is the
+    fp32 certificate's verdict, DC cleared; cubes in the calls' output order [stack][channel][by][bx].
+    shift (the sensitivity check only): the threshold tables G, E read at s + shift, clamped to the table."""
+    import oracle
+    assert channels == (3 if np.asarray(frames).ndim == 4 else 1)
+    p = qc.pkg().plan_query(8, 8, depth, steps)
+    cubes = np.ascontiguousarray(oracle.to_cubes(raster_of(frames, depth), 8, 8, depth), np.uint8)
+    n = cubes.shape[0]
+    q = np.empty(cubes.size, np.int32)
+    fl = np.empty(cubes.size, np.uint8)
+    val = np.empty(cubes.size, np.float32)
+    A = np.empty(n, np.float32)
+    ns = qc.n_steps(depth)
+    idx = np.minimum(np.arange(32) + shift, ns - 1)
+    t = [np.ascontiguousarray(p["enc_rstep"], np.float32), np.ascontiguousarray(p["enc_G"][idx], np.float32),
+         np.ascontiguousarray(p["enc_E"][idx], np.float32)]
+    _libs()[0].emulate_encode(cubes.ctypes.data, n, depth, t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data,
+                              p["coef_dc"], q.ctypes.data, fl.ctypes.data, val.ctypes.data, A.ctypes.data)
+    shape = (n, depth, 8, 8)
+    op = fl.reshape(shape).astype(bool)
+    op[:, 0, 0, 0] = False
+    q = q.reshape(shape)
+    # the DC as the kernels make it: JavaRound(S * coef_dc / step[0]) in fp64 (the emulation has step[0] = 1 in its text)
+    dc = (cubes.reshape(n, -1).sum(axis=1, dtype=np.int64).astype(np.float64) * p["coef_dc"]) / float(steps_of(steps, depth)[0])
+    q[:, 0, 0, 0] = (np.floor(dc) + (dc - np.floor(dc) >= 0.5)).astype(np.int32)
+    return q, op, cubes
+
+
+def encode_open(frames, depth, steps=None, channels=1):
+    """bool [cube][kz][ky][kx]: the coefficients the fp32 certificate leaves open (the DC never is)"""
+    return encode_emulate(frames, depth, steps, channels)[1]
+
+
+def dct_cubes(frames, depth):
+    """the oracle's fp64 DCT (Java semantics) of raster_of(frames), as cubes"""
+    import oracle
+    return oracle.to_cubes(qc.plan(depth).dct(raster_of(frames, depth)), 8, 8, depth)
+
+
+TIE, BAND = 1e-12, 1e-9  # split_8x8x8: 0.5 - d <= TIE is a tie; (TIE, BAND) must be empty
+
+
+def split_8x8x8(frames, open_mask, steps, dct=None):
+    """With the second certificate on (8x8x8), which open coefficients stay open for the Java fold and which the
+    fp64 recheck settles, from the oracle's fp64 DCT alone (not the kernel's fp64 path): with
+    d = |c / step - rint(c / step)|, an open coefficient with 0.5 - d < 1e-9 is an exact tie (fold); every other
+    one is rechecked.  Precondition (asserted): no open coefficient in the ambiguous band 1e-12 < 0.5 - d < 1e-9.
+    Returns (fold mask, rechecked mask); the predicted (n_flagged, n_rechecked) are their sums."""
+    d = dct_cubes(frames, 8) if dct is None else dct
+    v = d / qc.step_cube(steps_of(steps, 8), 8)
+    gap = 0.5 - np.abs(v - np.rint(v))
+    amb = open_mask & (gap > TIE) & (gap < BAND)
+    assert not amb.any(), f"{int(amb.sum())} open coefficients in the ambiguous band: another seed"
+    fold = open_mask & (gap < BAND)
+    return fold, open_mask & ~fold
+
+
+# ---- decode ---------------------------------------------------------------------------------------------------------
+
+L1_FACTOR = 1.0 + 2.0 ** -19  # decode_tile: the fp32 cube sum times (1.0f + 0x1p-19f)
+L1_SLACK = 2.0 ** -20         # the fp64 lane sums, the conversion and the five fp32 roundings: < 6 * 2^-24
+
+
+def _mi(l1f, G, E):
+    """decode_tile: m = fmin((double)l1_f * dec_G + dec_E, 0.5); mi = (uint32)ceil(fma(m, 2^32, 0.5)) + 1
+    (m * 2^32 is exact, so the fma is the plain sum's one rounding)"""
+    m = np.minimum(l1f * G + E, 0.5)
+    return np.ceil(m * 4294967296.0 + 0.5).astype(np.int64) + 1
+
+
+def decode_emulate(q, depth, steps, extra_margin):
+    """The decode certificate (decode_tile, dct3d_decode_dev.h) on int32 cubes q [n, depth, 8, 8]: the mask of
+    flagged lanes [n, lanes per cube] (the predicted n_flagged is 32 x its sum), and the bytes [n, depth, 8, 8] the kernel
+    packs from w's high word (the low half as a signed 16-bit value, saturated to [0, 255]).
+
+    Ownership (layout C, dec_b_to_c / dec_store_tile): a lane owns 32 pixels of one row y of its cube over every
+    depth z -- 8x8x8: 16 lanes per cube, lane (y, h) the pixels x = 4h .. 4h + 3 of z = 0 .. 7 (mask index 2 y + h);
+    8x8x4: 8 lanes per cube, lane y the pixels x = 0 .. 7 of z = 0 .. 3.  A lane is flagged when the low word of
+    w = v + kFixMagic of one of its pixels is < mi or > 2^32 - 1 - mi, or when its cube's L1 reaches dec_l1_max
+    (then all lanes of the cube).  DCT3D_OPT_DEC_MARGIN is added to dec_E on the host, in fp64.
+
+    The kernel's fp32 reduction of L1 is not restated: l1_f lies within L1 (1 + 2^-19) (1 +- 2^-20).  Asserted
+    preconditions: both ends give the same mi for every cube, and no cube's L1 lies that close to dec_l1_max."""
+    p = qc.pkg().plan_query(8, 8, depth, steps)
+    st = steps_of(steps, depth)
+    q = np.ascontiguousarray(q, np.int32).reshape(-1, depth, 8, 8)
+    n = q.shape[0]
+    w = np.empty(q.size, np.float64)
+    l1e = np.empty(n, np.float64)
+    _libs()[1].emulate_decode_quant_w(q.ctypes.data, n, depth, st.ctypes.data, w.ctypes.data, l1e.ctypes.data)
+    l1 = qc.l1(q, st, depth).astype(np.float64)  # exact integers (< 2^49)
+    assert np.array_equal(l1, l1e)
+    lo_l, hi_l = l1 * L1_FACTOR * (1.0 - L1_SLACK), l1 * L1_FACTOR * (1.0 + L1_SLACK)
+    lmax = float(p["dec_l1_max"])
+    assert not ((lo_l < lmax) & (hi_l >= lmax)).any(), "a cube's L1 within 2^-20 of dec_l1_max"
+    E = p["dec_E"] + float(extra_margin)
+    mi = _mi(lo_l, p["dec_G"], E)
+    assert np.array_equal(mi, _mi(hi_l, p["dec_G"], E)), "mi depends on the fp32 L1 reduction: another seed"
+    lo = (w.view(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64).reshape(n, depth, 8, 8)
+    bad = (lo < mi[:, None, None, None]) | (lo > 0xFFFFFFFF - mi[:, None, None, None])
+    if depth == 8:
+        lanes = bad.reshape(n, 8, 8, 2, 4).any(axis=(1, 4)).reshape(n, 16)  # [y][h]
+    else:
+        lanes = bad.any(axis=(1, 3))  # [y]
+    h16 = ((w.view(np.uint64) >> np.uint64(32)) & np.uint64(0xFFFF)).astype(np.int64)
+    byte = np.clip(np.where(h16 >= 32768, h16 - 65536, h16), 0, 255).astype(np.uint8).reshape(n, depth, 8, 8)
+    return lanes | (lo_l >= lmax)[:, None], byte
+
+
+def decode_open(q, depth, steps, extra_margin):
+    """the mask of flagged lanes alone (decode_emulate)"""
+    return decode_emulate(q, depth, steps, extra_margin)[0]
+
+
+def lane_pixels(lanes, depth):
+    """flagged lanes [n, lanes per cube] -> the mask of the pixels they own [n, depth, 8, 8]"""
+    n = lanes.shape[0]
+    if depth == 8:
+        return np.broadcast_to(lanes.reshape(n, 1, 8, 2, 1), (n, 8, 8, 2, 4)).reshape(n, 8, 8, 8)
+    return np.broadcast_to(lanes.reshape(n, 1, 8, 1), (n, 4, 8, 8))
+
+
+def guard_cubes(depth, name):
+    """the L1 guard case: four cubes, two just under and two just over dec_l1_max (quant_common.guard_cube, 2^-10 either
+    side: far outside decode_emulate's 2^-20 band): (q [4, depth, 8, 8], the mask of the cubes over the guard)"""
+    T = steps_of(table(name, depth), depth)
+    rng = np.random.default_rng(4100 + depth)
+    lmax = qc.l1_max(depth)
+    q = np.stack([qc.guard_cube(T, depth, rng, lmax * (1 + s * 2.0 ** -10)) for s in (-1, 1, 1, -1)])
+    over = qc.l1(q, T, depth) >= lmax
+    assert over.tolist() == [False, True, True, False]
+    return q, over
+
+
+# ---- bands ----------------------------------------------------------------------------------------------------------
+
+def band_counts(mask, stacks, channels, nby):
+    """per-unit mask [cube, ...] in the calls' order [stack][channel][by][bx] -> int64 [nby]: the count of each
+    horizontal band of one block row (over every stack and channel)"""
+    m = mask.reshape(stacks, channels, nby, -1)
+    return m.sum(axis=(0, 1, 3)).astype(np.int64)
+
+
+def band_frames(frames, by):
+    """block row by of the frames, cropped (the last band of a ragged height is shorter: the calls pad it)"""
+    return np.ascontiguousarray(frames[:, 8 * by:8 * by + 8])
+
+
+def band_cubes(q, stacks, channels, nby, by):
+    """the cubes of block row by, in the order the calls take for the cropped frames"""
+    s = q.shape[1:]
+    return np.ascontiguousarray(q.reshape((stacks, channels, nby, -1) + s)[:, :, by]).reshape((-1,) + s)
+
+
+def is_rich(counts):
+    """a case can see a shifted threshold: >= 20 open units in all, a non-zero count in >= a quarter of its bands"""
+    counts = np.asarray(counts)
+    return int(counts.sum()) >= 20 and 4 * int((counts > 0).sum()) >= counts.size
+
+
+def first_difference(pred, got, mask, stacks, channels, nby):
+    """for a failing case: the first band whose counts differ and the emulation's open positions in it
+    (pred, got: one row of counts per band)"""
+    pred, got = np.asarray(pred).reshape(nby, -1), np.asarray(got).reshape(nby, -1)
+    by = int(np.nonzero((pred != got).any(axis=1))[0][0])
+    m = mask.reshape((stacks, channels, nby, -1) + mask.shape[1:])[:, :, by]
+    return f"band {by}: predicted {pred[by].tolist()}, device {got[by].tolist()}; the emulation's open units " \
+           f"(stack, channel, bx, ...) {np.argwhere(m)[:16].tolist()}"
+
+
+# ---- the inputs and cases of test_gpu_certificates.py (checked on the CPU by test_cert_common.py) ----------------------
+
+TABLES = ("ref", "q1", "q12", "seeded")  # ref: no table set (None)
+
+
+def table(name, depth):
+    return None if name == "ref" else qc.tables(depth)[name]
+
+
+@functools.lru_cache(maxsize=None)
+def content(kind, depth, channels, w, h, stacks, seed=0):
+    """seeded frames [stacks depth, h, w] (channels = 3: [.., 3]), never modified.  uniform: pkg.synthetic's noise,
+    the content whose coefficients come near rounding ties (~1e-4 of them open under the reference table);
+    ties4: test_encode_8x8x4_inwave_replay's exact ties in half of the cubes; ramp_crop: block rows 58-65 and block
+    columns 186-193 of the 1080p ramp stack at frame 200, around cube 14829's exact tie
+    (test_encode_8x8x8_exact_tie_takes_java_fold)"""
+    p = qc.pkg()
+    f = stacks * depth
+
+    def plane(i):
+        if kind == "uniform":
+            return p.synthetic.frames(w, h, f, seed=0xC357 + 131 * i + seed, frame0=7 + 3 * i + seed, kind="uniform")
+        if kind == "ties4":
+            z, y, x = np.meshgrid(np.arange(f), np.arange(h), np.arange(w), indexing="ij")
+            v = 100 + ((x // 8 + y // 8) % 3) * 2 + 8 * ((z % 4 == 0) & ((y % 8 == 0) | ((y % 8 == 1) & (x % 8 < 2))))
+            v += 16 * ((z % 4 == 3) & (x % 8 == 4) & (y % 8 < 5) & ((x // 8) % 2 == 1))
+            return v.astype(np.uint8)
+        assert kind == "ramp_crop" and (w, h, f) == (64, 64, 8)
+        return p.synthetic.frames(1920, 1080, 8, kind="ramp", frame0=200)[:, 58 * 8:66 * 8, 186 * 8:194 * 8]
+
+    fr = plane(0) if channels == 1 else np.stack([plane(0), plane(1), plane(2)], axis=-1)
+    fr = np.ascontiguousarray(fr, np.uint8)
+    fr.setflags(write=False)
+    return fr
+
+
+class Case:
+    """one input of a call family; rich: the tables under which the case must be rich (is_rich, asserted)"""
+
+    def __init__(self, kind, depth, channels, w, h, stacks, rich=(), seed=0):
+        self.kind, self.depth, self.channels, self.w, self.h, self.stacks = kind, depth, channels, w, h, stacks
+        self.rich, self.seed = tuple(rich), seed
+        self.nby = (h + 7) // 8
+        self.id = f"{kind}-{w}x{h}x{stacks}-{'rgb' if channels == 3 else 'grey'}-d{depth}"
+
+    def frames(self):
+        return content(self.kind, self.depth, self.channels, self.w, self.h, self.stacks, self.seed)
+
+    def __repr__(self):
+        return self.id
+
+
+@functools.lru_cache(maxsize=4)
+def _case_dct(kind, depth, channels, w, h, stacks, seed):
+    d = dct_cubes(content(kind, depth, channels, w, h, stacks, seed), depth)
+    d.setflags(write=False)
+    return d
+
+
+def case_dct(c):
+    """the oracle's fp64 DCT of the case's padded (planar) raster as cubes, shared by the case's tables"""
+    return _case_dct(c.kind, c.depth, c.channels, c.w, c.h, c.stacks, c.seed)
+
+
+@functools.lru_cache(maxsize=8)
+def _case_open(kind, depth, channels, w, h, stacks, seed, name, shift):
+    q, op, _ = encode_emulate(content(kind, depth, channels, w, h, stacks, seed), depth, table(name, depth), channels, shift)
+    q.setflags(write=False)
+    op.setflags(write=False)
+    return q, op
+
+
+def case_open(c, name, shift=0):
+    """(the emulation's q, its open mask) of the case under table `name`"""
+    return _case_open(c.kind, c.depth, c.channels, c.w, c.h, c.stacks, c.seed, name, shift)
+
+
+def case_q_ref(c, name):
+    """the reference's coefficients (quant_common.py): the oracle's Java DCT, then the numpy quantiser"""
+    return qc.pkg().quantize_ref(case_dct(c), steps_of(table(name, c.depth), c.depth))
+
+
+# the encode cases, by call family (test_gpu_certificates.py a-f); RICH8 / RICH4: the tables under which the 8x8x8 /
+# 8x8x4 cases of these sizes are rich (q12, and at 8x8x4 the seeded table, leave too few coefficients open)
+RICH8, RICH4 = ("ref", "q1", "seeded"), ("ref", "q1")
+STACKS8 = [Case("uniform", 8, 1, 200, 72, 4, RICH8), Case("uniform", 8, 1, 24, 16, 5), Case("uniform", 8, 1, 8, 8, 1),
+           Case("ramp_crop", 8, 1, 64, 64, 1), Case("uniform", 8, 1, 1920, 1080, 1, TABLES)]
+STACKS4 = [Case("uniform", 4, 1, 200, 72, 4, RICH4), Case("uniform", 4, 1, 24, 16, 5), Case("uniform", 4, 1, 8, 8, 1),
+           Case("ties4", 4, 1, 200, 72, 3), Case("uniform", 4, 1, 1920, 1080, 1, TABLES)]
+RGB = [Case("uniform", 8, 3, 200, 72, 2, RICH8), Case("uniform", 8, 3, 24, 16, 5), Case("uniform", 8, 3, 8, 8, 1),
+       Case("uniform", 4, 3, 200, 72, 2, RICH4), Case("uniform", 4, 3, 24, 16, 5), Case("uniform", 4, 3, 8, 8, 1)]
+EDGE = [Case("uniform", d, ch, w, h, st, rich)
+        for d in (8, 4) for ch in (1, 3)
+        for (w, h, st, rich) in ((1366, 24, 2 if ch == 1 else 1, RICH8 if d == 8 else RICH4), (13, 11, 1, ()), (1, 1, 1, ()))]
+# the stream encode kernels that count: grey at sizes that are no multiple of 8, RGB at any size
+EG = [Case("uniform", d, 1, w, h, st, rich)
+      for d in (8, 4) for (w, h, st, rich) in ((1366, 24, 2, RICH8 if d == 8 else RICH4), (13, 11, 1, ()))] + \
+     [Case("uniform", d, 3, w, h, st, rich)
+      for d in (8, 4) for (w, h, st, rich) in ((200, 72, 2, RICH8 if d == 8 else RICH4), (24, 16, 5, ()), (13, 11, 1, ()))]
+
+# DCT3D_OPT_DEC_MARGIN values.  A lane owns 32 pixels and is flagged when one of them has its fractional part within
+# m of an integer: for fractional parts spread evenly a share 1 - (1 - 2 m)^32 of the lanes, so m = (1 - (1 - p)^(1/32)) / 2
+# gives 1.57e-4, 1.64e-3 and 1.07e-2 for p = 1 %, 10 % and 50 %.  Rounded, on the decode of uniform noise's coefficients
+# (200 x 72, cert_common.decode_open on the CPU) they flag 0.7-1.1 %, 9.0-10.0 % and 50.1-51.1 % of the lanes.
+MARGINS = (1.5e-4, 1.6e-3, 1.1e-2)
+DEC = [Case("uniform", d, ch, w, h, 1) for d in (8, 4) for ch in (1, 3) for (w, h) in ((200, 72), (1366, 24), (13, 11))]

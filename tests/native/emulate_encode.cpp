@@ -1,8 +1,15 @@
-// tests/native/emulate_encode.cpp -- TEST ONLY: host emulation of the fused encode kernel's fp32
-// arithmetic (csrc/dct3d_kernels.hip, encode_kernel): the same butterfly source
-// (csrc/dct_butterfly.h) in the same order -- pass X with the exact integer front and cube-mean
-// centring, pass Z, pass Y -- then the kernel's quantise/certify step.  Built by the tests with
-// g++ -O2 -ffp-contract=off; never linked into the product.
+// tests/native/emulate_encode.cpp -- TEST ONLY: host emulation of the encode kernels' fp32 arithmetic:
+// the same butterfly source (csrc/dct_butterfly.h) in the same order -- pass X with the exact integer
+// front and cube-mean centring, pass Z, pass Y -- then the quantise/certify step
+// (thr_s = fma(-A, G_s, 0.5f - E_s); open iff |q - rint(q)| >= thr_s).  It restates encode_body
+// (csrc/dct3d_encode_dev.h: encode_kernel, encode_rgb_kernel, 8x8x4), and stands for every hand-written
+// copy of that step, whose values are the same line by line: e16_body (encode16_kernel,
+// encode16_rgb_kernel, 8x8x8: tab_window_desc), encode_eg_kernel's own loop (csrc/dct3d_eg_fused_dev.h,
+// both depths), and their EDGE, PX = 3 and QT = 1 instantiations -- the tables {1 / step, G, E} are
+// arguments, so a quantiser table's plan goes through unchanged (step[0] of the DC's closed form is 1
+// here; cert_common.py divides).  tests/test_gpu_certificates.py holds the device to it: the count of
+// open coefficients each of those kernels reports equals this emulation's, exactly.  Built by the tests
+// with g++ -O2 -ffp-contract=off; never linked into the product.
 #include <cmath>
 #include <cstdint>
 #include <cstring>

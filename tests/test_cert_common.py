@@ -1,0 +1,134 @@
+"""CPU: cert_common.py, the predictions test_gpu_certificates.py compares the device's counts with.
+
+  * encode_open is test_emulation.py's emulation: the same flags on the same cubes;
+  * soundness, restated for the shapes and tables used on the GPU: every coefficient encode_open leaves closed has the
+    emulated q equal to the reference's (quant_common.py), every pixel of a lane decode_open does not flag has the
+    emulated byte equal to the oracle's decode;
+  * the preconditions of every GPU case hold -- richness, the empty ambiguous band of split_8x8x8, decode_open's
+    margin and guard bands -- so that a bad seed is found here, without a GPU;
+  * sensitivity: the thresholds read at s + 1 instead of s (the tables shifted in Python, no kernel built) change the
+    predicted count of every rich case: that mutation cannot pass the GPU module unseen."""
+import numpy as np
+import pytest
+
+import cert_common as cc
+import quant_common as qc
+from test_emulation import emu, run  # noqa: F401  (emu: the fixture that builds emulate_encode.cpp)
+
+ENCODE_CASES = cc.STACKS8 + cc.STACKS4 + cc.RGB + cc.EDGE + cc.EG
+_seen = set()
+ENCODE_CASES = [c for c in ENCODE_CASES if not (c.id in _seen or _seen.add(c.id))]  # (families share inputs)
+
+
+@pytest.mark.parametrize("depth", [8, 4])
+def test_encode_open_is_the_emulation_of_test_emulation(emu, pkg, oracle, depth):  # noqa: F811
+    for c in (cc.Case("uniform", depth, 1, 200, 72, 4), cc.Case("uniform", depth, 1, 13, 11, 1)):
+        cubes = oracle.to_cubes(cc.raster_of(c.frames(), depth), 8, 8, depth)
+        q, fl, _, _, _ = run(emu, pkg, cubes, depth)
+        q2, op, cubes2 = cc.encode_emulate(c.frames(), depth)
+        assert np.array_equal(cubes, cubes2) and np.array_equal(q, q2)
+        assert not fl[:, 0, 0, 0].any() and np.array_equal(op, fl)
+        assert np.array_equal(cc.encode_open(c.frames(), depth), fl)
+
+
+def test_rgb_raster_is_the_planar_stacked_one(pkg):
+    """channels = 3: per stack its R, then G, then B frames (dct3d.h), each plane padded as a grey one"""
+    c = cc.Case("uniform", 4, 3, 13, 11, 2)
+    fr = c.frames()
+    r = cc.raster_of(fr, 4)
+    assert r.shape == (24, 16, 16)
+    for s in range(2):
+        for ch in range(3):
+            assert np.array_equal(r[12 * s + 4 * ch:12 * s + 4 * ch + 4], pkg.pad_frames(fr[4 * s:4 * s + 4, :, :, ch]))
+    op = cc.encode_open(fr, 4, qc.tables(4)["q1"], channels=3)
+    planes = [cc.encode_open(np.ascontiguousarray(fr[..., ch]), 4, qc.tables(4)["q1"]) for ch in range(3)]
+    assert op.sum() == sum(p.sum() for p in planes)  # the count is the sum over the three planes
+
+
+@pytest.mark.parametrize("c", ENCODE_CASES, ids=repr)
+def test_encode_case_soundness_preconditions_sensitivity(c):
+    """soundness at the GPU module's shapes (under every table, what encode_open leaves closed is the reference's q, the
+    DC by its closed form); richness where the case claims it; split_8x8x8's empty band; and the shifted threshold
+    seen by every rich case.  (One function per case: the emulation and the oracle's DCT are computed once.)"""
+    for name in cc.TABLES:
+        q, op = cc.case_open(c, name)
+        bad = (q != cc.case_q_ref(c, name)) & ~op
+        assert not bad.any(), f"{name}: {int(bad.sum())} closed coefficients differ"
+        counts = cc.band_counts(op, c.stacks, c.channels, c.nby)
+        if c.depth == 8:
+            fold, rechk = cc.split_8x8x8(c.frames(), op, cc.table(name, 8), cc.case_dct(c))  # (asserts the band empty)
+            assert not (fold & rechk).any() and np.array_equal(fold | rechk, op)
+        if name in c.rich:
+            assert cc.is_rich(counts), f"{c.id} {name}: {counts.tolist()}"
+            shifted = cc.band_counts(cc.case_open(c, name, shift=1)[1], c.stacks, c.channels, c.nby)
+            assert shifted.sum() != counts.sum(), f"{c.id} {name}: the count does not see thr[s + 1]"
+            assert not np.array_equal(shifted, counts)
+        print(f"{c.id} {name}: {int(op.sum())} open, per band {counts.tolist() if c.nby <= 9 else '...'}")
+
+
+def test_every_table_has_a_rich_case_in_every_family():
+    for fam in (cc.STACKS8, cc.STACKS4):
+        assert {n for c in fam for n in c.rich} == set(cc.TABLES)
+    for fam in (cc.RGB, cc.EDGE, cc.EG):
+        for depth, want in ((8, cc.RICH8), (4, cc.RICH4)):
+            assert {n for c in fam if c.depth == depth for n in c.rich} == set(want)
+
+
+def test_ramp_crop_holds_the_exact_tie():
+    """cube 14829 of the 1080p ramp stack at frame 200 is block (61, 189): block (3, 3) of the crop, whose (0, 2, 2) is
+    10 = 0.5 * step exactly; the fp32 certificate leaves it open and split_8x8x8 sends it to the fold"""
+    c = cc.STACKS8[3]
+    assert c.kind == "ramp_crop" and 14829 == 61 * 240 + 189
+    _, op = cc.case_open(c, "ref")
+    fold, _ = cc.split_8x8x8(c.frames(), op, None, cc.case_dct(c))
+    assert op[27, 0, 2, 2] and fold[27, 0, 2, 2] and fold.sum() >= 1
+    assert abs(abs(cc.case_dct(c)[27, 0, 2, 2]) - 10.0) < 1e-9
+
+
+@pytest.mark.parametrize("name", ["ref", "seeded"])
+@pytest.mark.parametrize("c", cc.DEC, ids=repr)
+def test_decode_open_on_encoder_output(c, name):
+    """margin 0 flags nothing on an encoder's output; at every margin the GPU module uses the preconditions hold (they
+    are asserted inside), the shares are the ones MARGINS' comment states, and -- soundness -- every pixel of an
+    unflagged lane has the emulated byte equal to the oracle's decode, also under a margin as wide as 0.25"""
+    T = cc.table(name, c.depth)
+    q = cc.case_q_ref(c, name)
+    wp, hp = qc.pkg().padded_size(c.w, c.h)
+    import oracle
+    ref = oracle.to_cubes(qc.ref_decode(q, wp, hp, c.channels * c.stacks * c.depth, cc.steps_of(T, c.depth), c.depth),
+                          8, 8, c.depth)
+    shares = []
+    for m in (0.0,) + cc.MARGINS + (0.25,):
+        lanes, byte = cc.decode_emulate(q, c.depth, T, m)
+        cert = ~cc.lane_pixels(lanes, c.depth)
+        assert np.array_equal(byte[cert], ref[cert]), f"margin {m}: a certified pixel differs from the oracle"
+        shares.append(float(lanes.mean()))
+    assert shares[0] == 0.0
+    if (c.w, c.h) == (200, 72):
+        assert 0.005 < shares[1] < 0.015 and 0.08 < shares[2] < 0.12 and 0.45 < shares[3] < 0.55, shares
+    print(f"{c.id} {name}: flagged share at 0, MARGINS, 0.25: {shares}")
+
+
+@pytest.mark.parametrize("name", ["ref", "seeded"])
+@pytest.mark.parametrize("depth", [8, 4])
+def test_decode_guard_cubes(depth, name):
+    """the L1 guard case's preconditions (inside decode_emulate), and its prediction: the two cubes over dec_l1_max are
+    flagged whole, 64 depth pixels each"""
+    q, over = cc.guard_cubes(depth, name)
+    for m in (0.0, cc.MARGINS[1]):
+        lanes = cc.decode_open(q, depth, cc.table(name, depth), m)
+        assert lanes[over].all()
+        assert 32 * int(lanes[over].sum()) == 64 * depth * 2
+    assert lanes[~over].any() and not lanes[~over].all()  # at the 10 % margin the under cubes flag some lanes
+
+
+def test_lane_ownership_mask():
+    """lane_pixels: 8x8x8 lane 2 y + h owns x = 4h .. 4h + 3 of row y over z; 8x8x4 lane y owns row y over z"""
+    l8 = np.zeros((1, 16), bool)
+    l8[0, 2 * 5 + 1] = True
+    m8 = cc.lane_pixels(l8, 8)
+    assert m8.sum() == 32 and m8[0, :, 5, 4:].all()
+    l4 = np.zeros((1, 8), bool)
+    l4[0, 3] = True
+    m4 = cc.lane_pixels(l4, 4)
+    assert m4.sum() == 32 and m4[0, :, 3, :].all()
