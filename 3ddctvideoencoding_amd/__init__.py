@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "dct3d_encode_eg_frames", "dct3d_encode_eg_frames_dev", "dct3d_eg_fetch_channel",
     "dct3d_decode_eg_frames", "dct3d_decode_eg_frames_dev",
     "dct3d_ctx_set_quant", "dct3d_ctx_get_quant", "dct3d_plan_query_quant",
+    "dct3d_rate_frames", "dct3d_rate_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -138,6 +139,8 @@ def lib() -> C.CDLL:
         L.dct3d_eg_fetch_channel.argtypes = [vp, i32, vp, u64]
         L.dct3d_decode_eg_frames_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         L.dct3d_decode_eg_frames.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.dct3d_rate_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
+        L.dct3d_rate_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
         _lib = L
     return _lib
 
@@ -231,6 +234,18 @@ def dequantize_ref(q_cubes: np.ndarray, steps) -> np.ndarray:
     """Decoder.java:78-96 with step[x + y + z]: int32 [.., bd, bh, bw] -> fp64 (double) q * step (exact)."""
     q = np.asarray(q_cubes)
     return q.astype(np.float64) * _step_cube(steps, q.shape)
+
+
+RATE_MAX_TABLES = 32
+
+
+def pick_quality(bits_per_quality: dict, target_bits) -> int:
+    """The rate rule of the codec's rate= argument: the smallest quality whose bits are <= target_bits; if none
+    fits, the largest quality of the dict.  Nothing is assumed about how the bits vary with the quality."""
+    if not bits_per_quality:
+        raise ValueError("no qualities to pick from")
+    fits = [q for q, b in bits_per_quality.items() if b <= target_bits]
+    return int(min(fits)) if fits else int(max(bits_per_quality))
 
 
 def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8, steps=None) -> dict:
@@ -663,6 +678,40 @@ class Context:
             e.end_bits = [int(t) for t in eb]
             raise e
         return [int(t) for t in eb]
+
+    # ---- rate probe: the streams' exact sizes under several tables, no stream written ----
+    def _rate_tables(self, tables):
+        """tables (None | one table | a sequence of tables) -> (int32 [T, n_steps] or None, T)"""
+        if tables is None:
+            return None, 1
+        n = self.bw + self.bh + self.bd - 2
+        tb = np.stack([_steps_array(t) for t in ([tables] if np.ndim(tables[0]) == 0 else tables)])
+        if tb.shape[1] != n:
+            raise Dct3dError(DCT3D_EINVAL, "dct3d_rate_frames")
+        return np.ascontiguousarray(tb, np.int32), tb.shape[0]
+
+    def rate_frames(self, frames: np.ndarray, tables=None) -> np.ndarray:
+        """u8 frames as encode_eg_frames' -> uint64 [T, n_stacks, channels]: the bits encode_eg_frames appends to
+        channel ch's stream for stack s under tables[t] (None: the context's table, T = 1).  Exact; the context's
+        quantiser is neither used (tables given) nor changed, and no stream is written."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        tb, T = self._rate_tables(tables)
+        bits = np.zeros((T, n_stacks, channels), np.uint64)
+        _check(lib().dct3d_rate_frames(self._h, _ptr(frames), W, H, channels, n_stacks, None if tb is None else _ptr(tb), T,
+                                       _ptr(bits)), "dct3d_rate_frames")
+        return bits
+
+    def rate_frames_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables=None,
+                        d_cube_bits=None) -> np.ndarray:
+        """Device path of rate_frames: u8 frames on the device; d_cube_bits (optional; a tensor or an address) receives
+        uint16 [T, n_stacks, channels, cubes per stack and channel], the same sum per cube."""
+        tb, T = self._rate_tables(tables)
+        bits = np.zeros((T, n_stacks, channels), np.uint64)
+        _check(lib().dct3d_rate_frames_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks,
+                                           None if tb is None else _ptr(tb), T, _ptr(bits),
+                                           None if d_cube_bits is None else _tptr(d_cube_bits)), "dct3d_rate_frames_dev")
+        return bits
 
     def fill_synthetic_dev(self, d_frames, width: int, height: int, n_frames: int,
                            seed: int = synthetic.DEFAULT_SEED, frame0: int = 0, kind: str = "ramp") -> None:

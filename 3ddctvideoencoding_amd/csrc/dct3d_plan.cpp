@@ -351,6 +351,47 @@ void analyse_decoder(Plan& p, std::vector<double>& K, std::vector<double>& L1, d
 
 }  // namespace
 
+// The quantiser-dependent part of the encode certificate: {fp32(1 / step), G, E} per s = kx + ky + kz for the
+// table steps[0 .. kMaxS) (entries past the cube's largest sum: any step >= 1, never read by a kernel), from
+// the plan's per-coefficient analysis (enc_K, enc_L1, enc_dev, fwd_ngroups), none of which depends on the
+// table.  build_plan fills the plan's own tables with it; the rate call (dct3d_rate_frames*) makes one set
+// per candidate table from the context's one plan.
+void encoder_tables(const Plan& p, const int32_t* steps, float* rstep, float* G32, float* E32) {
+    const double u32 = std::ldexp(1.0, -24);
+    double G[kMaxS] = {}, E[kMaxS] = {};
+    for (int kz = 0; kz < p.cd; kz++)
+        for (int ky = 0; ky < 8; ky++)
+            for (int kx = 0; kx < 8; kx++) {
+                const int k = (kz * 8 + ky) * 8 + kx;
+                const int s = kx + ky + kz;
+                if (s == 0) continue;  // DC is produced exactly from the integer cube sum
+                const double step = (double)steps[s];
+                const double K = p.enc_K[k], L1 = p.enc_L1[k];
+                // |q_f - q_java| <= A*[K + 2.02u(L1+K) + 2^-50 L1]/step
+                //                   + [255*dev + (ng+16) 2^-52 255 L1]/step + 1e-12
+                // (every term but the last scales with 1/step, so a smaller step certifies less: at
+                // A G_s + E_s >= 0.5 the kernels' threshold is <= 0 and every coefficient of that s is
+                // open -- |qq - n| >= thr holds for any thr <= 0 -- never certified.  1e-12 covers the
+                // rounding of Java's quotient, <= 2^-41 for |q| < 2^13, whatever the step.)
+                const double gk = (K + 2.02 * u32 * (L1 + K) + std::ldexp(L1, -50)) / step;
+                const double ek = (255.0 * p.enc_dev[k] + (p.fwd_ngroups[k] + 16) * std::ldexp(255.0 * L1, -52)) / step + 1e-12;
+                G[s] = std::max(G[s], gk);
+                E[s] = std::max(E[s], ek);
+            }
+    for (int s = 0; s < kMaxS; s++) {
+        const double step = (double)steps[s];
+        rstep[s] = (float)(1.0 / step);
+        if (s == 0) {
+            G32[s] = 0.0f;
+            E32[s] = -INFINITY;  // threshold +inf: the DC is never flagged
+            continue;
+        }
+        // round up (conservative) and guard the fp32 evaluation of 0.5 - (A*G + E) in the kernel
+        G32[s] = std::nextafter((float)(G[s] * (1.0 + 1e-4)), INFINITY);
+        E32[s] = std::nextafter((float)(E[s] + 2e-7), INFINITY);
+    }
+}
+
 // =============================================================================================
 // Plan construction
 // =============================================================================================
@@ -452,38 +493,10 @@ bool build_plan(int cw, int ch, int cd, const int32_t* steps, Plan& p) {
 
     // ---- encoder certification tables ----
     analyse_encoder(p);
-    const double u32 = std::ldexp(1.0, -24);
-    double G[kMaxS] = {}, E[kMaxS] = {};
-    for (int kz = 0; kz < cd; kz++)
-        for (int ky = 0; ky < 8; ky++)
-            for (int kx = 0; kx < 8; kx++) {
-                const int k = (kz * 8 + ky) * 8 + kx;
-                const int s = kx + ky + kz;
-                if (s == 0) continue;  // DC is produced exactly from the integer cube sum
-                const double step = step_of(s);
-                const double K = p.enc_K[k], L1 = p.enc_L1[k];
-                // |q_f - q_java| <= A*[K + 2.02u(L1+K) + 2^-50 L1]/step
-                //                   + [255*dev + (ng+16) 2^-52 255 L1]/step + 1e-12
-                // (every term but the last scales with 1/step, so a smaller step certifies less: at
-                // A G_s + E_s >= 0.5 the kernels' threshold is <= 0 and every coefficient of that s is
-                // open -- |qq - n| >= thr holds for any thr <= 0 -- never certified.  1e-12 covers the
-                // rounding of Java's quotient, <= 2^-41 for |q| < 2^13, whatever the step.)
-                const double gk = (K + 2.02 * u32 * (L1 + K) + std::ldexp(L1, -50)) / step;
-                const double ek = (255.0 * p.enc_dev[k] + (p.fwd_ngroups[k] + 16) * std::ldexp(255.0 * L1, -52)) / step + 1e-12;
-                G[s] = std::max(G[s], gk);
-                E[s] = std::max(E[s], ek);
-            }
-    for (int s = 0; s < kMaxS; s++) {
-        const double step = step_of(s);
-        p.enc_rstep[s] = (float)(1.0 / step);
-        if (s == 0) {
-            p.enc_G[s] = 0.0f;
-            p.enc_E[s] = -INFINITY;  // threshold +inf: the DC is never flagged
-            continue;
-        }
-        // round up (conservative) and guard the fp32 evaluation of 0.5 - (A*G + E) in the kernel
-        p.enc_G[s] = std::nextafter((float)(G[s] * (1.0 + 1e-4)), INFINITY);
-        p.enc_E[s] = std::nextafter((float)(E[s] + 2e-7), INFINITY);
+    {
+        int32_t st[kMaxS];
+        for (int s = 0; s < kMaxS; s++) st[s] = (int32_t)step_of(s);
+        encoder_tables(p, st, p.enc_rstep, p.enc_G, p.enc_E);
     }
 
     // ---- second certificate (8x8x8): fp64 re-evaluation of a coefficient the fp32 one leaves open ----

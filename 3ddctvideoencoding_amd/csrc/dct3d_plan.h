@@ -76,5 +76,9 @@ bool build_plan(int cw, int ch, int cd, Plan& p);
 // The same for the quantiser steps[0 .. cw + ch + cd - 3] (nullptr: the reference's).  Also false when a
 // step lies outside [kMinStep, kMaxStep].
 bool build_plan(int cw, int ch, int cd, const int32_t* steps, Plan& p);
+// The certificate tables of p's block for another quantiser: rstep / G / E [kMaxS] (as Plan::enc_rstep, enc_G,
+// enc_E) for steps[0 .. kMaxS), every step >= 1.  Reads p.enc_K, enc_L1, enc_dev and fwd_ngroups alone, so a
+// built plan serves any number of tables; build_plan fills its own through it.
+void encoder_tables(const Plan& p, const int32_t* steps, float* rstep, float* G, float* E);
 
 }  // namespace dct3d

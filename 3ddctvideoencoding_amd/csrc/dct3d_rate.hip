@@ -1,0 +1,280 @@
+// dct3d_rate.hip -- the rate probe (dct3d_rate_frames*): the exact Exp-Golomb size of every cube
+// under several quantiser tables, from one transform per cube.  The width of a code does not depend on its
+// place in the stream, so a cube's cost is a plain sum over its coefficients: nothing is staged in diagonal
+// order, emitted or compacted, and the fp32 transform does not depend on the table.  A translation unit of
+// its own: no other kernel's code object changes with it.
+#include "dct3d_rate.h"
+#include "dct3d_encode_dev.h"
+
+namespace dct3d {
+
+static_assert(kRateTabN == kTabN, "a table's rows as the encode kernels'");
+
+// Bits of the signed order-0 Exp-Golomb code of q (ExpGolomb.c:32-64): code = max(2q, 1 - 2q), 2n - 1 bits for
+// a code of n bits
+__device__ __forceinline__ uint32_t rate_width(int q) {
+    const uint32_t code = (uint32_t)(q > 0 ? 2 * q : 1 - 2 * q);
+    return 63u - 2u * (uint32_t)__builtin_clz(code);
+}
+
+// The Java fold of one coefficient (replay_fold's sums, products and fold order: DCT.java:44-52) up to the
+// division: the folded value itself, valid in lane 0.  It does not depend on the table; the caller divides it
+// by each table's step.
+__device__ __forceinline__ double rate_fold(const ReplayIn& in, int cs, int lane, int* ssum, double* prod) {
+    ssum[lane] = 0;
+    wave_lds_sync();
+    if (lane * 8 < cs) {
+#pragma unroll
+        for (int bb = 0; bb < 4; bb++) {
+            const uint32_t g0 = (in.gr.x >> (8 * bb)) & 0xFF, g1 = (in.gr.y >> (8 * bb)) & 0xFF;
+            if (g0 < kMaxGroupsDev) atomicAdd(&ssum[g0], (int)((in.px.x >> (8 * bb)) & 0xFF));
+            if (g1 < kMaxGroupsDev) atomicAdd(&ssum[g1], (int)((in.px.y >> (8 * bb)) & 0xFF));
+        }
+    }
+    wave_lds_sync();
+    prod[lane] = __dmul_rn((double)ssum[lane], lane < in.ng ? in.cf : 0.0);
+    wave_lds_sync();
+    double acc = 0.0;
+    if (lane == 0) {
+#pragma unroll 1
+        for (int gi = 0; gi < in.ng; gi++) acc = __dadd_rn(acc, prod[gi]);  // DCT.java:50, in order
+    }
+    wave_lds_sync();
+    return acc;
+}
+
+// encode_eg_kernel's geometry: one wave owns 8 cubes, 8 lanes per cube; rows -> statistics -> transform as
+// there.  The coefficients then stay in registers, and a rolled loop over the launch's tables quantises and
+// certifies them exactly as encode_eg_kernel does (the same products, thresholds and DC), adding the code
+// widths of the certified values instead of staging codes.  The width of a value n held as an fp32 integer
+// comes from the exponent of its code c = max(2n, 1 - 2n), exact in fp32 (c < 2^14): 2 (e - 126) - 1 bits
+// for the biased exponent e, so a lane sums exponents and converts once.  The coefficients a table leaves
+// open go to the table's mask in LDS; after the loop the wave folds each coefficient that is open under any
+// table once (the Java fold does not depend on the table) and rounds the fold over the step of every table
+// that left it open.  Per cube and table one uint16 goes out (a cube costs < 2^15 bits: 512 codes of <= 27).
+// The wave's LDS region, free after the transform: the fold's scratch, the cubes' sums per table, the masks.
+template <int D, int PX, int EDGE>
+__global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RateParams R) {
+    constexpr int CS = 64 * D;
+    constexpr int NB = (D == 8) ? 8 : 4;
+    constexpr int NI = 7 + NB;
+    constexpr int NV = CS / 8;  // coefficients per lane
+    constexpr int MW = (D == 8) ? 2 : 1;  // mask words per lane
+    constexpr int RS_B = kMaxGroupsDev * (4 + 8);
+    constexpr int SUM_B = kRateTables * 8 * 4;
+    static_assert(RS_B + SUM_B + kRateTables * 64 * MW * 4 <= enc_wave_lds<D>(), "scratch, sums and masks fit the wave's region");
+    __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * enc_wave_lds<D>()];
+    __shared__ float4 s_tab[kRateTables * kTabN];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cube0 = (blockIdx.x * kWavesPerBlock + wave) * kCubesPerWave;
+    uint2 raw[D];
+    __builtin_amdgcn_s_setprio(3);  // the rows in flight first (as encode_eg_kernel)
+    load_channel_rows<D, 0, PX, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, R.ch, raw);
+    __builtin_amdgcn_s_setprio(0);
+    if (blockIdx.x == 0 && P.replay_clear) {  // the next call's counter slot
+#pragma unroll
+        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
+    }
+    if (cube0 >= P.n_cubes) return;  // wave-uniform
+    const int nt = R.n_tables;
+    // every wave writes the block's whole copy (identical bits) and reads only after its own writes (enc_tables)
+    for (int i = lane; i < nt * kTabN; i += kWave) s_tab[i] = R.tabs[i];
+    char* wl = lds + wave * enc_wave_lds<D>();
+    int* const ssum = (int*)wl;
+    double* const prod = (double*)(wl + kMaxGroupsDev * 4);
+    uint32_t* const sums = (uint32_t*)(wl + RS_B);         // [table][cube]
+    uint32_t* const msk = (uint32_t*)(wl + RS_B + SUM_B);  // [table][word][lane]
+    const int c = lane >> 3, j = lane & 7;
+    const int kz = (D == 8) ? j : (j >> 1);
+    const int kx0 = (D == 8) ? 0 : (j & 1) * 4;
+    const int so = kz + kx0;
+    const bool valid = cube0 + c < P.n_cubes;
+
+    float a[D][8];
+    to_float<D>(raw, a);
+    uint32_t S;
+    int m;
+    float A;
+    cube_stats<D>(raw, a, S, m, A);
+    asm volatile("" : "+v"(S), "+v"(m), "+v"(A));
+    float b[8][NB];
+    forward_cube<D, NB>(a, m, c, j, wl, b);
+
+    uint32_t fm[MW];  // open under any table: bit ky * NB + x
+#pragma unroll
+    for (int w = 0; w < MW; w++) fm[w] = 0u;
+#pragma unroll 1
+    for (int t = 0; t < nt; t++) {
+        const float4* tab = s_tab + t * kTabN;
+        int sz = so;
+        float rr[NI], thr[NI];
+        uint32_t es = 0, e00 = 0;  // the sum of the codes' exponents; the fp32 DC's
+        uint32_t om[MW];           // open under this table
+#pragma unroll
+        for (int w = 0; w < MW; w++) om[w] = 0u;
+#pragma unroll
+        for (int ky = 0; ky < 8; ky++) {
+            tab_window<NB, NI>(tab, sz, ky, A, rr, thr);
+            bool f = false;
+            float qq[NB];
+            uint32_t e[NB];
+#pragma unroll
+            for (int x = 0; x < NB; x++) {
+                qq[x] = b[ky][x] * rr[ky + x];
+                const float n = __builtin_rintf(qq[x]);
+                f |= __builtin_fabsf(qq[x] - n) >= thr[ky + x];
+                const float n2 = n + n;
+                e[x] = __float_as_uint(__builtin_fmaxf(n2, 1.0f - n2)) >> 23;
+                es += e[x];
+            }
+            if (ky == 0) e00 = e[0];
+            if (__builtin_expect(f, 0)) {
+                uint32_t bits = 0;
+#pragma unroll
+                for (int x = 0; x < NB; x++)
+                    if (__builtin_fabsf(qq[x] - __builtin_rintf(qq[x])) >= thr[ky + x]) {
+                        bits |= 1u << x;
+                        es -= e[x];
+                    }
+                om[(ky * NB) >> 5] |= bits << ((ky * NB) & 31);
+            }
+            asm volatile("" : "+v"(es), "+v"(om[0]));
+        }
+        // the lane's certified values (all NV but the open ones): sum of 2 (e - 126) - 1
+        uint32_t open = (uint32_t)__builtin_popcount(om[0]);
+        if constexpr (MW == 2) open += (uint32_t)__builtin_popcount(om[1]);
+        uint32_t bits = 2u * es - 253u * ((uint32_t)NV - open);
+        if (j == 0) {  // the DC: exact, from the integer cube sum (never open: its threshold is +inf)
+            const int dc = java_round_dev(__ddiv_rn((double)S * P.coef_dc, (double)tab[0].w));
+            bits += rate_width(dc) - (2u * e00 - 253u);
+        }
+        if (!valid) {
+            bits = 0u;
+#pragma unroll
+            for (int w = 0; w < MW; w++) om[w] = 0u;
+        }
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) bits += __shfl_xor(bits, o, 64);
+        if (j == 0) sums[t * 8 + c] = bits;
+#pragma unroll
+        for (int w = 0; w < MW; w++) {
+            msk[(t * MW + w) * 64 + lane] = om[w];
+            fm[w] |= om[w];
+        }
+    }
+    wave_lds_sync();
+
+    // the coefficients some table left open, one at a time by the whole wave (rare): one fold each, one
+    // division and rounding per table that left it open
+    {
+        ReplayGeom G{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride, P.ngroups, P.coef, P.group_of};
+        if constexpr (PX != 1) G.ch = R.ch;
+        if constexpr (EDGE != 0) G.height = P.height;
+        uint32_t nrep = 0;
+        for (;;) {
+            uint32_t any = fm[0];
+            if constexpr (MW == 2) any |= fm[1];
+            const unsigned long long who = __ballot(any != 0u);
+            if (who == 0ull) break;
+            const int src = __builtin_ctzll(who);
+            int mybit = fm[0] ? __builtin_ctz(fm[0]) : 0;
+            if constexpr (MW == 2) mybit = fm[0] ? mybit : (fm[1] ? 32 + __builtin_ctz(fm[1]) : 0);
+            const int bit = __shfl(mybit, src, 64);
+            const int sj = src & 7, sc = src >> 3;
+            const int skz = (D == 8) ? sj : (sj >> 1), skx0 = (D == 8) ? 0 : (sj & 1) * 4;
+            const int sky = bit / NB, skx = skx0 + bit % NB;
+            const uint32_t k = (uint32_t)((skz * 8 + sky) * 8 + skx);
+            const double acc = rate_fold(replay_load<D, PX, EDGE>(G, cube0 + sc, k, lane), CS, lane, ssum, prod);
+#pragma unroll 1
+            for (int t = 0; t < nt; t++) {
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)msk[(t * MW + (bit >> 5)) * 64 + src]);
+                if ((w >> (bit & 31)) & 1u) {  // wave-uniform
+                    if (lane == 0) {
+                        const int q = java_round_dev(__ddiv_rn(acc, (double)s_tab[t * kTabN + skx + sky + skz].w));
+                        sums[t * 8 + sc] += rate_width(q);
+                    }
+                    nrep++;
+                }
+            }
+            if (lane == src) {
+                if (fm[0]) fm[0] &= fm[0] - 1u;
+                else if constexpr (MW == 2) fm[1] &= fm[1] - 1u;
+            }
+            wave_lds_sync();
+        }
+        if (nrep && lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), nrep);
+    }
+
+    // lane 8 t + cc: cube cc's bits under table t (its place as the encode's [stack][channel][cube] blocks)
+    const uint32_t ot = (uint32_t)lane >> 3, og = cube0 + ((uint32_t)lane & 7u);
+    if (ot < (uint32_t)nt && og < P.n_cubes)
+        R.cube_bits[(size_t)ot * R.table_stride + enc_out_cube<PX>(P, og, R.ch)] = (uint16_t)sums[lane];
+}
+
+// One block per run of `run` cubes (a table's stack and channel): their sum.  The body goes as 8-byte loads
+// from the first 8-byte boundary; the few values before and after it one by one.
+__global__ __launch_bounds__(kBlock) void rate_sum_kernel(const uint16_t* cube_bits, uint32_t run, uint64_t* out) {
+    __shared__ uint64_t s_part[kWavesPerBlock];
+    const uint16_t* p = cube_bits + (size_t)blockIdx.x * run;
+    const uint32_t head = min(run, (uint32_t)(((8u - ((uintptr_t)p & 7u)) & 7u) / 2u));
+    const uint32_t nvec = (run - head) / 4u;
+    const uint2* v = (const uint2*)(p + head);
+    uint64_t s = 0;
+    for (uint32_t i = threadIdx.x; i < nvec; i += kBlock) {
+        const uint2 t = v[i];
+        s += (t.x & 0xFFFFu) + (t.x >> 16) + (t.y & 0xFFFFu) + (t.y >> 16);
+    }
+    if (threadIdx.x < head) s += p[threadIdx.x];
+    for (uint32_t i = head + nvec * 4u + threadIdx.x; i < run; i += kBlock) s += p[i];
+    uint32_t lo = (uint32_t)s, hi = (uint32_t)(s >> 32);
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const uint64_t t = ((uint64_t)(uint32_t)__shfl_xor((int)hi, o, 64) << 32) | (uint32_t)__shfl_xor((int)lo, o, 64);
+        s += t;
+        lo = (uint32_t)s;
+        hi = (uint32_t)(s >> 32);
+    }
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t r = 0;
+#pragma unroll
+        for (int i = 0; i < kWavesPerBlock; i++) r += s_part[i];
+        out[blockIdx.x] = r;
+    }
+}
+
+namespace {
+template <int D, int PX, int EDGE>
+void launch_rate_t(const EncodeParams& P, const RateParams& R, hipStream_t st) {
+    const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
+    hipLaunchKernelGGL((rate_kernel<D, PX, EDGE>), grid, dim3(kBlock), 0, st, P, R);
+}
+template <int D>
+void launch_rate_d(int px, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
+    if (px == 1) {
+        if (edge) launch_rate_t<D, 1, 1>(P, R, st);
+        else launch_rate_t<D, 1, 0>(P, R, st);
+    } else {
+        if (edge) launch_rate_t<D, 3, 1>(P, R, st);
+        else launch_rate_t<D, 3, 0>(P, R, st);
+    }
+}
+}  // namespace
+
+int launch_rate(int D, int px, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
+    if (P.n_cubes == 0) return 0;
+    if ((px != 1 && px != 3) || R.n_tables < 1 || R.n_tables > kRateTables) return -1;
+    if (D == 8) launch_rate_d<8>(px, edge, P, R, st);
+    else launch_rate_d<4>(px, edge, P, R, st);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_rate_sum(const uint16_t* cube_bits, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st) {
+    if (n_runs == 0) return 0;
+    if (n_runs > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(rate_sum_kernel, dim3((uint32_t)n_runs), dim3(kBlock), 0, st, cube_bits, run, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace dct3d

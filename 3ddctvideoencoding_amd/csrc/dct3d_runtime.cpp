@@ -21,6 +21,7 @@
 #include "../../include/dct3d.h"
 #include "dct3d_kernels.h"
 #include "dct3d_plan.h"
+#include "dct3d_rate.h"
 
 using namespace dct3d;
 
@@ -122,6 +123,12 @@ struct dct3d_ctx {
     // two-step option, and the three fronts' status words (3 x 6; their marks share d_egd_mark)
     DevBuf d_eg_out_x[2], d_egd_in_x[2], d_eg_q_ch, d_egd_status3;
     uint64_t eg_last_bytes_x[2] = {0, 0};
+    // rate probe (dct3d_rate_frames*): the candidate tables' rows (host copy, device), the per-cube bits when
+    // the caller keeps none, the per-(table, stack, channel) sums and their pinned host copy
+    std::vector<float> rate_tabs_host;
+    DevBuf d_rate_tabs, d_rate_bits, d_rate_sums;
+    uint64_t* h_rate = nullptr;
+    size_t h_rate_bytes = 0;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -371,8 +378,9 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_eg_off, &c->d_eg_bsum, &c->d_eg_status, &c->d_eg_out, &c->d_eg_q, &c->d_eg_ht,
                       &c->d_egd_exit, &c->d_egd_status, &c->d_egd_in, &c->d_egd_raster, &c->d_egd_mark, &c->d_egd_desc,
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
-                      &c->d_eg_q_ch, &c->d_egd_status3})
+                      &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums})
         b->release();
+    if (c->h_rate) (void)hipHostFree(c->h_rate);
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (auto& q : c->ev)
         for (auto& e : q)
@@ -1239,6 +1247,112 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
         eg_last_bytes(c, ch) = (tb[ch] + 7) / 8;
     }
     return DCT3D_OK;
+}
+
+// ---- rate probe: the streams' exact sizes under several tables, one transform per cube (dct3d.h) ----
+}  // extern "C"
+// the arguments of both rate calls (nothing is enqueued before they hold)
+static bool rate_args_ok(const dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                         const int32_t* tables, int n_tables, const uint64_t* bits, Geom* g, uint64_t* n_cubes) {
+    if (!c || !make_geom(w, h, channels, n_stacks, true, g, n_cubes)) return false;
+    if (n_tables < 1 || n_tables > DCT3D_RATE_MAX_TABLES || (!tables && n_tables != 1) || !bits) return false;
+    if (!frames && n_stacks) return false;
+    const int n_steps = (int)c->plan.steps.size();
+    if (tables)
+        for (int i = 0; i < n_tables * n_steps; i++)
+            if (tables[i] < kMinStep || tables[i] > kMaxStep) return false;
+    return true;
+}
+extern "C" {
+
+int dct3d_rate_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                          const int32_t* tables, int n_tables, uint64_t* bits, uint16_t* d_cube_bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    const int n_steps = (int)c->plan.steps.size();
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    call_begin(c);
+    c->last_units = 0;
+    if (n_cubes == 0) return DCT3D_OK;
+    // each table's {1 / step, G, 0.5 - E, step} rows from the context's one plan (encoder_tables: the rows
+    // dct3d_plan_query_quant reports for that table), as the encode kernels' LDS copy holds them (enc_tables)
+    static_assert(kRateTabN <= kMaxS, "a table's rows");
+    c->rate_tabs_host.resize((size_t)n_tables * kRateTabN * 4);
+    for (int t = 0; t < n_tables; t++) {
+        int32_t st[kMaxS];
+        float rstep[kMaxS], G[kMaxS], E[kMaxS];
+        for (int s = 0; s < kMaxS; s++)
+            st[s] = s < n_steps ? (tables ? tables[(size_t)t * n_steps + s] : c->plan.steps[s]) : reference_step(s);
+        encoder_tables(c->plan, st, rstep, G, E);
+        float* row = c->rate_tabs_host.data() + (size_t)t * kRateTabN * 4;
+        for (int s = 0; s < kRateTabN; s++, row += 4) {
+            row[0] = rstep[s];
+            row[1] = G[s];
+            row[2] = 0.5f - E[s];
+            row[3] = (float)st[s];
+        }
+    }
+    const uint64_t stride = (uint64_t)channels * n_cubes;                   // cubes of one table
+    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;       // sums
+    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
+    int rc;
+    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_rate_sums.grow(n_runs * sizeof(uint64_t))) ||
+        (!d_cube_bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))))
+        return rc;
+    if (c->h_rate_bytes < n_runs * sizeof(uint64_t)) {
+        if (c->h_rate) (void)hipHostFree(c->h_rate);
+        c->h_rate = nullptr;
+        c->h_rate_bytes = 0;
+        if (hipHostMalloc((void**)&c->h_rate, n_runs * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
+            c->h_rate = nullptr;
+            return DCT3D_ENOMEM;
+        }
+        c->h_rate_bytes = n_runs * sizeof(uint64_t);
+    }
+    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    uint16_t* const cube_bits = d_cube_bits ? d_cube_bits : (uint16_t*)c->d_rate_bits.p;
+    EncodeParams P;
+    fill_encode_params(c, P, d_frames, nullptr, g, n_cubes);
+    hipEvent_t* ev = timer_begin(c);
+    rc = DCT3D_OK;
+    // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
+    for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
+        for (int ch = 0; ch < channels && !rc; ch++) {
+            RateParams R;
+            R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
+            R.cube_bits = cube_bits + (size_t)t0 * stride;
+            R.table_stride = stride;
+            R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
+            R.ch = ch;
+            if (launch_rate(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream)) rc = DCT3D_EKERNEL;
+            else c->slot_used = true;
+        }
+    if (!rc && launch_rate_sum(cube_bits, (uint32_t)g.cps(), n_runs, (uint64_t*)c->d_rate_sums.p, c->stream)) rc = DCT3D_EKERNEL;
+    timer_end(c, ev);
+    if (!rc && hipMemcpyAsync(c->h_rate, c->d_rate_sums.p, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = DCT3D_EDEVICE;
+    // synchronous on return (the sums are a host result; the tables' host copy and buffers are free again)
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
+    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
+    if (rc) return rc;
+    memcpy(bits, c->h_rate, n_runs * sizeof(uint64_t));
+    return DCT3D_OK;
+}
+
+int dct3d_rate_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                      const int32_t* tables, int n_tables, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    const size_t in_bytes = (size_t)g.plane() * c->bd * n_stacks;  // the unpadded frames: one copy
+    int rc;
+    if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1))) return rc;
+    if (in_bytes && hipMemcpyAsync(c->h_in.p, frames, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    return dct3d_rate_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, tables, n_tables, bits, nullptr);
 }
 
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,

@@ -133,6 +133,115 @@ static void quant_json(const dct3d_ctx *ctx, int depth, char *buf, size_t cap) {
     snprintf(buf + o, cap - o, "]");
 }
 
+/* ---- the rate target (codec.h) ------------------------------------------------------------------ */
+int codec_parse_rate(const char *text, double *bpp) {
+    if (!text || !bpp || strncmp(text, "rate=", 5)) return 1;
+    const char *p = text + 5;
+    if (!((*p >= '0' && *p <= '9') || (*p == '.' && p[1] >= '0' && p[1] <= '9'))) return 1;
+    for (const char *c = p; *c; c++) /* plain decimal: no sign, blanks, exponent or hexadecimal */
+        if (!((*c >= '0' && *c <= '9') || *c == '.')) return 1;
+    char *end = NULL;
+    const double v = strtod(p, &end);
+    if (*end != '\0' || !(v > 0.0) || v > 1e9) return 1;
+    *bpp = v;
+    return 0;
+}
+
+static char g_rate_text[64]; /* codec_set_rate's text; "": none */
+
+int codec_set_rate(const char *text) {
+    if (text && strlen(text) >= sizeof(g_rate_text)) return 1;
+    if (text && text[0] && g_quant_text[0]) return 1; /* a quantiser is set: q= and rate= exclude each other */
+    snprintf(g_rate_text, sizeof(g_rate_text), "%s", text ? text : "");
+    return 0;
+}
+
+/* The rate target of a call: codec_set_rate's text, else DCT3D_CODEC_RATE.  *set = 0: none given.  1 after
+ * printing when the text does not parse or a quantiser is given too. */
+static int call_rate(double *bpp, int *set) {
+    const char *text = g_rate_text[0] ? g_rate_text : getenv("DCT3D_CODEC_RATE");
+    const char *qt = g_quant_text[0] ? g_quant_text : getenv("DCT3D_CODEC_QUANT");
+    *set = text && text[0];
+    if (!*set) return 0;
+    if (qt && qt[0]) {
+        printf("A quantiser ('%s') and a rate target ('%s') exclude each other\n", qt, text);
+        return 1;
+    }
+    if (codec_parse_rate(text, bpp)) {
+        printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", text);
+        return 1;
+    }
+    return 0;
+}
+/* the commands that take no rate target: 1 after printing when one is given */
+static int reject_rate(const char *what) {
+    double bpp;
+    int set;
+    if (call_rate(&bpp, &set)) return 1;
+    if (set) printf("rate= applies to single-device encodes only (%s): decode with the q=<n> that the encode printed\n", what);
+    return set;
+}
+
+/* The first pass of an encode with a rate target: the rate probe (dct3d_rate_frames) per batch over the fixed
+ * ladder of qualities, the bits summed over the file and the channels; the pick is the smallest quality whose
+ * bits fit bpp * width * height * frames (unpadded pixels, all channels together, Exp-Golomb bits before the
+ * deflate), or the largest when none fits.  Prints "rate: q=<n> bits=<total>", sets the context's quantiser to
+ * q=<n> and rewinds the input.  1 after printing on an error. */
+static const int kRateLadder[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64};
+#define RATE_LADDER_N ((int)(sizeof(kRateLadder) / sizeof(kRateLadder[0])))
+static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
+                           int channels, double bpp) {
+    const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
+    const size_t stack_bytes = (size_t)channels * width * height * depth;
+    int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
+    uint64_t tot[RATE_LADDER_N];
+    for (int i = 0; i < RATE_LADDER_N; i++) {
+        tot[i] = 0;
+        for (int s = 0; s < n; s++) {
+            const int v = kRateLadder[i] * s;
+            tabs[i * n + s] = v < 1 ? 1 : v > 255 ? 255 : v;
+        }
+    }
+    uint64_t *bits = (uint64_t *)malloc(sizeof(uint64_t) * RATE_LADDER_N * (size_t)batch * channels);
+    if (!bits) {
+        printf("Out of memory\n");
+        return 1;
+    }
+    int status = 0;
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        size_t got = 0, r;
+        const size_t want = stack_bytes * nb;
+        while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
+        if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as the encode's */
+        const int rc = dct3d_rate_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, bits);
+        if (rc) {
+            printf("Error running the rate probe: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        for (int i = 0; i < RATE_LADDER_N; i++)
+            for (int k = 0; k < nb * channels; k++) tot[i] += bits[(size_t)i * nb * channels + k];
+    }
+    free(bits);
+    if (status) return 1;
+    const double target = bpp * (double)width * (double)height * (double)frames;
+    int pick = RATE_LADDER_N - 1; /* none fits: the largest quality (the ladder ascends) */
+    for (int i = RATE_LADDER_N - 1; i >= 0; i--)
+        if ((double)tot[i] <= target) pick = i; /* the smallest that fits, whatever the order of the sizes */
+    printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
+    const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
+    if (rc) {
+        printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
+        return 1;
+    }
+    if (fseek(in, 0, SEEK_SET)) {
+        printf("Cannot rewind the input file for the second pass\n");
+        return 1;
+    }
+    return 0;
+}
+
 static int default_batch(void) {
     const char *e = getenv("DCT3D_CODEC_BATCH");
     int b = e ? atoi(e) : 16;
@@ -313,6 +422,7 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
                "of 8)\n", width, height, frames, depth);
         return 1;
     }
+    if (reject_rate("encode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -422,6 +532,7 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
         return 1;
     }
+    if (reject_rate("decode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -558,6 +669,9 @@ static int host_eg_on(void) {
 
 static int encode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
+    double rate_bpp = 0.0;
+    int rate_set = 0;
+    if (call_rate(&rate_bpp, &rate_set)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -612,6 +726,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             status = 1;
         }
     }
+    /* a rate target: the first pass picks the quality, the second encodes as q=<n> does */
+    if (!status && rate_set)
+        STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels, rate_bpp));
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
         size_t got = 0, r;
@@ -696,6 +813,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
 
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
+    if (reject_rate("decode")) return 1;
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
     const int host_eg = host_eg_on();

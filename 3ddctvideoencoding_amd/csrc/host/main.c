@@ -7,6 +7,8 @@
  *   every command takes a quantiser after the block depth (codec.h, codec_parse_quant): q=<int>, i.e. step
  *   max(1, <int> s) clipped to 255 (q=5: the reference's), or block_depth + 14 comma-separated steps in 1..255;
  *   the file does not record it: decode with the quantiser of the encode
+ *   the single-device encodes take rate=<bits per pixel> in the quantiser's place (codec.h, codec_parse_rate): two
+ *   passes, the first picks q from a fixed ladder and prints "rate: q=<n> bits=<total>"; decode with that q=<n>
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -34,6 +36,12 @@ static void usage(void) {
     printf("Every command takes a quantiser after the block depth: q=<int> (steps max(1, <int> * (x+y+z)), at most "
            "255; q=5 is the reference's) or <block depth + 14> comma-separated steps in 1..255.  The file does not "
            "record it: decode with the quantiser of the encode\n");
+    printf("encode and encode_rgb on one device take rate=<bits per pixel> in the quantiser's place: the target is "
+           "<bits per pixel> * width * height * frames (unpadded pixels, all channels together), measured on the "
+           "Exp-Golomb bits before the deflate.  A first pass over the input prices the ladder q = 1, 2, 3, 4, 5, 6, 8, "
+           "10, 12, 16, 20, 24, 32, 40, 48, 64, picks the smallest q that fits (64 when none does) and prints "
+           "'rate: q=<n> bits=<total>'; the second pass encodes as q=<n>.  Decode with that q=<n>: rate= on a decode, "
+           "together with q=, or with several devices is an error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -87,13 +95,38 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    if (argc > 9 && (depth == 8 || depth == 4)) { /* (any other depth: the entry point reports the geometry) */
+    int have_quant = 0, have_rate = 0;
+    for (int a = 9; a < argc && a < 11 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
-        if (codec_parse_quant(argv[9], depth, steps) || codec_set_quant(argv[9])) {
-            printf("Invalid quantiser '%s': q=<0..255>, or block depth + 14 comma-separated steps in 1..255\n", argv[9]);
+        double bpp;
+        const int is_rate = !strncmp(argv[a], "rate=", 5);
+        if (a == 10 && (is_rate ? have_rate : have_quant)) break; /* (a second argument counts only as the other kind) */
+        if (is_rate) {
+            if (codec_parse_rate(argv[a], &bpp)) {
+                printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (argv[1][0] != 'e' || n_dev > 1) {
+                printf("rate= applies to encode and encode_rgb on one device: decode with the q=<n> that the encode printed\n");
+                return 1;
+            }
+            have_rate = a;
+        } else if (codec_parse_quant(argv[a], depth, steps)) {
+            printf("Invalid quantiser '%s': q=<0..255>, or block depth + 14 comma-separated steps in 1..255\n", argv[a]);
             usage();
             return 1;
+        } else {
+            have_quant = a;
         }
+    }
+    if (have_quant && have_rate) {
+        printf("q= and rate= exclude each other\n");
+        return 1;
+    }
+    if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate]))) {
+        printf("Argument too long\n");
+        return 1;
     }
     if (!strcmp(argv[1], "encode"))
         return n_dev > 1 ? encode_multi(argv[2], argv[3], width, height, frames, devs, n_dev, depth, 0)

@@ -81,6 +81,25 @@ int decode_rgb_ex(const char *inputNamePattern, const char *outputFileName, int 
 int codec_parse_quant(const char *text, int blockDepth, int32_t *steps);
 int codec_set_quant(const char *text);
 
+/* A rate target in place of a quantiser (single-device encodes: encode, encode_ex, encode_rgb_ex): "rate=<bits
+ * per pixel>", a positive decimal number.  The target is bpp * width * height * frames bits, counted in unpadded
+ * pixels over all channels together, and it is measured on the Exp-Golomb bits BEFORE the deflate (the .bin is
+ * usually smaller).  The encode makes two passes over its input file: the first prices every batch under the
+ * fixed ladder q in {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64} (dct3d_rate_frames), sums the bits
+ * over the file and the channels, picks the smallest q whose bits are <= the target (the largest q when none
+ * fits) and prints one line "rate: q=<n> bits=<total>"; the second pass encodes as q=<n> does, byte for byte.
+ * The .bin stays headerless: decode it with the printed q=<n>.
+ *
+ * codec_parse_rate: 0 and *bpp for "rate=<positive number>"; 1 (*bpp untouched) on anything else ("rate=",
+ *   "rate=-1", "rate=abc", a quantiser's text).
+ * codec_set_rate: the rate target of every later encode call of this process, as such a text; NULL or "": none.
+ *   It overrides the environment variable DCT3D_CODEC_RATE.  A quantiser and a rate target exclude each other:
+ *   1 (nothing changes) while codec_set_quant holds a text, and a call that finds both (either by these calls
+ *   or by the environment) prints the reason and returns 1, as does a decode or a multi-device call that finds
+ *   a rate target.  Also 1 if the text is too long to keep. */
+int codec_parse_rate(const char *text, double *bpp);
+int codec_set_rate(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

@@ -403,6 +403,33 @@ int dct3d_decode_eg_frames(dct3d_ctx *ctx, const uint8_t *const bytes[], const u
                            const int start_bit[], int width, int height, int channels, int n_stacks,
                            uint8_t *frames, uint64_t end_bit[]);
 
+/* -------------------------------------------------------------------------------------------
+ * Rate probe (additive to ABI 9: detect it by symbol).  The exact size of the Exp-Golomb streams under
+ * several quantiser tables, from one transform per cube and with no stream written.
+ *   frames, width, height, channels, n_stacks   as dct3d_encode_eg_frames*.
+ *   tables    host, [n_tables][bw + bh + bd - 2] steps, each in [1, 255]; NULL with n_tables == 1: the
+ *             context's current table.  1 <= n_tables <= DCT3D_RATE_MAX_TABLES.
+ *   bits      host, [n_tables][n_stacks][channels]: bits[t][s][ch] is the number of bits that
+ *             dct3d_encode_eg_frames appends to stream ch for stack s on a context whose table is tables[t]
+ *             -- over the cubes q[s, ch] of dct3d_encode_frames under that table, the sum of the code widths
+ *             (2n - 1 for a code of n bits, code = max(2v, 1 - 2v)).  Summed over the stacks it is that call's
+ *             total_bits[ch] - carry_bits[ch].  Exact; there is no estimate.
+ *   d_cube_bits   optional device memory, [n_tables][n_stacks][channels][C] (C: the padded cubes per stack and
+ *             channel): the same sum per cube (a cube costs < 2^15 bits).
+ * The call neither reads (tables != NULL) nor changes the context's quantiser and is synchronous on return.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_encode_frames, n_tables outside 1..DCT3D_RATE_MAX_TABLES, tables
+ * == NULL with n_tables != 1, bits == NULL, a step outside [1, 255] (nothing is launched then).
+ * Statistics: n_units = padded coefficients of all channels x n_tables; n_flagged = the coefficient values
+ * settled by the exact Java fold, counted per table that left the coefficient open.  With n_tables == 1 it is
+ * what dct3d_encode_eg_frames_dev reports for the same frames under that table, where that call counts.
+ * ------------------------------------------------------------------------------------------- */
+#define DCT3D_RATE_MAX_TABLES 32
+int dct3d_rate_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                          int n_stacks, const int32_t *tables, int n_tables,
+                          uint64_t *bits, uint16_t *d_cube_bits);
+int dct3d_rate_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                      int n_stacks, const int32_t *tables, int n_tables, uint64_t *bits);
+
 #ifdef __cplusplus
 }
 #endif
