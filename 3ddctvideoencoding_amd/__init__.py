@@ -11,6 +11,7 @@ Since the package name starts with a digit, import it with
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -51,6 +52,7 @@ ABI_SYMBOLS = (
     "dct3d_decode_eg_frames", "dct3d_decode_eg_frames_dev",
     "dct3d_ctx_set_quant", "dct3d_ctx_get_quant", "dct3d_plan_query_quant",
     "dct3d_rate_frames", "dct3d_rate_frames_dev",
+    "dct3d_distortion_frames", "dct3d_distortion_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -141,6 +143,8 @@ def lib() -> C.CDLL:
         L.dct3d_decode_eg_frames.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         L.dct3d_rate_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
         L.dct3d_rate_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
+        L.dct3d_distortion_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.dct3d_distortion_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -246,6 +250,22 @@ def pick_quality(bits_per_quality: dict, target_bits) -> int:
         raise ValueError("no qualities to pick from")
     fits = [q for q, b in bits_per_quality.items() if b <= target_bits]
     return int(min(fits)) if fits else int(max(bits_per_quality))
+
+
+def psnr_db(sse, n_samples) -> float:
+    """10 log10(255^2 n_samples / sse) of 8-bit samples; inf for sse == 0."""
+    sse = int(sse)
+    return float("inf") if sse == 0 else 10.0 * math.log10(255.0 * 255.0 * float(n_samples) / float(sse))
+
+
+def pick_quality_psnr(sse_per_quality: dict, n_samples, target_db) -> int:
+    """The rule of the codec's psnr= argument: the largest quality (the coarsest quantiser) whose PSNR is >=
+    target_db; if none reaches it, the smallest quality of the dict.  Nothing is assumed about how the error
+    varies with the quality."""
+    if not sse_per_quality:
+        raise ValueError("no qualities to pick from")
+    ok = [q for q, e in sse_per_quality.items() if psnr_db(e, n_samples) >= target_db]
+    return int(max(ok)) if ok else int(min(sse_per_quality))
 
 
 def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8, steps=None) -> dict:
@@ -712,6 +732,35 @@ class Context:
                                            None if tb is None else _ptr(tb), T, _ptr(bits),
                                            None if d_cube_bits is None else _tptr(d_cube_bits)), "dct3d_rate_frames_dev")
         return bits
+
+    # ---- distortion probe: the exact squared error of encode + decode under several tables ----
+    def distortion_frames(self, frames: np.ndarray, tables=None, want_bits: bool = False):
+        """u8 frames as encode_frames' -> uint64 [T, n_stacks, channels]: the sum of (x - y)^2 over the unpadded
+        samples of stack s, channel ch, y = decode_frames(encode_frames(x)) under tables[t] (None: the context's
+        table, T = 1).  Exact; the context's quantiser is neither used (tables given) nor changed.  want_bits: the
+        pair (sse, bits), bits as rate_frames'."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        tb, T = self._rate_tables(tables)
+        sse = np.zeros((T, n_stacks, channels), np.uint64)
+        bits = np.zeros((T, n_stacks, channels), np.uint64) if want_bits else None
+        _check(lib().dct3d_distortion_frames(self._h, _ptr(frames), W, H, channels, n_stacks, None if tb is None else _ptr(tb),
+                                             T, _ptr(sse), None if bits is None else _ptr(bits)), "dct3d_distortion_frames")
+        return (sse, bits) if want_bits else sse
+
+    def distortion_frames_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables=None,
+                              d_cube_sse=None, want_bits: bool = False):
+        """Device path of distortion_frames: u8 frames on the device; d_cube_sse (optional; a tensor or an address)
+        receives uint32 [T, n_stacks, channels, cubes per stack and channel], the same sum per cube."""
+        tb, T = self._rate_tables(tables)
+        sse = np.zeros((T, n_stacks, channels), np.uint64)
+        bits = np.zeros((T, n_stacks, channels), np.uint64) if want_bits else None
+        _check(lib().dct3d_distortion_frames_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks,
+                                                 None if tb is None else _ptr(tb), T, _ptr(sse),
+                                                 None if bits is None else _ptr(bits),
+                                                 None if d_cube_sse is None else _tptr(d_cube_sse)),
+               "dct3d_distortion_frames_dev")
+        return (sse, bits) if want_bits else sse
 
     def fill_synthetic_dev(self, d_frames, width: int, height: int, n_frames: int,
                            seed: int = synthetic.DEFAULT_SEED, frame0: int = 0, kind: str = "ramp") -> None:

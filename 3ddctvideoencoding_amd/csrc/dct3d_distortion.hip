@@ -1,0 +1,435 @@
+// dct3d_distortion.hip -- the distortion probe (dct3d_distortion_frames*): the exact squared error
+// of encode + decode under several quantiser tables, from one row load and one forward transform per cube.
+// Per table the wave quantises and certifies its cubes as the encode does, puts the integers where the decode
+// expects its staged input, runs the certified fp64 decode tile with the bytes kept in registers, and compares
+// them with the rows it started from.  No coefficient and no decoded raster exists in memory.  A translation
+// unit of its own: no other kernel's code object changes with it.
+#include "dct3d_distortion.h"
+#include "dct3d_rate_dev.h"
+#include "dct3d_decode_dev.h"
+
+namespace dct3d {
+
+static_assert(kRateTabN == kTabN, "a table's rows as the encode kernels'");
+
+// The decode's rare replay re-reads a cube's quantised values: the int16 copy of the tile beside the decode
+// region (|q| < 2^15 for 8-bit frames and steps >= 1, so the copy is exact, whatever the cube's L1)
+template <int D>
+struct ReloadQ16 {
+    const int16_t* q16;   // [CPW][CS], the wave's tile
+    const double* steps;  // the table's fp64 steps
+    uint32_t cube0;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        constexpr int CS = 64 * D;
+        const int16_t* q = q16 + (size_t)(g - cube0) * CS;
+#pragma unroll
+        for (int i = 0; i < CS / 64; i++) {
+            const int k = lane + 64 * i;
+            const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
+            cf[k] = (double)q[k] * steps[kx + ky + kz];
+        }
+    }
+};
+
+// e16_body (dct3d_encode_dev.h) up to its quantiser: the statistics over the cube's 16 lanes (S: the sum, A: max
+// |x - mean|) and passes X / Z / Y, operation for operation, so the coefficients and the certificate's bounds
+// are encode16_kernel's.  Lane (c, kz = k, h) ends with b[ky][e], kx = 4h + e.  (A copy: splitting e16_body
+// itself changes the register allocation of the encode16 kernels, whose code objects stay as they are.)
+__device__ __forceinline__ void e16_forward(const uint2 (&raw)[4], char* wl, int lane, uint32_t& S, float& A,
+                                            float (&b)[8][4]) {
+    constexpr int CS = 512;
+    const int k = lane & 7, h = (lane >> 4) & 1;
+    const int c = (lane >> 5) * 2 + ((lane & 15) >> 3);
+    float a[4][8];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            a[r][e] = byte_of(raw[r].x, e);
+            a[r][e + 4] = byte_of(raw[r].y, e);
+        }
+    uint32_t mx = 0u, mn = 0x7F800000u;
+    S = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        S = __builtin_amdgcn_udot4(raw[r].x, 0x01010101u, S, false);
+        S = __builtin_amdgcn_udot4(raw[r].y, 0x01010101u, S, false);
+#pragma unroll
+        for (int x = 0; x < 8; x += 2) {
+            const uint32_t u0 = __float_as_uint(a[r][x]), u1 = __float_as_uint(a[r][x + 1]);
+            asm("v_max3_u32 %0, %1, %2, %3" : "=v"(mx) : "v"(mx), "v"(u0), "v"(u1));
+            asm("v_min3_u32 %0, %1, %2, %3" : "=v"(mn) : "v"(mn), "v"(u0), "v"(u1));
+        }
+    }
+#pragma unroll
+    for (int o = 1; o <= 16; o <<= 1) {
+        if (o == 8) continue;  // the cube's lanes: k bits (1, 2, 4) and h (16)
+        S += __shfl_xor(S, o, 64);
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+        mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
+    }
+    const int m = (int)((S + CS / 2) / CS);
+    A = fmaxf(__uint_as_float(mx) - (float)m, (float)m - __uint_as_float(mn));
+    asm volatile("" : "+v"(S), "+v"(A));
+    // pass X (exact integer front, centring folded into X0)
+    const float dcsub = 8.0f * (float)m;
+    pin(a[0]);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        fdct8<true, true>(a[r], dcsub);
+        if (r + 1 < 4) pin2(a[r], a[r + 1]);
+        else pin(a[r]);
+    }
+    // the lane pair's off-diagonal 4x4 blocks swapped: lines along z; pass Z
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[r][e]), __float_as_uint(a[r][4 + e]),
+                                                             false, false);
+            a[r][e] = __uint_as_float((uint32_t)sw[0]);
+            a[r][4 + e] = __uint_as_float((uint32_t)sw[1]);
+        }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        float col[8];
+#pragma unroll
+        for (int z = 0; z < 4; z++) {
+            col[z] = a[z][e];
+            col[4 + z] = a[z][4 + e];
+        }
+        pin(col);
+        fdct8<false, false>(col, 0.f);
+        pin(col);
+#pragma unroll
+        for (int z = 0; z < 4; z++) {
+            a[z][e] = col[z];
+            a[z][4 + e] = col[4 + z];
+        }
+    }
+    // LDS transpose in two y halves: lane (c, y = k, h) -> lane (c, kz = k, h); pass Y
+#pragma unroll
+    for (int rd = 0; rd < 2; rd++) {
+        if ((k >> 2) == rd) {
+            char* dst = wl + c * kE16TC + h * 64 + (k & 3) * 16;
+#pragma unroll
+            for (int kz = 0; kz < 8; kz++) {
+                const float* v = kz < 4 ? &a[kz][0] : &a[kz - 4][4];
+                *(float4*)(dst + kz * kE16TZ) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        wave_lds_sync();
+        const char* src = wl + c * kE16TC + k * kE16TZ + h * 64;
+#pragma unroll
+        for (int yy = 0; yy < 4; yy++) {
+            const float4 t = *(const float4*)(src + yy * 16);
+            b[4 * rd + yy][0] = t.x; b[4 * rd + yy][1] = t.y; b[4 * rd + yy][2] = t.z; b[4 * rd + yy][3] = t.w;
+        }
+        wave_lds_sync();
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        float col[8];
+#pragma unroll
+        for (int y = 0; y < 8; y++) col[y] = b[y][e];
+        pin(col);
+        fdct8<false, false>(col, 0.f);
+        pin(col);
+#pragma unroll
+        for (int y = 0; y < 8; y++) b[y][e] = col[y];
+    }
+}
+
+// The encode tile and the decode tile own the same cubes: 4 cubes x 16 lanes at 8x8x8 (e16_forward's lanes are
+// the decode's), 8 cubes x 8 lanes at 8x8x4 (encode_body's lanes; the decode's lanes of a cube are others, and
+// the integers cross over in the staging).  Encode side: lane (ec, kz, kx0) holds b[ky][x], kx = kx0 + x.
+// Decode side (layout C): lane (dc, y, x0) holds the bytes of x0 .. x0 + NXC - 1 of row y of every plane.
+// The wave's LDS region: the decode's region (first the forward transform's transposes, then per table the
+// staged integers, the decode's own transposes and replay scratch), the int16 copy of the staged integers
+// (ReloadQ16), the fold's scratch, the cubes' bits.
+template <int D, int PX, int EDGE>
+__global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, DistParams R) {
+    using G = DecGeom<D>;
+    constexpr int CS = 64 * D, CPW = G::CPW;
+    constexpr int NXC = (D == 8) ? 4 : 8, NW = NXC / 4;
+    constexpr int NV = 32;  // coefficients per lane
+    constexpr int Q16_OFF = kDecWaveLds;
+    constexpr int RS_OFF = Q16_OFF + CPW * CS * 2;
+    constexpr int SUM_OFF = RS_OFF + kMaxGroupsDev * (4 + 8);
+    constexpr int WLDS = SUM_OFF + 8 * 4;
+    static_assert(kE16Lds <= kDecWaveLds && enc_wave_lds<4>() <= kDecWaveLds, "the forward transform fits the decode's region");
+    static_assert(WLDS % 16 == 0 && Q16_OFF % 16 == 0, "aligned regions");
+    __shared__ __attribute__((aligned(16))) char lds[kWavesPerBlock * WLDS];
+    __shared__ float4 s_tab[kRateTables * kTabN];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cube0 = (blockIdx.x * kWavesPerBlock + wave) * CPW;
+    // encode side
+    const int ec = (D == 8) ? (lane >> 5) * 2 + ((lane & 15) >> 3) : lane >> 3;
+    const int kz = (D == 8) ? lane & 7 : (lane & 7) >> 1;
+    const int kx0 = (D == 8) ? 4 * ((lane >> 4) & 1) : (lane & 1) * 4;
+    const bool dcl = kz == 0 && kx0 == 0 && ((D == 8) || (lane & 7) == 0);  // the cube's DC lane
+    const bool evalid = cube0 + ec < P.n_cubes;
+    uint2 raw[4];
+    __builtin_amdgcn_s_setprio(3);  // the rows in flight first (as the encode kernels)
+    if constexpr (D == 8) load_channel_rows<4, 4, PX, EDGE>(P, cube0 + ec, evalid, lane & 7, (lane >> 4) & 1, R.ch, raw);
+    else load_channel_rows<4, 0, PX, EDGE>(P, cube0 + ec, evalid, lane & 7, 0, R.ch, raw);
+    __builtin_amdgcn_s_setprio(0);
+    if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);  // the next call's counter slot
+    if (cube0 >= P.n_cubes) return;  // wave-uniform
+    const int nt = R.n_tables;
+    // every wave writes the block's whole copy (identical bits) and reads only after its own writes (enc_tables)
+    for (int i = lane; i < nt * kTabN; i += kWave) s_tab[i] = R.tabs[i];
+    char* const wl = lds + wave * WLDS;
+    int16_t* const q16 = (int16_t*)(wl + Q16_OFF);
+    int* const ssum = (int*)(wl + RS_OFF);
+    double* const prod = (double*)(wl + RS_OFF + kMaxGroupsDev * 4);
+    uint32_t* const sums = (uint32_t*)(wl + SUM_OFF);  // [cube] bits under the current table
+
+    // decode side: the lane's source bytes in layout C (sw[z][wd] beside the decode's outw[z][wd]), the
+    // samples outside the frame masked out of both sides
+    const int dh = (lane >> 4) & 1, dk = lane & (D - 1);
+    const int dc = dec_cube_of_lane<D>(lane);
+    const int dy = (D == 8) ? dk : 4 * dh + dk, dx0 = (D == 8) ? 4 * dh : 0;
+    const bool dvalid = cube0 + dc < P.n_cubes;
+    uint32_t sw[D][NW];
+    if constexpr (D == 8) {  // rows y = k of frames 4h .. 4h + 3 -> x 4h .. 4h + 3 of all 8 (the lane pair's swap)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const auto t = __builtin_amdgcn_permlane16_swap(raw[r].x, raw[r].y, false, false);
+            sw[r][0] = (uint32_t)t[0];
+            sw[4 + r][0] = (uint32_t)t[1];
+        }
+    } else {  // the rows of encode lane (dc, j = y)
+#pragma unroll
+        for (int z = 0; z < 4; z++) {
+            sw[z][0] = (uint32_t)__shfl((int)raw[z].x, dc * 8 + dy, 64);
+            sw[z][1] = (uint32_t)__shfl((int)raw[z].y, dc * 8 + dy, 64);
+        }
+    }
+    uint32_t saa = 0;
+    uint32_t bmask[NW];
+    {
+        uint32_t npx = dvalid ? (uint32_t)NXC : 0u;
+        if constexpr (EDGE) {
+            const CubePos cp = cube_pos(P, min(cube0 + (uint32_t)dc, P.n_cubes - 1u));
+            const uint32_t row = cp.by * 8 + (uint32_t)dy, col = cp.bx * 8 + (uint32_t)dx0;
+            if (row >= P.height || col >= P.width) npx = 0u;
+            else npx = min(npx, P.width - col);
+        }
+#pragma unroll
+        for (int wd = 0; wd < NW; wd++) {
+            const uint32_t n = npx > 4u * wd ? min(npx - 4u * wd, 4u) : 0u;
+            bmask[wd] = n >= 4u ? 0xFFFFFFFFu : (1u << (8u * n)) - 1u;
+        }
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NW; wd++) {
+                sw[z][wd] &= bmask[wd];
+                saa = __builtin_amdgcn_udot4(sw[z][wd], sw[z][wd], saa, false);
+            }
+    }
+
+    // ---- statistics and the forward transform, once ----
+    uint32_t S;
+    float A;
+    float b[8][4];
+    if constexpr (D == 8) {
+        e16_forward(raw, wl, lane, S, A, b);
+    } else {
+        float a[4][8];
+        to_float<4>(raw, a);
+        int m;
+        cube_stats<4>(raw, a, S, m, A);
+        asm volatile("" : "+v"(S), "+v"(m), "+v"(A));
+        forward_cube<4, 4>(a, m, ec, lane & 7, wl, b);
+    }
+
+    DecodeParams DP = {};
+    DP.n_cubes = P.n_cubes;
+    DP.dec_G = R.dec_G;
+    DP.dec_E = R.dec_E;
+    DP.dec_l1_max = R.dec_l1_max;
+    DP.inv_coef_t = R.inv_coef_t;
+    DP.replay_count = P.replay_count;
+    ReplayGeom RG{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride, P.ngroups, P.coef, P.group_of};
+    if constexpr (PX != 1) RG.ch = R.ch;
+    if constexpr (EDGE != 0) RG.height = P.height;
+    const size_t ocube = enc_out_cube<PX>(P, min(cube0 + (uint32_t)dc, P.n_cubes - 1u), R.ch);  // the decode lane's cube
+    uint32_t nrep = 0;
+
+#pragma unroll 1
+    for (int t = 0; t < nt; t++) {
+        const float4* tab = s_tab + t * kTabN;
+        const double* steps = R.steps + t * kDistStepN;
+        // ---- quantise + certify with the encode's products and thresholds; the integers to the decode's
+        //      staging and to the int16 copy; the certified values' code widths from their exponents (rate_kernel) ----
+        int sz = kz + kx0;
+        float rr[11], thr[11];
+        uint32_t om = 0u;  // open under this table: bit 4 ky + x
+        uint32_t es = 0, e00 = 0;
+        const int dcq = java_round_dev(__ddiv_rn((double)S * P.coef_dc, (double)tab[0].w));  // the exact DC
+        char* const stg = wl + ec * G::SA_C + kz * G::SA_F + kx0 * 4;
+        int16_t* const s16 = q16 + ec * CS + kz * 64 + kx0;
+#pragma unroll
+        for (int ky = 0; ky < 8; ky++) {
+            tab_window<4, 11>(tab, sz, ky, A, rr, thr);
+            bool f = false;
+            float qq[4];
+            uint32_t e[4];
+            int qi[4];
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+                qq[x] = b[ky][x] * rr[ky + x];
+                const float n = __builtin_rintf(qq[x]);
+                f |= __builtin_fabsf(qq[x] - n) >= thr[ky + x];
+                const float n2 = n + n;
+                e[x] = __float_as_uint(__builtin_fmaxf(n2, 1.0f - n2)) >> 23;
+                es += e[x];
+                qi[x] = (int)n;
+            }
+            if (ky == 0) {
+                e00 = e[0];
+                if (dcl) qi[0] = dcq;
+            }
+            if (__builtin_expect(f, 0)) {
+                uint32_t bits = 0;
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+                    if (__builtin_fabsf(qq[x] - __builtin_rintf(qq[x])) >= thr[ky + x]) {
+                        bits |= 1u << x;
+                        es -= e[x];
+                    }
+                om |= bits << (4 * ky);
+            }
+            *(int4*)(stg + ky * 32) = make_int4(qi[0], qi[1], qi[2], qi[3]);
+            *(uint2*)(s16 + ky * 8) = make_uint2(__builtin_amdgcn_perm(qi[1], qi[0], 0x05040100u),
+                                                 __builtin_amdgcn_perm(qi[3], qi[2], 0x05040100u));
+            asm volatile("" : "+v"(es), "+v"(om));
+        }
+        if (dcl && (om & 1u)) {  // the DC is exact already (its threshold is +inf: never open in practice)
+            om &= ~1u;
+            es += e00;
+        }
+        uint32_t bits = 2u * es - 253u * ((uint32_t)NV - (uint32_t)__builtin_popcount(om));
+        if (dcl) bits += rate_width(dcq) - (2u * e00 - 253u);
+        if (!evalid) {
+            bits = 0u;
+            om = 0u;
+        }
+        bits += __shfl_xor(bits, 1, 64);
+        bits += __shfl_xor(bits, 2, 64);
+        bits += __shfl_xor(bits, 4, 64);
+        if constexpr (D == 8) bits += __shfl_xor(bits, 16, 64);
+        if (dcl) sums[ec] = bits;
+        wave_lds_sync();
+
+        // ---- the coefficients the certificate left open, one at a time by the whole wave (rare): the Java fold,
+        //      divided by this table's step, written over the provisional value in both copies ----
+        for (;;) {
+            const unsigned long long who = __ballot(om != 0u);
+            if (who == 0ull) break;
+            const int src = __builtin_ctzll(who);
+            const int bit = __shfl(om ? __builtin_ctz(om) : 0, src, 64);
+            const int sc = (D == 8) ? (src >> 5) * 2 + ((src & 15) >> 3) : src >> 3;
+            const int skz = (D == 8) ? src & 7 : (src & 7) >> 1;
+            const int skx = ((D == 8) ? 4 * ((src >> 4) & 1) : (src & 1) * 4) + (bit & 3), sky = bit >> 2;
+            const uint32_t k = (uint32_t)((skz * 8 + sky) * 8 + skx);
+            const double acc = rate_fold(replay_load<D, PX, EDGE>(RG, cube0 + sc, k, lane), CS, lane, ssum, prod);
+            if (lane == 0) {
+                const int q = java_round_dev(__ddiv_rn(acc, (double)tab[skx + sky + skz].w));
+                *(int*)(wl + sc * G::SA_C + skz * G::SA_F + (sky * 8 + skx) * 4) = q;
+                q16[sc * CS + k] = (int16_t)q;
+                sums[sc] += rate_width(q);
+            }
+            nrep++;
+            if (lane == src) om &= om - 1u;
+            wave_lds_sync();
+        }
+        if (R.cube_bits && lane < CPW && cube0 + lane < P.n_cubes)
+            R.cube_bits[(size_t)t * R.table_stride + enc_out_cube<PX>(P, cube0 + lane, R.ch)] = (uint16_t)sums[lane];
+
+        // ---- the decode tile on the staged integers, its bytes kept; the squared error inside the frame:
+        //      sum (x - y)^2 = sum x^2 + sum y^2 - 2 sum x y, three byte dot products per word ----
+        uint32_t outw[D][NW];
+        bool kv;
+        decode_tile<D, false, false, true, 0, 1>(DP, wl, lane, cube0, [] {}, ReloadQ16<D>{q16, steps, cube0}, &outw[0][0],
+                                                 &kv, steps);
+        uint32_t sbb = 0, sab = 0;
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NW; wd++) {
+                const uint32_t y = outw[z][wd] & bmask[wd];
+                sbb = __builtin_amdgcn_udot4(y, y, sbb, false);
+                sab = __builtin_amdgcn_udot4(sw[z][wd], y, sab, false);
+            }
+        uint32_t sse = saa + sbb - 2u * sab;  // < 2^32 for the cube: 512 x 255^2
+        sse += __shfl_xor(sse, 1, 64);
+        sse += __shfl_xor(sse, 2, 64);
+        if constexpr (D == 8) sse += __shfl_xor(sse, 4, 64);
+        sse += __shfl_xor(sse, 16, 64);
+        if (dk == 0 && dh == 0 && dvalid) R.cube_sse[(size_t)t * R.table_stride + ocube] = sse;
+        wave_lds_sync();  // the next table rewrites the staging
+    }
+    if (nrep && lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), nrep);
+}
+
+// One block per run of `run` cubes (a table's stack and channel): their sum (rate_sum_kernel for uint32)
+__global__ __launch_bounds__(kBlock) void distortion_sum_kernel(const uint32_t* cube_sse, uint32_t run, uint64_t* out) {
+    __shared__ uint64_t s_part[kWavesPerBlock];
+    const uint32_t* p = cube_sse + (size_t)blockIdx.x * run;
+    uint64_t s = 0;
+    for (uint32_t i = threadIdx.x; i < run; i += kBlock) s += p[i];
+    uint32_t lo = (uint32_t)s, hi = (uint32_t)(s >> 32);
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const uint64_t t = ((uint64_t)(uint32_t)__shfl_xor((int)hi, o, 64) << 32) | (uint32_t)__shfl_xor((int)lo, o, 64);
+        s += t;
+        lo = (uint32_t)s;
+        hi = (uint32_t)(s >> 32);
+    }
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t r = 0;
+#pragma unroll
+        for (int i = 0; i < kWavesPerBlock; i++) r += s_part[i];
+        out[blockIdx.x] = r;
+    }
+}
+
+namespace {
+template <int D, int PX, int EDGE>
+void launch_dist_t(const EncodeParams& P, const DistParams& R, hipStream_t st) {
+    const dim3 grid(grid_blocks(P.n_cubes, DecGeom<D>::CPW));
+    hipLaunchKernelGGL((distortion_kernel<D, PX, EDGE>), grid, dim3(kBlock), 0, st, P, R);
+}
+template <int D>
+void launch_dist_d(int px, int edge, const EncodeParams& P, const DistParams& R, hipStream_t st) {
+    if (px == 1) {
+        if (edge) launch_dist_t<D, 1, 1>(P, R, st);
+        else launch_dist_t<D, 1, 0>(P, R, st);
+    } else {
+        if (edge) launch_dist_t<D, 3, 1>(P, R, st);
+        else launch_dist_t<D, 3, 0>(P, R, st);
+    }
+}
+}  // namespace
+
+int launch_distortion(int D, int px, int edge, const EncodeParams& P, const DistParams& R, hipStream_t st) {
+    if (P.n_cubes == 0) return 0;
+    if ((px != 1 && px != 3) || R.n_tables < 1 || R.n_tables > kRateTables) return -1;
+    if (D == 8) launch_dist_d<8>(px, edge, P, R, st);
+    else launch_dist_d<4>(px, edge, P, R, st);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_distortion_sum(const uint32_t* cube_sse, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st) {
+    if (n_runs == 0) return 0;
+    if (n_runs > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(distortion_sum_kernel, dim3((uint32_t)n_runs), dim3(kBlock), 0, st, cube_sse, run, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace dct3d

@@ -19,6 +19,7 @@
  * decoded (the stream has no index), so the device calls chain and alternate over the devices; the only
  * overlap is the previous batch's raster write (several devices) -- the next window is inflated after
  * the running decode returns.  Decoding does not get faster with more devices. */
+#include <math.h>
 #include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -134,24 +135,29 @@ static void quant_json(const dct3d_ctx *ctx, int depth, char *buf, size_t cap) {
 }
 
 /* ---- the rate target (codec.h) ------------------------------------------------------------------ */
-int codec_parse_rate(const char *text, double *bpp) {
-    if (!text || !bpp || strncmp(text, "rate=", 5)) return 1;
-    const char *p = text + 5;
+/* "<prefix><plain positive decimal>": no sign, blanks, exponent or hexadecimal; 0 < value <= 1e9 */
+static int parse_positive(const char *text, const char *prefix, double *value) {
+    const size_t n = strlen(prefix);
+    if (!text || !value || strncmp(text, prefix, n)) return 1;
+    const char *p = text + n;
     if (!((*p >= '0' && *p <= '9') || (*p == '.' && p[1] >= '0' && p[1] <= '9'))) return 1;
-    for (const char *c = p; *c; c++) /* plain decimal: no sign, blanks, exponent or hexadecimal */
+    for (const char *c = p; *c; c++)
         if (!((*c >= '0' && *c <= '9') || *c == '.')) return 1;
     char *end = NULL;
     const double v = strtod(p, &end);
     if (*end != '\0' || !(v > 0.0) || v > 1e9) return 1;
-    *bpp = v;
+    *value = v;
     return 0;
 }
 
+int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, "rate=", bpp); }
+
 static char g_rate_text[64]; /* codec_set_rate's text; "": none */
+static char g_psnr_text[64]; /* codec_set_psnr's text; "": none */
 
 int codec_set_rate(const char *text) {
     if (text && strlen(text) >= sizeof(g_rate_text)) return 1;
-    if (text && text[0] && g_quant_text[0]) return 1; /* a quantiser is set: q= and rate= exclude each other */
+    if (text && text[0] && (g_quant_text[0] || g_psnr_text[0])) return 1; /* q=, rate= and psnr= exclude each other */
     snprintf(g_rate_text, sizeof(g_rate_text), "%s", text ? text : "");
     return 0;
 }
@@ -182,27 +188,77 @@ static int reject_rate(const char *what) {
     return set;
 }
 
+/* ---- the PSNR target (codec.h) ------------------------------------------------------------------ */
+int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, "psnr=", db); }
+
+int codec_set_psnr(const char *text) {
+    if (text && strlen(text) >= sizeof(g_psnr_text)) return 1;
+    if (text && text[0] && (g_quant_text[0] || g_rate_text[0])) return 1; /* q=, rate= and psnr= exclude each other */
+    snprintf(g_psnr_text, sizeof(g_psnr_text), "%s", text ? text : "");
+    return 0;
+}
+
+/* The PSNR target of a call: codec_set_psnr's text, else DCT3D_CODEC_PSNR.  *set = 0: none given.  1 after
+ * printing when the text does not parse or a quantiser or a rate target is given too. */
+static int call_psnr(double *db, int *set) {
+    const char *text = g_psnr_text[0] ? g_psnr_text : getenv("DCT3D_CODEC_PSNR");
+    const char *qt = g_quant_text[0] ? g_quant_text : getenv("DCT3D_CODEC_QUANT");
+    const char *rt = g_rate_text[0] ? g_rate_text : getenv("DCT3D_CODEC_RATE");
+    *set = text && text[0];
+    if (!*set) return 0;
+    if (qt && qt[0]) {
+        printf("A quantiser ('%s') and a PSNR target ('%s') exclude each other\n", qt, text);
+        return 1;
+    }
+    if (rt && rt[0]) {
+        printf("A rate target ('%s') and a PSNR target ('%s') exclude each other\n", rt, text);
+        return 1;
+    }
+    if (codec_parse_psnr(text, db)) {
+        printf("Invalid psnr target '%s': psnr=<dB>, a positive number\n", text);
+        return 1;
+    }
+    return 0;
+}
+/* the commands that take no PSNR target: 1 after printing when one is given */
+static int reject_psnr(const char *what) {
+    double db;
+    int set;
+    if (call_psnr(&db, &set)) return 1;
+    if (set) printf("psnr= applies to single-device encodes only (%s): decode with the q=<n> that the encode printed\n", what);
+    return set;
+}
+
 /* The first pass of an encode with a rate target: the rate probe (dct3d_rate_frames) per batch over the fixed
  * ladder of qualities, the bits summed over the file and the channels; the pick is the smallest quality whose
  * bits fit bpp * width * height * frames (unpadded pixels, all channels together, Exp-Golomb bits before the
  * deflate), or the largest when none fits.  Prints "rate: q=<n> bits=<total>", sets the context's quantiser to
- * q=<n> and rewinds the input.  1 after printing on an error. */
+ * q=<n> and rewinds the input.  1 after printing on an error.
+ * by_psnr: the first pass of an encode with a PSNR target instead: the distortion probe (dct3d_distortion_frames)
+ * per batch over the same ladder, the squared errors and the bits summed over the file and the channels; the PSNR
+ * of a quality is taken over all unpadded samples of all channels together (the zero-filled frames of a short last
+ * stack count as frames); the pick is the largest quality whose PSNR is >= target, or the smallest when none
+ * reaches it.  Prints "psnr: q=<n> psnr=<dB> bits=<total>". */
 static const int kRateLadder[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64};
 #define RATE_LADDER_N ((int)(sizeof(kRateLadder) / sizeof(kRateLadder[0])))
+static double psnr_of(uint64_t sse, double n_samples) {
+    return sse ? 10.0 * log10(255.0 * 255.0 * n_samples / (double)sse) : INFINITY;
+}
 static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
-                           int channels, double bpp) {
+                           int channels, double target, int by_psnr) {
     const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
     const size_t stack_bytes = (size_t)channels * width * height * depth;
     int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
-    uint64_t tot[RATE_LADDER_N];
+    uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N];
     for (int i = 0; i < RATE_LADDER_N; i++) {
-        tot[i] = 0;
+        tot[i] = err[i] = 0;
         for (int s = 0; s < n; s++) {
             const int v = kRateLadder[i] * s;
             tabs[i * n + s] = v < 1 ? 1 : v > 255 ? 255 : v;
         }
     }
-    uint64_t *bits = (uint64_t *)malloc(sizeof(uint64_t) * RATE_LADDER_N * (size_t)batch * channels);
+    const size_t n_sums = (size_t)RATE_LADDER_N * batch * channels;
+    uint64_t *bits = (uint64_t *)malloc(sizeof(uint64_t) * n_sums * 2), *sse = bits ? bits + n_sums : NULL;
     if (!bits) {
         printf("Out of memory\n");
         return 1;
@@ -214,22 +270,35 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
         const size_t want = stack_bytes * nb;
         while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
         if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as the encode's */
-        const int rc = dct3d_rate_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, bits);
+        const int rc = by_psnr ? dct3d_distortion_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, sse, bits)
+                               : dct3d_rate_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, bits);
         if (rc) {
-            printf("Error running the rate probe: %s\n", dct3d_strerror(rc));
+            printf("Error running the %s probe: %s\n", by_psnr ? "distortion" : "rate", dct3d_strerror(rc));
             status = 1;
             break;
         }
         for (int i = 0; i < RATE_LADDER_N; i++)
-            for (int k = 0; k < nb * channels; k++) tot[i] += bits[(size_t)i * nb * channels + k];
+            for (int k = 0; k < nb * channels; k++) {
+                tot[i] += bits[(size_t)i * nb * channels + k];
+                if (by_psnr) err[i] += sse[(size_t)i * nb * channels + k];
+            }
     }
     free(bits);
     if (status) return 1;
-    const double target = bpp * (double)width * (double)height * (double)frames;
-    int pick = RATE_LADDER_N - 1; /* none fits: the largest quality (the ladder ascends) */
-    for (int i = RATE_LADDER_N - 1; i >= 0; i--)
-        if ((double)tot[i] <= target) pick = i; /* the smallest that fits, whatever the order of the sizes */
-    printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
+    int pick;
+    if (by_psnr) {
+        const double n_samples = (double)width * (double)height * (double)channels * (double)n_stacks * (double)depth;
+        pick = 0; /* none reaches the target: the smallest quality (the ladder ascends) */
+        for (int i = 0; i < RATE_LADDER_N; i++)
+            if (psnr_of(err[i], n_samples) >= target) pick = i; /* the largest that reaches it, whatever the order */
+        printf("psnr: q=%d psnr=%.3f bits=%llu\n", kRateLadder[pick], psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
+    } else {
+        const double target_bits = target * (double)width * (double)height * (double)frames;
+        pick = RATE_LADDER_N - 1; /* none fits: the largest quality (the ladder ascends) */
+        for (int i = RATE_LADDER_N - 1; i >= 0; i--)
+            if ((double)tot[i] <= target_bits) pick = i; /* the smallest that fits, whatever the order of the sizes */
+        printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
+    }
     const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
     if (rc) {
         printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
@@ -423,6 +492,7 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
         return 1;
     }
     if (reject_rate("encode_multi")) return 1;
+    if (reject_psnr("encode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -533,6 +603,7 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         return 1;
     }
     if (reject_rate("decode_multi")) return 1;
+    if (reject_psnr("decode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -672,6 +743,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     double rate_bpp = 0.0;
     int rate_set = 0;
     if (call_rate(&rate_bpp, &rate_set)) return 1;
+    double psnr_db = 0.0;
+    int psnr_set = 0;
+    if (call_psnr(&psnr_db, &psnr_set)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -727,8 +801,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         }
     }
     /* a rate target: the first pass picks the quality, the second encodes as q=<n> does */
-    if (!status && rate_set)
-        STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels, rate_bpp));
+    if (!status && (rate_set || psnr_set))
+        STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
+                                              psnr_set ? psnr_db : rate_bpp, psnr_set));
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
         size_t got = 0, r;
@@ -814,6 +889,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
     if (reject_rate("decode")) return 1;
+    if (reject_psnr("decode")) return 1;
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
     const int host_eg = host_eg_on();

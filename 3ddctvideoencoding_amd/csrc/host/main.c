@@ -9,6 +9,8 @@
  *   the file does not record it: decode with the quantiser of the encode
  *   the single-device encodes take rate=<bits per pixel> in the quantiser's place (codec.h, codec_parse_rate): two
  *   passes, the first picks q from a fixed ladder and prints "rate: q=<n> bits=<total>"; decode with that q=<n>
+ *   ... or psnr=<dB> (codec_parse_psnr): the first pass picks the largest q of the ladder whose PSNR reaches the
+ *   target and prints "psnr: q=<n> psnr=<dB> bits=<total>"
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -42,6 +44,10 @@ static void usage(void) {
            "10, 12, 16, 20, 24, 32, 40, 48, 64, picks the smallest q that fits (64 when none does) and prints "
            "'rate: q=<n> bits=<total>'; the second pass encodes as q=<n>.  Decode with that q=<n>: rate= on a decode, "
            "together with q=, or with several devices is an error\n");
+    printf("... or psnr=<dB>: the first pass measures the exact squared error of encode + decode under the same ladder, "
+           "takes each q's PSNR over all unpadded samples of all channels together, picks the largest q whose PSNR is "
+           ">= <dB> (1 when none reaches it) and prints 'psnr: q=<n> psnr=<dB> bits=<total>'; the second pass encodes as "
+           "q=<n>.  psnr= on a decode, together with q= or rate=, or with several devices is an error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -95,23 +101,26 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0;
+    int have_quant = 0, have_rate = 0, have_psnr = 0;
     for (int a = 9; a < argc && a < 11 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
-        double bpp;
-        const int is_rate = !strncmp(argv[a], "rate=", 5);
-        if (a == 10 && (is_rate ? have_rate : have_quant)) break; /* (a second argument counts only as the other kind) */
-        if (is_rate) {
-            if (codec_parse_rate(argv[a], &bpp)) {
-                printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", argv[a]);
+        double v;
+        const int is_rate = !strncmp(argv[a], "rate=", 5), is_psnr = !strncmp(argv[a], "psnr=", 5);
+        if (a == 10 && (is_rate ? have_rate : is_psnr ? have_psnr : have_quant)) break; /* (a second argument counts only as another kind) */
+        if (is_rate || is_psnr) {
+            if (is_rate ? codec_parse_rate(argv[a], &v) : codec_parse_psnr(argv[a], &v)) {
+                if (is_rate) printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", argv[a]);
+                else printf("Invalid psnr target '%s': psnr=<dB>, a positive number\n", argv[a]);
                 usage();
                 return 1;
             }
             if (argv[1][0] != 'e' || n_dev > 1) {
-                printf("rate= applies to encode and encode_rgb on one device: decode with the q=<n> that the encode printed\n");
+                printf("%s applies to encode and encode_rgb on one device: decode with the q=<n> that the encode printed\n",
+                       is_rate ? "rate=" : "psnr=");
                 return 1;
             }
-            have_rate = a;
+            if (is_rate) have_rate = a;
+            else have_psnr = a;
         } else if (codec_parse_quant(argv[a], depth, steps)) {
             printf("Invalid quantiser '%s': q=<0..255>, or block depth + 14 comma-separated steps in 1..255\n", argv[a]);
             usage();
@@ -120,11 +129,12 @@ int main(int argc, char *argv[]) {
             have_quant = a;
         }
     }
-    if (have_quant && have_rate) {
-        printf("q= and rate= exclude each other\n");
+    if ((have_quant != 0) + (have_rate != 0) + (have_psnr != 0) > 1) {
+        printf("%s and %s exclude each other\n", have_quant ? "q=" : "rate=", have_psnr ? "psnr=" : "rate=");
         return 1;
     }
-    if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate]))) {
+    if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate])) ||
+        (have_psnr && codec_set_psnr(argv[have_psnr]))) {
         printf("Argument too long\n");
         return 1;
     }

@@ -100,6 +100,25 @@ int codec_set_quant(const char *text);
 int codec_parse_rate(const char *text, double *bpp);
 int codec_set_rate(const char *text);
 
+/* A PSNR target in place of a quantiser (the same single-device encodes): "psnr=<dB>", a positive decimal number.
+ * The encode makes two passes over its input file: the first runs the distortion probe (dct3d_distortion_frames)
+ * per batch over the rate target's ladder of q, sums the squared errors and the bits over the file and the
+ * channels, takes each q's PSNR = 10 log10(255^2 N / sse) over all N unpadded samples of all channels together
+ * (the zero-filled frames of a short last stack count), picks the largest q whose PSNR is >= the target (the
+ * smallest q when none reaches it) and prints one line "psnr: q=<n> psnr=<dB, 3 decimals> bits=<total>"; the
+ * second pass encodes as q=<n> does, byte for byte.  The .bin stays headerless: decode it with the printed q=<n>.
+ *
+ * codec_parse_psnr: 0 and *db for "psnr=<positive number>"; 1 (*db untouched) on anything else, as
+ *   codec_parse_rate.
+ * codec_set_psnr: the PSNR target of every later encode call of this process, as such a text; NULL or "": none.
+ *   It overrides the environment variable DCT3D_CODEC_PSNR.  A quantiser, a rate target and a PSNR target
+ *   exclude each other: 1 (nothing changes) while codec_set_quant or codec_set_rate holds a text (and
+ *   codec_set_rate returns 1 while this holds one), and a call that finds two of them (either by these calls or
+ *   by the environment) prints the reason and returns 1, as does a decode or a multi-device call that finds a
+ *   PSNR target.  Also 1 if the text is too long to keep. */
+int codec_parse_psnr(const char *text, double *db);
+int codec_set_psnr(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

@@ -430,6 +430,31 @@ int dct3d_rate_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, in
 int dct3d_rate_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
                       int n_stacks, const int32_t *tables, int n_tables, uint64_t *bits);
 
+/* ---------------------------------------------------------------------------------------------
+ * Distortion probe (additive to ABI 9; detect by symbol): the exact squared error of encode + decode under
+ * several quantiser tables, from one row load and one forward transform per cube; no coefficient and no
+ * decoded raster is written.  With y_t = dct3d_decode_frames(dct3d_encode_frames(x)), both on
+ * a context whose table is tables[t]:
+ *   frames, width, height, channels, n_stacks, tables, n_tables   as dct3d_rate_frames*.
+ *   sse       host, [n_tables][n_stacks][channels]: sse[t][s][ch] = sum (x - y_t)^2, as integers, over the
+ *             unpadded samples of stack s, channel ch (padded columns and rows are coded, not counted).
+ *   bits      host, the same shape, or NULL: exactly what dct3d_rate_frames returns for the same arguments.
+ *   d_cube_sse    optional device memory, uint32 [n_tables][n_stacks][channels][C] (d_cube_bits' layout): the
+ *             same sum per cube over its samples inside the frame (512 x 255^2 < 2^32).
+ * The call writes no stream, neither reads (tables != NULL) nor changes the context's quantiser, honours
+ * DCT3D_OPT_DEC_MARGIN as dct3d_decode_frames does, and is synchronous on return; the host-pointer call
+ * moves the frames in chunks of whole stacks.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_rate_frames, with sse in the place of bits.
+ * Statistics: n_units = padded coefficients of all channels x n_tables; n_flagged = the coefficient values
+ * settled by the exact Java fold, counted per table as in the rate call, plus what the decode's exact replay
+ * counts (32 samples per replayed lane, as dct3d_decode_frames).
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_distortion_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                                int n_stacks, const int32_t *tables, int n_tables,
+                                uint64_t *sse, uint64_t *bits, uint32_t *d_cube_sse);
+int dct3d_distortion_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                            int n_stacks, const int32_t *tables, int n_tables, uint64_t *sse, uint64_t *bits);
+
 #ifdef __cplusplus
 }
 #endif
