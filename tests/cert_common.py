@@ -1,6 +1,7 @@
-"""Shared by test_cert_common.py (CPU) and test_gpu_certificates.py (GPU): what the host emulations of the kernels'
-arithmetic predict for the counts dct3d_get_stats reports -- which coefficients the fp32 encode certificate leaves
-open, which lanes the decode certificate flags, and how the 8x8x8 second certificate splits the open ones.
+"""Shared by test_cert_common.py (CPU), test_gpu_certificates.py and test_gpu_probe_certificates.py (GPU): what the
+host emulations of the kernels' arithmetic predict for the counts dct3d_get_stats reports -- which coefficients the
+fp32 encode certificate leaves open, which lanes the decode certificate flags, how the 8x8x8 second certificate splits
+the open ones, and what the rate and distortion probes count under several tables.
 
 The emulations are tests/native/emulate_encode.cpp and emulate_decode_quant.cpp, built here as test_emulation.py
 builds them (g++ -O2 -ffp-contract=off -fno-fast-math, into a temporary directory).  With contraction off on both
@@ -45,6 +46,16 @@ def steps_of(steps, depth):
     return qc.pkg().quant_table(5, depth) if steps is None else np.ascontiguousarray(steps, np.int32)
 
 
+@functools.lru_cache(maxsize=None)
+def _plan_of(depth, key):
+    return qc.pkg().plan_query(8, 8, depth, None if key is None else np.frombuffer(key, np.int32))
+
+
+def plan_of(depth, steps):
+    """plan_query for the table (None: the reference's), made once per table: the planner's analysis takes ~0.4 s"""
+    return _plan_of(depth, None if steps is None else np.ascontiguousarray(steps, np.int32).tobytes())
+
+
 def raster_of(frames, depth):
     """frames [F, h, w] or packed [F, h, w, 3], any h, w -> the edge-padded raster the calls are defined on, RGB as
     the planar-stacked raster of dct3d.h (per stack: its R, G, B frames): [channels F, Hp, Wp]"""
@@ -58,7 +69,7 @@ def encode_emulate(frames, depth, steps=None, channels=1, shift=0):
     shift (the sensitivity check only): the threshold tables G, E read at s + shift, clamped to the table."""
     import oracle
     assert channels == (3 if np.asarray(frames).ndim == 4 else 1)
-    p = qc.pkg().plan_query(8, 8, depth, steps)
+    p = plan_of(depth, steps)
     cubes = np.ascontiguousarray(oracle.to_cubes(raster_of(frames, depth), 8, 8, depth), np.uint8)
     n = cubes.shape[0]
     q = np.empty(cubes.size, np.int32)
@@ -136,7 +147,14 @@ def decode_emulate(q, depth, steps, extra_margin):
 
     The kernel's fp32 reduction of L1 is not restated: l1_f lies within L1 (1 + 2^-19) (1 +- 2^-20).  Asserted
     preconditions: both ends give the same mi for every cube, and no cube's L1 lies that close to dec_l1_max."""
-    p = qc.pkg().plan_query(8, 8, depth, steps)
+    lanes, byte = decode_emulate_margins(q, depth, steps, (extra_margin,))
+    return lanes[0], byte
+
+
+def decode_emulate_margins(q, depth, steps, margins):
+    """decode_emulate for several margins from one run of the emulated transform (w does not depend on the margin):
+    ([the mask of flagged lanes per margin], the bytes); the preconditions are asserted for every margin"""
+    p = plan_of(depth, steps)
     st = steps_of(steps, depth)
     q = np.ascontiguousarray(q, np.int32).reshape(-1, depth, 8, 8)
     n = q.shape[0]
@@ -148,18 +166,23 @@ def decode_emulate(q, depth, steps, extra_margin):
     lo_l, hi_l = l1 * L1_FACTOR * (1.0 - L1_SLACK), l1 * L1_FACTOR * (1.0 + L1_SLACK)
     lmax = float(p["dec_l1_max"])
     assert not ((lo_l < lmax) & (hi_l >= lmax)).any(), "a cube's L1 within 2^-20 of dec_l1_max"
-    E = p["dec_E"] + float(extra_margin)
-    mi = _mi(lo_l, p["dec_G"], E)
-    assert np.array_equal(mi, _mi(hi_l, p["dec_G"], E)), "mi depends on the fp32 L1 reduction: another seed"
     lo = (w.view(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64).reshape(n, depth, 8, 8)
-    bad = (lo < mi[:, None, None, None]) | (lo > 0xFFFFFFFF - mi[:, None, None, None])
+    # a lane's verdict needs only the least and the greatest low word of its 32 pixels (the kernel's lo_min, lo_max)
     if depth == 8:
-        lanes = bad.reshape(n, 8, 8, 2, 4).any(axis=(1, 4)).reshape(n, 16)  # [y][h]
+        lo = lo.reshape(n, 8, 8, 2, 4)
+        lo_min, lo_max = lo.min(axis=(1, 4)).reshape(n, 16), lo.max(axis=(1, 4)).reshape(n, 16)  # [y][h]
     else:
-        lanes = bad.any(axis=(1, 3))  # [y]
+        lo_min, lo_max = lo.min(axis=(1, 3)), lo.max(axis=(1, 3))  # [y]
+    out = []
+    for extra_margin in margins:
+        E = p["dec_E"] + float(extra_margin)
+        mi = _mi(lo_l, p["dec_G"], E)
+        assert np.array_equal(mi, _mi(hi_l, p["dec_G"], E)), "mi depends on the fp32 L1 reduction: another seed"
+        lanes = (lo_min < mi[:, None]) | (lo_max > 0xFFFFFFFF - mi[:, None])
+        out.append(lanes | (lo_l >= lmax)[:, None])
     h16 = ((w.view(np.uint64) >> np.uint64(32)) & np.uint64(0xFFFF)).astype(np.int64)
     byte = np.clip(np.where(h16 >= 32768, h16 - 65536, h16), 0, 255).astype(np.uint8).reshape(n, depth, 8, 8)
-    return lanes | (lo_l >= lmax)[:, None], byte
+    return out, byte
 
 
 def decode_open(q, depth, steps, extra_margin):
@@ -229,7 +252,10 @@ TABLES = ("ref", "q1", "q12", "seeded")  # ref: no table set (None)
 
 
 def table(name, depth):
-    return None if name == "ref" else qc.tables(depth)[name]
+    """ref: None; qt<n>: quant_table(n); every other name: quant_common.tables"""
+    if name == "ref":
+        return None
+    return qc.pkg().quant_table(int(name[2:]), depth) if name.startswith("qt") else qc.tables(depth)[name]
 
 
 @functools.lru_cache(maxsize=None)
@@ -329,3 +355,100 @@ EG = [Case("uniform", d, 1, w, h, st, rich)
 # (200 x 72, cert_common.decode_open on the CPU) they flag 0.7-1.1 %, 9.0-10.0 % and 50.1-51.1 % of the lanes.
 MARGINS = (1.5e-4, 1.6e-3, 1.1e-2)
 DEC = [Case("uniform", d, ch, w, h, 1) for d in (8, 4) for ch in (1, 3) for (w, h) in ((200, 72), (1366, 24), (13, 11))]
+
+
+# ---- the rate and distortion probes (test_gpu_probe_certificates.py) ------------------------------------------------
+# rate_kernel and distortion_kernel certify in loops of their own, from table rows that probe-only host code builds
+# (dct3d_rate_frames_dev, dct3d_distortion_frames_dev), and add what they fold into the same counter.
+
+# 11 tables: two launches of up to 8.  (quant_table(24), not 20: under 20 one lane of the 200 x 72 x 4 case at 8x8x8
+# decodes within the margin-0 certificate's reach, and the distortion count at margin 0 is to be the encode term alone.)
+PROBE_TABLES = TABLES + ("all255", "ones", "q2", "qt3", "qt7", "qt24", "qt64")
+PROBE_SETS = dict({n: (n,) for n in PROBE_TABLES}, four=TABLES, eleven=PROBE_TABLES)
+
+
+def with_total(v):
+    """per-band counts -> the same with the whole raster's count last"""
+    v = np.asarray(v, np.int64)
+    return np.concatenate([v, [v.sum()]])
+
+
+@functools.lru_cache(maxsize=None)
+def probe_open_counts(c, name, shift=0):
+    """int64 [nby + 1]: the coefficients the emulation leaves open under table `name`, per band and in all (kept
+    per case and table: the sets share them)"""
+    v = with_total(band_counts(case_open(c, name, shift)[1], c.stacks, c.channels, c.nby))
+    v.setflags(write=False)
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def probe_decode_lanes(c, name, margins):
+    """the lanes the decode certificate flags on the reference's coefficients under table `name`, one mask
+    [cube, lanes per cube] per margin (a tuple of margins; kept per case and table).  The probe's decode tile runs
+    with EDGE = 0 on whole padded cubes of the integers the encode side staged (the reference's, once the folds have
+    settled the open ones); its constants do not depend on the table, DCT3D_OPT_DEC_MARGIN is added as
+    decode_emulate adds it."""
+    return tuple(decode_emulate_margins(case_q_ref(c, name), c.depth, table(name, c.depth), margins)[0])
+
+
+def probe_lane_counts(c, name, margin):
+    """int64 [nby + 1]: the lanes probe_decode_lanes flags at `margin`, per band and in all (the margins of
+    PROBE_MARGINS from one run of the emulation)"""
+    ms = PROBE_MARGINS if margin in PROBE_MARGINS else (margin,)
+    return with_total(band_counts(probe_decode_lanes(c, name, ms)[ms.index(margin)], c.stacks, c.channels, c.nby))
+
+
+def rate_probe_counts(c, names, shift=0):
+    """rate_kernel's n_flagged for the tables `names` in one call, int64 [nby + 1] (per band, then the whole raster):
+    a coefficient open under k of the tables is folded once and counted k times -- the sum over the tables of the
+    open coefficients; the DC is never counted; every geometry counts"""
+    return sum(probe_open_counts(c, n, shift) for n in names)
+
+
+def distortion_probe_counts(c, names, margin, shift=0):
+    """distortion_kernel's n_flagged, int64 [nby + 1]: per table the open coefficients (every one takes the fold, at
+    8x8x8 too: the probe has no second certificate) plus 32 per lane the decode tile replays"""
+    return sum(probe_open_counts(c, n, shift) + 32 * probe_lane_counts(c, n, margin) for n in names)
+
+
+PROBE_MARGINS = (0.0,) + MARGINS[:2]
+# grey at multiples of 8 (which the stream encode does not count, and the probes do), the ragged and RGB lists of
+# EG, 1 x 1, and the grey 1080p stack of each depth.  The sets a case runs under: probe_sets.
+PROBE_CASES = STACKS8[:3] + STACKS4[:3] + EG + [c for c in EDGE if (c.w, c.h) == (1, 1)] + [STACKS8[4], STACKS4[4]]
+
+
+def probe_sets(c):
+    """the table sets of a probe case: each of TABLES alone, the four in one call, the 11 in one call.  At 1080p the
+    seven other tables run alone as well, before the 11: a table's reference there costs about a second of host
+    time, and each case then pays for one table's"""
+    if (c.w, c.h) == (1920, 1080):
+        return TABLES + ("four",) + PROBE_TABLES[4:] + ("eleven",)
+    return TABLES + ("four", "eleven")
+
+
+def probe_rich(c, set_name):
+    """whether the case claims richness under the set: a set is rich when one of its tables is"""
+    return any(n in c.rich for n in PROBE_SETS[set_name])
+
+
+# distortion_sum_kernel (and rate_sum_kernel): 256 threads, thread i sums the run's values i, i + 256, ...; a butterfly
+# over 1, 2, 4, 8, 16, 32 lanes inside each wave of 64, the uint64 partial sent as two 32-bit halves.
+SUM_BLOCK = 256
+
+
+def sum_partials(values, lanes):
+    """int64 [256 / lanes]: the partial sums each aligned group of `lanes` lanes holds after the butterfly's steps
+    below `lanes`, for one run of per-cube values"""
+    v = np.asarray(values, np.int64).reshape(-1)
+    pad = np.zeros(-(-v.size // SUM_BLOCK) * SUM_BLOCK, np.int64)
+    pad[:v.size] = v
+    return pad.reshape(-1, SUM_BLOCK).sum(axis=0).reshape(-1, lanes).sum(axis=1)
+
+
+# the case whose partial sums pass 2^32 while shuffles remain: uniform noise under all255, one grey stack; every
+# 8-lane partial of every wave >= 2^32 (asserted from the reference's cube sums by the test).  The sizes: the
+# smallest multiple-of-8 height at widths 2560 / 3840 that meets the condition, measured on the reference (DESIGN 2):
+# a cube costs 1,981,851 (8x8x8) / 990,577 (8x8x4) on average, the least 8-lane partial is 1.0019 / 1.0035 x 2^32
+# (one block row less: 0.9982 / 0.9998).
+BIG_SUM = {8: (2560, 1744), 4: (3840, 2328)}

@@ -7,7 +7,10 @@
   * the preconditions of every GPU case hold -- richness, the empty ambiguous band of split_8x8x8, decode_open's
     margin and guard bands -- so that a bad seed is found here, without a GPU;
   * sensitivity: the thresholds read at s + 1 instead of s (the tables shifted in Python, no kernel built) change the
-    predicted count of every rich case: that mutation cannot pass the GPU module unseen."""
+    predicted count of every rich case: that mutation cannot pass the GPU module unseen;
+  * the same for the rate and distortion probes' predictions (test_gpu_probe_certificates.py): soundness under the
+    probe-only tables, the decode preconditions at every margin used, a set's count as the sum of its tables', and
+    the shifted threshold seen by every rich set."""
 import numpy as np
 import pytest
 
@@ -132,3 +135,80 @@ def test_lane_ownership_mask():
     l4[0, 3] = True
     m4 = cc.lane_pixels(l4, 4)
     assert m4.sum() == 32 and m4[0, :, 3, :].all()
+
+
+# ---- the probes' predictions (test_gpu_probe_certificates.py) ---------------------------------------------------------
+
+def _probe_tables(c):
+    seen = []
+    for s in cc.probe_sets(c):
+        seen += [n for n in cc.PROBE_SETS[s] if n not in seen]
+    return seen
+
+
+def test_probe_cases_are_the_listed_ones():
+    ids = [c.id for c in cc.PROBE_CASES]
+    assert len(ids) == len(set(ids)) == 22
+    for d in (8, 4):
+        want = [f"uniform-{s}-grey-d{d}" for s in ("200x72x4", "24x16x5", "8x8x1", "1366x24x2", "13x11x1", "1x1x1", "1920x1080x1")] + \
+               [f"uniform-{s}-rgb-d{d}" for s in ("200x72x2", "24x16x5", "13x11x1", "1x1x1")]
+        assert set(want) == {i for i in ids if i.endswith(f"d{d}")}
+    assert len(cc.PROBE_TABLES) == len(set(cc.PROBE_TABLES)) == 11 and cc.PROBE_SETS["four"] == cc.TABLES
+    for c in cc.PROBE_CASES:
+        sets = cc.probe_sets(c)
+        assert sets[:5] == cc.TABLES + ("four",) and sets[-1] == "eleven" and len(sets) == (13 if c.w == 1920 else 6)
+
+
+@pytest.mark.parametrize("c", cc.PROBE_CASES, ids=repr)
+def test_probe_predictions(c):
+    """per probe case: under every table of its sets the emulation is sound (what it leaves closed is the reference's
+    q, also under the probe-only tables) and decode_emulate's preconditions hold at each of PROBE_MARGINS, with no
+    lane flagged at margin 0; the prediction of a set is the sum of its tables' (a coefficient open under k tables
+    counts k times); and on the rich cases the thresholds read at s + 1 change the predicted count of every rich
+    set, rate and distortion: the counts can see a table row taken one entry off."""
+    names = _probe_tables(c)
+    lanes = {}
+    for n in names:
+        q, op = cc.case_open(c, n)
+        bad = (q != cc.case_q_ref(c, n)) & ~op
+        assert not bad.any(), f"{n}: {int(bad.sum())} closed coefficients differ"
+        assert not op[:, 0, 0, 0].any()
+        lanes[n] = cc.probe_decode_lanes(c, n, cc.PROBE_MARGINS)  # (asserts the preconditions)
+        assert not lanes[n][0].any(), f"{c.id} {n}: a lane flagged at margin 0: another seed"
+        if n in c.rich:
+            assert cc.is_rich(cc.probe_open_counts(c, n)[:-1]), f"{c.id} {n}"
+    for s in cc.probe_sets(c):
+        tabs = cc.PROBE_SETS[s]
+        rate = cc.rate_probe_counts(c, tabs)
+        assert rate.shape == (c.nby + 1,) and rate[-1] == rate[:-1].sum()
+        assert np.array_equal(rate, sum(cc.rate_probe_counts(c, (n,)) for n in tabs))
+        for i, m in enumerate(cc.PROBE_MARGINS):
+            dist = cc.distortion_probe_counts(c, tabs, m)
+            assert np.array_equal(dist, sum(cc.distortion_probe_counts(c, (n,), m) for n in tabs))
+            assert dist[-1] == rate[-1] + 32 * sum(int(lanes[n][i].sum()) for n in tabs)
+        if cc.probe_rich(c, s):
+            assert cc.is_rich(rate[:-1])
+            shifted = cc.rate_probe_counts(c, tabs, shift=1)
+            assert shifted[-1] != rate[-1] and not np.array_equal(shifted, rate), f"{c.id} {s}: rate does not see thr[s + 1]"
+            assert cc.distortion_probe_counts(c, tabs, 0.0, shift=1)[-1] != cc.distortion_probe_counts(c, tabs, 0.0)[-1]
+        print(f"{c.id} {s}: rate {int(rate[-1])}, distortion at {cc.PROBE_MARGINS}: "
+              f"{[int(cc.distortion_probe_counts(c, tabs, m)[-1]) for m in cc.PROBE_MARGINS]}")
+
+
+def test_probe_reference_is_ref_frames():
+    """the GPU module takes the reference's q from case_q_ref (one DCT per case, shared by its tables): it is
+    quant_common.ref_frames' q, grey and RGB, ragged sizes included"""
+    for c in (cc.EG[1], cc.EG[4]):
+        for n in ("ref", "all255", "qt7"):
+            T = cc.steps_of(cc.table(n, c.depth), c.depth)
+            assert np.array_equal(cc.case_q_ref(c, n), qc.ref_frames(c.frames(), T, c.depth)[0])
+
+
+def test_sum_partials_is_the_sum_kernels_partition():
+    """thread i of 256 sums the values i, i + 256, ...; 8-lane groups are the threads 8 g .. 8 g + 7"""
+    v = np.arange(1000, dtype=np.int64) ** 2
+    p1 = cc.sum_partials(v, 1)
+    assert p1.shape == (256,) and p1[3] == sum(int(v[i]) for i in range(3, 1000, 256))
+    p8 = cc.sum_partials(v, 8)
+    assert p8.shape == (32,) and p8[2] == p1[16:24].sum() and cc.sum_partials(v, 64).sum() == v.sum()
+    assert all(h % 8 == 0 and w % 8 == 0 for w, h in cc.BIG_SUM.values())
