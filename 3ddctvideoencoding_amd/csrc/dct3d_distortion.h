@@ -10,17 +10,12 @@ constexpr int kDistStepN = 32;  // fp64 steps per table, s = kx + ky + kz (as De
 // distortion_kernel codes channel `ch` of the cubes of EncodeParams P (as launch_rate's) under n_tables tables
 // and decodes them again: per table and cube the squared error of the decoded bytes against the source bytes
 // inside the frame, and optionally the cube's Exp-Golomb bits.
-struct DistParams {
-    const float4* tabs;     // [n_tables][kRateTabN] {fp32(1 / step_s), G_s, 0.5 - E_s, step_s} (as RateParams)
-    const double* steps;    // [n_tables][kDistStepN] the decode's steps
-    uint32_t* cube_sse;     // [n_tables][table_stride]: cube g of channel ch at enc_out_cube
-    uint16_t* cube_bits;    // the same layout, or nullptr
-    uint64_t table_stride;  // cubes of one table: channels * P.n_cubes
+struct DistParams : RateParams {  // (cube_bits may be nullptr here)
+    const double* steps;       // [n_tables][kDistStepN] the decode's steps
+    uint32_t* cube_sse;        // [n_tables][table_stride]: cube g of channel ch at enc_out_cube
     const double* inv_coef_t;  // the decode's certificate and replay (as DecodeParams)
     double dec_G, dec_E;
     float dec_l1_max;
-    int n_tables;           // 1 .. kRateTables
-    int ch;
 };
 
 // px = 1 grey | 3 packed RGB24, edge = 0 | 1 (frames of any size)

@@ -5,12 +5,10 @@
 // them with the rows it started from.  No coefficient and no decoded raster exists in memory.  A translation
 // unit of its own: no other kernel's code object changes with it.
 #include "dct3d_distortion.h"
-#include "dct3d_rate_dev.h"
+#include "dct3d_probe_dev.h"
 #include "dct3d_decode_dev.h"
 
 namespace dct3d {
-
-static_assert(kRateTabN == kTabN, "a table's rows as the encode kernels'");
 
 // The decode's rare replay re-reads a cube's quantised values: the int16 copy of the tile beside the decode
 // region (|q| < 2^15 for 8-bit frames and steps >= 1, so the copy is exact, whatever the cube's L1)
@@ -164,10 +162,10 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t cube0 = (blockIdx.x * kWavesPerBlock + wave) * CPW;
     // encode side
-    const int ec = (D == 8) ? (lane >> 5) * 2 + ((lane & 15) >> 3) : lane >> 3;
-    const int kz = (D == 8) ? lane & 7 : (lane & 7) >> 1;
-    const int kx0 = (D == 8) ? 4 * ((lane >> 4) & 1) : (lane & 1) * 4;
-    const bool dcl = kz == 0 && kx0 == 0 && ((D == 8) || (lane & 7) == 0);  // the cube's DC lane
+    const auto enc_lane = [](int ln) { return (D == 8) ? probe_lane16(ln) : probe_lane8<4>(ln); };
+    const ProbeLane L = enc_lane(lane);
+    const int ec = L.c, kz = L.kz, kx0 = L.kx0;
+    const bool dcl = L.dc();  // the cube's DC lane
     const bool evalid = cube0 + ec < P.n_cubes;
     uint2 raw[4];
     __builtin_amdgcn_s_setprio(3);  // the rows in flight first (as the encode kernels)
@@ -177,8 +175,7 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
     if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);  // the next call's counter slot
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     const int nt = R.n_tables;
-    // every wave writes the block's whole copy (identical bits) and reads only after its own writes (enc_tables)
-    for (int i = lane; i < nt * kTabN; i += kWave) s_tab[i] = R.tabs[i];
+    probe_fill_tabs(s_tab, R, lane);
     char* const wl = lds + wave * WLDS;
     int16_t* const q16 = (int16_t*)(wl + Q16_OFF);
     int* const ssum = (int*)(wl + RS_OFF);
@@ -252,9 +249,7 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
     DP.dec_l1_max = R.dec_l1_max;
     DP.inv_coef_t = R.inv_coef_t;
     DP.replay_count = P.replay_count;
-    ReplayGeom RG{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride, P.ngroups, P.coef, P.group_of};
-    if constexpr (PX != 1) RG.ch = R.ch;
-    if constexpr (EDGE != 0) RG.height = P.height;
+    const ReplayGeom RG = probe_replay_geom<PX, EDGE>(P, R.ch);
     const size_t ocube = enc_out_cube<PX>(P, min(cube0 + (uint32_t)dc, P.n_cubes - 1u), R.ch);  // the decode lane's cube
     uint32_t nrep = 0;
 
@@ -262,60 +257,25 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
     for (int t = 0; t < nt; t++) {
         const float4* tab = s_tab + t * kTabN;
         const double* steps = R.steps + t * kDistStepN;
-        // ---- quantise + certify with the encode's products and thresholds; the integers to the decode's
-        //      staging and to the int16 copy; the certified values' code widths from their exponents (rate_kernel) ----
-        int sz = kz + kx0;
-        float rr[11], thr[11];
-        uint32_t om = 0u;  // open under this table: bit 4 ky + x
-        uint32_t es = 0, e00 = 0;
-        const int dcq = java_round_dev(__ddiv_rn((double)S * P.coef_dc, (double)tab[0].w));  // the exact DC
+        // ---- quantise + certify with the encode's products and thresholds (probe_quantise); the integers, the
+        //      exact DC among them, to the decode's staging and to the int16 copy ----
+        uint32_t es, e00, om[1];  // om: open under this table, bit 4 ky + x
+        const int dcq = probe_dc(S, P.coef_dc, tab);
         char* const stg = wl + ec * G::SA_C + kz * G::SA_F + kx0 * 4;
         int16_t* const s16 = q16 + ec * CS + kz * 64 + kx0;
-#pragma unroll
-        for (int ky = 0; ky < 8; ky++) {
-            tab_window<4, 11>(tab, sz, ky, A, rr, thr);
-            bool f = false;
-            float qq[4];
-            uint32_t e[4];
+        probe_quantise<4, 11, 1>(tab, kz + kx0, A, b, es, e00, om, [&](int ky, const float (&n)[4]) {
             int qi[4];
 #pragma unroll
-            for (int x = 0; x < 4; x++) {
-                qq[x] = b[ky][x] * rr[ky + x];
-                const float n = __builtin_rintf(qq[x]);
-                f |= __builtin_fabsf(qq[x] - n) >= thr[ky + x];
-                const float n2 = n + n;
-                e[x] = __float_as_uint(__builtin_fmaxf(n2, 1.0f - n2)) >> 23;
-                es += e[x];
-                qi[x] = (int)n;
-            }
-            if (ky == 0) {
-                e00 = e[0];
-                if (dcl) qi[0] = dcq;
-            }
-            if (__builtin_expect(f, 0)) {
-                uint32_t bits = 0;
-#pragma unroll
-                for (int x = 0; x < 4; x++)
-                    if (__builtin_fabsf(qq[x] - __builtin_rintf(qq[x])) >= thr[ky + x]) {
-                        bits |= 1u << x;
-                        es -= e[x];
-                    }
-                om |= bits << (4 * ky);
-            }
+            for (int x = 0; x < 4; x++) qi[x] = (int)n[x];
+            if (ky == 0 && dcl) qi[0] = dcq;
             *(int4*)(stg + ky * 32) = make_int4(qi[0], qi[1], qi[2], qi[3]);
             *(uint2*)(s16 + ky * 8) = make_uint2(__builtin_amdgcn_perm(qi[1], qi[0], 0x05040100u),
                                                  __builtin_amdgcn_perm(qi[3], qi[2], 0x05040100u));
-            asm volatile("" : "+v"(es), "+v"(om));
-        }
-        if (dcl && (om & 1u)) {  // the DC is exact already (its threshold is +inf: never open in practice)
-            om &= ~1u;
-            es += e00;
-        }
-        uint32_t bits = 2u * es - 253u * ((uint32_t)NV - (uint32_t)__builtin_popcount(om));
-        if (dcl) bits += rate_width(dcq) - (2u * e00 - 253u);
+        });
+        uint32_t bits = probe_lane_bits<NV, 1>(es, e00, om, dcl, dcq);
         if (!evalid) {
             bits = 0u;
-            om = 0u;
+            om[0] = 0u;
         }
         bits += __shfl_xor(bits, 1, 64);
         bits += __shfl_xor(bits, 2, 64);
@@ -325,25 +285,26 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
         wave_lds_sync();
 
         // ---- the coefficients the certificate left open, one at a time by the whole wave (rare): the Java fold,
-        //      divided by this table's step, written over the provisional value in both copies ----
+        //      divided by this table's step, written over the provisional value in both copies.  (Per table and
+        //      before the decode, which needs the value; the rate probe folds once for all tables after its loop.) ----
         for (;;) {
-            const unsigned long long who = __ballot(om != 0u);
+            const unsigned long long who = __ballot(om[0] != 0u);
             if (who == 0ull) break;
             const int src = __builtin_ctzll(who);
-            const int bit = __shfl(om ? __builtin_ctz(om) : 0, src, 64);
-            const int sc = (D == 8) ? (src >> 5) * 2 + ((src & 15) >> 3) : src >> 3;
-            const int skz = (D == 8) ? src & 7 : (src & 7) >> 1;
-            const int skx = ((D == 8) ? 4 * ((src >> 4) & 1) : (src & 1) * 4) + (bit & 3), sky = bit >> 2;
-            const uint32_t k = (uint32_t)((skz * 8 + sky) * 8 + skx);
+            const int bit = __shfl(om[0] ? __builtin_ctz(om[0]) : 0, src, 64);
+            const ProbeLane SL = enc_lane(src);
+            const int sc = SL.c;
+            int ss;
+            const uint32_t k = SL.template coef<4>(bit, ss);
             const double acc = rate_fold(replay_load<D, PX, EDGE>(RG, cube0 + sc, k, lane), CS, lane, ssum, prod);
             if (lane == 0) {
-                const int q = java_round_dev(__ddiv_rn(acc, (double)tab[skx + sky + skz].w));
-                *(int*)(wl + sc * G::SA_C + skz * G::SA_F + (sky * 8 + skx) * 4) = q;
+                const int q = java_round_dev(__ddiv_rn(acc, (double)tab[ss].w));
+                *(int*)(wl + sc * G::SA_C + (k >> 6) * G::SA_F + (k & 63) * 4) = q;
                 q16[sc * CS + k] = (int16_t)q;
                 sums[sc] += rate_width(q);
             }
             nrep++;
-            if (lane == src) om &= om - 1u;
+            if (lane == src) om[0] &= om[0] - 1u;
             wave_lds_sync();
         }
         if (R.cube_bits && lane < CPW && cube0 + lane < P.n_cubes)
@@ -377,52 +338,18 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
 
 // One block per run of `run` cubes (a table's stack and channel): their sum (rate_sum_kernel for uint32)
 __global__ __launch_bounds__(kBlock) void distortion_sum_kernel(const uint32_t* cube_sse, uint32_t run, uint64_t* out) {
-    __shared__ uint64_t s_part[kWavesPerBlock];
     const uint32_t* p = cube_sse + (size_t)blockIdx.x * run;
     uint64_t s = 0;
     for (uint32_t i = threadIdx.x; i < run; i += kBlock) s += p[i];
-    uint32_t lo = (uint32_t)s, hi = (uint32_t)(s >> 32);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint64_t t = ((uint64_t)(uint32_t)__shfl_xor((int)hi, o, 64) << 32) | (uint32_t)__shfl_xor((int)lo, o, 64);
-        s += t;
-        lo = (uint32_t)s;
-        hi = (uint32_t)(s >> 32);
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t r = 0;
-#pragma unroll
-        for (int i = 0; i < kWavesPerBlock; i++) r += s_part[i];
-        out[blockIdx.x] = r;
-    }
+    const uint64_t r = probe_block_sum(s);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
-
-namespace {
-template <int D, int PX, int EDGE>
-void launch_dist_t(const EncodeParams& P, const DistParams& R, hipStream_t st) {
-    const dim3 grid(grid_blocks(P.n_cubes, DecGeom<D>::CPW));
-    hipLaunchKernelGGL((distortion_kernel<D, PX, EDGE>), grid, dim3(kBlock), 0, st, P, R);
-}
-template <int D>
-void launch_dist_d(int px, int edge, const EncodeParams& P, const DistParams& R, hipStream_t st) {
-    if (px == 1) {
-        if (edge) launch_dist_t<D, 1, 1>(P, R, st);
-        else launch_dist_t<D, 1, 0>(P, R, st);
-    } else {
-        if (edge) launch_dist_t<D, 3, 1>(P, R, st);
-        else launch_dist_t<D, 3, 0>(P, R, st);
-    }
-}
-}  // namespace
 
 int launch_distortion(int D, int px, int edge, const EncodeParams& P, const DistParams& R, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if ((px != 1 && px != 3) || R.n_tables < 1 || R.n_tables > kRateTables) return -1;
-    if (D == 8) launch_dist_d<8>(px, edge, P, R, st);
-    else launch_dist_d<4>(px, edge, P, R, st);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return probe_dispatch(D, px, edge, P, R, [&](auto d, auto p, auto e) {
+        const dim3 grid(grid_blocks(P.n_cubes, DecGeom<decltype(d)::value>::CPW));
+        hipLaunchKernelGGL((distortion_kernel<decltype(d)::value, decltype(p)::value, decltype(e)::value>), grid, dim3(kBlock), 0, st, P, R);
+    });
 }
 
 int launch_distortion_sum(const uint32_t* cube_sse, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st) {

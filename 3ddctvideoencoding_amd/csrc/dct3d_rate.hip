@@ -4,11 +4,9 @@
 // order, emitted or compacted, and the fp32 transform does not depend on the table.  A translation unit of
 // its own: no other kernel's code object changes with it.
 #include "dct3d_rate.h"
-#include "dct3d_rate_dev.h"
+#include "dct3d_probe_dev.h"
 
 namespace dct3d {
-
-static_assert(kRateTabN == kTabN, "a table's rows as the encode kernels'");
 
 // encode_eg_kernel's geometry: one wave owns 8 cubes, 8 lanes per cube; rows -> statistics -> transform as
 // there.  The coefficients then stay in registers, and a rolled loop over the launch's tables quantises and
@@ -38,23 +36,17 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
     __builtin_amdgcn_s_setprio(3);  // the rows in flight first (as encode_eg_kernel)
     load_channel_rows<D, 0, PX, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, R.ch, raw);
     __builtin_amdgcn_s_setprio(0);
-    if (blockIdx.x == 0 && P.replay_clear) {  // the next call's counter slot
-#pragma unroll
-        for (int i = 0; i < 2 * kCountSpread / kBlock; i++) P.replay_clear[i * kBlock + threadIdx.x] = 0u;
-    }
+    if (blockIdx.x == 0 && P.replay_clear) enc_clear_next_slot(P);  // the next call's counter slot
     if (cube0 >= P.n_cubes) return;  // wave-uniform
     const int nt = R.n_tables;
-    // every wave writes the block's whole copy (identical bits) and reads only after its own writes (enc_tables)
-    for (int i = lane; i < nt * kTabN; i += kWave) s_tab[i] = R.tabs[i];
+    probe_fill_tabs(s_tab, R, lane);
     char* wl = lds + wave * enc_wave_lds<D>();
     int* const ssum = (int*)wl;
     double* const prod = (double*)(wl + kMaxGroupsDev * 4);
     uint32_t* const sums = (uint32_t*)(wl + RS_B);         // [table][cube]
     uint32_t* const msk = (uint32_t*)(wl + RS_B + SUM_B);  // [table][word][lane]
-    const int c = lane >> 3, j = lane & 7;
-    const int kz = (D == 8) ? j : (j >> 1);
-    const int kx0 = (D == 8) ? 0 : (j & 1) * 4;
-    const int so = kz + kx0;
+    const ProbeLane L = probe_lane8<D>(lane);
+    const int c = L.c, j = lane & 7;
     const bool valid = cube0 + c < P.n_cubes;
 
     float a[D][8];
@@ -73,48 +65,9 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
 #pragma unroll 1
     for (int t = 0; t < nt; t++) {
         const float4* tab = s_tab + t * kTabN;
-        int sz = so;
-        float rr[NI], thr[NI];
-        uint32_t es = 0, e00 = 0;  // the sum of the codes' exponents; the fp32 DC's
-        uint32_t om[MW];           // open under this table
-#pragma unroll
-        for (int w = 0; w < MW; w++) om[w] = 0u;
-#pragma unroll
-        for (int ky = 0; ky < 8; ky++) {
-            tab_window<NB, NI>(tab, sz, ky, A, rr, thr);
-            bool f = false;
-            float qq[NB];
-            uint32_t e[NB];
-#pragma unroll
-            for (int x = 0; x < NB; x++) {
-                qq[x] = b[ky][x] * rr[ky + x];
-                const float n = __builtin_rintf(qq[x]);
-                f |= __builtin_fabsf(qq[x] - n) >= thr[ky + x];
-                const float n2 = n + n;
-                e[x] = __float_as_uint(__builtin_fmaxf(n2, 1.0f - n2)) >> 23;
-                es += e[x];
-            }
-            if (ky == 0) e00 = e[0];
-            if (__builtin_expect(f, 0)) {
-                uint32_t bits = 0;
-#pragma unroll
-                for (int x = 0; x < NB; x++)
-                    if (__builtin_fabsf(qq[x] - __builtin_rintf(qq[x])) >= thr[ky + x]) {
-                        bits |= 1u << x;
-                        es -= e[x];
-                    }
-                om[(ky * NB) >> 5] |= bits << ((ky * NB) & 31);
-            }
-            asm volatile("" : "+v"(es), "+v"(om[0]));
-        }
-        // the lane's certified values (all NV but the open ones): sum of 2 (e - 126) - 1
-        uint32_t open = (uint32_t)__builtin_popcount(om[0]);
-        if constexpr (MW == 2) open += (uint32_t)__builtin_popcount(om[1]);
-        uint32_t bits = 2u * es - 253u * ((uint32_t)NV - open);
-        if (j == 0) {  // the DC: exact, from the integer cube sum (never open: its threshold is +inf)
-            const int dc = java_round_dev(__ddiv_rn((double)S * P.coef_dc, (double)tab[0].w));
-            bits += rate_width(dc) - (2u * e00 - 253u);
-        }
+        uint32_t es, e00, om[MW];  // the sum of the codes' exponents; the fp32 DC's; open under this table
+        probe_quantise<NB, NI, MW>(tab, L.kz + L.kx0, A, b, es, e00, om, [](int, const float (&)[NB]) {});
+        uint32_t bits = probe_lane_bits<NV, MW>(es, e00, om, L.dc(), L.dc() ? probe_dc(S, P.coef_dc, tab) : 0);
         if (!valid) {
             bits = 0u;
 #pragma unroll
@@ -132,11 +85,10 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
     wave_lds_sync();
 
     // the coefficients some table left open, one at a time by the whole wave (rare): one fold each, one
-    // division and rounding per table that left it open
+    // division and rounding per table that left it open.  (The distortion probe folds per table instead, before
+    // that table's decode, which needs the value.)
     {
-        ReplayGeom G{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride, P.ngroups, P.coef, P.group_of};
-        if constexpr (PX != 1) G.ch = R.ch;
-        if constexpr (EDGE != 0) G.height = P.height;
+        const ReplayGeom G = probe_replay_geom<PX, EDGE>(P, R.ch);
         uint32_t nrep = 0;
         for (;;) {
             uint32_t any = fm[0];
@@ -147,17 +99,17 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
             int mybit = fm[0] ? __builtin_ctz(fm[0]) : 0;
             if constexpr (MW == 2) mybit = fm[0] ? mybit : (fm[1] ? 32 + __builtin_ctz(fm[1]) : 0);
             const int bit = __shfl(mybit, src, 64);
-            const int sj = src & 7, sc = src >> 3;
-            const int skz = (D == 8) ? sj : (sj >> 1), skx0 = (D == 8) ? 0 : (sj & 1) * 4;
-            const int sky = bit / NB, skx = skx0 + bit % NB;
-            const uint32_t k = (uint32_t)((skz * 8 + sky) * 8 + skx);
+            const ProbeLane SL = probe_lane8<D>(src);
+            const int sc = SL.c;
+            int ss;
+            const uint32_t k = SL.template coef<NB>(bit, ss);
             const double acc = rate_fold(replay_load<D, PX, EDGE>(G, cube0 + sc, k, lane), CS, lane, ssum, prod);
 #pragma unroll 1
             for (int t = 0; t < nt; t++) {
                 const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)msk[(t * MW + (bit >> 5)) * 64 + src]);
                 if ((w >> (bit & 31)) & 1u) {  // wave-uniform
                     if (lane == 0) {
-                        const int q = java_round_dev(__ddiv_rn(acc, (double)s_tab[t * kTabN + skx + sky + skz].w));
+                        const int q = java_round_dev(__ddiv_rn(acc, (double)s_tab[t * kTabN + ss].w));
                         sums[t * 8 + sc] += rate_width(q);
                     }
                     nrep++;
@@ -181,7 +133,6 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
 // One block per run of `run` cubes (a table's stack and channel): their sum.  The body goes as 8-byte loads
 // from the first 8-byte boundary; the few values before and after it one by one.
 __global__ __launch_bounds__(kBlock) void rate_sum_kernel(const uint16_t* cube_bits, uint32_t run, uint64_t* out) {
-    __shared__ uint64_t s_part[kWavesPerBlock];
     const uint16_t* p = cube_bits + (size_t)blockIdx.x * run;
     const uint32_t head = min(run, (uint32_t)(((8u - ((uintptr_t)p & 7u)) & 7u) / 2u));
     const uint32_t nvec = (run - head) / 4u;
@@ -193,48 +144,15 @@ __global__ __launch_bounds__(kBlock) void rate_sum_kernel(const uint16_t* cube_b
     }
     if (threadIdx.x < head) s += p[threadIdx.x];
     for (uint32_t i = head + nvec * 4u + threadIdx.x; i < run; i += kBlock) s += p[i];
-    uint32_t lo = (uint32_t)s, hi = (uint32_t)(s >> 32);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint64_t t = ((uint64_t)(uint32_t)__shfl_xor((int)hi, o, 64) << 32) | (uint32_t)__shfl_xor((int)lo, o, 64);
-        s += t;
-        lo = (uint32_t)s;
-        hi = (uint32_t)(s >> 32);
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t r = 0;
-#pragma unroll
-        for (int i = 0; i < kWavesPerBlock; i++) r += s_part[i];
-        out[blockIdx.x] = r;
-    }
+    const uint64_t r = probe_block_sum(s);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
-
-namespace {
-template <int D, int PX, int EDGE>
-void launch_rate_t(const EncodeParams& P, const RateParams& R, hipStream_t st) {
-    const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
-    hipLaunchKernelGGL((rate_kernel<D, PX, EDGE>), grid, dim3(kBlock), 0, st, P, R);
-}
-template <int D>
-void launch_rate_d(int px, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
-    if (px == 1) {
-        if (edge) launch_rate_t<D, 1, 1>(P, R, st);
-        else launch_rate_t<D, 1, 0>(P, R, st);
-    } else {
-        if (edge) launch_rate_t<D, 3, 1>(P, R, st);
-        else launch_rate_t<D, 3, 0>(P, R, st);
-    }
-}
-}  // namespace
 
 int launch_rate(int D, int px, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if ((px != 1 && px != 3) || R.n_tables < 1 || R.n_tables > kRateTables) return -1;
-    if (D == 8) launch_rate_d<8>(px, edge, P, R, st);
-    else launch_rate_d<4>(px, edge, P, R, st);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return probe_dispatch(D, px, edge, P, R, [&](auto d, auto p, auto e) {
+        const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
+        hipLaunchKernelGGL((rate_kernel<decltype(d)::value, decltype(p)::value, decltype(e)::value>), grid, dim3(kBlock), 0, st, P, R);
+    });
 }
 
 int launch_rate_sum(const uint16_t* cube_bits, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st) {

@@ -1269,120 +1269,20 @@ static bool rate_args_ok(const dct3d_ctx* c, const uint8_t* frames, int w, int h
             if (tables[i] < kMinStep || tables[i] > kMaxStep) return false;
     return true;
 }
-extern "C" {
-
-int dct3d_rate_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
-                          const int32_t* tables, int n_tables, uint64_t* bits, uint16_t* d_cube_bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+// Each table's {1 / step, G, 0.5 - E, step} rows from the context's one plan (encoder_tables: the rows
+// dct3d_plan_query_quant reports for that table), as the encode kernels' LDS copy holds them (enc_tables); with
+// want_steps its steps in fp64 too (as the decode kernels' table)
+static void probe_tables(dct3d_ctx* c, const int32_t* tables, int n_tables, bool want_steps) {
+    static_assert(kRateTabN <= kMaxS && kDistStepN == kMaxS, "a table's rows and steps");
     const int n_steps = (int)c->plan.steps.size();
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    c->last_units = 0;
-    if (n_cubes == 0) return DCT3D_OK;
-    // each table's {1 / step, G, 0.5 - E, step} rows from the context's one plan (encoder_tables: the rows
-    // dct3d_plan_query_quant reports for that table), as the encode kernels' LDS copy holds them (enc_tables)
-    static_assert(kRateTabN <= kMaxS, "a table's rows");
     c->rate_tabs_host.resize((size_t)n_tables * kRateTabN * 4);
-    for (int t = 0; t < n_tables; t++) {
-        int32_t st[kMaxS];
-        float rstep[kMaxS], G[kMaxS], E[kMaxS];
-        for (int s = 0; s < kMaxS; s++)
-            st[s] = s < n_steps ? (tables ? tables[(size_t)t * n_steps + s] : c->plan.steps[s]) : reference_step(s);
-        encoder_tables(c->plan, st, rstep, G, E);
-        float* row = c->rate_tabs_host.data() + (size_t)t * kRateTabN * 4;
-        for (int s = 0; s < kRateTabN; s++, row += 4) {
-            row[0] = rstep[s];
-            row[1] = G[s];
-            row[2] = 0.5f - E[s];
-            row[3] = (float)st[s];
-        }
-    }
-    const uint64_t stride = (uint64_t)channels * n_cubes;                   // cubes of one table
-    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;       // sums
-    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
-    int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_rate_sums.grow(n_runs * sizeof(uint64_t))) ||
-        (!d_cube_bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))))
-        return rc;
-    if (c->h_rate_bytes < n_runs * sizeof(uint64_t)) {
-        if (c->h_rate) (void)hipHostFree(c->h_rate);
-        c->h_rate = nullptr;
-        c->h_rate_bytes = 0;
-        if (hipHostMalloc((void**)&c->h_rate, n_runs * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
-            c->h_rate = nullptr;
-            return DCT3D_ENOMEM;
-        }
-        c->h_rate_bytes = n_runs * sizeof(uint64_t);
-    }
-    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
-    uint16_t* const cube_bits = d_cube_bits ? d_cube_bits : (uint16_t*)c->d_rate_bits.p;
-    EncodeParams P;
-    fill_encode_params(c, P, d_frames, nullptr, g, n_cubes);
-    hipEvent_t* ev = timer_begin(c);
-    rc = DCT3D_OK;
-    // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
-    for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
-        for (int ch = 0; ch < channels && !rc; ch++) {
-            RateParams R;
-            R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
-            R.cube_bits = cube_bits + (size_t)t0 * stride;
-            R.table_stride = stride;
-            R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
-            R.ch = ch;
-            if (launch_rate(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream)) rc = DCT3D_EKERNEL;
-            else c->slot_used = true;
-        }
-    if (!rc && launch_rate_sum(cube_bits, (uint32_t)g.cps(), n_runs, (uint64_t*)c->d_rate_sums.p, c->stream)) rc = DCT3D_EKERNEL;
-    timer_end(c, ev);
-    if (!rc && hipMemcpyAsync(c->h_rate, c->d_rate_sums.p, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = DCT3D_EDEVICE;
-    // synchronous on return (the sums are a host result; the tables' host copy and buffers are free again)
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
-    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
-    if (rc) return rc;
-    memcpy(bits, c->h_rate, n_runs * sizeof(uint64_t));
-    return DCT3D_OK;
-}
-
-int dct3d_rate_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                      const int32_t* tables, int n_tables, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    const size_t in_bytes = (size_t)g.plane() * c->bd * n_stacks;  // the unpadded frames: one copy
-    int rc;
-    if ((rc = c->h_in.grow(in_bytes ? in_bytes : 1))) return rc;
-    if (in_bytes && hipMemcpyAsync(c->h_in.p, frames, in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
-    return dct3d_rate_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, n_stacks, tables, n_tables, bits, nullptr);
-}
-
-// ---- distortion probe: the exact squared error of encode + decode under several tables, one transform per
-//      cube and one certified decode tile per cube and table (dct3d.h; DESIGN 4j) ----
-int dct3d_distortion_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
-                                const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
-    const int n_steps = (int)c->plan.steps.size();
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    if (!c->batch) c->last_units = 0;
-    if (n_cubes == 0) return DCT3D_OK;
-    // each table's certificate rows (as the rate probe's) and its steps in fp64 (as the decode kernels' table)
-    c->rate_tabs_host.resize((size_t)n_tables * kRateTabN * 4);
-    c->dist_steps_host.resize((size_t)n_tables * kDistStepN);
-    static_assert(kDistStepN == kMaxS, "a table's steps");
+    c->dist_steps_host.resize(want_steps ? (size_t)n_tables * kDistStepN : 0);
     for (int t = 0; t < n_tables; t++) {
         int32_t st[kMaxS];
         float rstep[kMaxS], G[kMaxS], E[kMaxS];
         for (int s = 0; s < kMaxS; s++) {
             st[s] = s < n_steps ? (tables ? tables[(size_t)t * n_steps + s] : c->plan.steps[s]) : reference_step(s);
-            c->dist_steps_host[(size_t)t * kDistStepN + s] = (double)st[s];
+            if (want_steps) c->dist_steps_host[(size_t)t * kDistStepN + s] = (double)st[s];
         }
         encoder_tables(c->plan, st, rstep, G, E);
         float* row = c->rate_tabs_host.data() + (size_t)t * kRateTabN * 4;
@@ -1393,83 +1293,109 @@ int dct3d_distortion_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, in
             row[3] = (float)st[s];
         }
     }
+}
+
+// the pinned buffer the probes' sums come back in
+static int probe_grow_pinned(dct3d_ctx* c, size_t bytes) {
+    if (c->h_rate_bytes >= bytes) return DCT3D_OK;
+    if (c->h_rate) (void)hipHostFree(c->h_rate);
+    c->h_rate = nullptr;
+    c->h_rate_bytes = 0;
+    if (hipHostMalloc((void**)&c->h_rate, bytes, hipHostMallocDefault) != hipSuccess) {
+        c->h_rate = nullptr;
+        return DCT3D_ENOMEM;
+    }
+    c->h_rate_bytes = bytes;
+    return DCT3D_OK;
+}
+
+// Both probes on frames in device memory (the arguments hold: rate_args_ok).  sse: the distortion probe (bits
+// optional; d_cube_sse the caller's per-cube buffer or nullptr); no sse: the rate probe (d_cube_bits likewise).
+static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                     uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse, uint16_t* d_cube_bits) {
+    const bool dist = sse != nullptr;
+    const int channels = g.px;
+    const uint64_t n_cubes = g.cps() * (uint64_t)n_stacks;  // per channel
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    call_begin(c);
+    if (!c->batch) c->last_units = 0;
+    if (n_cubes == 0) return DCT3D_OK;
+    probe_tables(c, tables, n_tables, dist);
     const uint64_t stride = (uint64_t)channels * n_cubes;              // cubes of one table
-    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;  // sums (twice with the bits)
+    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;  // sums (the squared errors, then the bits)
     const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
     const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
-    const size_t sum_bytes = (bits ? 2 : 1) * n_runs * sizeof(uint64_t);
+    const size_t sum_bytes = ((dist ? 1 : 0) + (bits ? 1 : 0)) * n_runs * sizeof(uint64_t);
     int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_dist_steps.grow(step_bytes)) || (rc = c->d_rate_sums.grow(sum_bytes)) ||
-        (!d_cube_sse && (rc = c->d_dist_sse.grow((size_t)n_tables * stride * sizeof(uint32_t)))) ||
-        (bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))))
+    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (dist && (rc = c->d_dist_steps.grow(step_bytes))) ||
+        (rc = c->d_rate_sums.grow(sum_bytes)) ||
+        (dist && !d_cube_sse && (rc = c->d_dist_sse.grow((size_t)n_tables * stride * sizeof(uint32_t)))) ||
+        (bits && !d_cube_bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))) ||
+        (rc = probe_grow_pinned(c, sum_bytes)))
         return rc;
-    if (c->h_rate_bytes < sum_bytes) {
-        if (c->h_rate) (void)hipHostFree(c->h_rate);
-        c->h_rate = nullptr;
-        c->h_rate_bytes = 0;
-        if (hipHostMalloc((void**)&c->h_rate, sum_bytes, hipHostMallocDefault) != hipSuccess) {
-            c->h_rate = nullptr;
-            return DCT3D_ENOMEM;
-        }
-        c->h_rate_bytes = sum_bytes;
-    }
     if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        (dist && hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess))
         return DCT3D_EDEVICE;
     uint32_t* const cube_sse = d_cube_sse ? d_cube_sse : (uint32_t*)c->d_dist_sse.p;
-    uint16_t* const cube_bits = bits ? (uint16_t*)c->d_rate_bits.p : nullptr;
+    uint16_t* const cube_bits = d_cube_bits ? d_cube_bits : bits ? (uint16_t*)c->d_rate_bits.p : nullptr;
     EncodeParams P;
     fill_encode_params(c, P, d_frames, nullptr, g, n_cubes);
-    DecodeParams DP;  // the certificate's constants and the replay's table, the test margin included
-    fill_decode_params(c, DP, nullptr, nullptr, g, n_cubes);
+    DistParams R = {};
+    R.table_stride = stride;
+    if (dist) {  // the decode's certificate constants and the replay's table, the test margin included
+        DecodeParams DP;
+        fill_decode_params(c, DP, nullptr, nullptr, g, n_cubes);
+        R.inv_coef_t = DP.inv_coef_t;
+        R.dec_G = DP.dec_G;
+        R.dec_E = DP.dec_E;
+        R.dec_l1_max = DP.dec_l1_max;
+    }
     hipEvent_t* ev = timer_begin(c);
     rc = DCT3D_OK;
-    // kRateTables tables per launch, one launch per channel (as the rate probe)
+    // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
     for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
         for (int ch = 0; ch < channels && !rc; ch++) {
-            DistParams R;
             R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
-            R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
-            R.cube_sse = cube_sse + (size_t)t0 * stride;
             R.cube_bits = cube_bits ? cube_bits + (size_t)t0 * stride : nullptr;
-            R.table_stride = stride;
-            R.inv_coef_t = DP.inv_coef_t;
-            R.dec_G = DP.dec_G;
-            R.dec_E = DP.dec_E;
-            R.dec_l1_max = DP.dec_l1_max;
             R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
             R.ch = ch;
-            if (launch_distortion(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream)) rc = DCT3D_EKERNEL;
+            if (dist) {
+                R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
+                R.cube_sse = cube_sse + (size_t)t0 * stride;
+            }
+            if (dist ? launch_distortion(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream)
+                     : launch_rate(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream))
+                rc = DCT3D_EKERNEL;
             else c->slot_used = true;
         }
     uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
-    if (!rc && launch_distortion_sum(cube_sse, (uint32_t)g.cps(), n_runs, d_sums, c->stream)) rc = DCT3D_EKERNEL;
-    if (!rc && bits && launch_rate_sum(cube_bits, (uint32_t)g.cps(), n_runs, d_sums + n_runs, c->stream)) rc = DCT3D_EKERNEL;
+    uint64_t* const d_bit_sums = d_sums + (dist ? n_runs : 0);
+    if (!rc && dist && launch_distortion_sum(cube_sse, (uint32_t)g.cps(), n_runs, d_sums, c->stream)) rc = DCT3D_EKERNEL;
+    if (!rc && bits && launch_rate_sum(cube_bits, (uint32_t)g.cps(), n_runs, d_bit_sums, c->stream)) rc = DCT3D_EKERNEL;
     timer_end(c, ev);
     if (!rc && hipMemcpyAsync(c->h_rate, d_sums, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
     // synchronous on return (the sums are a host result; the tables' host copies and buffers are free again)
     if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
     if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
     if (rc) return rc;
-    memcpy(sse, c->h_rate, n_runs * sizeof(uint64_t));
-    if (bits) memcpy(bits, c->h_rate + n_runs, n_runs * sizeof(uint64_t));
+    if (dist) memcpy(sse, c->h_rate, n_runs * sizeof(uint64_t));
+    if (bits) memcpy(bits, c->h_rate + (d_bit_sums - d_sums), n_runs * sizeof(uint64_t));
     return DCT3D_OK;
 }
 
-// The host-pointer call: the frames go up in chunks of whole stacks (one staging buffer of bounded size), each
-// chunk's sums land at its stacks' places; the chunks' statistics add up (batch).
-int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                            const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+// Both probes on frames in host memory: the frames go up in chunks of whole stacks (one staging buffer of 64 MiB
+// at most, or one stack), each chunk's sums land at its stacks' places; the chunks' statistics add up (batch).
+static int probe_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                      uint64_t* sse, uint64_t* bits) {
+    const int channels = g.px;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     const size_t stack_bytes = (size_t)g.plane() * c->bd;  // the unpadded frames of one stack
-    constexpr size_t kChunkBytes = (size_t)64 << 20;  // (as the host-pointer pipeline's chunks)
+    constexpr size_t kChunkBytes = (size_t)64 << 20;       // (as the host-pointer pipeline's chunks)
     const int per = stack_bytes ? (int)std::max<size_t>(1, std::min<size_t>(kChunkBytes / stack_bytes, (size_t)(n_stacks > 0 ? n_stacks : 1))) : 1;
     int rc;
     if ((rc = c->h_in.grow(stack_bytes * per ? stack_bytes * per : 1))) return rc;
     std::vector<uint64_t> part((size_t)2 * n_tables * per * channels);
+    c->last_units = 0;  // (no stack: no chunk)
     batch_begin(c);
     rc = DCT3D_OK;
     for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
@@ -1479,16 +1405,52 @@ int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, i
             rc = DCT3D_EDEVICE;
             break;
         }
-        uint64_t* const pb = bits ? part.data() + (size_t)n_tables * run : nullptr;
-        rc = dct3d_distortion_frames_dev(c, (const uint8_t*)c->h_in.p, w, h, channels, ns, tables, n_tables, part.data(), pb, nullptr);
+        uint64_t* const ps = sse ? part.data() : nullptr;
+        uint64_t* const pb = bits ? part.data() + (sse ? (size_t)n_tables * run : 0) : nullptr;
+        rc = probe_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, ps, pb, nullptr, nullptr);
         for (int t = 0; t < n_tables && !rc; t++) {
             const size_t dst = ((size_t)t * n_stacks + s0) * channels;
-            memcpy(sse + dst, part.data() + (size_t)t * run, run * sizeof(uint64_t));
+            if (sse) memcpy(sse + dst, ps + (size_t)t * run, run * sizeof(uint64_t));
             if (bits) memcpy(bits + dst, pb + (size_t)t * run, run * sizeof(uint64_t));
         }
     }
     batch_end(c);
     return rc;
+}
+extern "C" {
+
+int dct3d_rate_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                          const int32_t* tables, int n_tables, uint64_t* bits, uint16_t* d_cube_bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, nullptr, bits, nullptr, d_cube_bits);
+}
+
+int dct3d_rate_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                      const int32_t* tables, int n_tables, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    return probe_host(c, frames, g, n_stacks, tables, n_tables, nullptr, bits);
+}
+
+// ---- distortion probe: the exact squared error of encode + decode under several tables, one transform per
+//      cube and one certified decode tile per cube and table (dct3d.h; DESIGN 4j) ----
+int dct3d_distortion_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                                const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, sse, bits, d_cube_sse, nullptr);
+}
+
+int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                            const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits);
 }
 
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,

@@ -150,83 +150,69 @@ static int parse_positive(const char *text, const char *prefix, double *value) {
     return 0;
 }
 
-int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, "rate=", bpp); }
-
+/* What selects a call's quantiser: the table itself or one of the targets.  A target is "<prefix><number>"; q=,
+ * rate= and psnr= exclude each other: one may not be set (codec_set_*) while another is, and a call that finds
+ * one (set or in the environment) beside an entry before it in this list refuses. */
 static char g_rate_text[64]; /* codec_set_rate's text; "": none */
 static char g_psnr_text[64]; /* codec_set_psnr's text; "": none */
+enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_N };
+static const struct {
+    const char *prefix, *env, *noun, *unit;
+    char *text;
+    size_t cap;
+} kSel[SEL_N] = {
+    {"q=", "DCT3D_CODEC_QUANT", "quantiser", NULL, g_quant_text, sizeof(g_quant_text)},
+    {"rate=", "DCT3D_CODEC_RATE", "rate target", "bits per pixel", g_rate_text, sizeof(g_rate_text)},
+    {"psnr=", "DCT3D_CODEC_PSNR", "PSNR target", "dB", g_psnr_text, sizeof(g_psnr_text)},
+};
+static const char *sel_text(int i) { return kSel[i].text[0] ? kSel[i].text : getenv(kSel[i].env); }
 
-int codec_set_rate(const char *text) {
-    if (text && strlen(text) >= sizeof(g_rate_text)) return 1;
-    if (text && text[0] && (g_quant_text[0] || g_psnr_text[0])) return 1; /* q=, rate= and psnr= exclude each other */
-    snprintf(g_rate_text, sizeof(g_rate_text), "%s", text ? text : "");
+int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, kSel[SEL_RATE].prefix, bpp); }
+int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR].prefix, db); }
+
+static int set_target(int i, const char *text) {
+    if (text && strlen(text) >= kSel[i].cap) return 1;
+    for (int o = 0; o < SEL_N; o++)
+        if (o != i && text && text[0] && kSel[o].text[0]) return 1;
+    snprintf(kSel[i].text, kSel[i].cap, "%s", text ? text : "");
     return 0;
 }
+int codec_set_rate(const char *text) { return set_target(SEL_RATE, text); }
+int codec_set_psnr(const char *text) { return set_target(SEL_PSNR, text); }
 
-/* The rate target of a call: codec_set_rate's text, else DCT3D_CODEC_RATE.  *set = 0: none given.  1 after
- * printing when the text does not parse or a quantiser is given too. */
-static int call_rate(double *bpp, int *set) {
-    const char *text = g_rate_text[0] ? g_rate_text : getenv("DCT3D_CODEC_RATE");
-    const char *qt = g_quant_text[0] ? g_quant_text : getenv("DCT3D_CODEC_QUANT");
+/* Target i of a call: codec_set_*'s text, else the environment variable.  *set = 0: none given.  1 after printing
+ * when the text does not parse or a quantiser or an earlier target is given too. */
+static int call_target(int i, double *value, int *set) {
+    const char *text = sel_text(i);
     *set = text && text[0];
     if (!*set) return 0;
-    if (qt && qt[0]) {
-        printf("A quantiser ('%s') and a rate target ('%s') exclude each other\n", qt, text);
-        return 1;
+    for (int o = 0; o < i; o++) {
+        const char *ot = sel_text(o);
+        if (ot && ot[0]) {
+            printf("A %s ('%s') and a %s ('%s') exclude each other\n", kSel[o].noun, ot, kSel[i].noun, text);
+            return 1;
+        }
     }
-    if (codec_parse_rate(text, bpp)) {
-        printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", text);
-        return 1;
-    }
-    return 0;
-}
-/* the commands that take no rate target: 1 after printing when one is given */
-static int reject_rate(const char *what) {
-    double bpp;
-    int set;
-    if (call_rate(&bpp, &set)) return 1;
-    if (set) printf("rate= applies to single-device encodes only (%s): decode with the q=<n> that the encode printed\n", what);
-    return set;
-}
-
-/* ---- the PSNR target (codec.h) ------------------------------------------------------------------ */
-int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, "psnr=", db); }
-
-int codec_set_psnr(const char *text) {
-    if (text && strlen(text) >= sizeof(g_psnr_text)) return 1;
-    if (text && text[0] && (g_quant_text[0] || g_rate_text[0])) return 1; /* q=, rate= and psnr= exclude each other */
-    snprintf(g_psnr_text, sizeof(g_psnr_text), "%s", text ? text : "");
-    return 0;
-}
-
-/* The PSNR target of a call: codec_set_psnr's text, else DCT3D_CODEC_PSNR.  *set = 0: none given.  1 after
- * printing when the text does not parse or a quantiser or a rate target is given too. */
-static int call_psnr(double *db, int *set) {
-    const char *text = g_psnr_text[0] ? g_psnr_text : getenv("DCT3D_CODEC_PSNR");
-    const char *qt = g_quant_text[0] ? g_quant_text : getenv("DCT3D_CODEC_QUANT");
-    const char *rt = g_rate_text[0] ? g_rate_text : getenv("DCT3D_CODEC_RATE");
-    *set = text && text[0];
-    if (!*set) return 0;
-    if (qt && qt[0]) {
-        printf("A quantiser ('%s') and a PSNR target ('%s') exclude each other\n", qt, text);
-        return 1;
-    }
-    if (rt && rt[0]) {
-        printf("A rate target ('%s') and a PSNR target ('%s') exclude each other\n", rt, text);
-        return 1;
-    }
-    if (codec_parse_psnr(text, db)) {
-        printf("Invalid psnr target '%s': psnr=<dB>, a positive number\n", text);
+    if (parse_positive(text, kSel[i].prefix, value)) {
+        printf("Invalid %.*s target '%s': %s<%s>, a positive number\n", (int)strlen(kSel[i].prefix) - 1, kSel[i].prefix,
+               text, kSel[i].prefix, kSel[i].unit);
         return 1;
     }
     return 0;
 }
-/* the commands that take no PSNR target: 1 after printing when one is given */
-static int reject_psnr(const char *what) {
-    double db;
-    int set;
-    if (call_psnr(&db, &set)) return 1;
-    if (set) printf("psnr= applies to single-device encodes only (%s): decode with the q=<n> that the encode printed\n", what);
-    return set;
+/* the commands that take no target: 1 after printing when one is given */
+static int reject_targets(const char *what) {
+    for (int i = SEL_RATE; i < SEL_N; i++) {
+        double v;
+        int set;
+        if (call_target(i, &v, &set)) return 1;
+        if (set) {
+            printf("%s applies to single-device encodes only (%s): decode with the q=<n> that the encode printed\n",
+                   kSel[i].prefix, what);
+            return 1;
+        }
+    }
+    return 0;
 }
 
 /* The first pass of an encode with a rate target: the rate probe (dct3d_rate_frames) per batch over the fixed
@@ -491,8 +477,7 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
                "of 8)\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_rate("encode_multi")) return 1;
-    if (reject_psnr("encode_multi")) return 1;
+    if (reject_targets("encode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -602,8 +587,7 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_rate("decode_multi")) return 1;
-    if (reject_psnr("decode_multi")) return 1;
+    if (reject_targets("decode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -742,10 +726,10 @@ static int encode_any(const char *inName, const char *outName, int width, int he
                       int depth, int batch, int channels) {
     double rate_bpp = 0.0;
     int rate_set = 0;
-    if (call_rate(&rate_bpp, &rate_set)) return 1;
+    if (call_target(SEL_RATE, &rate_bpp, &rate_set)) return 1;
     double psnr_db = 0.0;
     int psnr_set = 0;
-    if (call_psnr(&psnr_db, &psnr_set)) return 1;
+    if (call_target(SEL_PSNR, &psnr_db, &psnr_set)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -888,8 +872,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
 
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
-    if (reject_rate("decode")) return 1;
-    if (reject_psnr("decode")) return 1;
+    if (reject_targets("decode")) return 1;
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
     const int host_eg = host_eg_on();

@@ -416,7 +416,9 @@ int dct3d_decode_eg_frames(dct3d_ctx *ctx, const uint8_t *const bytes[], const u
  *             total_bits[ch] - carry_bits[ch].  Exact; there is no estimate.
  *   d_cube_bits   optional device memory, [n_tables][n_stacks][channels][C] (C: the padded cubes per stack and
  *             channel): the same sum per cube (a cube costs < 2^15 bits).
- * The call neither reads (tables != NULL) nor changes the context's quantiser and is synchronous on return.
+ * The call neither reads (tables != NULL) nor changes the context's quantiser and is synchronous on return; the
+ * host-pointer call moves the frames in chunks of whole stacks (64 MiB of staging at most, or one stack), its
+ * numbers and statistics those of one call.
  * Errors.  DCT3D_EINVAL: the cases of dct3d_encode_frames, n_tables outside 1..DCT3D_RATE_MAX_TABLES, tables
  * == NULL with n_tables != 1, bits == NULL, a step outside [1, 255] (nothing is launched then).
  * Statistics: n_units = padded coefficients of all channels x n_tables; n_flagged = the coefficient values
@@ -443,7 +445,7 @@ int dct3d_rate_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int heig
  *             same sum per cube over its samples inside the frame (512 x 255^2 < 2^32).
  * The call writes no stream, neither reads (tables != NULL) nor changes the context's quantiser, honours
  * DCT3D_OPT_DEC_MARGIN as dct3d_decode_frames does, and is synchronous on return; the host-pointer call
- * moves the frames in chunks of whole stacks.
+ * moves the frames in chunks of whole stacks, as dct3d_rate_frames does.
  * Errors.  DCT3D_EINVAL: the cases of dct3d_rate_frames, with sse in the place of bits.
  * Statistics: n_units = padded coefficients of all channels x n_tables; n_flagged = the coefficient values
  * settled by the exact Java fold, counted per table as in the rate call, plus what the decode's exact replay

@@ -122,6 +122,28 @@ def test_bits_equal_the_reference(gpu_ctx8, gpu_ctx4, depth, geom, n_tables):
     assert np.array_equal(host, bits)
 
 
+@pytest.mark.parametrize("depth", [8, 4])
+def test_host_call_in_several_chunks(gpu_ctx8, gpu_ctx4, depth):
+    """1b: 40 frames of 1920 x 1080 (79 MiB) go up in two chunks of whole stacks on the host-pointer path (5 stacks
+    as 4 + 1, 10 as 8 + 2): every (table, stack) sum lands at its place (the device call's numbers), and the chunks'
+    statistics add up."""
+    import torch
+    ctx = _ctx(depth, gpu_ctx8, gpu_ctx4)
+    w, h, stacks = 1920, 1080, 40 // depth
+    fr = np.random.default_rng(20261020).integers(0, 256, (40, h, w), dtype=np.uint8)
+    fr[8:16] //= 4  # stacks that differ in what they cost
+    tabs = [_table(depth, "q2"), _table(depth, "q12")]
+    bits = ctx.rate_frames_dev(torch.from_numpy(fr).cuda(), w, h, 1, stacks, tabs)
+    dev = ctx.stats()
+    assert dev["n_units"] == 2 * fr.size
+    host = ctx.rate_frames(fr, tabs)
+    st = ctx.stats()
+    assert st["n_units"] == 2 * fr.size
+    assert st["n_flagged"] == dev["n_flagged"]
+    assert np.array_equal(host, bits)
+    assert len(set(int(v) for v in bits[0, :, 0])) == stacks  # no two stacks alike: a misplaced chunk would show
+
+
 @pytest.mark.parametrize("geom", ["rare", "rare_rgb"])
 @pytest.mark.parametrize("depth", [8, 4])
 def test_rare_path(gpu_ctx8, gpu_ctx4, depth, geom):
