@@ -752,4 +752,11 @@ __global__ __launch_bounds__(kBlock, 3) void decode_rgb_kernel(typename DecodeAr
     dec_store_tile<D, false, 3, EDGE>(P, wl, (int)(threadIdx.x & 63), cube0, out3, valid);
 }
 
+// (host) the int32 decode kernel of a variant: one name for the two kernels
+template <int D, int PX, int EDGE, int QT>
+constexpr auto decode_kernel_of() -> void (*)(typename DecodeArgs<QT>::type) {
+    if constexpr (PX == 1) return decode_kernel<D, EDGE, QT>;
+    else return decode_rgb_kernel<D, EDGE, QT>;
+}
+
 }  // namespace dct3d

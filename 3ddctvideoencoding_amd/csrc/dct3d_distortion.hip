@@ -356,7 +356,7 @@ int launch_distortion_sum(const uint32_t* cube_sse, uint32_t run, uint64_t n_run
     if (n_runs == 0) return 0;
     if (n_runs > 0x7FFFFFFFull) return -1;
     hipLaunchKernelGGL(distortion_sum_kernel, dim3((uint32_t)n_runs), dim3(kBlock), 0, st, cube_sse, run, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 }  // namespace dct3d

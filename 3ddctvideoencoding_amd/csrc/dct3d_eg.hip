@@ -1422,8 +1422,8 @@ int launch_eg_encode(int D, const EgParams& P, hipStream_t st) {
     const uint64_t cube_blocks = (P.n_cubes + kEgWaves - 1) / kEgWaves;
     const uint64_t n_chunks = (P.n_cubes + kScanChunk - 1) / kScanChunk;
     if (cube_blocks > 0x7FFFFFFFull) return -1;
-    if (D == 8) hipLaunchKernelGGL(eg_len_kernel<8>, dim3((uint32_t)cube_blocks), dim3(kEgBlock), 0, st, P);
-    else hipLaunchKernelGGL(eg_len_kernel<4>, dim3((uint32_t)cube_blocks), dim3(kEgBlock), 0, st, P);
+    const auto len = [&](auto d) { hipLaunchKernelGGL(eg_len_kernel<d>, dim3((uint32_t)cube_blocks), dim3(kEgBlock), 0, st, P); };
+    if (!with_depth(D, len)) return -1;
     hipLaunchKernelGGL(eg_scan_reduce_kernel, dim3((uint32_t)n_chunks), dim3(kEgBlock), 0, st, P);
     hipLaunchKernelGGL(eg_scan_top_kernel, dim3(1), dim3(1024), 0, st, P, (uint32_t)n_chunks);
     hipLaunchKernelGGL(eg_scan_apply_kernel, dim3((uint32_t)n_chunks), dim3(kEgBlock), 0, st, P);
@@ -1434,10 +1434,9 @@ int launch_eg_encode(int D, const EgParams& P, hipStream_t st) {
         wgrid = cus * 8;
     }
     const uint32_t wblocks = (uint32_t)(cube_blocks < (uint64_t)wgrid ? cube_blocks : (uint64_t)wgrid);
-    if (D == 8) hipLaunchKernelGGL(eg_write_kernel<8>, dim3(wblocks), dim3(kEgBlock), 0, st, P);
-    else hipLaunchKernelGGL(eg_write_kernel<4>, dim3(wblocks), dim3(kEgBlock), 0, st, P);
+    with_depth(D, [&](auto d) { hipLaunchKernelGGL(eg_write_kernel<d>, dim3(wblocks), dim3(kEgBlock), 0, st, P); });
     hipLaunchKernelGGL(eg_stitch_kernel, dim3((uint32_t)((P.n_cubes + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 }  // namespace dct3d
@@ -1460,7 +1459,7 @@ int launch_eg_sync(const EgDecParams& P, int iteration, int resolve, hipStream_t
 #endif
     hipLaunchKernelGGL(eg_sync_kernel, dim3((uint32_t)((P.n_chunks + per - 1) / per)), dim3(kEgBlock), 0, st, P,
                        iteration, (int)rs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 int launch_eg_scan(const EgParams& P, hipStream_t st) {
@@ -1469,7 +1468,7 @@ int launch_eg_scan(const EgParams& P, hipStream_t st) {
     hipLaunchKernelGGL(eg_scan_reduce_kernel, dim3((uint32_t)n_chunks), dim3(kEgBlock), 0, st, P);
     hipLaunchKernelGGL(eg_scan_top_kernel, dim3(1), dim3(1024), 0, st, P, (uint32_t)n_chunks);
     hipLaunchKernelGGL(eg_scan_apply_kernel, dim3((uint32_t)n_chunks), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 int launch_eg_compact(const EgParams& P, const uint32_t* slot, uint32_t seg_cap, hipStream_t st) {
@@ -1479,13 +1478,13 @@ int launch_eg_compact(const EgParams& P, const uint32_t* slot, uint32_t seg_cap,
     const uint64_t blocks = (P.n_cubes + per - 1) / per;
     hipLaunchKernelGGL(eg_compact_kernel, dim3((uint32_t)blocks), dim3(kEgBlock), 0, st, P, slot, seg_cap);
     hipLaunchKernelGGL(eg_stitch_kernel, dim3((uint32_t)((P.n_cubes + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 int launch_eg_stitch(const EgParams& P, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     hipLaunchKernelGGL(eg_stitch_kernel, dim3((uint32_t)((P.n_cubes + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 // desc: one zeroed word per block (front_blocks); force_fail (test option): every block fails
@@ -1495,7 +1494,7 @@ int launch_eg_front(const EgDecParams& P, uint64_t* desc, int force_fail, hipStr
     const uint64_t blocks = front_blocks(P.n_chunks);
     if (blocks > 0x7FFFFFFFull) return -1;
     hipLaunchKernelGGL(eg_front_kernel, dim3((uint32_t)blocks), dim3(kEgBlock), 0, st, P, desc, force_fail);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 int launch_eg_dscan(const EgDecParams& P, const EgParams& S, hipStream_t st) {
@@ -1503,7 +1502,7 @@ int launch_eg_dscan(const EgDecParams& P, const EgParams& S, hipStream_t st) {
     const uint64_t nb = (P.n_chunks + kScanChunk - 1) / kScanChunk;
     hipLaunchKernelGGL(eg_dscan_reduce_kernel, dim3((uint32_t)nb), dim3(kEgBlock), 0, st, P);
     hipLaunchKernelGGL(eg_scan_top_kernel, dim3(1), dim3(1024), 0, st, S, (uint32_t)nb);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 int launch_eg_mark(const EgDecParams& P, hipStream_t st) {
     if (P.n_chunks == 0) return 0;
@@ -1512,16 +1511,15 @@ int launch_eg_mark(const EgDecParams& P, hipStream_t st) {
     hipLaunchKernelGGL(eg_mark_diag2_kernel, dim3((uint32_t)((P.n_chunks + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
 #endif
     hipLaunchKernelGGL(eg_mark_kernel, dim3((uint32_t)((P.n_chunks + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 int launch_eg_emit(int D, const EgDecParams& P, hipStream_t st) {
     const uint64_t waves = (P.n_values / kMarkVals + 63) / 64;
     if (waves == 0) return 0;
     const uint32_t blocks = (uint32_t)((waves + kEgWaves - 1) / kEgWaves);
-    if (D == 8) hipLaunchKernelGGL(eg_emit_kernel<8>, dim3(blocks), dim3(kEgBlock), 0, st, P);
-    else hipLaunchKernelGGL(eg_emit_kernel<4>, dim3(blocks), dim3(kEgBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const auto emit = [&](auto d) { hipLaunchKernelGGL(eg_emit_kernel<d>, dim3(blocks), dim3(kEgBlock), 0, st, P); };
+    return with_depth(D, emit) ? launched() : -1;
 }
 
 int launch_eg_decode_write(int D, const EgDecParams& P, hipStream_t st) {

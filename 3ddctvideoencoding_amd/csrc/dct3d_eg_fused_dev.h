@@ -165,7 +165,7 @@ __device__ __forceinline__ uint32_t k1_code_off(uint32_t k) {
 }
 
 // PX = 3 (dct3d_eg_frames.hip): a packed RGB24 raster, the launch coding channel E.ch of the RGB cubes (one
-// stream per channel: a launch chain each).  EDGE = 1: frames of any size, P as launch_encode_edge's.  Both
+// stream per channel: a launch chain each).  EDGE = 1: frames of any size, P as launch_encode's for it.  Both
 // only change the row loads and the replay's reloads; these instantiations also count their exact replays
 // (P.replay_count) and zero the next call's counter slot, as the int32 encode kernels do.
 template <int D, int PX = 1, int EDGE = 0, int QT = 0>
@@ -418,7 +418,7 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
 // is transformed, so the mark -> window -> parse chain of global round trips is paid once per wave, not
 // once per group.  Carried across the transform: the NWP words, the lane's mark relative to the window
 // (32 bits) and two wave-uniform 64-bit values (scalar registers).  NG = 1: no look-ahead.
-// EDGE = 1 (dct3d_eg_frames.hip): frames of any size, P as launch_decode_edge's (blk_store off): the stores
+// EDGE = 1 (dct3d_eg_frames.hip): frames of any size, P as launch_decode's for it (blk_store off): the stores
 // are cropped, nothing else differs.
 template <int D, int NG, int EDGE = 0, int QT = 0>
 __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArgs<QT>::type P, EgDecParams E) {

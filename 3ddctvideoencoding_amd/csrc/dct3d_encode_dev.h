@@ -1285,4 +1285,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
 }
 
+// (host) the int32 encode kernel of a variant: one name for the four kernels
+template <int D, int PX, int EDGE, int QT>
+constexpr auto encode_kernel_of() -> void (*)(EncodeParams) {
+    if constexpr (D == 8 && PX == 1) return encode16_kernel<0, EDGE, QT>;
+    else if constexpr (D == 8) return encode16_rgb_kernel<EDGE, QT>;
+    else if constexpr (PX == 1) return encode_kernel<EDGE, QT>;
+    else return encode_rgb_kernel<EDGE, QT>;
+}
+
 }  // namespace dct3d

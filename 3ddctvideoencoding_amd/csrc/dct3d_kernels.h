@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "dct3d_geom.h"
+#include "dct3d_variant.h"
 
 namespace dct3d {
 
@@ -15,6 +16,9 @@ constexpr int kGM4Dev = 48;        // == kMaxGroups4 in dct3d_plan.h (8x8x4 in-w
 // to word blockIdx & (kCountSpread - 1)): 10^5 same-address atomics per call serialise at the L2
 // (~12 ns each, longer than the whole kernel); the host sums the words.
 constexpr int kCountSpread = 512;
+
+// a launcher's verdict: 0 once its launches were accepted
+inline int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 // (FastDiv and the host side of the address fields below -- n_cubes .. stack_stride, blk_store: dct3d_geom.h)
 struct EncodeParams {
@@ -95,14 +99,6 @@ struct Fwd64Params {
 
 int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n_cubes, hipStream_t st);
 int launch_fwd64_raster(int D, const Fwd64Params& P, hipStream_t st);
-int launch_encode(int D, const EncodeParams& P, hipStream_t st);
-// Packed RGB24 (uint8 [frame][y][x][3]) <-> int32 cubes laid out [stack][channel][cube]: n_cubes counts the
-// RGB cubes (a third of the int32 side's), plane and stack_stride are in bytes (3 per pixel), width in pixels
-int launch_encode_rgb(int D, const EncodeParams& P, hipStream_t st);
-// Frames whose width or height is no multiple of 8 (px = 1 grey, 3 packed RGB24): the same kernels with the
-// edge padding (encode) and the crop (decode) in their addressing; P describes the unpadded frames (width,
-// height, plane, stack_stride) and the padded raster's cubes (nbx, cubes_per_stack, n_cubes)
-int launch_encode_edge(int D, int px, const EncodeParams& P, hipStream_t st);
 struct EgParams {
     const int32_t* q;          // cube-major quantised values
     uint64_t n_cubes;
@@ -237,27 +233,27 @@ __device__ __forceinline__ uint64_t mark_serial(const uint16_t* mark, const uint
     return gb + off;
 }
 
-int launch_decode(int D, const DecodeParams& P, hipStream_t st);
-int launch_decode_rgb(int D, const DecodeParams& P, hipStream_t st);
-int launch_decode_edge(int D, int px, const DecodeParams& P, hipStream_t st);
-int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
-// The int32 raster kernels with the quantiser's table (dct3d_quant.hip): px = 1 grey | 3 packed RGB24, edge =
-// 0 | 1 (frames of any size); P as the launcher's of the same geometry above, P.tab64 with the steps' tail
-int launch_encode_qt(int D, int px, int edge, const EncodeParams& P, hipStream_t st);
-int launch_decode_qt(int D, int px, int edge, const DecodeParamsQ& P, hipStream_t st);
-// Frames of any size and packed RGB24 through the fused Exp-Golomb kernels (dct3d_eg_frames.hip).  Encode: px =
-// 1 grey (edge = 1 only), 3 packed RGB24 (edge = 0 or 1), channel E.ch of the RGB cubes per launch; P as
-// launch_encode_rgb's / launch_encode_edge's.  Decode: grey with the crop (P as launch_decode_edge's, 8 groups
-// per wave), or packed RGB24 from three streams (edge = 0: P as launch_decode_rgb's).  P.cube_base as
-// launch_decode_eg's.
-int launch_encode_eg_frames(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
-int launch_decode_eg_edge(int D, const DecodeParams& P, const EgDecParams& E, hipStream_t st);
-int launch_decode_eg_rgb(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, hipStream_t st);
-// The fused Exp-Golomb kernels with the quantiser's table (dct3d_quant_eg.hip), every geometry: px, edge and P
-// as launch_encode_eg / launch_encode_eg_frames and launch_decode_eg (8 groups per wave) / _eg_edge / _eg_rgb
-int launch_encode_eg_qt(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
-int launch_decode_eg_qt(int D, int edge, const DecodeParamsQ& P, const EgDecParams& E, hipStream_t st);
-int launch_decode_eg_rgb_qt(int D, int edge, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
+// The kernels of a variant (dct3d_variant.h), one launcher per family; the router (dct3d_router.cpp) hands the
+// call to the unit that holds the variant, launch_*_in<Unit> (dct3d_launch.h, instantiated by that unit).
+// Encode, P: the unpadded frames (width, height, plane and stack_stride, in bytes) and the padded raster's cubes
+// (nbx, cubes_per_stack, n_cubes; packed RGB24: n_cubes counts the RGB cubes, a third of the int32 side's, laid
+// out [stack][channel][cube]); qt: P.tab64 with the steps' tail.  Decode, P: the same, P.steps for qt (the
+// other kernels take its DecodeParams part).
+int launch_encode(const Variant& v, const EncodeParams& P, hipStream_t st);
+int launch_decode(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
+// The fused Exp-Golomb kernels: channel E.ch of the RGB cubes per encode launch; P.cube_base: the decode's first
+// cube (a chunk of whole stacks).  Grey stream decode: groups_per_wave = 1, 2, 4 or 8 groups of CPW cubes per
+// wave, the next one's loads ahead, in the variant of grey multiples of 8 and the reference steps (every other
+// value, every other variant: 8).  Packed RGB24 stream decode: from three streams.
+int launch_encode_eg(const Variant& v, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, hipStream_t st);
+int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
+template <class Unit> int launch_encode_in(const Variant& v, const EncodeParams& P, hipStream_t st);
+template <class Unit> int launch_decode_in(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
+template <class Unit> int launch_encode_eg_in(const Variant& v, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
+template <class Unit>
+int launch_decode_eg_in(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, hipStream_t st);
+template <class Unit> int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =
 // segments, P.bits = seg_bits)
@@ -278,8 +274,5 @@ int launch_eg_dscan(const EgDecParams& P, const EgParams& S, hipStream_t st);
 uint64_t front_blocks(uint64_t n_chunks);
 int launch_eg_front(const EgDecParams& P, uint64_t* desc, int force_fail, hipStream_t st);
 int launch_eg_emit(int D, const EgDecParams& P, hipStream_t st);
-// fused stream -> raster decode: values parsed at the marks straight into the decode's LDS staging
-// groups_per_wave: 1, 2, 4 or 8 (other values: 8) groups of CPW cubes per wave, the next one's loads ahead
-int launch_decode_eg(int D, const DecodeParams& P, const EgDecParams& E, int groups_per_wave, hipStream_t st);
 
 }  // namespace dct3d

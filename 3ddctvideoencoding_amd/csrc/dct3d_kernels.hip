@@ -19,7 +19,7 @@
 // L1 -> inverse passes Y, X, Z (the last one adds the fixed-point offset) -> certificate on the low
 // words, 16-bit floors saturated to bytes -> raster stores; uncertified cubes are replayed whole in the
 // wave (exact Java InverseDCT fold) before the stores.
-#include "dct3d_eg_fused_dev.h"
+#include "dct3d_launch.h"
 
 namespace dct3d {
 
@@ -145,14 +145,10 @@ __global__ __launch_bounds__(kBlock, 4) void cube_f32_kernel(const float* __rest
 int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n_cubes, hipStream_t st) {
     const uint32_t blocks = dec_grid(D, n_cubes);
     if (!blocks) return 0;
-    if (D == 8) {
-        if (inverse) hipLaunchKernelGGL((cube_f32_kernel<8, true>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
-        else hipLaunchKernelGGL((cube_f32_kernel<8, false>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
-    } else {
-        if (inverse) hipLaunchKernelGGL((cube_f32_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
-        else hipLaunchKernelGGL((cube_f32_kernel<4, false>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return with_depth(D, [&](auto d) {
+        if (inverse) hipLaunchKernelGGL((cube_f32_kernel<d, true>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
+        else hipLaunchKernelGGL((cube_f32_kernel<d, false>), dim3(blocks), dim3(kBlock), 0, st, in, out, n_cubes);
+    }) ? launched() : -1;
 }
 
 
@@ -163,61 +159,11 @@ int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n
 // 8x8x4 = encode_kernel (8 lanes per cube, in-wave exact replay, one launch).  Both store the int32
 // output non-temporally.  The variants that lost (8 lanes per cube at 8x8x8, plain stores, NT loads,
 // LDS-padded occupancy) are recorded in profiles/r01/encode_variant_sweep.txt, not built.
-namespace {
-template <int D>
-void launch_enc_eg_t(const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
-    hipLaunchKernelGGL((encode_eg_kernel<D>), dim3(grid_blocks(P.n_cubes, kCubesPerWave)), dim3(kBlock), 0, st, P, E);
-}
-}  // namespace
-
-int launch_encode(int D, const EncodeParams& P, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    const dim3 grid(enc_grid(D, P));
-    if (D == 8) hipLaunchKernelGGL((encode16_kernel<>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((encode_kernel<>), grid, dim3(kBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_encode_eg(int D, const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if (D == 8) launch_enc_eg_t<8>(P, E, st);
-    else launch_enc_eg_t<4>(P, E, st);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// One butterfly per pin group (pin groups 1 / 2 / 4 / none measured within 1 %; non-temporal dword
+// Decode: one butterfly per pin group (pin groups 1 / 2 / 4 / none measured within 1 %; non-temporal dword
 // output stores were 26 % slower: profiles/r01/decode_variant_sweep.txt).
-int launch_decode(int D, const DecodeParams& P, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    const dim3 grid(dec_grid(D, P.n_cubes));
-    if (D == 8) hipLaunchKernelGGL((decode_kernel<8>), grid, dim3(kBlock), 0, st, P);
-    else hipLaunchKernelGGL((decode_kernel<4>), grid, dim3(kBlock), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-namespace {
-template <int D, int NG>
-void launch_dec_eg_t(const DecodeParams& P, const EgDecParams& E, hipStream_t st) {
-    const dim3 grid(dec_grid(D, P.n_cubes - P.cube_base, NG));  // cube_base: a multiple of the cubes per wave
-    hipLaunchKernelGGL((decode_eg_kernel<D, NG>), grid, dim3(kBlock), 0, st, P, E);
-}
-template <int D>
-void launch_dec_eg_d(const DecodeParams& P, const EgDecParams& E, int ng, hipStream_t st) {
-    switch (ng) {
-        case 1: launch_dec_eg_t<D, 1>(P, E, st); break;
-        case 2: launch_dec_eg_t<D, 2>(P, E, st); break;
-        case 4: launch_dec_eg_t<D, 4>(P, E, st); break;
-        default: launch_dec_eg_t<D, 8>(P, E, st); break;
-    }
-}
-}  // namespace
-
-int launch_decode_eg(int D, const DecodeParams& P, const EgDecParams& E, int groups_per_wave, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if (D == 8) launch_dec_eg_d<8>(P, E, groups_per_wave, st);
-    else launch_dec_eg_d<4>(P, E, groups_per_wave, st);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
+template int launch_encode_in<RasterPlain>(const Variant&, const EncodeParams&, hipStream_t);
+template int launch_decode_in<RasterPlain>(const Variant&, const DecodeParamsQ&, hipStream_t);
+template int launch_encode_eg_in<StreamPlain>(const Variant&, const EncodeParams&, const EgFusedParams&, hipStream_t);
+template int launch_decode_eg_in<StreamPlain>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, hipStream_t);
 
 }  // namespace dct3d

@@ -117,9 +117,8 @@ __global__ __launch_bounds__(256) void fwd64_raster_kernel(Fwd64Params P) {
 int launch_fwd64_raster(int D, const Fwd64Params& P, hipStream_t st) {
     const uint32_t blocks = (P.n_cubes + 31) / 32;
     if (!blocks) return 0;
-    if (D == 8) hipLaunchKernelGGL(fwd64_raster_kernel<8>, dim3(blocks), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(fwd64_raster_kernel<4>, dim3(blocks), dim3(256), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const auto fwd = [&](auto d) { hipLaunchKernelGGL(fwd64_raster_kernel<d>, dim3(blocks), dim3(256), 0, st, P); };
+    return with_depth(D, fwd) ? launched() : -1;
 }
 
 }  // namespace dct3d

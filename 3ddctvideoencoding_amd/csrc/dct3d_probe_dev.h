@@ -3,7 +3,6 @@
 // division by a table's step, the lanes' places in the two encode geometries, the sum kernels' block
 // reduction and the dispatch from the runtime's (D, px, edge) to a kernel instance.
 #pragma once
-#include <type_traits>
 #include "dct3d_encode_dev.h"
 #include "dct3d_rate.h"
 
@@ -171,18 +170,8 @@ __device__ __forceinline__ uint64_t probe_block_sum(uint64_t s) {
 template <class F>
 int probe_dispatch(int D, int px, int edge, const EncodeParams& P, const RateParams& R, F&& f) {
     if (P.n_cubes == 0) return 0;
-    if ((px != 1 && px != 3) || R.n_tables < 1 || R.n_tables > kRateTables) return -1;
-    const auto with_d = [&](auto d) {
-        const auto with_px = [&](auto p) {
-            if (edge) f(d, p, std::integral_constant<int, 1>{});
-            else f(d, p, std::integral_constant<int, 0>{});
-        };
-        if (px == 1) with_px(std::integral_constant<int, 1>{});
-        else with_px(std::integral_constant<int, 3>{});
-    };
-    if (D == 8) with_d(std::integral_constant<int, 8>{});
-    else with_d(std::integral_constant<int, 4>{});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (R.n_tables < 1 || R.n_tables > kRateTables) return -1;
+    return with_variant(D, px, edge, f) ? launched() : -1;
 }
 
 }  // namespace dct3d

@@ -7,43 +7,11 @@
 // from the table where the product kernels compute sb + 5 j.  A translation unit of its own: the other
 // kernels' code objects do not change with it, and a context whose table is the reference's never comes
 // here (the runtime launches the existing kernels for it).
-#include "dct3d_encode_dev.h"
-#include "dct3d_decode_dev.h"
+#include "dct3d_launch.h"
 
 namespace dct3d {
 
-int launch_encode_qt(int D, int px, int edge, const EncodeParams& P, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if (px != 1 && px != 3) return -1;
-    const dim3 grid(enc_grid(D, P)), blk(kBlock);
-    switch ((D == 8 ? 4 : 0) + (px == 3 ? 2 : 0) + (edge ? 1 : 0)) {
-        case 7: hipLaunchKernelGGL((encode16_rgb_kernel<1, 1>), grid, blk, 0, st, P); break;
-        case 6: hipLaunchKernelGGL((encode16_rgb_kernel<0, 1>), grid, blk, 0, st, P); break;
-        case 5: hipLaunchKernelGGL((encode16_kernel<0, 1, 1>), grid, blk, 0, st, P); break;
-        case 4: hipLaunchKernelGGL((encode16_kernel<0, 0, 1>), grid, blk, 0, st, P); break;
-        case 3: hipLaunchKernelGGL((encode_rgb_kernel<1, 1>), grid, blk, 0, st, P); break;
-        case 2: hipLaunchKernelGGL((encode_rgb_kernel<0, 1>), grid, blk, 0, st, P); break;
-        case 1: hipLaunchKernelGGL((encode_kernel<1, 1>), grid, blk, 0, st, P); break;
-        default: hipLaunchKernelGGL((encode_kernel<0, 1>), grid, blk, 0, st, P); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_decode_qt(int D, int px, int edge, const DecodeParamsQ& P, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if ((px != 1 && px != 3) || !P.steps) return -1;
-    const dim3 grid(dec_grid(D, P.n_cubes)), blk(kBlock);
-    switch ((D == 8 ? 4 : 0) + (px == 3 ? 2 : 0) + (edge ? 1 : 0)) {
-        case 7: hipLaunchKernelGGL((decode_rgb_kernel<8, 1, 1>), grid, blk, 0, st, P); break;
-        case 6: hipLaunchKernelGGL((decode_rgb_kernel<8, 0, 1>), grid, blk, 0, st, P); break;
-        case 5: hipLaunchKernelGGL((decode_kernel<8, 1, 1>), grid, blk, 0, st, P); break;
-        case 4: hipLaunchKernelGGL((decode_kernel<8, 0, 1>), grid, blk, 0, st, P); break;
-        case 3: hipLaunchKernelGGL((decode_rgb_kernel<4, 1, 1>), grid, blk, 0, st, P); break;
-        case 2: hipLaunchKernelGGL((decode_rgb_kernel<4, 0, 1>), grid, blk, 0, st, P); break;
-        case 1: hipLaunchKernelGGL((decode_kernel<4, 1, 1>), grid, blk, 0, st, P); break;
-        default: hipLaunchKernelGGL((decode_kernel<4, 0, 1>), grid, blk, 0, st, P); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+template int launch_encode_in<RasterQuant>(const Variant&, const EncodeParams&, hipStream_t);
+template int launch_decode_in<RasterQuant>(const Variant&, const DecodeParamsQ&, hipStream_t);
 
 }  // namespace dct3d

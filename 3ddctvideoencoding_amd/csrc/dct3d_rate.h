@@ -8,7 +8,7 @@ namespace dct3d {
 constexpr int kRateTables = 8;   // quantiser tables priced by one launch (their rows live in the block's LDS)
 constexpr int kRateTabN = 24;    // rows per table, s = kx + ky + kz < 22 (== kTabN, dct3d_encode_dev.h)
 
-// rate_kernel prices channel `ch` of the cubes of EncodeParams P (as launch_encode_eg_frames': raster and
+// rate_kernel prices channel `ch` of the cubes of EncodeParams P (as launch_encode_eg's: raster and
 // address fields, the fold tables ngroups / coef / group_of, coef_dc, the counter slots) under n_tables tables.
 struct RateParams {
     const float4* tabs;     // [n_tables][kRateTabN] {fp32(1 / step_s), G_s, 0.5 - E_s, step_s}

@@ -159,7 +159,7 @@ int launch_rate_sum(const uint16_t* cube_bits, uint32_t run, uint64_t n_runs, ui
     if (n_runs == 0) return 0;
     if (n_runs > 0x7FFFFFFFull) return -1;
     hipLaunchKernelGGL(rate_sum_kernel, dim3((uint32_t)n_runs), dim3(kBlock), 0, st, cube_bits, run, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
 }
 
 }  // namespace dct3d

@@ -285,8 +285,11 @@ static int upload_quant_tables(dct3d_ctx* c) {
     for (int s = 0; s < kMaxS; s++) t64[kQtStepOff + s] = s < (int)p.steps.size() ? p.steps[s] : reference_step(s);
     return upload(c->d_tabs64, t64, sizeof(t64));
 }
-// the context's calls run the table kernels (else: the product kernels, the reference steps in their text)
-static bool use_qt(const dct3d_ctx* c) { return !c->plan.reference_quant || c->opt_quant_force; }
+// The kernels' variant for geometry g.  qt: the context's calls run the table kernels (else: the product
+// kernels, the reference steps in their text)
+static Variant variant_of(const dct3d_ctx* c, const Geom& g) {
+    return Variant{c->bd, g.px, g.edge(), !c->plan.reference_quant || c->opt_quant_force};
+}
 static const double* qt_steps(const dct3d_ctx* c) { return (const double*)c->d_tabs64.p + kQtStepOff; }
 
 int dct3d_ctx_set_quant(dct3d_ctx* c, const int32_t* steps, int n) {
@@ -647,18 +650,10 @@ static int encode_dev(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g, uint
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     call_begin(c);
     if (n_cubes == 0) return DCT3D_OK;
-    const int D = c->bd;
     EncodeParams P;
     fill_encode_params(c, P, d_raster, d_q, g, n_cubes);
     hipEvent_t* ev = timer_begin(c);
-    int lrc;
-    if (use_qt(c)) lrc = launch_encode_qt(D, g.px, g.edge() ? 1 : 0, P, c->stream);
-    else switch (2 * g.px + (g.edge() ? 1 : 0)) {
-        case 2: lrc = launch_encode(D, P, c->stream); break;
-        case 6: lrc = launch_encode_rgb(D, P, c->stream); break;
-        default: lrc = launch_encode_edge(D, g.px, P, c->stream);  // (the row loads clamped to the frame)
-    }
-    if (lrc) return DCT3D_EKERNEL;
+    if (launch_encode(variant_of(c, g), P, c->stream)) return DCT3D_EKERNEL;
     timer_end(c, ev);
     count_slot_used(c, (uint64_t)g.px * n_cubes * (uint64_t)c->plan.cs);
     if (d_dct) return forward_f64_raster(c, d_raster, g.w, g.h, n_cubes, d_dct);
@@ -669,19 +664,11 @@ static int decode_dev(dct3d_ctx* c, const int32_t* d_q, const Geom& g, uint64_t 
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     call_begin(c);
     if (n_cubes == 0) return DCT3D_OK;
-    const int D = c->bd;
     DecodeParamsQ P;  // (the product kernels take its DecodeParams part)
     fill_decode_params(c, P, d_q, d_raster, g, n_cubes);
     P.steps = qt_steps(c);
     hipEvent_t* ev = timer_begin(c);
-    int lrc;
-    if (use_qt(c)) lrc = launch_decode_qt(D, g.px, g.edge() ? 1 : 0, P, c->stream);
-    else switch (2 * g.px + (g.edge() ? 1 : 0)) {
-        case 2: lrc = launch_decode(D, P, c->stream); break;
-        case 6: lrc = launch_decode_rgb(D, P, c->stream); break;
-        default: lrc = launch_decode_edge(D, g.px, P, c->stream);  // (the stores cropped to the frame)
-    }
-    if (lrc) return DCT3D_EKERNEL;
+    if (launch_decode(variant_of(c, g), P, c->stream)) return DCT3D_EKERNEL;
     timer_end(c, ev);
     count_slot_used(c, (uint64_t)g.px * n_cubes * (uint64_t)c->plan.cs);
     return DCT3D_OK;
@@ -1026,7 +1013,6 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
                            uint8_t carry_byte, int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
     const bool plain = g.px == 1 && !g.edge();  // dct3d_encode_eg_dev's geometry: its kernel
     int rc;
-    const int D = c->bd;
     const uint64_t n_seg = (n_cubes + 7) / 8, n_chunks = (n_seg + 4095) / 4096;
     // worst case per lane: cs/8 values x 27 bits (|q| <= 255 sqrt(cs) -> codes <= 27 bits)
     const uint32_t seg_cap = (uint32_t)(64 * (((c->plan.cs / 8) * 27 + 31) / 32));
@@ -1072,10 +1058,7 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    if (use_qt(c) ? launch_encode_eg_qt(D, g.px, g.edge() ? 1 : 0, P, E, c->stream)
-        : plain   ? launch_encode_eg(D, P, E, c->stream)
-                  : launch_encode_eg_frames(D, g.px, g.edge() ? 1 : 0, P, E, c->stream))
-        return DCT3D_EKERNEL;
+    if (launch_encode_eg(variant_of(c, g), P, E, c->stream)) return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
     if (ev) (void)hipEventRecord(ev[2], c->stream);
@@ -1350,6 +1333,7 @@ static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n
         R.dec_E = DP.dec_E;
         R.dec_l1_max = DP.dec_l1_max;
     }
+    const Variant v = variant_of(c, g);  // (the probes read tables of their own: no qt)
     hipEvent_t* ev = timer_begin(c);
     rc = DCT3D_OK;
     // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
@@ -1363,8 +1347,7 @@ static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n
                 R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
                 R.cube_sse = cube_sse + (size_t)t0 * stride;
             }
-            if (dist ? launch_distortion(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream)
-                     : launch_rate(c->bd, g.px, g.edge() ? 1 : 0, P, R, c->stream))
+            if (dist ? launch_distortion(v.D, v.px, v.edge, P, R, c->stream) : launch_rate(v.D, v.px, v.edge, P, R, c->stream))
                 rc = DCT3D_EKERNEL;
             else c->slot_used = true;
         }
@@ -1662,7 +1645,7 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
     fill_decode_params(c, P, nullptr, out_stack0 - (size_t)st0 * g.plane() * D, g, (st0 + ns) * cps);
     P.cube_base = (uint32_t)(st0 * cps);
     P.steps = qt_steps(c);
-    const bool qt = use_qt(c);
+    const Variant v = variant_of(c, g);
     hipEvent_t* ev = timer_begin(c);
     int lrc;
     if (g.px == 3) {
@@ -1670,14 +1653,9 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = qt ? launch_decode_eg_rgb_qt(D, g.edge() ? 1 : 0, P, R, c->stream)
-                 : launch_decode_eg_rgb(D, g.edge() ? 1 : 0, P, R, c->stream);
-    } else if (qt) {
-        lrc = launch_decode_eg_qt(D, g.edge() ? 1 : 0, P, E[0], c->stream);
-    } else if (g.edge()) {
-        lrc = launch_decode_eg_edge(D, P, E[0], c->stream);
-    } else {
-        lrc = launch_decode_eg(D, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
+        lrc = launch_decode_eg_rgb(v, P, R, c->stream);
+    } else {  // (the test option's groups per wave: where the variant's unit builds them)
+        lrc = launch_decode_eg(v, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
     }
     if (lrc) return DCT3D_EKERNEL;
     timer_end(c, ev);

@@ -18,7 +18,7 @@ DEV_SRCS  := $(CSRC)/dct3d_kernels.hip $(CSRC)/dct3d_kernels_f.hip $(CSRC)/dct3d
              $(CSRC)/dct3d_edge.hip $(CSRC)/dct3d_eg_frames.hip $(CSRC)/dct3d_quant.hip $(CSRC)/dct3d_quant_eg.hip \
              $(CSRC)/dct3d_rate.hip $(CSRC)/dct3d_distortion.hip
 DIAG_SRCS := $(CSRC)/dct3d_diag.hip
-HOST_SRCS := $(CSRC)/dct3d_plan.cpp $(CSRC)/dct3d_runtime.cpp
+HOST_SRCS := $(CSRC)/dct3d_plan.cpp $(CSRC)/dct3d_runtime.cpp $(CSRC)/dct3d_router.cpp
 HDRS      := $(wildcard $(CSRC)/*.h) include/dct3d.h include/dct3d_diag.h
 CODEC_SRCS := $(wildcard $(CSRC)/host/*.c)
 CODEC_LIB_SRCS := $(filter-out $(CSRC)/host/main.c,$(CODEC_SRCS))

@@ -29,8 +29,10 @@ def functions(tree, unit, tmp):
         if end < 0:  # a data symbol after the last function
             continue
         body = s[m.end():end]
-        # instructions and labels only: no comments, no directives
-        lines = [re.sub(r"\s*;.*$", "", ln).strip() for ln in body.splitlines()]
+        # instructions and labels only: no comments, no directives.  A local label carries the function's place
+        # in its unit's output (.LBB<place>_<block>), which changes with the order of instantiation and says
+        # nothing about the function: the place is dropped, the block numbers stay.
+        lines = [re.sub(r"\.L(BB|JTI)\d+_", r".L\1_", re.sub(r"\s*;.*$", "", ln)).strip() for ln in body.splitlines()]
         fns[m.group(1)] = [ln for ln in lines if ln and not ln.startswith(".") or ln.startswith(".LBB")]
     return fns
 
