@@ -53,6 +53,8 @@ ABI_SYMBOLS = (
     "dct3d_ctx_set_quant", "dct3d_ctx_get_quant", "dct3d_plan_query_quant",
     "dct3d_rate_frames", "dct3d_rate_frames_dev",
     "dct3d_distortion_frames", "dct3d_distortion_frames_dev",
+    "dct3d_encode_eg_frames_vq", "dct3d_encode_eg_frames_vq_dev",
+    "dct3d_decode_eg_frames_vq", "dct3d_decode_eg_frames_vq_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -145,6 +147,11 @@ def lib() -> C.CDLL:
         L.dct3d_rate_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
         L.dct3d_distortion_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
         L.dct3d_distortion_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
+        # (the base stream calls' lists with tables, n_tables, stack_table behind n_stacks)
+        L.dct3d_encode_eg_frames_vq_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.dct3d_encode_eg_frames_vq.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+        L.dct3d_decode_eg_frames_vq_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.dct3d_decode_eg_frames_vq.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -266,6 +273,30 @@ def pick_quality_psnr(sse_per_quality: dict, n_samples, target_db) -> int:
         raise ValueError("no qualities to pick from")
     ok = [q for q, e in sse_per_quality.items() if psnr_db(e, n_samples) >= target_db]
     return int(max(ok)) if ok else int(min(sse_per_quality))
+
+
+def pick_stack_qualities(bits, qualities, target_bits_per_stack) -> list:
+    """pick_quality per stack: bits [T, n_stacks, channels] as rate_frames returns them for the tables of
+    `qualities` (T of them); stack s gets pick_quality of its bits summed over the channels against
+    target_bits_per_stack.  One quality per stack, in stack order; no other rule, nothing assumed monotone."""
+    bits = np.asarray(bits)
+    qualities = [int(q) for q in qualities]
+    if bits.ndim != 3 or bits.shape[0] != len(qualities):
+        raise ValueError("bits must be [len(qualities), n_stacks, channels]")
+    return [pick_quality({q: int(bits[t, s, :].astype(object).sum()) for t, q in enumerate(qualities)}, target_bits_per_stack)
+            for s in range(bits.shape[1])]
+
+
+def pick_stack_qualities_psnr(sse, qualities, n_samples_per_stack, target_db) -> list:
+    """pick_quality_psnr per stack: sse [T, n_stacks, channels] as distortion_frames returns it for the tables of
+    `qualities`; stack s gets pick_quality_psnr of its squared error summed over the channels, over
+    n_samples_per_stack samples (all channels' unpadded samples of one stack)."""
+    sse = np.asarray(sse)
+    qualities = [int(q) for q in qualities]
+    if sse.ndim != 3 or sse.shape[0] != len(qualities):
+        raise ValueError("sse must be [len(qualities), n_stacks, channels]")
+    return [pick_quality_psnr({q: int(sse[t, s, :].astype(object).sum()) for t, q in enumerate(qualities)},
+                              n_samples_per_stack, target_db) for s in range(sse.shape[1])]
 
 
 def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8, steps=None) -> dict:
@@ -695,6 +726,92 @@ class Context:
         rc = lib().dct3d_decode_eg_frames_dev(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _tptr(d_frames), eb)
         if rc != DCT3D_OK:
             e = Dct3dError(rc, "dct3d_decode_eg_frames_dev")
+            e.end_bits = [int(t) for t in eb]
+            raise e
+        return [int(t) for t in eb]
+
+    # ---- the same four calls with a quantiser table per stack (include/dct3d.h) ----
+    def _vq_args(self, tables, stack_table, n_stacks: int, what: str):
+        """(int32 [T, n_steps], T, uint8 [n_stacks]) as the C-ABI takes them; a wrong shape is DCT3D_EINVAL"""
+        if tables is None or stack_table is None:
+            raise Dct3dError(DCT3D_EINVAL, what)
+        tb, T = self._rate_tables(tables)
+        m = np.asarray(stack_table)
+        if m.ndim != 1 or m.size != n_stacks or np.any(m < 0) or np.any(m > 255) or np.any(m != np.floor(m)):
+            raise Dct3dError(DCT3D_EINVAL, what)
+        return tb, T, np.ascontiguousarray(m, np.uint8)
+
+    def encode_eg_frames_vq(self, frames: np.ndarray, tables, stack_table, carry=None) -> list:
+        """encode_eg_frames with stack s of every channel coded under tables[stack_table[s]] (a palette of 1..32
+        tables, one uint8 entry per stack).  The context's quantiser is neither used nor changed."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_encode_eg_frames_vq")
+        carry = list(carry) if carry is not None else [(0, 0)] * channels
+        if len(carry) != channels:
+            raise ValueError("one (carry_byte, carry_bits) per channel")
+        cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
+        cn = (C.c_int * channels)(*[n for _, n in carry])
+        tb = (C.c_uint64 * channels)()
+        _check(lib().dct3d_encode_eg_frames_vq(self._h, _ptr(frames), W, H, channels, n_stacks, _ptr(tq), T,
+                                               _ptr(m), cb, cn, tb),
+               "dct3d_encode_eg_frames_vq")
+        res = []
+        for ch in range(channels):
+            out = np.empty(eg_stream_bytes(tb[ch]), np.uint8)
+            _check(lib().dct3d_eg_fetch_channel(self._h, ch, _ptr(out) if out.size else None, out.size),
+                   "dct3d_eg_fetch_channel")
+            res.append((out.tobytes(), int(tb[ch])))
+        return res
+
+    def decode_eg_frames_vq(self, streams, width: int, height: int, n_stacks: int, tables, stack_table, start_bits=None):
+        """decode_eg_frames under the same palette and map as encode_eg_frames_vq"""
+        channels = len(streams)
+        if channels not in (1, 3):
+            raise Dct3dError(DCT3D_EINVAL, "dct3d_decode_eg_frames_vq")
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_decode_eg_frames_vq")
+        start_bits = list(start_bits) if start_bits is not None else [0] * channels
+        bufs = [np.frombuffer(b, np.uint8) for b in streams]
+        ptrs = (C.c_void_p * channels)(*[_ptr(b) if b.size else None for b in bufs])
+        nb = (C.c_uint64 * channels)(*[b.size for b in bufs])
+        sb = (C.c_int * channels)(*start_bits)
+        eb = (C.c_uint64 * channels)()
+        out = np.empty((n_stacks * self.bd, height, width) + ((3,) if channels == 3 else ()), np.uint8)
+        _check(lib().dct3d_decode_eg_frames_vq(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T, _ptr(m),
+                                               _ptr(out), eb), "dct3d_decode_eg_frames_vq")
+        return out, [int(e) for e in eb]
+
+    def encode_eg_frames_vq_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables, stack_table,
+                                d_outs, out_caps, carry=None) -> list:
+        """encode_eg_frames_dev with a table per stack; errors as there (.total_bits on DCT3D_ENOSPC)"""
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_encode_eg_frames_vq_dev")
+        carry = list(carry) if carry is not None else [(0, 0)] * channels
+        cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
+        cn = (C.c_int * channels)(*[n for _, n in carry])
+        outs = (C.c_void_p * channels)(*[_tptr(t) for t in d_outs])
+        caps = (C.c_uint64 * channels)(*out_caps)
+        tb = (C.c_uint64 * channels)()
+        rc = lib().dct3d_encode_eg_frames_vq_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks, _ptr(tq), T,
+                                                 _ptr(m), cb, cn, outs, caps, tb)
+        if rc != DCT3D_OK:
+            e = Dct3dError(rc, "dct3d_encode_eg_frames_vq_dev")
+            e.total_bits = [int(t) for t in tb]
+            raise e
+        return [int(t) for t in tb]
+
+    def decode_eg_frames_vq_dev(self, d_streams, nbytes, start_bits, width: int, height: int, n_stacks: int, tables,
+                                stack_table, d_frames) -> list:
+        """decode_eg_frames_dev with a table per stack; errors as there (.end_bits of the good streams)"""
+        channels = len(d_streams)
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_decode_eg_frames_vq_dev")
+        ptrs = (C.c_void_p * channels)(*[_tptr(t) for t in d_streams])
+        nb = (C.c_uint64 * channels)(*nbytes)
+        sb = (C.c_uint64 * channels)(*start_bits)
+        eb = (C.c_uint64 * channels)()
+        rc = lib().dct3d_decode_eg_frames_vq_dev(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T,
+                                                 _ptr(m), _tptr(d_frames), eb)
+        if rc != DCT3D_OK:
+            e = Dct3dError(rc, "dct3d_decode_eg_frames_vq_dev")
             e.end_bits = [int(t) for t in eb]
             raise e
         return [int(t) for t in eb]

@@ -23,6 +23,7 @@
 #include "dct3d_plan.h"
 #include "dct3d_distortion.h"
 #include "dct3d_rate.h"
+#include "dct3d_vq.h"
 
 using namespace dct3d;
 
@@ -134,6 +135,20 @@ struct dct3d_ctx {
     // squared errors when the caller keeps none; the rows, bits, sums and pinned copy are the rate probe's
     std::vector<double> dist_steps_host;
     DevBuf d_dist_steps, d_dist_sse;
+    // per-stack quantiser tables (dct3d_*_eg_frames_vq*): the call's fp64 steps, map and palette rows in one
+    // device buffer and its host copy (VqParams' layout), and -- while such a call runs the stream calls' host
+    // bodies -- the kernels' view of them (else nullptr)
+    // (the host copy is pinned: the upload is one asynchronous DMA, no staging and no wait; the palette's rows
+    // and steps are kept from call to call and rebuilt only when the tables change)
+    DevBuf d_vq;
+    uint8_t* vq_host = nullptr;
+    uint8_t* vq_host_dev = nullptr;  // its device-side address (launch_vq_upload reads it)
+    size_t vq_host_bytes = 0;
+    std::vector<int32_t> vq_tables;
+    std::vector<float> vq_rows;
+    std::vector<double> vq_steps;
+    VqParams vq_params = {};
+    const VqParams* vq = nullptr;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -387,9 +402,10 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_egd_exit, &c->d_egd_status, &c->d_egd_in, &c->d_egd_raster, &c->d_egd_mark, &c->d_egd_desc,
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
                       &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums,
-                      &c->d_dist_steps, &c->d_dist_sse})
+                      &c->d_dist_steps, &c->d_dist_sse, &c->d_vq})
         b->release();
     if (c->h_rate) (void)hipHostFree(c->h_rate);
+    if (c->vq_host) (void)hipHostFree(c->vq_host);
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (auto& q : c->ev)
         for (auto& e : q)
@@ -1058,7 +1074,9 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    if (launch_encode_eg(variant_of(c, g), P, E, c->stream)) return DCT3D_EKERNEL;
+    const Variant v = variant_of(c, g);
+    if (c->vq ? launch_encode_eg_vq(v.D, v.px, v.edge, P, E, *c->vq, c->stream) : launch_encode_eg(v, P, E, c->stream))
+        return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
     if (ev) (void)hipEventRecord(ev[2], c->stream);
@@ -1653,7 +1671,9 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = launch_decode_eg_rgb(v, P, R, c->stream);
+        lrc = c->vq ? launch_decode_eg_rgb_vq(v.D, v.edge, P, R, *c->vq, c->stream) : launch_decode_eg_rgb(v, P, R, c->stream);
+    } else if (c->vq) {  // (the map is indexed by the call's stacks: the chunks' cube indices are the call's)
+        lrc = launch_decode_eg_vq(v.D, v.edge, P, E[0], *c->vq, c->stream);
     } else {  // (the test option's groups per wave: where the variant's unit builds them)
         lrc = launch_decode_eg(v, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
     }
@@ -1831,6 +1851,113 @@ int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uin
         return hipStreamSynchronize(c->stream) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
     }
     return decode_eg_run(c, d_bytes, nbytes, sb, g, n_stacks, n_cubes, nullptr, frames, end_bit);
+}
+
+// ---- per-stack quantiser tables in the fused stream calls (dct3d.h) ----
+}  // extern "C"
+// The three extra arguments of a vq call: checked, the palette's rows and steps made from the context's one plan
+// (probe_tables: encoder_tables per entry, no plan rebuild), and steps, map and rows queued to the device on the
+// context stream as one block laid out as VqParams says (launch_vq_upload, from the context's pinned copy).  From here to vq_end the stream calls' host bodies
+// launch the vq kernels.
+static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, const int32_t* tables, int n_tables,
+                    const uint8_t* stack_table) {
+    if (!c || !tables || !stack_table || n_tables < 1 || n_tables > kVqMaxTables) return DCT3D_EINVAL;
+    if (c->opt_eg_two_step) return DCT3D_EINVAL;  // the int32 intermediate has no table per stack (dct3d.h)
+    Geom g;
+    uint64_t n_cubes;
+    if (!make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
+    const int n_steps = (int)c->plan.steps.size();
+    for (int i = 0; i < n_tables * n_steps; i++)
+        if (tables[i] < kMinStep || tables[i] > kMaxStep) return DCT3D_EINVAL;
+    for (int s = 0; s < n_stacks; s++)
+        if (stack_table[s] >= n_tables) return DCT3D_EINVAL;
+    if (n_stacks == 0) return DCT3D_OK;  // (nothing to upload; the base call ends before any launch)
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    static_assert(kVqTabN == kRateTabN && kVqStepN == kDistStepN && kVqMaxTables == DCT3D_RATE_MAX_TABLES, "the probes' layouts");
+    const size_t n_ints = (size_t)n_tables * n_steps;
+    if (c->vq_tables.size() != n_ints || memcmp(c->vq_tables.data(), tables, n_ints * sizeof(int32_t)) != 0) {
+        probe_tables(c, tables, n_tables, true);  // (the probes' host vectors: copied out, a probe call rewrites them)
+        c->vq_rows = c->rate_tabs_host;
+        c->vq_steps = c->dist_steps_host;
+        c->vq_tables.assign(tables, tables + n_ints);
+    }
+    const size_t tab_bytes = c->vq_rows.size() * sizeof(float), step_bytes = c->vq_steps.size() * sizeof(double);
+    const size_t map_off = kVqStepsBytes + sizeof(FastDiv);
+    const size_t tab_off = (map_off + (size_t)n_stacks + 15) & ~(size_t)15;  // the rows: 16-byte aligned
+    const size_t blob_bytes = tab_off + tab_bytes;
+    int rc;
+    if (c->vq_host_bytes < blob_bytes) {
+        // (a call that returned has started its last kernel: the copy out of the old block is over)
+        if (c->vq_host) (void)hipHostFree(c->vq_host);
+        c->vq_host = nullptr;
+        c->vq_host_bytes = 0;
+        if (hipHostMalloc((void**)&c->vq_host, blob_bytes + 4096, hipHostMallocDefault) != hipSuccess) {
+            c->vq_host = nullptr;
+            return DCT3D_ENOMEM;
+        }
+        if (hipHostGetDevicePointer((void**)&c->vq_host_dev, c->vq_host, 0) != hipSuccess) {
+            (void)hipHostFree(c->vq_host);
+            c->vq_host = nullptr;
+            return DCT3D_EDEVICE;
+        }
+        c->vq_host_bytes = blob_bytes + 4096;
+    }
+    uint8_t* const blob = c->vq_host;
+    memcpy(blob, c->vq_steps.data(), step_bytes);
+    const FastDiv div = fast_div((uint32_t)g.cps());
+    memcpy(blob + kVqStepsBytes, &div, sizeof(div));
+    memcpy(blob + map_off, stack_table, (size_t)n_stacks);
+    memcpy(blob + tab_off, c->vq_rows.data(), tab_bytes);
+    const size_t n16 = (blob_bytes + 15) / 16;  // (the pinned block has 4 KiB to spare behind blob_bytes)
+    if ((rc = c->d_vq.grow(n16 * 16))) return rc;
+    char* const d = (char*)c->d_vq.p;
+    if (launch_vq_upload(c->vq_host_dev, d, (uint32_t)n16, c->stream)) return DCT3D_EKERNEL;
+    c->vq_params = VqParams{(const float4*)(d + tab_off), (const double*)d, vq_map_behind((const double*)d)};
+    c->vq = &c->vq_params;
+    return DCT3D_OK;
+}
+// the call is over.  A call that ended before its kernels ran (an argument the base call refuses, a stream with
+// no data, a failed launch) may leave the upload queued: it reads the context's pinned copy, which the next call
+// rewrites, so the stream is waited for
+static int vq_end(dct3d_ctx* c, int rc) {
+    if (c->vq && rc != DCT3D_OK) (void)stream_wait(c);
+    c->vq = nullptr;
+    return rc;
+}
+extern "C" {
+
+int dct3d_encode_eg_frames_vq_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                                  const int32_t* tables, int n_tables, const uint8_t* stack_table,
+                                  const uint8_t carry_byte[], const int carry_bits[], uint8_t* const d_out[],
+                                  const uint64_t out_cap[], uint64_t total_bits[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, stack_table);
+    if (rc) return rc;
+    return vq_end(c, dct3d_encode_eg_frames_dev(c, d_frames, w, h, channels, n_stacks, carry_byte, carry_bits, d_out, out_cap, total_bits));
+}
+
+int dct3d_encode_eg_frames_vq(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                              const int32_t* tables, int n_tables, const uint8_t* stack_table,
+                              const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, stack_table);
+    if (rc) return rc;
+    return vq_end(c, dct3d_encode_eg_frames(c, frames, w, h, channels, n_stacks, carry_byte, carry_bits, total_bits));
+}
+
+int dct3d_decode_eg_frames_vq_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], const uint64_t nbytes[],
+                                  const uint64_t start_bit[], int w, int h, int channels, int n_stacks,
+                                  const int32_t* tables, int n_tables, const uint8_t* stack_table, uint8_t* d_frames,
+                                  uint64_t end_bit[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, stack_table);
+    if (rc) return rc;
+    return vq_end(c, dct3d_decode_eg_frames_dev(c, d_bytes, nbytes, start_bit, w, h, channels, n_stacks, d_frames, end_bit));
+}
+
+int dct3d_decode_eg_frames_vq(dct3d_ctx* c, const uint8_t* const bytes[], const uint64_t nbytes[], const int start_bit[],
+                              int w, int h, int channels, int n_stacks, const int32_t* tables, int n_tables,
+                              const uint8_t* stack_table, uint8_t* frames, uint64_t end_bit[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, stack_table);
+    if (rc) return rc;
+    return vq_end(c, dct3d_decode_eg_frames(c, bytes, nbytes, start_bit, w, h, channels, n_stacks, frames, end_bit));
 }
 
 }  // extern "C"

@@ -1,0 +1,44 @@
+// dct3d_vq.h -- per-stack quantiser tables in the fused stream calls (dct3d_encode_eg_frames_vq* /
+// dct3d_decode_eg_frames_vq*): the kernels' parameters and launchers (dct3d_vq_enc.hip,
+// dct3d_vq_dec.hip), shared with the C-ABI runtime.  A family of its own beside the variant's qt axis: the
+// kernels are routed by depth, pixel format and edge alone.
+#pragma once
+#include "dct3d_kernels.h"
+
+namespace dct3d {
+
+constexpr int kVqMaxTables = 32;  // == DCT3D_RATE_MAX_TABLES: the palette's size
+constexpr int kVqTabN = 24;       // rows per table (== kTabN, dct3d_encode_dev.h)
+constexpr int kVqStepN = 32;      // fp64 steps per table (the decode kernels' layout, as distortion_kernel's)
+
+// The palette and the map of one call.  Cube g (global index: the encode's from 0, the decode's from
+// P.cube_base on) lies in stack g / cubes_per_stack and is coded with table map[that stack].
+// In device memory the steps are a block of kVqMaxTables tables whatever n_tables is, followed by the FastDiv of
+// cubes_per_stack and then the map itself (vq_div_behind, vq_map_behind): the decode's rare exact replay finds
+// all three from `steps` alone, so its reload functor is no larger than the QT = 1 kernels' (one more member
+// and it no longer travels in registers into the replay's out-of-line body: the kernel would take scratch).
+struct VqParams {
+    const float4* tabs;   // encode: [n_tables][kVqTabN] {fp32(1 / step_s), G_s, 0.5 - E_s, step_s}
+    const double* steps;  // decode: [kVqMaxTables][kVqStepN] step_s (the first n_tables filled)
+    const uint8_t* map;   // [n_stacks] table of each stack, < n_tables; == vq_map_behind(steps)
+};
+constexpr size_t kVqStepsBytes = (size_t)kVqMaxTables * kVqStepN * sizeof(double);
+__host__ __device__ inline const FastDiv* vq_div_behind(const double* steps) {
+    return (const FastDiv*)((const char*)steps + kVqStepsBytes);
+}
+__host__ __device__ inline const uint8_t* vq_map_behind(const double* steps) {
+    return (const uint8_t*)steps + kVqStepsBytes + sizeof(FastDiv);
+}
+
+// px = 1 grey | 3 packed RGB24, edge = 0 | 1 (frames of any size).  Encode: channel E.ch per launch, as
+// launch_encode_eg.  Decode: grey from one stream (8 groups per wave), packed RGB24 from three.
+int launch_encode_eg_vq(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st);
+int launch_decode_eg_vq(int D, int edge, const DecodeParams& P, const EgDecParams& E, const VqParams& V, hipStream_t st);
+int launch_decode_eg_rgb_vq(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st);
+// A call's block (steps, FastDiv, map, rows: some KiB) from the context's pinned host copy -- src, its device-side
+// address -- to device memory, as a kernel on the call's stream: a copy-engine transfer in front of the first
+// kernel cost the call a hand-over between two queues, longer than the transfer itself.
+// n16: 16-byte words; both buffers hold that many.
+int launch_vq_upload(const void* src, void* dst, uint32_t n16, hipStream_t st);
+
+}  // namespace dct3d

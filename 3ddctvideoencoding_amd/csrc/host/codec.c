@@ -230,19 +230,137 @@ static const int kRateLadder[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 4
 static double psnr_of(uint64_t sse, double n_samples) {
     return sse ? 10.0 * log10(255.0 * 255.0 * n_samples / (double)sse) : INFINITY;
 }
-static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
-                           int channels, double target, int by_psnr) {
-    const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
-    const size_t stack_bytes = (size_t)channels * width * height * depth;
-    int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
-    uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N];
-    for (int i = 0; i < RATE_LADDER_N; i++) {
-        tot[i] = err[i] = 0;
+/* the ladder's tables, [RATE_LADDER_N][depth + 14]: step[s] = max(1, q s) clipped to 255, as q=<n> */
+static void ladder_tables(int depth, int32_t *tabs) {
+    const int n = depth + 14;
+    for (int i = 0; i < RATE_LADDER_N; i++)
         for (int s = 0; s < n; s++) {
             const int v = kRateLadder[i] * s;
             tabs[i * n + s] = v < 1 ? 1 : v > 255 ? 255 : v;
         }
+}
+/* the two rules over one ladder of sums (a file's, or a stack's): the smallest quality whose bits fit, the
+ * largest when none does; the largest quality whose PSNR reaches the target, the smallest when none does */
+static int pick_by_rate(const uint64_t *tot, double target_bits) {
+    int pick = RATE_LADDER_N - 1; /* none fits: the largest quality (the ladder ascends) */
+    for (int i = RATE_LADDER_N - 1; i >= 0; i--)
+        if ((double)tot[i] <= target_bits) pick = i; /* the smallest that fits, whatever the order of the sizes */
+    return pick;
+}
+static int pick_by_psnr(const uint64_t *err, double n_samples, double target_db) {
+    int pick = 0; /* none reaches the target: the smallest quality (the ladder ascends) */
+    for (int i = 0; i < RATE_LADDER_N; i++)
+        if (psnr_of(err[i], n_samples) >= target_db) pick = i; /* the largest that reaches it, whatever the order */
+    return pick;
+}
+
+/* ---- the per-stack quality map (codec.h) ---------------------------------------------------------- */
+static char g_qmap_text[4096]; /* codec_set_qmap's text; "": none */
+
+int codec_set_qmap(const char *text) {
+    if (text && strlen(text) >= sizeof(g_qmap_text)) return 1;
+    if (text && text[0] && g_quant_text[0]) return 1; /* a quantiser is set */
+    snprintf(g_qmap_text, sizeof(g_qmap_text), "%s", text ? text : "");
+    return 0;
+}
+
+static int ladder_index(long q) {
+    for (int i = 0; i < RATE_LADDER_N; i++)
+        if (kRateLadder[i] == q) return i;
+    return -1;
+}
+
+int codec_parse_qmap(const char *path, int n_stacks, int *qualities) {
+    if (!path || !path[0] || n_stacks <= 0 || !qualities) return 1;
+    FILE *f = fopen(path, "r");
+    if (!f) return 1;
+    int *q = (int *)malloc(sizeof(int) * (size_t)n_stacks);
+    int n = 0, bad = q == NULL;
+    char line[64];
+    while (!bad && fgets(line, sizeof(line), f)) {
+        size_t len = strlen(line);
+        if (len && line[len - 1] == '\n') line[--len] = '\0';
+        if (len && line[len - 1] == '\r') line[--len] = '\0';
+        char *end = NULL;
+        const long v = (line[0] >= '0' && line[0] <= '9') ? strtol(line, &end, 10) : -1;
+        if (v < 0 || *end != '\0' || ladder_index(v) < 0 || n >= n_stacks) bad = 1; /* (n >= n_stacks: a line too many) */
+        else q[n++] = (int)v;
     }
+    fclose(f);
+    if (!bad && n != n_stacks) bad = 1;
+    if (!bad) memcpy(qualities, q, sizeof(int) * (size_t)n_stacks);
+    free(q);
+    return bad;
+}
+
+/* The map of a call: codec_set_qmap's text, else DCT3D_CODEC_QMAP.  *path = NULL: none given.  1 after printing when
+ * the text is no "qmap=<path>", a quantiser is given too, or the call runs the host Exp-Golomb path. */
+static int call_qmap(const char **path) {
+    const char *text = g_qmap_text[0] ? g_qmap_text : getenv("DCT3D_CODEC_QMAP");
+    *path = NULL;
+    if (!text || !text[0]) return 0;
+    if (strncmp(text, "qmap=", 5) || !text[5]) {
+        printf("Invalid quality map '%s': qmap=<path>\n", text);
+        return 1;
+    }
+    const char *qt = sel_text(SEL_QUANT);
+    if (qt && qt[0]) {
+        printf("A quantiser ('%s') and a quality map ('%s') exclude each other\n", qt, text);
+        return 1;
+    }
+    const char *he = getenv("DCT3D_CODEC_HOST_EG");
+    if (he && he[0] == '1') {
+        printf("qmap= needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
+    *path = text + 5;
+    return 0;
+}
+/* the commands that take no map: 1 after printing when one is given */
+static int reject_qmap(const char *what) {
+    const char *text = g_qmap_text[0] ? g_qmap_text : getenv("DCT3D_CODEC_QMAP");
+    if (!text || !text[0]) return 0;
+    printf("qmap= applies to single-device encodes and decodes only (%s)\n", what);
+    return 1;
+}
+/* reads the call's map into ladder indices, one per stack: 1 after printing on an error */
+static int read_qmap(const char *path, int n_stacks, uint8_t *index) {
+    int *q = (int *)malloc(sizeof(int) * (size_t)n_stacks);
+    if (!q || codec_parse_qmap(path, n_stacks, q)) {
+        printf("Invalid quality map file '%s': %d lines, one per stack, each a quality of the ladder\n", path, n_stacks);
+        free(q);
+        return 1;
+    }
+    for (int s = 0; s < n_stacks; s++) index[s] = (uint8_t)ladder_index(q[s]);
+    free(q);
+    return 0;
+}
+static int write_qmap(const char *path, int n_stacks, const uint8_t *index) {
+    FILE *f = fopen(path, "w");
+    if (!f) {
+        printf("Cannot open output file %s\n", path);
+        return 1;
+    }
+    for (int s = 0; s < n_stacks; s++) fprintf(f, "%d\n", kRateLadder[index[s]]);
+    if (fflush(f) || fclose(f)) {
+        printf("Error writing the quality map %s\n", path);
+        return 1;
+    }
+    return 0;
+}
+
+/* stack_pick (with a quality map): the rules per stack instead -- stack s's bits and squared error summed over the
+ * channels, the rate target's budget that of `depth` frames, the PSNR over the stack's unpadded samples of all
+ * channels (the zero-filled frames of a short last stack count); stack_pick[s] = the ladder index.  Prints
+ * "qmap: stacks=<n> bits=<total>" and leaves the context's quantiser alone. */
+static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
+                           int channels, double target, int by_psnr, uint8_t *stack_pick) {
+    const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
+    const size_t stack_bytes = (size_t)channels * width * height * depth;
+    int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
+    uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N], map_bits = 0;
+    ladder_tables(depth, tabs);
+    for (int i = 0; i < RATE_LADDER_N; i++) tot[i] = err[i] = 0;
     const size_t n_sums = (size_t)RATE_LADDER_N * batch * channels;
     uint64_t *bits = (uint64_t *)malloc(sizeof(uint64_t) * n_sums * 2), *sse = bits ? bits + n_sums : NULL;
     if (!bits) {
@@ -268,27 +386,40 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
                 tot[i] += bits[(size_t)i * nb * channels + k];
                 if (by_psnr) err[i] += sse[(size_t)i * nb * channels + k];
             }
+        for (int s = 0; stack_pick && s < nb; s++) { /* the same rules on this stack's sums */
+            uint64_t sb[RATE_LADDER_N], se[RATE_LADDER_N];
+            for (int i = 0; i < RATE_LADDER_N; i++) {
+                sb[i] = se[i] = 0;
+                for (int ch = 0; ch < channels; ch++) {
+                    sb[i] += bits[((size_t)i * nb + s) * channels + ch];
+                    if (by_psnr) se[i] += sse[((size_t)i * nb + s) * channels + ch];
+                }
+            }
+            const double px = (double)width * (double)height * (double)depth;
+            const int p = by_psnr ? pick_by_psnr(se, px * (double)channels, target) : pick_by_rate(sb, target * px);
+            stack_pick[s0 + s] = (uint8_t)p;
+            map_bits += sb[p];
+        }
     }
     free(bits);
     if (status) return 1;
-    int pick;
-    if (by_psnr) {
-        const double n_samples = (double)width * (double)height * (double)channels * (double)n_stacks * (double)depth;
-        pick = 0; /* none reaches the target: the smallest quality (the ladder ascends) */
-        for (int i = 0; i < RATE_LADDER_N; i++)
-            if (psnr_of(err[i], n_samples) >= target) pick = i; /* the largest that reaches it, whatever the order */
-        printf("psnr: q=%d psnr=%.3f bits=%llu\n", kRateLadder[pick], psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
+    if (stack_pick) {
+        printf("qmap: stacks=%d bits=%llu\n", n_stacks, (unsigned long long)map_bits);
     } else {
-        const double target_bits = target * (double)width * (double)height * (double)frames;
-        pick = RATE_LADDER_N - 1; /* none fits: the largest quality (the ladder ascends) */
-        for (int i = RATE_LADDER_N - 1; i >= 0; i--)
-            if ((double)tot[i] <= target_bits) pick = i; /* the smallest that fits, whatever the order of the sizes */
-        printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
-    }
-    const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
-    if (rc) {
-        printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
-        return 1;
+        int pick;
+        if (by_psnr) {
+            const double n_samples = (double)width * (double)height * (double)channels * (double)n_stacks * (double)depth;
+            pick = pick_by_psnr(err, n_samples, target);
+            printf("psnr: q=%d psnr=%.3f bits=%llu\n", kRateLadder[pick], psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
+        } else {
+            pick = pick_by_rate(tot, target * (double)width * (double)height * (double)frames);
+            printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
+        }
+        const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
+        if (rc) {
+            printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
+            return 1;
+        }
     }
     if (fseek(in, 0, SEEK_SET)) {
         printf("Cannot rewind the input file for the second pass\n");
@@ -477,7 +608,7 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
                "of 8)\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_targets("encode_multi")) return 1;
+    if (reject_targets("encode_multi") || reject_qmap("encode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -587,7 +718,7 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_targets("decode_multi")) return 1;
+    if (reject_targets("decode_multi") || reject_qmap("decode_multi")) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -730,10 +861,29 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     double psnr_db = 0.0;
     int psnr_set = 0;
     if (call_target(SEL_PSNR, &psnr_db, &psnr_set)) return 1;
+    /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
+    const char *qmap_path = NULL;
+    if (call_qmap(&qmap_path)) return 1;
+    uint8_t *qmap = NULL;
+    int32_t qmap_tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
+    if (qmap_path) {
+        const int ns = (frames + depth - 1) / depth;
+        qmap = (uint8_t *)calloc((size_t)ns, 1);
+        if (!qmap) {
+            printf("Out of memory\n");
+            return 1;
+        }
+        if (!rate_set && !psnr_set && read_qmap(qmap_path, ns, qmap)) {
+            free(qmap);
+            return 1;
+        }
+        ladder_tables(depth, qmap_tabs);
+    }
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
         printf("Cannot open input file %s\n", inName);
+        free(qmap);
         return 1;
     }
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
@@ -787,7 +937,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     /* a rate target: the first pass picks the quality, the second encodes as q=<n> does */
     if (!status && (rate_set || psnr_set))
         STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
-                                              psnr_set ? psnr_db : rate_bpp, psnr_set));
+                                              psnr_set ? psnr_db : rate_bpp, psnr_set, qmap));
+    if (!status && qmap && (rate_set || psnr_set)) status = write_qmap(qmap_path, n_stacks, qmap);
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
         size_t got = 0, r;
@@ -818,7 +969,11 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             int cbits[3] = {0, 0, 0};
             uint64_t tb[3] = {0, 0, 0};
             for (int ch = 0; ch < channels; ch++) dct3d_entropy_enc_carry(ent[ch], &cb[ch], &cbits[ch]);
-            STAGE(t_dev, rc = dct3d_encode_eg_frames(ctx, fr, width, height, channels, nb, cb, cbits, tb));
+            if (qmap) /* stack s0 + s under the ladder's table qmap[s0 + s] */
+                STAGE(t_dev, rc = dct3d_encode_eg_frames_vq(ctx, fr, width, height, channels, nb, qmap_tabs, RATE_LADDER_N,
+                                                            qmap + s0, cb, cbits, tb));
+            else
+                STAGE(t_dev, rc = dct3d_encode_eg_frames(ctx, fr, width, height, channels, nb, cb, cbits, tb));
             for (int ch = 0; ch < channels && !rc; ch++) {
                 const size_t nbytes = (size_t)((tb[ch] + 7) / 8);
                 if (nbytes > eg_cap) {
@@ -855,6 +1010,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     free(fr);
     free(q);
     free(eg);
+    free(qmap);
     char qtext[QUANT_MAX_STEPS * 5 + 8];
     quant_json(ctx, depth, qtext, sizeof(qtext));
     if (ctx) dct3d_ctx_destroy(ctx);
@@ -873,6 +1029,23 @@ static int encode_any(const char *inName, const char *outName, int width, int he
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
     if (reject_targets("decode")) return 1;
+    const char *qmap_path = NULL;
+    if (call_qmap(&qmap_path)) return 1;
+    uint8_t *qmap = NULL;
+    int32_t qmap_tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
+    if (qmap_path) { /* read before any file is made */
+        const int ns = (frames + depth - 1) / depth;
+        qmap = (uint8_t *)calloc((size_t)ns, 1);
+        if (!qmap) {
+            printf("Out of memory\n");
+            return 1;
+        }
+        if (read_qmap(qmap_path, ns, qmap)) {
+            free(qmap);
+            return 1;
+        }
+        ladder_tables(depth, qmap_tabs);
+    }
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
     const int host_eg = host_eg_on();
@@ -948,7 +1121,11 @@ static int decode_any(const char *inName, const char *outName, int width, int he
                     rc = DCT3D_EINVAL;
                     break;
                 }
-                STAGE(t_dev, rc = dct3d_decode_eg_frames(ctx, p, len, bit, width, height, channels, nb, fr, eb));
+                if (qmap)
+                    STAGE(t_dev, rc = dct3d_decode_eg_frames_vq(ctx, p, len, bit, width, height, channels, nb, qmap_tabs,
+                                                                RATE_LADDER_N, qmap + s0, fr, eb));
+                else
+                    STAGE(t_dev, rc = dct3d_decode_eg_frames(ctx, p, len, bit, width, height, channels, nb, fr, eb));
                 if (rc == DCT3D_ENODATA) { /* some channel needs more of its stream than estimated? */
                     int more = 0;
                     for (int ch = 0; ch < channels; ch++)
@@ -994,6 +1171,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     }
     free(fr);
     free(q);
+    free(qmap);
     char qtext[QUANT_MAX_STEPS * 5 + 8];
     quant_json(ctx, depth, qtext, sizeof(qtext));
     if (ctx) dct3d_ctx_destroy(ctx);

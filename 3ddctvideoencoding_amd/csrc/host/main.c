@@ -11,6 +11,9 @@
  *   passes, the first picks q from a fixed ladder and prints "rate: q=<n> bits=<total>"; decode with that q=<n>
  *   ... or psnr=<dB> (codec_parse_psnr): the first pass picks the largest q of the ladder whose PSNR reaches the
  *   target and prints "psnr: q=<n> psnr=<dB> bits=<total>"
+ *   the single-device commands take qmap=<path> (codec.h, codec_set_qmap): one ladder quality per stack, one per
+ *   line; written by an encode that also has rate= or psnr= (the rule applied per stack), read by an encode without
+ *   a target and by a decode; not together with q= or several devices
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -48,6 +51,12 @@ static void usage(void) {
            "takes each q's PSNR over all unpadded samples of all channels together, picks the largest q whose PSNR is "
            ">= <dB> (1 when none reaches it) and prints 'psnr: q=<n> psnr=<dB> bits=<total>'; the second pass encodes as "
            "q=<n>.  psnr= on a decode, together with q= or rate=, or with several devices is an error\n");
+    printf("The commands on one device take qmap=<path>, a text file of one ladder quality per stack (one per line, in "
+           "stack order): stack s of every channel is coded as q=<that quality> codes it.  With rate= or psnr= the "
+           "first pass applies the target's rule per stack (budget <bits per pixel> * width * height * block depth "
+           "per stack; PSNR over the stack's samples), WRITES the map and prints 'qmap: stacks=<n> bits=<total>'; an "
+           "encode without a target and a decode READ it.  qmap= together with q=, with several devices, or a file "
+           "with another line count or a quality outside the ladder is an error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -101,13 +110,25 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0;
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0;
     for (int a = 9; a < argc && a < 11 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
         const int is_rate = !strncmp(argv[a], "rate=", 5), is_psnr = !strncmp(argv[a], "psnr=", 5);
-        if (a == 10 && (is_rate ? have_rate : is_psnr ? have_psnr : have_quant)) break; /* (a second argument counts only as another kind) */
-        if (is_rate || is_psnr) {
+        const int is_qmap = !strncmp(argv[a], "qmap=", 5);
+        if (a == 10 && (is_rate ? have_rate : is_psnr ? have_psnr : is_qmap ? have_qmap : have_quant)) break; /* (a second argument counts only as another kind) */
+        if (is_qmap) {
+            if (!argv[a][5]) {
+                printf("Invalid quality map '%s': qmap=<path>\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (n_dev > 1) {
+                printf("qmap= applies to the commands on one device\n");
+                return 1;
+            }
+            have_qmap = a;
+        } else if (is_rate || is_psnr) {
             if (is_rate ? codec_parse_rate(argv[a], &v) : codec_parse_psnr(argv[a], &v)) {
                 if (is_rate) printf("Invalid rate target '%s': rate=<bits per pixel>, a positive number\n", argv[a]);
                 else printf("Invalid psnr target '%s': psnr=<dB>, a positive number\n", argv[a]);
@@ -133,8 +154,12 @@ int main(int argc, char *argv[]) {
         printf("%s and %s exclude each other\n", have_quant ? "q=" : "rate=", have_psnr ? "psnr=" : "rate=");
         return 1;
     }
+    if (have_quant && have_qmap) {
+        printf("q= and qmap= exclude each other\n");
+        return 1;
+    }
     if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate])) ||
-        (have_psnr && codec_set_psnr(argv[have_psnr]))) {
+        (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap]))) {
         printf("Argument too long\n");
         return 1;
     }

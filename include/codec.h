@@ -119,6 +119,30 @@ int codec_set_rate(const char *text);
 int codec_parse_psnr(const char *text, double *db);
 int codec_set_psnr(const char *text);
 
+/* A quality per stack (the single-device calls: encode, encode_ex, encode_rgb_ex and their decodes): "qmap=<path>"
+ * names a text file with one line per stack, in stack order, each a quality of the ladder above; stack s of every
+ * channel is coded as q=<that quality> codes it (dct3d_encode_eg_frames_vq / dct3d_decode_eg_frames_vq, the ladder
+ * as the palette).  The map travels beside the .bin as width, height, frame count, block depth and q= do: the .bin
+ * stays the reference's headerless format, and with no map every file is byte for byte what it was.
+ *   encode with rate= or psnr= AND qmap=   the first pass applies the target's rule per stack and WRITES the map:
+ *       the rate target's budget is bpp * width * height * blockDepth bits for every stack, the stack's bits summed
+ *       over the channels; the PSNR is taken over the stack's unpadded samples of all channels (the zero-filled
+ *       frames of a short last stack count).  Prints "qmap: stacks=<n> bits=<total>"; the second pass encodes with
+ *       the map.
+ *   encode with qmap= alone, decode with qmap=   READ the map.  A constant map gives the q=<n> file byte for byte.
+ * Errors (a line printed, 1 returned, before any output file is made): qmap= together with a quantiser, on the
+ * several-device calls, with DCT3D_CODEC_HOST_EG=1, a file whose line count is not the stack count, a line that is
+ * no quality of the ladder.
+ *
+ * codec_parse_qmap: reads the file `path` (the path itself, without "qmap="): 0 and qualities[0 .. nStacks-1], or
+ *   1 (qualities untouched) if the file cannot be read, is empty, has another line count, or holds a line that is
+ *   not exactly a ladder quality in decimal.
+ * codec_set_qmap: the map of every later single-device call of this process, as the text "qmap=<path>"; NULL or
+ *   "": none.  It overrides the environment variable DCT3D_CODEC_QMAP.  1 (nothing changes) while codec_set_quant
+ *   holds a text, or if the text is too long to keep. */
+int codec_parse_qmap(const char *path, int nStacks, int *qualities);
+int codec_set_qmap(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

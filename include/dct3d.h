@@ -457,6 +457,43 @@ int dct3d_distortion_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int wid
 int dct3d_distortion_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
                             int n_stacks, const int32_t *tables, int n_tables, uint64_t *sse, uint64_t *bits);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-stack quantiser tables in the fused stream calls (additive to ABI 9; detect by symbol).
+ * The four dct3d_*_eg_frames* calls with three more host arguments, copied before the call returns:
+ *   tables       [n_tables][bw + bh + bd - 2] steps, each in [1, 255]: a palette of 1 <= n_tables <=
+ *                DCT3D_RATE_MAX_TABLES tables (the layout the probes take).
+ *   stack_table  [n_stacks], each entry < n_tables: stack s of EVERY channel is coded with
+ *                tables[stack_table[s]].
+ * Channel ch's stream is the stream dct3d_encode_eg_frames writes when, stack by stack, the context's table is
+ * tables[stack_table[s]]: the chain of n_stacks single-stack base calls with dct3d_ctx_set_quant before each
+ * and the carry of each handed to the next, byte for byte; the decode is the inverse under the same map.  Every
+ * value is certified or replayed exactly under its own stack's table, as with one table.  The calls neither
+ * read nor change the context's quantiser (as the probes), rebuild no plan and wait for nothing a base call
+ * does not wait for.  Everything else -- frames, streams, carries, return points, DCT3D_ENOSPC with every
+ * total_bits[ch] set, DCT3D_ENODATA with the good streams' end_bit[ch] -- is the base call's; n_units and
+ * n_flagged are the sums the chain of base calls reports.
+ * DCT3D_EINVAL in addition to the base calls' cases: a NULL among the three, n_tables outside 1..32, a step
+ * outside [1, 255], a stack_table entry >= n_tables, or DCT3D_OPT_EG_TWO_STEP set on the context (the int32
+ * intermediate has no table per stack: the option is refused, not ignored).  DCT3D_OPT_EG_FORCE_RETRY,
+ * DCT3D_OPT_EG_NO_RESOLVE and DCT3D_OPT_DEC_MARGIN act as on the base calls.
+ * dct3d_eg_fetch_channel serves dct3d_encode_eg_frames_vq as it serves dct3d_encode_eg_frames.
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_encode_eg_frames_vq_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                                  int n_stacks, const int32_t *tables, int n_tables, const uint8_t *stack_table,
+                                  const uint8_t carry_byte[], const int carry_bits[], uint8_t *const d_out[],
+                                  const uint64_t out_cap[], uint64_t total_bits[]);
+int dct3d_encode_eg_frames_vq(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                              int n_stacks, const int32_t *tables, int n_tables, const uint8_t *stack_table,
+                              const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]);
+int dct3d_decode_eg_frames_vq_dev(dct3d_ctx *ctx, const uint8_t *const d_bytes[], const uint64_t nbytes[],
+                                  const uint64_t start_bit[], int width, int height, int channels, int n_stacks,
+                                  const int32_t *tables, int n_tables, const uint8_t *stack_table,
+                                  uint8_t *d_frames, uint64_t end_bit[]);
+int dct3d_decode_eg_frames_vq(dct3d_ctx *ctx, const uint8_t *const bytes[], const uint64_t nbytes[],
+                              const int start_bit[], int width, int height, int channels, int n_stacks,
+                              const int32_t *tables, int n_tables, const uint8_t *stack_table, uint8_t *frames,
+                              uint64_t end_bit[]);
+
 #ifdef __cplusplus
 }
 #endif
