@@ -2,12 +2,21 @@
 // (encode_eg_kernel) and stream -> raster (decode_eg_kernel, decode_eg_rgb_kernel), with no int32 cube-major
 // intermediate.  Instantiated by dct3d_kernels.hip (grey rasters whose width and height are multiples of 8)
 // and dct3d_eg_frames.hip (frames of any size and packed RGB24: the same code with the edge padding, the
-// crop and the channel pick / mix in its addressing).
+// crop and the channel pick / mix in its addressing), dct3d_quant_eg.hip (QT = 1: the context's quantiser table)
+// and dct3d_vq_enc.hip / dct3d_vq_dec.hip (QT = 2: a table per stack).
 #pragma once
 #include "dct3d_encode_dev.h"
 #include "dct3d_decode_dev.h"
+#include "dct3d_vq.h"
 
 namespace dct3d {
+
+// QT of the three kernels below: 0 the reference's steps (in the text), 1 the context's table, 2 a table per
+// stack.  QT = 2 exists on the device side only -- Variant::qt stays {0, 1}; the vq launchers pick it by depth,
+// pixel format and edge -- and brings one more kernel argument, the call's VqParams, as the kernel's trailing
+// pack: empty for QT 0 and 1, whose parameters and launch sites are the same with and without it.
+static_assert(kVqTabN == kTabN, "a palette table's rows as the encode kernels'");
+__device__ __forceinline__ const VqParams& vq_of(const VqParams& V) { return V; }  // the pack's one element
 
 // =============================================================================================
 // Fused encode + Exp-Golomb, K1 (dct3d_encode_eg_dev; encoder.c:206-274 up to the deflate)
@@ -168,8 +177,20 @@ __device__ __forceinline__ uint32_t k1_code_off(uint32_t k) {
 // stream per channel: a launch chain each).  EDGE = 1: frames of any size, P as launch_encode's for it.  Both
 // only change the row loads and the replay's reloads; these instantiations also count their exact replays
 // (P.replay_count) and zero the next call's counter slot, as the int32 encode kernels do.
-template <int D, int PX = 1, int EDGE = 0, int QT = 0>
-__global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, EgFusedParams E) {
+// QT = 2 (dct3d_vq_enc.hip): the table rows {1 / step, G, 0.5 - E, step} are chosen per cube.  Cube c of a wave
+// lies in stack (cube0 + c) / cubes_per_stack and takes the palette entry the map names for that stack.
+// Where the rows live: in the wave's own staging region, between the transform and the code staging.  After
+// forward_cube the region is free (the coefficients are in registers) until the codes are staged, so the wave
+// copies the rows of its (up to 8) cubes' tables there, 3 KiB of the region's 8.25 KiB (4.1 KiB at 8x8x4), and
+// the quantise loop reads them through tab_window exactly as the QT = 1 kernel reads the block's copy.  No LDS
+// is added (the block still fits a quarter of the CU's; the unused s_tab is dropped), no table register is held
+// across the transform.  Cubes that share a table share a copy (the slot of the first such cube), so a wave
+// inside one stack -- every wave but a few at 1080p -- reads one table at wave-uniform addresses, as the QT = 1
+// kernel does.  The DC's step is read before the codes overwrite the copy; the rare exact replay takes the
+// source cube's rows from global memory.
+template <int D, int PX = 1, int EDGE = 0, int QT = 0, class... VQ>
+__global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, EgFusedParams E, VQ... vq) {
+    static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
     constexpr int CS = 64 * D;
     constexpr int NB = (D == 8) ? 8 : 4;
     constexpr int NI = 7 + NB;
@@ -198,6 +219,11 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     // they queue behind the computing waves' VALU work; c7 -0.4 %, profiles/r05/c7_ab/7_prio)
     __builtin_amdgcn_s_setprio(3);
     load_channel_rows<D, 0, PX, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, E.ch, raw);
+    [[maybe_unused]] uint32_t ti = 0;  // QT = 2: the table of the lane's cube (a cube past the end: entry 0, never used)
+    if constexpr (QT == 2) {
+        const VqParams& V = vq_of(vq...);
+        if (cube0 + (lane >> 3) < P.n_cubes) ti = V.map[fdiv(cube0 + (lane >> 3), P.div_cps)];
+    }
     __builtin_amdgcn_s_setprio(0);
     if constexpr (PX != 1 || EDGE != 0) {
         // (written out, not enc_clear_next_slot: through the call the 8x8x8 instantiations' text changes)
@@ -216,7 +242,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     }
     __syncthreads();
     if (cube0 >= P.n_cubes) return;  // wave-uniform, after the barrier
-    enc_tables<QT>(P, s_tab, lane);
+    if constexpr (QT != 2) enc_tables<QT>(P, s_tab, lane);
     char* wl = lds + wave * enc_wave_lds<D>();
     char* rs = RS_TAIL ? wl + 8 * CUBE_B : rs_extra + wave * RS_B;
     static_assert((8 * CUBE_B) % 8 == 0 && RS_B % 8 == 0, "replay scratch alignment");
@@ -232,9 +258,41 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     int m;
     float A;
     cube_stats<D>(raw, a, S, m, A);
-    asm volatile("" : "+v"(S), "+v"(m), "+v"(A));
+    if constexpr (QT == 2) asm volatile("" : "+v"(S), "+v"(m), "+v"(A), "+v"(ti));
+    else asm volatile("" : "+v"(S), "+v"(m), "+v"(A));
     float b[8][NB];
     forward_cube<D, NB>(a, m, c, j, wl, b);
+
+    const float4* tab = s_tab;  // the table the lane quantises with: the block's copy, or (QT = 2) its cube's
+    if constexpr (QT == 2) {
+        // the wave's tables into its region (free until the codes are staged): the copy of cube cc's table at
+        // slot cc, 3 rows per lane; a cube reads the slot of the first cube of the wave with its table.  A
+        // cube's copy: 25 rows apart (400 B: the 8 copies' rows on distinct 4-bank groups)
+        constexpr int SLOT = kTabN + 1;
+        static_assert(8 * SLOT * (int)sizeof(float4) <= enc_wave_lds<D>(), "the wave's table copies fit its region");
+        const VqParams& V = vq_of(vq...);
+        wave_lds_sync();  // the transform's last reads of the region
+        float4 row[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const int i = lane + 64 * r, cc = i / kTabN;  // 192 rows = 8 cubes x kTabN
+            const uint32_t tc = (uint32_t)__shfl((int)ti, cc * 8, 64);
+            row[r] = V.tabs[tc * kTabN + (uint32_t)(i - cc * kTabN)];
+        }
+        int slot = c;
+#pragma unroll
+        for (int cc = 7; cc >= 0; cc--) {
+            const uint32_t tc = (uint32_t)__builtin_amdgcn_readlane((int)ti, cc * 8);
+            if (tc == ti) slot = cc;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const int i = lane + 64 * r, cc = i / kTabN;
+            ((float4*)wl)[cc * SLOT + (i - cc * kTabN)] = row[r];
+        }
+        wave_lds_sync();
+        tab = (const float4*)wl + slot * SLOT;
+    }
 
     int sz = so;
     float rr[NI], thr[NI];
@@ -243,7 +301,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
 #pragma unroll
     for (int ky = 0; ky < 8; ky++) {
         pin(b[ky]);
-        tab_window<NB, NI>(s_tab, sz, ky, A, rr, thr);
+        tab_window<NB, NI>(tab, sz, ky, A, rr, thr);
         bool f = false;
         float qq[NB];
 #pragma unroll
@@ -266,11 +324,12 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
         asm volatile("" : "+v"(fm_lo), "+v"(fm_hi));
     }
     if (j == 0) {
-        if constexpr (QT) qv[0][0] = java_round_dev(__ddiv_rn((double)S * P.coef_dc, enc_step<1>(s_tab, 0)));
+        if constexpr (QT) qv[0][0] = java_round_dev(__ddiv_rn((double)S * P.coef_dc, enc_step<1>(tab, 0)));  // step[0]
         else qv[0][0] = java_round_dev((double)S * P.coef_dc);  // exact DC (single Java group)
         fm_lo &= ~1u;
     }
     if (!valid) fm_lo = fm_hi = 0;
+    if constexpr (QT == 2) wave_lds_sync();  // the last reads of the table copies: the codes overwrite them
 
     // stage the cubes' Exp-Golomb codes as uint16, cube-major (k = (kz*8 + ky)*8 + kx at byte 2k of cube c)
 #pragma unroll
@@ -285,7 +344,8 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     }
     wave_lds_sync();
 
-    // exact replay of the uncertified coefficients, one at a time by the whole wave (rare)
+    // exact replay of the uncertified coefficients, one at a time by the whole wave (rare); QT = 2: each under
+    // the source cube's table (its rows from global memory: the region holds the codes now)
     {
         ReplayGeom R{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride,
                      E.ngroups, E.coef, E.group_of};
@@ -298,10 +358,12 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
             const int src = __builtin_ctzll(who);
             const int mybit = fm_lo ? __builtin_ctz(fm_lo) : (fm_hi ? 32 + __builtin_ctz(fm_hi) : 0);
             const int bit = __shfl(mybit, src, 64);
+            const float4* rtab = s_tab;
+            if constexpr (QT == 2) rtab = vq_of(vq...).tabs + (uint32_t)__shfl((int)ti, src, 64) * kTabN;
             const int sj = src & 7, sc = src >> 3;
             const int skz = (D == 8) ? sj : (sj >> 1), skx0 = (D == 8) ? 0 : (sj & 1) * 4;
             const uint32_t k = (uint32_t)((skz * 8 + bit / NB) * 8 + skx0 + bit % NB);
-            const int q = exact_coef<D, PX, EDGE, QT>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4), s_tab);
+            const int q = exact_coef<D, PX, EDGE, (QT != 0)>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4), rtab);
             if constexpr (PX != 1 || EDGE != 0) nrep++;
             if (lane == 0) *(uint16_t*)(wl + sc * CUBE_B + k1_code_off<D>(k)) = (uint16_t)(q > 0 ? 2 * q : 1 - 2 * q);
             if (lane == src) {
@@ -358,6 +420,30 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
 // in decode_kernel.  No int32 cube-major array is written or read.
 // The rare exact replay re-parses its cube from the stream at the cube's marks (lanes 0 .. CS/32 - 1,
 // 32 values each, global reads: the wave's window is gone by then).
+// The three functors below differ in the step of sum s = kx + ky + kz for cube g -- QT = 0: the reference's, in
+// the text; 1: steps[s]; 2: the table of g's stack, found behind steps (vq_map_behind, vq_div_behind) -- and share
+// this body.  They stay three types of five and six members: decode_replay_lane's out-of-line body is named after
+// its functor, and with more members the functor leaves registers.
+template <int D, int QT>
+__device__ __forceinline__ void reload_stream(const uint32_t* words, uint64_t n_words, const uint16_t* mark,
+                                              const uint64_t* mark_base, const uint16_t* diag, const double* steps,
+                                              uint32_t g, double* cf, int lane) {
+    constexpr int PARTS = 64 * D / 32;
+    if (lane < PARTS) {
+        if constexpr (QT == 2) steps += (size_t)kVqStepN * vq_map_behind(steps)[fdiv(g, *vq_div_behind(steps))];
+        BitReader<GlobalBits> r{GlobalBits{words, n_words}, 0, 0, 0, 0};
+        r.seek(mark_serial(mark, mark_base, (uint64_t)g * PARTS + lane));
+        for (int i = 0; i < 32; i++) {
+            uint32_t code = 1u;
+            (void)r.get(code);
+            const int k = diag[lane * 32 + i];
+            const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
+            if constexpr (QT) cf[k] = (double)eg_value(code) * steps[kx + ky + kz];
+            else cf[k] = (double)eg_value(code) * (double)max(1, 5 * (kx + ky + kz));
+        }
+    }
+}
+
 template <int D>
 struct ReloadStream {
     const uint32_t* words;
@@ -366,18 +452,7 @@ struct ReloadStream {
     const uint64_t* mark_base;
     const uint16_t* diag;  // the block's LDS copy
     __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
-        constexpr int PARTS = 64 * D / 32;
-        if (lane < PARTS) {
-            BitReader<GlobalBits> r{GlobalBits{words, n_words}, 0, 0, 0, 0};
-            r.seek(mark_serial(mark, mark_base, (uint64_t)g * PARTS + lane));
-            for (int i = 0; i < 32; i++) {
-                uint32_t code = 1u;
-                (void)r.get(code);
-                const int k = diag[lane * 32 + i];
-                const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
-                cf[k] = (double)eg_value(code) * (double)max(1, 5 * (kx + ky + kz));
-            }
-        }
+        reload_stream<D, 0>(words, n_words, mark, mark_base, diag, nullptr, g, cf, lane);
     }
 };
 
@@ -390,20 +465,56 @@ struct ReloadStreamQ {  // ReloadStream with the quantiser's table (QT = 1): ste
     const uint16_t* diag;
     const double* steps;
     __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
-        constexpr int PARTS = 64 * D / 32;
-        if (lane < PARTS) {
-            BitReader<GlobalBits> r{GlobalBits{words, n_words}, 0, 0, 0, 0};
-            r.seek(mark_serial(mark, mark_base, (uint64_t)g * PARTS + lane));
-            for (int i = 0; i < 32; i++) {
-                uint32_t code = 1u;
-                (void)r.get(code);
-                const int k = diag[lane * 32 + i];
-                const int kz = k / 64, ky = (k / 8) & 7, kx = k & 7;
-                cf[k] = (double)eg_value(code) * steps[kx + ky + kz];
-            }
-        }
+        reload_stream<D, 1>(words, n_words, mark, mark_base, diag, steps, g, cf, lane);
     }
 };
+
+template <int D>
+struct ReloadStreamVq {  // ReloadStreamQ with the table of the replayed cube's stack (steps: VqParams::steps)
+    const uint32_t* words;
+    uint64_t n_words;
+    const uint16_t* mark;
+    const uint64_t* mark_base;
+    const uint16_t* diag;
+    const double* steps;
+    __device__ __forceinline__ void operator()(uint32_t g, double* cf, int lane) const {
+        reload_stream<D, 2>(words, n_words, mark, mark_base, diag, steps, g, cf, lane);
+    }
+};
+
+// QT = 2 (dct3d_vq_dec.hip): the one difference from QT = 1 is the step pointer handed to decode_tile<..., QT =
+// 1>, which already takes the lane's steps from a pointer by plain cached global loads: it is per lane, steps +
+// 32 * map[stack of the lane's cube], into the palette's [n_tables][32] fp64 array.  CODES' integer |q| * step
+// products and the exact replay's re-parse (ReloadStreamVq) use the same entry.
+// The pointer for the lane's cube g (g < n_cubes: whole stacks, so the stack is inside the map).  decode_tile
+// reads qsteps[4 h + k + j], j < 11: the pointer is formed as the palette's wave-uniform base plus one 32-bit lane
+// offset (< 2^11 entries: 32 tables of 32 steps) that already holds 4 h + k, so that the loads keep a scalar
+// base and one offset register, as the QT = 1 kernel's do.
+template <int D>
+__device__ __forceinline__ const double* vq_lane_steps(const VqParams& V, const DecodeParams& P, uint32_t g, int lane) {
+    const uint32_t hk = (uint32_t)(4 * ((lane >> 4) & 1) + (lane & (D - 1)));
+    const uint32_t o = ((uint32_t)kVqStepN * V.map[fdiv(g, P.div_cps)] + hk) & 0x7FFu;
+    return (V.steps + o) - hk;
+}
+
+// The lane's 32 parsed codes, each to its diagonal position in the wave's staging: 8 offsets per 16-byte read
+// of the block's offset table
+template <int D, uint32_t SOFF>
+__device__ __forceinline__ void dec_scatter_codes(char* wl, const uint16_t* s_soff, int lane, const uint32_t (&v)[32]) {
+    using G = DecGeom<D>;
+    constexpr uint32_t PARTS = G::CS / 32;
+    const uint32_t c = lane / PARTS, part = lane % PARTS;
+    char* cb = wl + c * G::SA_C;
+    const uint4* so = (const uint4*)(s_soff + part * SOFF);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint4 o = so[q];
+        const uint32_t w[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            *(uint32_t*)(cb + ((w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu)) = v[q * 8 + e];
+    }
+}
 
 // lane 0's 64-bit value in scalar registers (readfirstlane returns int: widened from uint32_t, unsigned)
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
@@ -420,8 +531,9 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
 // (32 bits) and two wave-uniform 64-bit values (scalar registers).  NG = 1: no look-ahead.
 // EDGE = 1 (dct3d_eg_frames.hip): frames of any size, P as launch_decode's for it (blk_store off): the stores
 // are cropped, nothing else differs.
-template <int D, int NG, int EDGE = 0, int QT = 0>
-__global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArgs<QT>::type P, EgDecParams E) {
+template <int D, int NG, int EDGE = 0, int QT = 0, class... VQ>
+__global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArgs<QT>::type P, EgDecParams E, VQ... vq) {
+    static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
     using G = DecGeom<D>;
     constexpr uint32_t CS = G::CS, PARTS = CS / 32, CPW = G::CPW;
     static_assert(CPW * CS == 2048 && PARTS * CPW == 64, "one wave = 64 marks");
@@ -558,22 +670,20 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArg
         if (i + 1 < NG) open_window(lane, gb_n, myl_n, last_n, w0, rel, span, pw);  // in flight during the transform
         __builtin_amdgcn_s_setprio(2);
         wave_lds_sync();
-        {  // each value to its diagonal position in the staging: 8 offsets per 16-byte table read
-            const uint32_t c = lane / PARTS, part = lane % PARTS;
-            char* cb = wl + c * G::SA_C;
-            const uint4* so = (const uint4*)(s_soff + part * SOFF);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint4 o = so[q];
-                const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++)
-                    *(uint32_t*)(cb + ((w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu)) = v[q * 8 + e];
-            }
-        }
+        dec_scatter_codes<D, SOFF>(wl, s_soff, lane, v);
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
-        if constexpr (QT)
+        if constexpr (QT == 2) {
+            // the steps of the lane's cube (a lane whose cube is past the end: the last cube's, its output
+            // unused), looked up here and not earlier (the opaque lane: no register is held across the parse for it)
+            const VqParams& V = vq_of(vq...);
+            int ql = lane;
+            asm volatile("" : "+v"(ql));
+            const double* const qs = vq_lane_steps<D>(V, P, min(cube0 + (uint32_t)dec_cube_of_lane<D>(ql), P.n_cubes - 1), ql);
+            decode_tile<D, (NG > 1), true, false, EDGE, 1>(
+                P, wl, lane, cube0, [] {},
+                ReloadStreamVq<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag, V.steps}, nullptr, nullptr, qs);
+        } else if constexpr (QT)
             decode_tile<D, (NG > 1), true, false, EDGE, 1>(P, wl, lane, cube0, [] {},
                                                            ReloadStreamQ<D>{E.words, E.n_words, E.mark, E.mark_base, s_diag, dec_steps(P)},
                                                            nullptr, nullptr, dec_steps(P));
@@ -595,8 +705,9 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArg
 // replay re-parses its cube from stream ch.  The channels' bytes are merged in registers and dec_store_tile<PX
 // = 3> writes every packed byte once.  One group per wave (no look-ahead across groups).  A launch whose
 // streams are not all valid (any front's verdict) writes nothing.
-template <int D, int EDGE = 0, int QT = 0>
-__global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename DecodeArgs<QT>::type P, EgDecRgbParams E) {
+template <int D, int EDGE = 0, int QT = 0, class... VQ>
+__global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename DecodeArgs<QT>::type P, EgDecRgbParams E, VQ... vq) {
+    static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
     using G = DecGeom<D>;
     constexpr uint32_t CS = G::CS, PARTS = CS / 32, CPW = G::CPW;
     static_assert(CPW * CS == 2048 && PARTS * CPW == 64, "one wave = 64 marks");
@@ -678,23 +789,21 @@ __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename Decod
             parse_codes<32>(L, win, nwin, w0, fits, long_codes, rel, v);
         }
         wave_lds_sync();
-        {  // each value to its diagonal position in the staging: 8 offsets per 16-byte table read
-            const uint32_t c = lane / PARTS, part = lane % PARTS;
-            char* cb = wl + c * G::SA_C;
-            const uint4* so = (const uint4*)(s_soff + part * SOFF);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint4 o = so[q];
-                const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++)
-                    *(uint32_t*)(cb + ((w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu)) = v[q * 8 + e];
-            }
-        }
+        dec_scatter_codes<D, SOFF>(wl, s_soff, lane, v);
         wave_lds_sync();
         __builtin_amdgcn_s_setprio(0);  // the transform
         uint32_t outw[D][NW];
-        if constexpr (QT)
+        if constexpr (QT == 2) {
+            // the steps of the lane's cube (all three channels of a stack share its table), looked up here and
+            // not earlier (the opaque lane: no register is held across the parse for it)
+            const VqParams& V = vq_of(vq...);
+            int ql = lane;
+            asm volatile("" : "+v"(ql));
+            const double* const qs = vq_lane_steps<D>(V, P, min(cube0 + (uint32_t)dec_cube_of_lane<D>(ql), P.n_cubes - 1), ql);
+            decode_tile<D, false, true, true, 0, 1>(
+                P, wl, lane, cube0, [] {},
+                ReloadStreamVq<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag, V.steps}, &outw[0][0], &valid, qs);
+        } else if constexpr (QT)
             decode_tile<D, false, true, true, 0, 1>(P, wl, lane, cube0, [] {},
                                                     ReloadStreamQ<D>{S.words, S.n_words, S.mark, S.mark_base, s_diag, dec_steps(P)},
                                                     &outw[0][0], &valid, dec_steps(P));

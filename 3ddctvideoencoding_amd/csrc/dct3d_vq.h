@@ -1,14 +1,15 @@
 // dct3d_vq.h -- per-stack quantiser tables in the fused stream calls (dct3d_encode_eg_frames_vq* /
-// dct3d_decode_eg_frames_vq*): the kernels' parameters and launchers (dct3d_vq_enc.hip,
-// dct3d_vq_dec.hip), shared with the C-ABI runtime.  A family of its own beside the variant's qt axis: the
-// kernels are routed by depth, pixel format and edge alone.
+// dct3d_decode_eg_frames_vq*): the kernels' extra parameter and their launchers (dct3d_vq_enc.hip,
+// dct3d_vq_dec.hip), shared with the C-ABI runtime.  The kernels are the QT = 2 instances of the shared stream
+// kernels (dct3d_eg_fused_dev.h, which includes this header for VqParams), beside the variant's qt axis: they are
+// routed by depth, pixel format and edge alone.
 #pragma once
 #include "dct3d_kernels.h"
 
 namespace dct3d {
 
 constexpr int kVqMaxTables = 32;  // == DCT3D_RATE_MAX_TABLES: the palette's size
-constexpr int kVqTabN = 24;       // rows per table (== kTabN, dct3d_encode_dev.h)
+constexpr int kVqTabN = 24;       // rows per table (== kTabN: asserted in dct3d_eg_fused_dev.h)
 constexpr int kVqStepN = 32;      // fp64 steps per table (the decode kernels' layout, as distortion_kernel's)
 
 // The palette and the map of one call.  Cube g (global index: the encode's from 0, the decode's from
