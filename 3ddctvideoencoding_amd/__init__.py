@@ -35,6 +35,9 @@ DCT3D_OPT_EG_FORCE_RETRY = 8
 DCT3D_OPT_EG_DEC_GROUPS = 9
 DCT3D_OPT_EG_FUSED_FRONT = 10
 DCT3D_OPT_QUANT_FORCE_TABLE = 11
+# the colour transform of the packed RGB24 stream calls and the rate probe (dct3d.h; rgb_to_ycbcr below)
+DCT3D_OPT_COLOUR = 12
+DCT3D_COLOUR_PLANES, DCT3D_COLOUR_YCBCR = 0, 1
 
 # Every symbol include/dct3d.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -245,6 +248,38 @@ def dequantize_ref(q_cubes: np.ndarray, steps) -> np.ndarray:
     """Decoder.java:78-96 with step[x + y + z]: int32 [.., bd, bh, bw] -> fp64 (double) q * step (exact)."""
     q = np.asarray(q_cubes)
     return q.astype(np.float64) * _step_cube(steps, q.shape)
+
+
+def _colour_in(frames) -> np.ndarray:
+    a = np.asarray(frames)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("a colour array's last axis holds the 3 samples of a pixel")
+    return a.astype(np.int64)
+
+
+def ycbcr_to_rgb_unclamped(frames) -> np.ndarray:
+    """ycbcr_to_rgb before its clamp to [0, 255]: int64 [.., 3] (the tests' view of what the clamp does)."""
+    a = _colour_in(frames)
+    y, u, v = a[..., 0], a[..., 1] - 128, a[..., 2] - 128
+    return np.stack((y + ((91881 * v + 32768) >> 16), y + ((-22554 * u - 46802 * v + 32768) >> 16),
+                     y + ((116130 * u + 32768) >> 16)), axis=-1)
+
+
+def rgb_to_ycbcr(frames) -> np.ndarray:
+    """The definition of DCT3D_COLOUR_YCBCR's forward transform in numpy (dct3d.h): JFIF full-range BT.601 in
+    16-bit fixed point, uint8 [.., 3] (R, G, B) -> uint8 [.., 3] (Y, Cb, Cr), int64 inside, >> a floor.  No clamp:
+    every numerator lies in [0, 2^24) (tests/test_ycc_ref.py, all 2^24 colours)."""
+    a = _colour_in(frames)
+    r, g, b = a[..., 0], a[..., 1], a[..., 2]
+    out = np.stack(((19595 * r + 38470 * g + 7471 * b + 32768) >> 16,
+                    (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16,
+                    (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16), axis=-1)
+    return out.astype(np.uint8)
+
+
+def ycbcr_to_rgb(frames) -> np.ndarray:
+    """The inverse transform's definition: uint8 [.., 3] (Y, Cb, Cr) -> uint8 [.., 3] (R, G, B), clamped."""
+    return np.clip(ycbcr_to_rgb_unclamped(frames), 0, 255).astype(np.uint8)
 
 
 RATE_MAX_TABLES = 32

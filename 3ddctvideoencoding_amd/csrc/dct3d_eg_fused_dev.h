@@ -188,7 +188,10 @@ __device__ __forceinline__ uint32_t k1_code_off(uint32_t k) {
 // inside one stack -- every wave but a few at 1080p -- reads one table at wave-uniform addresses, as the QT = 1
 // kernel does.  The DC's step is read before the codes overwrite the copy; the rare exact replay takes the
 // source cube's rows from global memory.
-template <int D, int PX = 1, int EDGE = 0, int QT = 0, class... VQ>
+// CT = 1 (dct3d_ycc.hip; DCT3D_OPT_COLOUR), with PX = 3: channel E.ch is plane Y, Cb or Cr of the
+// pixels' colour transform, computed where the channel's bytes are picked (ycc_pick8: the row loads and the exact
+// replay's reload, which therefore folds the bytes the main path saw).  Nothing else changes.
+template <int D, int PX = 1, int EDGE = 0, int QT = 0, int CT = 0, class... VQ>
 __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, EgFusedParams E, VQ... vq) {
     static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
     constexpr int CS = 64 * D;
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
     // the rows in flight first, issued at the top priority (as encode16_kernel's: under oldest-first issue
     // they queue behind the computing waves' VALU work; c7 -0.4 %, profiles/r05/c7_ab/7_prio)
     __builtin_amdgcn_s_setprio(3);
-    load_channel_rows<D, 0, PX, EDGE>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, E.ch, raw);
+    load_channel_rows<D, 0, PX, EDGE, CT>(P, cube0 + (lane >> 3), cube0 + (lane >> 3) < P.n_cubes, lane & 7, 0, E.ch, raw);
     [[maybe_unused]] uint32_t ti = 0;  // QT = 2: the table of the lane's cube (a cube past the end: entry 0, never used)
     if constexpr (QT == 2) {
         const VqParams& V = vq_of(vq...);
@@ -363,7 +366,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
             const int sj = src & 7, sc = src >> 3;
             const int skz = (D == 8) ? sj : (sj >> 1), skx0 = (D == 8) ? 0 : (sj & 1) * 4;
             const uint32_t k = (uint32_t)((skz * 8 + bit / NB) * 8 + skx0 + bit % NB);
-            const int q = exact_coef<D, PX, EDGE, (QT != 0)>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4), rtab);
+            const int q = exact_coef<D, PX, EDGE, (QT != 0), CT>(R, cube0 + sc, k, lane, (int*)rs, (double*)(rs + kMaxGroupsDev * 4), rtab);
             if constexpr (PX != 1 || EDGE != 0) nrep++;
             if (lane == 0) *(uint16_t*)(wl + sc * CUBE_B + k1_code_off<D>(k)) = (uint16_t)(q > 0 ? 2 * q : 1 - 2 * q);
             if (lane == src) {
@@ -698,6 +701,39 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArg
     }
 }
 
+// The inverse colour transform of 4 packed pixels, the 12 bytes {a, b, c} = Y, Cb, Cr of pixel p at
+// bytes 3 p .. 3 p + 2, in place: with u = Cb - 128, v = Cr - 128
+//   R = clamp(Y + ((91881 v + 32768) >> 16)), G = clamp(Y + ((-22554 u - 46802 v + 32768) >> 16)),
+//   B = clamp(Y + ((116130 u + 32768) >> 16)), clamp to [0, 255], >> arithmetic.
+// Y enters the numerator as Y << 16 (an integer moves through the floor unchanged).  The factors fit 24 signed bits
+// and the numerators 32, so the 24-bit multiplies are exact.
+// The shifted values pass an empty asm before the clamp: left to itself the compiler fuses shift, clamp and pack
+// of two values into v_ashr_pk_u8_i32 and ORs the other two bytes into its result, taking the result's upper half
+// for zero; on the MI355X those bytes came back wrong (bytes 2 and 3 of every word).  So: one shift and
+// one v_med3_i32 per value, and the 12 bytes packed by v_perm_b32.
+__device__ __forceinline__ void ycc_to_rgb4(uint32_t& a, uint32_t& b, uint32_t& c) {
+    const uint32_t d[3] = {a, b, c};
+    uint32_t o[12];  // byte 3 p + i: component i of pixel p, in the low byte
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        int t[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) t[i] = (int)((d[(3 * p + i) >> 2] >> (8 * ((3 * p + i) & 3))) & 0xFFu);
+        const int y = (t[0] << 16) + 32768, u = t[1] - 128, v = t[2] - 128;
+        int rgb[3] = {(y + __mul24(91881, v)) >> 16, (y + __mul24(-22554, u) + __mul24(-46802, v)) >> 16,
+                      (y + __mul24(116130, u)) >> 16};
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            asm volatile("" : "+v"(rgb[i]));
+            o[3 * p + i] = (uint32_t)min(max(rgb[i], 0), 255);
+        }
+    }
+    constexpr uint32_t kPair = 0x0c0c0400u, kJoin = 0x05040100u;  // byte 0 of two registers; two such halves
+    a = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[3], o[2], kPair), __builtin_amdgcn_perm(o[1], o[0], kPair), kJoin);
+    b = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[7], o[6], kPair), __builtin_amdgcn_perm(o[5], o[4], kPair), kJoin);
+    c = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[11], o[10], kPair), __builtin_amdgcn_perm(o[9], o[8], kPair), kJoin);
+}
+
 // Packed RGB24, stream -> raster (dct3d_decode_eg_frames_dev, channels = 3): one Exp-Golomb stream per channel,
 // cube g of stream ch being channel ch of RGB cube g.  It is decode_rgb_kernel's loop over the three channels of
 // the wave's tile, each channel's staging filled as in decode_eg_kernel -- the window of stream ch at the tile's
@@ -705,7 +741,9 @@ __global__ __launch_bounds__(kBlock, 4) void decode_eg_kernel(typename DecodeArg
 // replay re-parses its cube from stream ch.  The channels' bytes are merged in registers and dec_store_tile<PX
 // = 3> writes every packed byte once.  One group per wave (no look-ahead across groups).  A launch whose
 // streams are not all valid (any front's verdict) writes nothing.
-template <int D, int EDGE = 0, int QT = 0, class... VQ>
+// CT = 1 (dct3d_ycc.hip; DCT3D_OPT_COLOUR): the streams hold Y, Cb, Cr; the merged bytes go through
+// ycc_to_rgb4 in registers before the one store.  Lanes that store nothing transform garbage.
+template <int D, int EDGE = 0, int QT = 0, int CT = 0, class... VQ>
 __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename DecodeArgs<QT>::type P, EgDecRgbParams E, VQ... vq) {
     static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
     using G = DecGeom<D>;
@@ -822,6 +860,12 @@ __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename Decod
                 out3[z][3 * wd + 1] = __builtin_amdgcn_perm(out3[z][3 * wd + 1], outw[z][wd], s1);
                 out3[z][3 * wd + 2] = __builtin_amdgcn_perm(out3[z][3 * wd + 2], outw[z][wd], s2);
             }
+    }
+    if constexpr (CT == 1) {  // Y, Cb, Cr -> R, G, B in place, 4 pixels (3 words) at a time
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NW; wd++) ycc_to_rgb4(out3[z][3 * wd], out3[z][3 * wd + 1], out3[z][3 * wd + 2]);
     }
     __builtin_amdgcn_s_setprio(2);  // the store phase ahead of the computing waves
     dec_store_tile<D, false, 3, EDGE>(P, wl, (int)(threadIdx.x & 63), cube0, out3, valid);

@@ -122,6 +122,35 @@ __device__ __forceinline__ uint2 rgb_pick8(const uint2 (&w)[3], int ch) {
     return make_uint2(__builtin_amdgcn_perm(w[1].x, __builtin_amdgcn_perm(w[0].y, w[0].x, s1), s2),
                       __builtin_amdgcn_perm(w[2].y, __builtin_amdgcn_perm(w[2].x, w[1].y, s1), s2));
 }
+// YCbCr (CT = 1: DCT3D_OPT_COLOUR): plane ch of the JFIF full-range BT.601 transform of the lane's 8
+// pixels in 16-bit fixed point, (cR R + cG G + cB B + off) >> 16.  The channel is launch-uniform: four scalar
+// constants.  Every numerator lies in [0, 2^24) (all 2^24 colours checked on the host, tests/test_ycc_ref.py),
+// so the 24-bit multiply-adds are exact and byte 2 of a numerator is the result: no clamp.
+__device__ __forceinline__ uint2 ycc_pick8(const uint2 (&w)[3], int ch) {
+    const int cr = ch == 0 ? 19595 : ch == 1 ? -11059 : 32768;
+    const int cg = ch == 0 ? 38470 : ch == 1 ? -21709 : -27439;
+    const int cb = ch == 0 ? 7471 : ch == 1 ? 32768 : -5329;
+    const int off = ch == 0 ? 32768 : (128 << 16) + 32767;
+    const uint32_t d[6] = {w[0].x, w[0].y, w[1].x, w[1].y, w[2].x, w[2].y};
+    uint32_t n[8];
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        int b[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) b[i] = (int)((d[(3 * p + i) >> 2] >> (8 * ((3 * p + i) & 3))) & 0xFFu);
+        n[p] = (uint32_t)(__mul24(cr, b[0]) + __mul24(cg, b[1]) + __mul24(cb, b[2]) + off);
+    }
+    // byte 2 of n[0..3] and of n[4..7]
+    constexpr uint32_t kPair = 0x0c0c0602u, kJoin = 0x05040100u;
+    return make_uint2(__builtin_amdgcn_perm(__builtin_amdgcn_perm(n[3], n[2], kPair), __builtin_amdgcn_perm(n[1], n[0], kPair), kJoin),
+                      __builtin_amdgcn_perm(__builtin_amdgcn_perm(n[7], n[6], kPair), __builtin_amdgcn_perm(n[5], n[4], kPair), kJoin));
+}
+// the 8 bytes of channel ch that a lane codes: the plane itself, or (CT = 1) the YCbCr plane
+template <int CT>
+__device__ __forceinline__ uint2 channel_pick8(const uint2 (&w)[3], int ch) {
+    if constexpr (CT == 1) return ycc_pick8(w, ch);
+    else return rgb_pick8(w, ch);
+}
 // Cube g of a packed RGB24 raster (stack s = g / cubes_per_stack) -> its cube in channel ch's block of
 // the output, layout [stack][channel][cube]; grey: g itself
 template <int PX>
@@ -176,7 +205,7 @@ __device__ __forceinline__ void load_cube_rows(const EncodeParams& P, uint32_t g
 }
 // The rows of channel ch alone (the rare paths' reloads, the fused encode's one channel per launch): one
 // row's 24 bytes in registers at a time.  Grey: the rows themselves.
-template <int N, int ZM, int PX, int EDGE>
+template <int N, int ZM, int PX, int EDGE, int CT = 0>
 __device__ __forceinline__ void load_channel_rows(const EncodeParams& P, uint32_t g, bool valid, int y, int h, int ch,
                                                   uint2 (&raw)[N]) {
     if constexpr (PX == 1) {
@@ -190,7 +219,7 @@ __device__ __forceinline__ void load_channel_rows(const EncodeParams& P, uint32_
             for (int z = 0; z < N; z++) {
                 uint2 w[PX];
                 row_load<PX, EDGE>(frame_src<ZM, EDGE>(e.p, h, z, P.plane), P.width, w);
-                raw[z] = edge_fix(rgb_pick8(w, ch), e.sh);
+                raw[z] = edge_fix(channel_pick8<CT>(w, ch), e.sh);
                 asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
             }
         }
@@ -679,7 +708,7 @@ struct ReplayIn {
     double cf;
     uint2 px, gr;
 };
-template <int D, int PX = 1, int EDGE = 0>
+template <int D, int PX = 1, int EDGE = 0, int CT = 0>
 __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g, uint32_t k, int lane) {
     constexpr int CS = 64 * D;
     ReplayIn in;
@@ -696,7 +725,7 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
             uint2 w[PX];
             row_load<PX, 1>(e.p + (size_t)z * R.plane, R.width, w);
             if constexpr (PX == 1) in.px = edge_fix(w[0], e.sh);
-            else in.px = edge_fix(rgb_pick8(w, R.ch), e.sh);
+            else in.px = edge_fix(channel_pick8<CT>(w, R.ch), e.sh);
         } else if constexpr (PX == 1) {
             const uint8_t* src = R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
                                  (size_t)(by * 8 + y) * R.width + bx * 8;
@@ -705,7 +734,7 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
             uint2 w[3];
             row_load<3, 0>(R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane +
                                3 * ((size_t)(by * 8 + y) * R.width + bx * 8), R.width, w);
-            in.px = rgb_pick8(w, R.ch);
+            in.px = channel_pick8<CT>(w, R.ch);
         }
         in.gr = *(const uint2*)(R.group_of + (size_t)k * CS + lane * 8);
     }
@@ -759,10 +788,10 @@ __device__ __forceinline__ int replay_fold(const ReplayIn& in, uint32_t k, int l
     wave_lds_sync();
     return q;
 }
-template <int D, int PX = 1, int EDGE = 0, int QT = 0>
+template <int D, int PX = 1, int EDGE = 0, int QT = 0, int CT = 0>
 __device__ __forceinline__ int exact_coef(const ReplayGeom& R, uint32_t g, uint32_t k, int lane, int* ssum,
                                           double* prod, const float4* tab = nullptr) {
-    return replay_fold<D, false, QT>(replay_load<D, PX, EDGE>(R, g, k, lane), k, lane, ssum, prod, tab);
+    return replay_fold<D, false, QT>(replay_load<D, PX, EDGE, CT>(R, g, k, lane), k, lane, ssum, prod, tab);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // dct3d_launch.h -- the five kernel families' launch ladders, each written once.  launch_*_in<Unit> walks the
 // variant's picks (dct3d_variant.h) and launches under `if constexpr (Unit::holds(...))`: a unit that
 // instantiates a ladder builds exactly the kernels its predicate admits, and answers -1 for any other variant
-// (a value outside an axis included).  A unit's launcher section is one explicit instantiation per family.
+// (a value outside an axis included).  The stream encode and the packed RGB24 stream decode also walk the colour
+// axis (with_variant_colour).  A unit's launcher section is one explicit instantiation per family.
 #pragma once
 #include "dct3d_eg_fused_dev.h"
 
@@ -39,10 +40,10 @@ template <class Unit>
 int launch_encode_eg_in(const Variant& v, const EncodeParams& P, const EgFusedParams& E, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     int rc = -1;
-    with_variant(v, [&](auto d, auto p, auto e, auto q) {
-        if constexpr (Unit::holds(d, p, e, q)) {
+    with_variant_colour(v, [&](auto d, auto p, auto e, auto q, auto ct) {
+        if constexpr (Unit::holds(d, p, e, q, ct)) {
             const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
-            hipLaunchKernelGGL((encode_eg_kernel<d, p, e, q>), grid, dim3(kBlock), 0, st, P, E);
+            hipLaunchKernelGGL((encode_eg_kernel<d, p, e, q, ct>), grid, dim3(kBlock), 0, st, P, E);
             rc = launched();
         }
     });
@@ -72,11 +73,11 @@ template <class Unit>
 int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     int rc = -1;
-    with_variant(v, [&](auto d, auto p, auto e, auto q) {
-        if constexpr (p == 3 && Unit::holds(d, p, e, q)) {
+    with_variant_colour(v, [&](auto d, auto p, auto e, auto q, auto ct) {
+        if constexpr (p == 3 && Unit::holds(d, p, e, q, ct)) {
             if (q && !P.steps) return;
             const dim3 grid(dec_grid(d, P.n_cubes - P.cube_base));
-            hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, q>), grid, dim3(kBlock), 0, st, P, E);
+            hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, q, ct>), grid, dim3(kBlock), 0, st, P, E);
             rc = launched();
         }
     });

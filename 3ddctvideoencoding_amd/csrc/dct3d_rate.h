@@ -21,6 +21,8 @@ struct RateParams {
 
 // px = 1 grey | 3 packed RGB24, edge = 0 | 1 (frames of any size)
 int launch_rate(int D, int px, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st);
+// packed RGB24 with the YCbCr colour transform: channel R.ch of the Y, Cb, Cr planes (dct3d_ycc.hip)
+int launch_rate_ycc(int D, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st);
 // out[r] = the sum of cube_bits[r * run .. r * run + run), r < n_runs
 int launch_rate_sum(const uint16_t* cube_bits, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st);
 

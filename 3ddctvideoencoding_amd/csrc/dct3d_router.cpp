@@ -19,7 +19,7 @@ int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams
 }
 // (no packed RGB24 variant is in StreamPlain, which builds no such ladder)
 int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st) {
-    using RgbUnits = Units<StreamFrames, StreamQuant>;
+    using RgbUnits = Units<StreamFrames, StreamQuant, StreamYcc>;
     return RgbUnits::route(v, [&](auto u) { return launch_decode_eg_rgb_in<decltype(u)>(v, P, E, st); });
 }
 

@@ -79,6 +79,7 @@ struct dct3d_ctx {
     bool opt_eg_force_retry = false;
     bool opt_eg_fused_front = false;
     int opt_eg_dec_groups = 0;  // fused stream decode: groups per wave (0: the default, 8)
+    int opt_colour = 0;            // DCT3D_OPT_COLOUR: 1 = the packed RGB24 stream calls and the rate probe code Y, Cb, Cr
     bool opt_quant_force = false;  // the table kernels even for the reference table (DCT3D_OPT_QUANT_FORCE_TABLE)
     // certify-or-replay state
     uint64_t last_units = 0;
@@ -305,6 +306,14 @@ static int upload_quant_tables(dct3d_ctx* c) {
 static Variant variant_of(const dct3d_ctx* c, const Geom& g) {
     return Variant{c->bd, g.px, g.edge(), !c->plan.reference_quant || c->opt_quant_force};
 }
+// the stream kernels' and the rate probe's: the colour transform acts on packed RGB24 alone
+static Variant stream_variant_of(const dct3d_ctx* c, const Geom& g) {
+    Variant v = variant_of(c, g);
+    v.colour = (c->opt_colour && g.px == 3) ? 1 : 0;
+    return v;
+}
+// a call on packed frames that has no colour stage refuses the option (dct3d.h)
+static bool colour_refused(const dct3d_ctx* c, int px) { return c && c->opt_colour && px == 3; }
 static const double* qt_steps(const dct3d_ctx* c) { return (const double*)c->d_tabs64.p + kQtStepOff; }
 
 int dct3d_ctx_set_quant(dct3d_ctx* c, const int32_t* steps, int n) {
@@ -462,6 +471,10 @@ int dct3d_ctx_set_option(dct3d_ctx* c, int option, double value) {
         case DCT3D_OPT_EG_FORCE_RETRY: c->opt_eg_force_retry = value != 0.0; return DCT3D_OK;
         case DCT3D_OPT_EG_FUSED_FRONT: c->opt_eg_fused_front = value != 0.0; return DCT3D_OK;
         case DCT3D_OPT_QUANT_FORCE_TABLE: c->opt_quant_force = value != 0.0; return DCT3D_OK;
+        case DCT3D_OPT_COLOUR:
+            if (value != (double)DCT3D_COLOUR_PLANES && value != (double)DCT3D_COLOUR_YCBCR) return DCT3D_EINVAL;
+            c->opt_colour = (int)value;
+            return DCT3D_OK;
         case DCT3D_OPT_EG_DEC_GROUPS:
             if (value != 0.0 && value != 1.0 && value != 2.0 && value != 4.0 && value != 8.0) return DCT3D_EINVAL;
             c->opt_eg_dec_groups = (int)value;
@@ -657,7 +670,7 @@ static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q
 // the arguments every raster call shares, and its geometry
 static int check_args(const dct3d_ctx* c, const void* a, const void* b, int w, int h, int px, int n_stacks, bool any_size,
                       Geom* g, uint64_t* n_cubes) {
-    if (!c || ((!a || !b) && n_stacks)) return DCT3D_EINVAL;
+    if (!c || ((!a || !b) && n_stacks) || colour_refused(c, px)) return DCT3D_EINVAL;
     return make_geom(w, h, px, n_stacks, any_size, g, n_cubes) ? DCT3D_OK : DCT3D_EINVAL;
 }
 
@@ -1074,8 +1087,10 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    const Variant v = variant_of(c, g);
-    if (c->vq ? launch_encode_eg_vq(v.D, v.px, v.edge, P, E, *c->vq, c->stream) : launch_encode_eg(v, P, E, c->stream))
+    const Variant v = stream_variant_of(c, g);
+    if (c->vq ? (v.colour ? launch_encode_eg_vq_ycc(v.D, v.edge, P, E, *c->vq, c->stream)
+                          : launch_encode_eg_vq(v.D, v.px, v.edge, P, E, *c->vq, c->stream))
+              : launch_encode_eg(v, P, E, c->stream))
         return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
@@ -1183,6 +1198,7 @@ int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int
     uint64_t n_cubes;
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !d_out || !out_cap || !total_bits) return DCT3D_EINVAL;
+    if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;  // the int32 intermediate has no colour stage
     if (eg_aligned(g))
         return dct3d_encode_eg_dev(c, d_frames, w, h, n_stacks, carry_byte[0], carry_bits[0], d_out[0], out_cap[0], total_bits);
     if (!d_frames && n_stacks) return DCT3D_EINVAL;
@@ -1208,6 +1224,7 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
     uint64_t n_cubes;
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !total_bits) return DCT3D_EINVAL;
+    if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;
     if (eg_aligned(g)) return dct3d_encode_eg(c, frames, w, h, n_stacks, carry_byte[0], carry_bits[0], total_bits);
     if (!frames && n_stacks) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
@@ -1351,7 +1368,7 @@ static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n
         R.dec_E = DP.dec_E;
         R.dec_l1_max = DP.dec_l1_max;
     }
-    const Variant v = variant_of(c, g);  // (the probes read tables of their own: no qt)
+    const Variant v = stream_variant_of(c, g);  // (the probes read tables of their own: no qt; colour: the rate probe)
     hipEvent_t* ev = timer_begin(c);
     rc = DCT3D_OK;
     // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
@@ -1365,7 +1382,9 @@ static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n
                 R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
                 R.cube_sse = cube_sse + (size_t)t0 * stride;
             }
-            if (dist ? launch_distortion(v.D, v.px, v.edge, P, R, c->stream) : launch_rate(v.D, v.px, v.edge, P, R, c->stream))
+            if (dist       ? launch_distortion(v.D, v.px, v.edge, P, R, c->stream)
+                : v.colour ? launch_rate_ycc(v.D, v.edge, P, R, c->stream)
+                           : launch_rate(v.D, v.px, v.edge, P, R, c->stream))
                 rc = DCT3D_EKERNEL;
             else c->slot_used = true;
         }
@@ -1443,6 +1462,7 @@ int dct3d_distortion_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, in
     Geom g;
     uint64_t n_cubes;
     if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (colour_refused(c, channels)) return DCT3D_EINVAL;
     return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, sse, bits, d_cube_sse, nullptr);
 }
 
@@ -1451,6 +1471,7 @@ int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, i
     Geom g;
     uint64_t n_cubes;
     if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (colour_refused(c, channels)) return DCT3D_EINVAL;
     return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits);
 }
 
@@ -1663,7 +1684,7 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
     fill_decode_params(c, P, nullptr, out_stack0 - (size_t)st0 * g.plane() * D, g, (st0 + ns) * cps);
     P.cube_base = (uint32_t)(st0 * cps);
     P.steps = qt_steps(c);
-    const Variant v = variant_of(c, g);
+    const Variant v = stream_variant_of(c, g);
     hipEvent_t* ev = timer_begin(c);
     int lrc;
     if (g.px == 3) {
@@ -1671,7 +1692,9 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = c->vq ? launch_decode_eg_rgb_vq(v.D, v.edge, P, R, *c->vq, c->stream) : launch_decode_eg_rgb(v, P, R, c->stream);
+        lrc = !c->vq    ? launch_decode_eg_rgb(v, P, R, c->stream)
+              : v.colour ? launch_decode_eg_rgb_vq_ycc(v.D, v.edge, P, R, *c->vq, c->stream)
+                         : launch_decode_eg_rgb_vq(v.D, v.edge, P, R, *c->vq, c->stream);
     } else if (c->vq) {  // (the map is indexed by the call's stacks: the chunks' cube indices are the call's)
         lrc = launch_decode_eg_vq(v.D, v.edge, P, E[0], *c->vq, c->stream);
     } else {  // (the test option's groups per wave: where the variant's unit builds them)
@@ -1781,6 +1804,7 @@ int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], con
     uint64_t n_cubes;
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!d_bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
+    if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;  // the int32 intermediate has no colour stage
     if (eg_aligned(g)) return dct3d_decode_eg_dev(c, d_bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, d_frames, end_bit);
     if (n_stacks && !d_frames) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
@@ -1824,6 +1848,7 @@ int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uin
     uint64_t n_cubes;
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
+    if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;
     int rc;
     if (eg_aligned(g)) return dct3d_decode_eg(c, bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, frames, end_bit);
     if (n_stacks && !frames) return DCT3D_EINVAL;

@@ -1,5 +1,5 @@
-// dct3d_variant.h -- a kernel's variant (depth, pixel format, edge, quantiser table), the picks that turn the
-// runtime's values into template arguments, and which translation unit holds which variant: the one place that
+// dct3d_variant.h -- a kernel's variant (depth, pixel format, edge, quantiser table, colour transform), the picks
+// that turn the runtime's values into template arguments, and which translation unit holds which variant: the one place that
 // says so.  A unit instantiates what its predicate admits (dct3d_launch.h) and the router sends a variant to
 // the unit whose predicate admits it (dct3d_router.cpp), so the two cannot disagree.
 // Plain C++ (no HIP include): the units, the router, the runtime and a CPU test (tests/test_variant.py) share it.
@@ -9,9 +9,11 @@
 namespace dct3d {
 
 // D: 8 | 4 frames per cube.  px: 1 grey | 3 packed RGB24.  edge: 1 = the width or the height is no multiple of 8
-// (padding and crop in the addressing).  qt: 1 = the steps come from the context's table.
+// (padding and crop in the addressing).  qt: 1 = the steps come from the context's table.  colour: 1 = the three
+// streams of packed RGB24 hold the Y, Cb, Cr planes (DCT3D_OPT_COLOUR; px = 3 and the stream family only).
 struct Variant {
     int D, px, edge, qt;
+    int colour = 0;
 };
 
 template <int V>
@@ -52,33 +54,47 @@ bool with_variant(const Variant& v, F&& f) {
     with_variant(v.D, v.px, v.edge, [&](auto d, auto p, auto e) { called = with_flag(v.qt, [&](auto q) { f(d, p, e, q); }); });
     return called;
 }
+// f(d, p, e, q, ct): the colour axis as well (the stream ladders of packed RGB24)
+template <class F>
+bool with_variant_colour(const Variant& v, F&& f) {
+    bool called = false;
+    with_variant(v, [&](auto d, auto p, auto e, auto q) { called = with_flag(v.colour, [&](auto ct) { f(d, p, e, q, ct); }); });
+    return called;
+}
 
 // ---- which unit holds which variant.  Raster: the int32 encode and decode kernels.  Stream: the fused
-//      Exp-Golomb encode and the two stream decodes (grey: px = 1, RGB: px = 3). ----
+//      Exp-Golomb encode and the two stream decodes (grey: px = 1, RGB: px = 3).  A variant with the colour
+//      transform belongs to StreamYcc whatever its edge and table, and to no raster unit. ----
 struct RasterPlain {  // dct3d_kernels.hip
-    static constexpr bool holds(int, int px, int edge, int qt) { return px == 1 && !edge && !qt; }
+    static constexpr bool holds(int, int px, int edge, int qt, int colour = 0) { return px == 1 && !edge && !qt && !colour; }
 };
 struct RasterRgb {  // dct3d_rgb.hip
-    static constexpr bool holds(int, int px, int edge, int qt) { return px == 3 && !edge && !qt; }
+    static constexpr bool holds(int, int px, int edge, int qt, int colour = 0) { return px == 3 && !edge && !qt && !colour; }
 };
 struct RasterEdge {  // dct3d_edge.hip
-    static constexpr bool holds(int, int, int edge, int qt) { return edge && !qt; }
+    static constexpr bool holds(int, int, int edge, int qt, int colour = 0) { return edge && !qt && !colour; }
 };
 struct RasterQuant {  // dct3d_quant.hip
-    static constexpr bool holds(int, int, int, int qt) { return qt; }
+    static constexpr bool holds(int, int, int, int qt, int colour = 0) { return qt && !colour; }
 };
 // all_groups: the grey stream decode at 1 | 2 | 4 | 8 groups of cubes per wave (else: 8 alone, the default)
 struct StreamPlain {  // dct3d_kernels.hip
     static constexpr bool all_groups = true;
-    static constexpr bool holds(int, int px, int edge, int qt) { return px == 1 && !edge && !qt; }
+    static constexpr bool holds(int, int px, int edge, int qt, int colour = 0) { return px == 1 && !edge && !qt && !colour; }
 };
 struct StreamFrames {  // dct3d_eg_frames.hip
     static constexpr bool all_groups = false;
-    static constexpr bool holds(int D, int px, int edge, int qt) { return !qt && !StreamPlain::holds(D, px, edge, qt); }
+    static constexpr bool holds(int D, int px, int edge, int qt, int colour = 0) {
+        return !qt && !colour && !StreamPlain::holds(D, px, edge, qt);
+    }
 };
 struct StreamQuant {  // dct3d_quant_eg.hip
     static constexpr bool all_groups = false;
-    static constexpr bool holds(int, int, int, int qt) { return qt; }
+    static constexpr bool holds(int, int, int, int qt, int colour = 0) { return qt && !colour; }
+};
+struct StreamYcc {  // dct3d_ycc.hip
+    static constexpr bool all_groups = false;
+    static constexpr bool holds(int, int px, int, int, int colour = 0) { return px == 3 && colour == 1; }
 };
 
 // f(Const<groups>): the grey stream decode's groups per wave in unit U (a count U does not build: 8)
@@ -97,27 +113,30 @@ void with_groups(int groups_per_wave, F&& f) {
 // A family's units.  index: the unit that holds v (-1: none); route: f(U{}) for that unit, or -1.
 template <class... U>
 struct Units {
-    static constexpr int count(const Variant& v) { return (int(U::holds(v.D, v.px, v.edge, v.qt)) + ...); }
+    static constexpr int count(const Variant& v) { return (int(U::holds(v.D, v.px, v.edge, v.qt, v.colour)) + ...); }
     static constexpr int index(const Variant& v) {
         int i = 0, at = -1;
-        ((U::holds(v.D, v.px, v.edge, v.qt) ? (at = i++) : i++), ...);
+        ((U::holds(v.D, v.px, v.edge, v.qt, v.colour) ? (at = i++) : i++), ...);
         return at;
     }
     template <class F>
     static int route(const Variant& v, F&& f) {
         int rc = -1;
-        (void)((U::holds(v.D, v.px, v.edge, v.qt) && (rc = f(U{}), true)) || ...);
+        (void)((U::holds(v.D, v.px, v.edge, v.qt, v.colour) && (rc = f(U{}), true)) || ...);
         return rc;
     }
-    // every variant in exactly one unit
-    static constexpr bool partition() {
-        for (int i = 0; i < 16; i++)
-            if (count(Variant{i & 8 ? 8 : 4, i & 4 ? 3 : 1, (i >> 1) & 1, i & 1}) != 1) return false;
+    // every variant in exactly one unit; with the colour transform: the packed RGB24 variants of a family that
+    // has the transform (colour_px3) in exactly one unit, every other one in none
+    static constexpr bool partition(bool colour_px3) {
+        for (int i = 0; i < 32; i++) {
+            const Variant v{i & 8 ? 8 : 4, i & 4 ? 3 : 1, (i >> 1) & 1, i & 1, i >> 4};
+            if (count(v) != (v.colour ? int(colour_px3 && v.px == 3) : 1)) return false;
+        }
         return true;
     }
 };
 using RasterUnits = Units<RasterPlain, RasterRgb, RasterEdge, RasterQuant>;
-using StreamUnits = Units<StreamPlain, StreamFrames, StreamQuant>;
-static_assert(RasterUnits::partition() && StreamUnits::partition(), "each variant belongs to one unit of its family");
+using StreamUnits = Units<StreamPlain, StreamFrames, StreamQuant, StreamYcc>;
+static_assert(RasterUnits::partition(false) && StreamUnits::partition(true), "each variant belongs to one unit of its family");
 
 }  // namespace dct3d

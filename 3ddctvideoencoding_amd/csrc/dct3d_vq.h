@@ -36,6 +36,9 @@ __host__ __device__ inline const uint8_t* vq_map_behind(const double* steps) {
 int launch_encode_eg_vq(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st);
 int launch_decode_eg_vq(int D, int edge, const DecodeParams& P, const EgDecParams& E, const VqParams& V, hipStream_t st);
 int launch_decode_eg_rgb_vq(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st);
+// the same with the YCbCr colour transform (dct3d_ycc.hip; packed RGB24 alone)
+int launch_encode_eg_vq_ycc(int D, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st);
+int launch_decode_eg_rgb_vq_ycc(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st);
 // A call's block (steps, FastDiv, map, rows: some KiB) from the context's pinned host copy -- src, its device-side
 // address -- to device memory, as a kernel on the call's stream: a copy-engine transfer in front of the first
 // kernel cost the call a hand-over between two queues, longer than the transfer itself.

@@ -25,7 +25,7 @@ int launch_decode_eg_rgb_vq(int D, int edge, const DecodeParams& P, const EgDecR
     int rc = -1;
     with_variant(D, 3, edge, [&](auto d, auto, auto e) {
         const dim3 grid(dec_grid(d, P.n_cubes - P.cube_base));
-        hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
+        hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, 0, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
         rc = launched();
     });
     return rc;

@@ -24,7 +24,7 @@ int launch_encode_eg_vq(int D, int px, int edge, const EncodeParams& P, const Eg
     int rc = -1;
     with_variant(D, px, edge, [&](auto d, auto p, auto e) {
         const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
-        hipLaunchKernelGGL((encode_eg_kernel<d, p, e, 2, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
+        hipLaunchKernelGGL((encode_eg_kernel<d, p, e, 2, 0, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
         rc = launched();
     });
     return rc;

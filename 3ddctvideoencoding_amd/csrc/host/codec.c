@@ -54,6 +54,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
                       int depth, int batch, int channels);
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels);
+static int host_eg_on(void);
 static int geometry_ok(int width, int height, int frames, int depth) {
     return width > 0 && height > 0 && frames > 0 && (depth == 8 || depth == 4);
 }
@@ -322,6 +323,50 @@ static int reject_qmap(const char *what) {
     if (!text || !text[0]) return 0;
     printf("qmap= applies to single-device encodes and decodes only (%s)\n", what);
     return 1;
+}
+
+static char g_colour_text[16]; /* codec_set_colour's text; "": none */
+
+int codec_set_colour(const char *text) {
+    if (text && strlen(text) >= sizeof(g_colour_text)) return 1;
+    snprintf(g_colour_text, sizeof(g_colour_text), "%s", text ? text : "");
+    return 0;
+}
+/* The colour mode of a call on `channels` channels: codec_set_colour's text, else DCT3D_CODEC_YCC ("1", "0" or the
+ * text).  *ycc = 1: the Y, Cb, Cr planes.  1 after printing when the text is no "ycc=0|1", or the mode is on for a
+ * call that has no colour stage: grey (what names it), a PSNR target, the host Exp-Golomb path. */
+static int call_colour(const char *what, int channels, int psnr_set, int *ycc) {
+    const char *text = g_colour_text[0] ? g_colour_text : getenv("DCT3D_CODEC_YCC");
+    *ycc = 0;
+    if (!text || !text[0]) return 0;
+    const char *v = strncmp(text, "ycc=", 4) ? text : text + 4;
+    if ((v[0] != '0' && v[0] != '1') || v[1]) {
+        printf("Invalid colour mode '%s': ycc=0 or ycc=1\n", text);
+        return 1;
+    }
+    if (v[0] == '0') return 0;
+    if (channels != 3) {
+        printf("ycc= applies to encode_rgb and decode_rgb on one device (%s)\n", what);
+        return 1;
+    }
+    if (psnr_set) {
+        printf("ycc=1 and psnr= exclude each other: the distortion probe would measure the Y, Cb, Cr planes, not the "
+               "RGB samples\n");
+        return 1;
+    }
+    if (host_eg_on()) {
+        printf("ycc=1 needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
+    *ycc = 1;
+    return 0;
+}
+/* the context of a call codes the Y, Cb, Cr planes: 1 after printing on an error */
+static int ctx_apply_colour(dct3d_ctx *ctx, int ycc) {
+    if (!ycc) return 0;
+    const int rc = dct3d_ctx_set_option(ctx, DCT3D_OPT_COLOUR, DCT3D_COLOUR_YCBCR);
+    if (rc) printf("Error setting the colour transform: %s\n", dct3d_strerror(rc));
+    return rc != 0;
 }
 /* reads the call's map into ladder indices, one per stack: 1 after printing on an error */
 static int read_qmap(const char *path, int n_stacks, uint8_t *index) {
@@ -609,6 +654,8 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
         return 1;
     }
     if (reject_targets("encode_multi") || reject_qmap("encode_multi")) return 1;
+    int ycc;
+    if (call_colour("encode_multi", 1, 0, &ycc)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -719,6 +766,8 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         return 1;
     }
     if (reject_targets("decode_multi") || reject_qmap("decode_multi")) return 1;
+    int ycc;
+    if (call_colour("decode_multi", 1, 0, &ycc)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -861,6 +910,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     double psnr_db = 0.0;
     int psnr_set = 0;
     if (call_target(SEL_PSNR, &psnr_db, &psnr_set)) return 1;
+    int ycc;
+    if (call_colour("encode", channels, psnr_set, &ycc)) return 1;
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
     const char *qmap_path = NULL;
     if (call_qmap(&qmap_path)) return 1;
@@ -913,7 +964,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
         } else {
-            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth));
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth; /* of the frames as they are */
@@ -1029,6 +1080,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
 static int decode_any(const char *inName, const char *outName, int width, int height, int frames, int platformIndex,
                       int depth, int batch, int channels) {
     if (reject_targets("decode")) return 1;
+    int ycc;
+    if (call_colour("decode", channels, 0, &ycc)) return 1;
     const char *qmap_path = NULL;
     if (call_qmap(&qmap_path)) return 1;
     uint8_t *qmap = NULL;
@@ -1071,7 +1124,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
         } else {
-            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth));
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth;

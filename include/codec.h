@@ -143,6 +143,21 @@ int codec_set_psnr(const char *text);
 int codec_parse_qmap(const char *path, int nStacks, int *qualities);
 int codec_set_qmap(const char *text);
 
+/* The colour transform of the packed RGB24 calls on one device (encode_rgb_ex, decode_rgb_ex): "ycc=1" codes the Y,
+ * Cb and Cr planes of the frames (dct3d.h, DCT3D_OPT_COLOUR = DCT3D_COLOUR_YCBCR: JFIF full-range BT.601 in 16-bit
+ * fixed point, computed inside the device stream calls) in place of their R, G and B planes; "ycc=0" is none.  The
+ * three files then hold Y, Cb, Cr under the names .red / .green / .blue; they are byte for byte what encode_rgb_ex
+ * without it writes for the transformed frames.  The .bin does not record the mode, as it does not record the
+ * quantiser: decode with the ycc= of the encode.  rate=, and rate= with qmap=, price the transformed planes.
+ * Errors (a line printed, 1 returned, before any output file is made): a text that is neither "ycc=0" nor "ycc=1";
+ * ycc=1 on a grey call or a several-device call; ycc=1 with psnr= (the distortion probe measures planes, and the
+ * Y, Cb, Cr planes' error is not the samples'); ycc=1 with DCT3D_CODEC_HOST_EG=1 (the int32 path has no colour
+ * stage).
+ * codec_set_colour: the mode of every later call of this process, as such a text; NULL or "": none.  It overrides
+ *   the environment variable DCT3D_CODEC_YCC ("1" or "0", or the text itself).  1 (nothing changes) if the text is
+ *   too long to keep. */
+int codec_set_colour(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

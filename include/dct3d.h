@@ -149,7 +149,44 @@ int dct3d_ctx_info(const dct3d_ctx *ctx, int *device, int *block_d, void **hip_s
 #define DCT3D_OPT_QUANT_FORCE_TABLE 11 /* test: 1: a context whose quantiser is the reference table runs the
                                          table kernels (dct3d_ctx_set_quant) too, reading max(1, 5 s) from
                                          the table instead of having it in their text */
+/* Not a test option: the colour transform of the packed RGB24 stream calls and the rate probe (additive to ABI
+ * 9; see "YCbCr colour transform" below).  Values DCT3D_COLOUR_PLANES (0, the default) and DCT3D_COLOUR_YCBCR
+ * (1); any other value: DCT3D_EINVAL. */
+#define DCT3D_OPT_COLOUR 12
+#define DCT3D_COLOUR_PLANES 0
+#define DCT3D_COLOUR_YCBCR 1
 int dct3d_ctx_set_option(dct3d_ctx *ctx, int option, double value);
+
+/* ---------------------------------------------------------------------------------------------
+ * YCbCr colour transform (additive to ABI 9).  With DCT3D_OPT_COLOUR =
+ * DCT3D_COLOUR_YCBCR the three streams of a packed RGB24 call hold the Y, Cb and Cr planes of the frames
+ * instead of their R, G and B planes.  The transform is JFIF full-range BT.601 in 16-bit fixed point and is
+ * DEFINED by these integers (>> arithmetic, i.e. floor; all inputs and outputs bytes):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   u = Cb - 128, v = Cr - 128
+ *   R' = clamp(Y + (( 91881 v + 32768) >> 16), 0, 255)
+ *   G' = clamp(Y + ((-22554 u - 46802 v + 32768) >> 16), 0, 255)
+ *   B' = clamp(Y + ((116130 u + 32768) >> 16), 0, 255)
+ * Write T for the forward transform of a packed raster (Y, Cb, Cr in the places of R, G, B) and T^-1 for the
+ * inverse.  With channels == 3 and the option on:
+ *   dct3d_encode_eg_frames[_dev], dct3d_encode_eg_frames_vq[_dev]  give, on `frames`, every result the same
+ *       call gives with the option off on T(frames): the streams byte for byte, total_bits[ch], DCT3D_ENOSPC,
+ *       the statistics;
+ *   dct3d_rate_frames[_dev]  likewise: bits, d_cube_bits, n_flagged;
+ *   dct3d_decode_eg_frames[_dev], dct3d_decode_eg_frames_vq[_dev]  write T^-1 of the frames the same call
+ *       writes with the option off; end_bit[ch], the error codes and the statistics are unchanged.
+ * The transform runs inside those calls' kernels, on the bytes a lane holds anyway: no launch and no memory
+ * traffic is added.  A round trip T^-1(T(x)) is off by at most 1 per sample before any quantisation.
+ * With channels == 1 the option does nothing (the same kernels run).  The calls that have no colour stage
+ * refuse the option instead of ignoring it -- DCT3D_EINVAL, nothing launched, the next call unaffected:
+ *   dct3d_encode_frames* / dct3d_decode_frames* with channels == 3 and dct3d_*_stacks_rgb* (int32 cubes);
+ *   dct3d_distortion_frames* with channels == 3 (its error would be the Y, Cb, Cr planes', not the samples');
+ *   the _eg_frames* calls with channels == 3 on a context that also has DCT3D_OPT_EG_TWO_STEP (the _vq calls
+ *       refuse that option anyway).
+ * DCT3D_OPT_DEC_MARGIN, DCT3D_OPT_EG_NO_RESOLVE and DCT3D_OPT_EG_FORCE_RETRY act as without the option.
+ * ------------------------------------------------------------------------------------------- */
 
 /* ---------------------------------------------------------------------------------------------
  * Quantiser tables (additive to ABI 9).  A quantiser is one integer step per s = kx + ky + kz of a
