@@ -12,9 +12,8 @@
 namespace dct3d {
 
 // QT of the three kernels below: 0 the reference's steps (in the text), 1 the context's table, 2 a table per
-// stack.  QT = 2 exists on the device side only -- Variant::qt stays {0, 1}; the vq launchers pick it by depth,
-// pixel format and edge -- and brings one more kernel argument, the call's VqParams, as the kernel's trailing
-// pack: empty for QT 0 and 1, whose parameters and launch sites are the same with and without it.
+// stack: Variant::qt in the stream family (dct3d_variant.h).  QT = 2 brings one more kernel argument, the call's
+// VqParams, as the kernel's trailing pack: empty for QT 0 and 1, whose parameters are the same with and without it.
 static_assert(kVqTabN == kTabN, "a palette table's rows as the encode kernels'");
 __device__ __forceinline__ const VqParams& vq_of(const VqParams& V) { return V; }  // the pack's one element
 

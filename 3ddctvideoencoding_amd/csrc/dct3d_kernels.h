@@ -244,16 +244,22 @@ int launch_decode(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
 // The fused Exp-Golomb kernels: channel E.ch of the RGB cubes per encode launch; P.cube_base: the decode's first
 // cube (a chunk of whole stacks).  Grey stream decode: groups_per_wave = 1, 2, 4 or 8 groups of CPW cubes per
 // wave, the next one's loads ahead, in the variant of grey multiples of 8 and the reference steps (every other
-// value, every other variant: 8).  Packed RGB24 stream decode: from three streams.
-int launch_encode_eg(const Variant& v, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
-int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, hipStream_t st);
-int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
+// value, every other variant: 8).  Packed RGB24 stream decode: from three streams.  V: the call's palette and map
+// (dct3d_vq.h) for qt = 2, a table per stack; else nullptr.
+struct VqParams;
+int launch_encode_eg(const Variant& v, const EncodeParams& P, const EgFusedParams& E, const VqParams* V, hipStream_t st);
+int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, const VqParams* V,
+                     hipStream_t st);
+int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st);
 template <class Unit> int launch_encode_in(const Variant& v, const EncodeParams& P, hipStream_t st);
 template <class Unit> int launch_decode_in(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
-template <class Unit> int launch_encode_eg_in(const Variant& v, const EncodeParams& P, const EgFusedParams& E, hipStream_t st);
 template <class Unit>
-int launch_decode_eg_in(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, hipStream_t st);
-template <class Unit> int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, hipStream_t st);
+int launch_encode_eg_in(const Variant& v, const EncodeParams& P, const EgFusedParams& E, const VqParams* V, hipStream_t st);
+template <class Unit>
+int launch_decode_eg_in(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, const VqParams* V,
+                        hipStream_t st);
+template <class Unit>
+int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =
 // segments, P.bits = seg_bits)

@@ -163,7 +163,7 @@ int launch_cube_f32(int D, bool inverse, const float* in, float* out, uint32_t n
 // output stores were 26 % slower: profiles/r01/decode_variant_sweep.txt).
 template int launch_encode_in<RasterPlain>(const Variant&, const EncodeParams&, hipStream_t);
 template int launch_decode_in<RasterPlain>(const Variant&, const DecodeParamsQ&, hipStream_t);
-template int launch_encode_eg_in<StreamPlain>(const Variant&, const EncodeParams&, const EgFusedParams&, hipStream_t);
-template int launch_decode_eg_in<StreamPlain>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, hipStream_t);
+template int launch_encode_eg_in<StreamPlain>(const Variant&, const EncodeParams&, const EgFusedParams&, const VqParams*, hipStream_t);
+template int launch_decode_eg_in<StreamPlain>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, const VqParams*, hipStream_t);
 
 }  // namespace dct3d

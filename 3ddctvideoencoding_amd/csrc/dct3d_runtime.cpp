@@ -306,9 +306,12 @@ static int upload_quant_tables(dct3d_ctx* c) {
 static Variant variant_of(const dct3d_ctx* c, const Geom& g) {
     return Variant{c->bd, g.px, g.edge(), !c->plan.reference_quant || c->opt_quant_force};
 }
-// the stream kernels' and the rate probe's: the colour transform acts on packed RGB24 alone
+// the stream kernels' and the rate probe's: the colour transform acts on packed RGB24 alone; qt = 2 while a vq
+// call is open (vq_begin .. vq_end: a table per stack, c->vq; the one place that turns it into a variant.  No
+// probe runs inside one, and probe_dev reads no qt)
 static Variant stream_variant_of(const dct3d_ctx* c, const Geom& g) {
     Variant v = variant_of(c, g);
+    if (c->vq) v.qt = 2;
     v.colour = (c->opt_colour && g.px == 3) ? 1 : 0;
     return v;
 }
@@ -1087,11 +1090,7 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    const Variant v = stream_variant_of(c, g);
-    if (c->vq ? (v.colour ? launch_encode_eg_vq_ycc(v.D, v.edge, P, E, *c->vq, c->stream)
-                          : launch_encode_eg_vq(v.D, v.px, v.edge, P, E, *c->vq, c->stream))
-              : launch_encode_eg(v, P, E, c->stream))
-        return DCT3D_EKERNEL;
+    if (launch_encode_eg(stream_variant_of(c, g), P, E, c->vq, c->stream)) return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
     if (ev) (void)hipEventRecord(ev[2], c->stream);
@@ -1692,13 +1691,10 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = !c->vq    ? launch_decode_eg_rgb(v, P, R, c->stream)
-              : v.colour ? launch_decode_eg_rgb_vq_ycc(v.D, v.edge, P, R, *c->vq, c->stream)
-                         : launch_decode_eg_rgb_vq(v.D, v.edge, P, R, *c->vq, c->stream);
-    } else if (c->vq) {  // (the map is indexed by the call's stacks: the chunks' cube indices are the call's)
-        lrc = launch_decode_eg_vq(v.D, v.edge, P, E[0], *c->vq, c->stream);
-    } else {  // (the test option's groups per wave: where the variant's unit builds them)
-        lrc = launch_decode_eg(v, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->stream);
+        lrc = launch_decode_eg_rgb(v, P, R, c->vq, c->stream);
+    } else {  // (the test option's groups per wave: where the variant's unit builds them.  A vq call's map is
+              // indexed by the call's stacks: the chunks' cube indices are the call's)
+        lrc = launch_decode_eg(v, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->vq, c->stream);
     }
     if (lrc) return DCT3D_EKERNEL;
     timer_end(c, ev);

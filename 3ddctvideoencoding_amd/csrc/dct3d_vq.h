@@ -1,8 +1,8 @@
 // dct3d_vq.h -- per-stack quantiser tables in the fused stream calls (dct3d_encode_eg_frames_vq* /
-// dct3d_decode_eg_frames_vq*): the kernels' extra parameter and their launchers (dct3d_vq_enc.hip,
-// dct3d_vq_dec.hip), shared with the C-ABI runtime.  The kernels are the QT = 2 instances of the shared stream
-// kernels (dct3d_eg_fused_dev.h, which includes this header for VqParams), beside the variant's qt axis: they are
-// routed by depth, pixel format and edge alone.
+// dct3d_decode_eg_frames_vq*): the kernels' extra parameter and the upload of a call's block,
+// shared with the C-ABI runtime.  The kernels are the QT = 2 instances of the shared stream kernels
+// (dct3d_eg_fused_dev.h, which includes this header for VqParams): qt = 2 of the variant (dct3d_variant.h), launched
+// by the stream ladders (dct3d_launch.h) in the StreamVq unit, with the colour transform in StreamYcc.
 #pragma once
 #include "dct3d_kernels.h"
 
@@ -31,14 +31,6 @@ __host__ __device__ inline const uint8_t* vq_map_behind(const double* steps) {
     return (const uint8_t*)steps + kVqStepsBytes + sizeof(FastDiv);
 }
 
-// px = 1 grey | 3 packed RGB24, edge = 0 | 1 (frames of any size).  Encode: channel E.ch per launch, as
-// launch_encode_eg.  Decode: grey from one stream (8 groups per wave), packed RGB24 from three.
-int launch_encode_eg_vq(int D, int px, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st);
-int launch_decode_eg_vq(int D, int edge, const DecodeParams& P, const EgDecParams& E, const VqParams& V, hipStream_t st);
-int launch_decode_eg_rgb_vq(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st);
-// the same with the YCbCr colour transform (dct3d_ycc.hip; packed RGB24 alone)
-int launch_encode_eg_vq_ycc(int D, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st);
-int launch_decode_eg_rgb_vq_ycc(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st);
 // A call's block (steps, FastDiv, map, rows: some KiB) from the context's pinned host copy -- src, its device-side
 // address -- to device memory, as a kernel on the call's stream: a copy-engine transfer in front of the first
 // kernel cost the call a hand-over between two queues, longer than the transfer itself.

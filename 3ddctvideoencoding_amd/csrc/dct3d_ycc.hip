@@ -1,7 +1,7 @@
 // dct3d_ycc.hip -- the YCbCr colour transform fused into the packed RGB24 stream calls and the rate probe
 // (DCT3D_OPT_COLOUR = DCT3D_COLOUR_YCBCR): the CT = 1 instances of encode_eg_kernel and
-// decode_eg_rgb_kernel (dct3d_eg_fused_dev.h) under every table mode (QT = 0, 1: the StreamYcc unit's ladders;
-// QT = 2: the per-stack launchers, as dct3d_vq_enc.hip / dct3d_vq_dec.hip) and of rate_kernel (dct3d_rate_dev.h).
+// decode_eg_rgb_kernel (dct3d_eg_fused_dev.h) under every table mode (QT = 0, 1, 2: the StreamYcc unit's ladders)
+// and of rate_kernel (dct3d_rate_dev.h).
 // The transform sits where a channel's bytes are picked out of a lane's 24 (ycc_pick8: the row loads and the exact
 // replay's reload) and, in the decode, on the merged bytes in registers before the one store (ycc_to_rgb4): no
 // launch and no memory traffic is added.  A translation unit of its own: no other code object changes, and a
@@ -11,34 +11,10 @@
 
 namespace dct3d {
 
-template int launch_encode_eg_in<StreamYcc>(const Variant&, const EncodeParams&, const EgFusedParams&, hipStream_t);
+template int launch_encode_eg_in<StreamYcc>(const Variant&, const EncodeParams&, const EgFusedParams&, const VqParams*, hipStream_t);
 // (no grey variant is in StreamYcc: this ladder launches nothing and answers -1)
-template int launch_decode_eg_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, hipStream_t);
-template int launch_decode_eg_rgb_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, hipStream_t);
-
-int launch_encode_eg_vq_ycc(int D, int edge, const EncodeParams& P, const EgFusedParams& E, const VqParams& V, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if (!V.tabs || !V.map) return -1;
-    int rc = -1;
-    with_variant(D, 3, edge, [&](auto d, auto, auto e) {
-        const dim3 grid(grid_blocks(P.n_cubes, kCubesPerWave));
-        hipLaunchKernelGGL((encode_eg_kernel<d, 3, e, 2, 1, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
-        rc = launched();
-    });
-    return rc;
-}
-
-int launch_decode_eg_rgb_vq_ycc(int D, int edge, const DecodeParams& P, const EgDecRgbParams& E, const VqParams& V, hipStream_t st) {
-    if (P.n_cubes == 0) return 0;
-    if (!V.steps || !V.map) return -1;
-    int rc = -1;
-    with_variant(D, 3, edge, [&](auto d, auto, auto e) {
-        const dim3 grid(dec_grid(d, P.n_cubes - P.cube_base));
-        hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, 1, VqParams>), grid, dim3(kBlock), 0, st, P, E, V);
-        rc = launched();
-    });
-    return rc;
-}
+template int launch_decode_eg_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, const VqParams*, hipStream_t);
+template int launch_decode_eg_rgb_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, const VqParams*, hipStream_t);
 
 int launch_rate_ycc(int D, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
     return probe_dispatch(D, 3, edge, P, R, [&](auto d, auto, auto e) {

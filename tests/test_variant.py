@@ -1,6 +1,7 @@
 """CPU: which translation unit holds which kernel variant (csrc/dct3d_variant.h), compiled with g++
 (tests/native/variant_check.cpp runs the real header) and compared with a table written out here, and the picks
-that turn the runtime's four values into template arguments."""
+that turn the runtime's values into template arguments: four for the raster ladders and the probes, five (the
+table axis to 2, a table per stack, and the colour transform) for the stream ladders."""
 import ctypes as C
 import itertools
 import os
@@ -10,8 +11,9 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RASTER, STREAM = 0, 1
+VQ = "dct3d_vq_enc.hip + dct3d_vq_dec.hip"  # one unit: the encode ladder in the first file, the decodes in the second
 UNITS = {RASTER: ["dct3d_kernels.hip", "dct3d_rgb.hip", "dct3d_edge.hip", "dct3d_quant.hip"],
-         STREAM: ["dct3d_kernels.hip", "dct3d_eg_frames.hip", "dct3d_quant_eg.hip"]}
+         STREAM: ["dct3d_kernels.hip", "dct3d_eg_frames.hip", "dct3d_quant_eg.hip", VQ, "dct3d_ycc.hip"]}
 # (px, edge, qt) -> the unit, at either depth: what the runtime's conditionals chose before there was a variant
 # header (encode_dev / decode_dev: the table kernels if the context uses its table, else by 2 px + edge; the
 # stream encode chain: the table kernels, else the plain grey kernel, else the frames unit; the stream decode:
@@ -26,10 +28,31 @@ HOLDER = {
              (1, 0, 1): "dct3d_quant_eg.hip", (1, 1, 1): "dct3d_quant_eg.hip",
              (3, 0, 1): "dct3d_quant_eg.hip", (3, 1, 1): "dct3d_quant_eg.hip"},
 }
+# (px, edge, qt, colour) -> the unit (None: held by none, routed nowhere) where qt = 2 or colour = 1: what the
+# runtime's conditionals chose before qt = 2 was a value of the key (a vq call: the colour launchers of the ycc unit
+# for packed RGB24 with the transform, else the vq unit's; no vq call: the ladders, the ycc unit for the transform).
+# The stream family alone has either; the transform acts on packed RGB24 alone.
+HOLDER5 = {
+    RASTER: {(px, edge, qt, colour): None
+             for px, edge, qt, colour in itertools.product((1, 3), (0, 1), (0, 1, 2), (0, 1)) if qt == 2 or colour},
+    STREAM: {(1, 0, 2, 0): VQ, (1, 1, 2, 0): VQ, (3, 0, 2, 0): VQ, (3, 1, 2, 0): VQ,
+             (3, 0, 0, 1): "dct3d_ycc.hip", (3, 1, 0, 1): "dct3d_ycc.hip",
+             (3, 0, 1, 1): "dct3d_ycc.hip", (3, 1, 1, 1): "dct3d_ycc.hip",
+             (3, 0, 2, 1): "dct3d_ycc.hip", (3, 1, 2, 1): "dct3d_ycc.hip",
+             (1, 0, 0, 1): None, (1, 1, 0, 1): None, (1, 0, 1, 1): None, (1, 1, 1, 1): None,
+             (1, 0, 2, 1): None, (1, 1, 2, 1): None},
+}
 VALID = list(itertools.product((8, 4), (1, 3), (0, 1), (0, 1)))
+VALID5 = list(itertools.product((8, 4), (1, 3), (0, 1), (0, 1, 2), (0, 1)))
 # one axis just outside its values, the others valid
 OUTSIDE = ([(D, 1, 0, 0) for D in (2, 16)] + [(8, px, 0, 0) for px in (0, 2)] + [(8, 1, 2, 0), (8, 1, 0, 2)] +
            [(16, 3, 1, 1), (4, 2, 1, 1), (4, 3, 2, 1), (4, 3, 1, 2)])
+OUTSIDE5 = ([(D, 1, 0, 0, 0) for D in (2, 16)] + [(8, px, 0, 0, 0) for px in (0, 2)] + [(8, 1, 2, 0, 0)] +
+            [(8, 1, 0, 3, 0), (8, 1, 0, -1, 0), (8, 3, 0, 0, 2), (4, 3, 1, 3, 1), (4, 3, 1, -1, 1), (4, 3, 1, 2, 2)])
+
+
+def holder(family, px, edge, qt, colour):
+    return HOLDER5[family][(px, edge, qt, colour)] if qt == 2 or colour else HOLDER[family][(px, edge, qt)]
 
 
 @pytest.fixture(scope="module")
@@ -40,27 +63,62 @@ def vlib(tmp_path_factory):
                     os.path.join(REPO, "tests", "native", "variant_check.cpp"), "-o", str(out)], check=True)
     L = C.CDLL(str(out))
     for f in (L.variant_held_by, L.variant_index, L.variant_routed_to):
-        f.argtypes = [C.c_int] * 5
+        f.argtypes = [C.c_int] * 6
     L.variant_pick4.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
     L.variant_pick3.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_int)] * 2
+    L.variant_pick5.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2
     L.variant_groups.argtypes = [C.c_int] * 2
     return L
 
 
 def test_the_table_names_every_variant():
-    assert len(VALID) == 16
+    assert len(VALID) == 16 and len(VALID5) == 2 * 2 * 2 * 3 * 2
     for family in (RASTER, STREAM):
         assert sorted(HOLDER[family]) == sorted({v[1:] for v in VALID})
-        assert set(HOLDER[family].values()) == set(UNITS[family])
+        assert sorted(HOLDER5[family]) == sorted({v[1:] for v in VALID5 if v[3] == 2 or v[4]})
+        assert set(HOLDER[family].values()) | set(HOLDER5[family].values()) - {None} == set(UNITS[family])
+    assert set(HOLDER[RASTER].values()) == set(UNITS[RASTER])
+    assert set(HOLDER[STREAM].values()) == set(UNITS[STREAM][:3])
 
 
 @pytest.mark.parametrize("family", [RASTER, STREAM])
 def test_each_variant_is_held_by_exactly_the_unit_of_the_table(vlib, family):
     for D, px, edge, qt in VALID:
         want = UNITS[family].index(HOLDER[family][(px, edge, qt)])
-        assert vlib.variant_held_by(family, D, px, edge, qt) == 1 << want, (D, px, edge, qt)  # that unit and no other
-        assert vlib.variant_index(family, D, px, edge, qt) == want
-        assert vlib.variant_routed_to(family, D, px, edge, qt) == want  # (one call of the router's functor)
+        assert vlib.variant_held_by(family, D, px, edge, qt, 0) == 1 << want, (D, px, edge, qt)  # that unit and no other
+        assert vlib.variant_index(family, D, px, edge, qt, 0) == want
+        assert vlib.variant_routed_to(family, D, px, edge, qt, 0) == want  # (one call of the router's functor)
+
+
+@pytest.mark.parametrize("family", [RASTER, STREAM])
+def test_each_table_per_stack_and_colour_variant_is_held_by_exactly_the_unit_of_the_table(vlib, family):
+    for v in VALID5:
+        unit = holder(family, *v[1:])
+        want = -1 if unit is None else UNITS[family].index(unit)
+        assert vlib.variant_held_by(family, *v) == (0 if unit is None else 1 << want), v
+        assert vlib.variant_index(family, *v) == want, v
+        assert vlib.variant_routed_to(family, *v) == want, v  # (-1: the router's functor never called)
+
+
+def test_the_stream_rows_say_what_the_units_are_for():
+    for D, px, edge, qt, colour in VALID5:
+        unit = holder(STREAM, px, edge, qt, colour)
+        if colour:
+            assert unit == ("dct3d_ycc.hip" if px == 3 else None)
+        elif qt == 2:
+            assert unit == VQ
+        assert holder(RASTER, px, edge, qt, colour) is None or (qt < 2 and not colour)
+
+
+def test_a_value_outside_an_axis_is_held_by_no_unit(vlib):
+    for family in (RASTER, STREAM):
+        for D, px, edge in itertools.product((8, 4), (1, 3), (0, 1)):
+            for qt, colour in [(3, 0), (-1, 0), (0, 2), (2, 2), (3, 1)]:
+                if (qt, colour) == (3, 1) and family == STREAM and px == 3:
+                    continue  # (StreamYcc holds packed RGB24 with the transform whatever the table: the pick refuses)
+                v = (D, px, edge, qt, colour)
+                assert vlib.variant_held_by(family, *v) == 0, v
+                assert vlib.variant_index(family, *v) == -1 and vlib.variant_routed_to(family, *v) == -1, v
 
 
 def test_with_variant_hands_over_the_four_values(vlib):
@@ -74,6 +132,14 @@ def test_with_variant_hands_over_the_four_values(vlib):
         assert tuple(out)[:3] == v[:3] and said.value == 1
 
 
+def test_with_stream_variant_hands_over_the_five_values(vlib):
+    out, said = (C.c_int * 5)(), C.c_int()
+    for v in VALID5:
+        out[:] = [-1] * 5
+        assert vlib.variant_pick5(*v, out, C.byref(said)) == 1, v
+        assert tuple(out) == v and said.value == 1, v
+
+
 def test_values_outside_an_axis_call_nothing_and_say_so(vlib):
     out, said = (C.c_int * 4)(), C.c_int(7)
     for v in OUTSIDE:
@@ -84,9 +150,16 @@ def test_values_outside_an_axis_call_nothing_and_say_so(vlib):
         assert said.value == 0, v
 
 
+def test_values_outside_a_stream_axis_call_nothing_and_say_so(vlib):
+    out, said = (C.c_int * 5)(), C.c_int(7)
+    for v in OUTSIDE5:
+        assert vlib.variant_pick5(*v, out, C.byref(said)) == 0, v
+        assert said.value == 0, v
+
+
 def test_group_pick(vlib):
     """the grey stream decode's groups per wave: 1 | 2 | 4 | 8 in the plain unit (any other value: 8), 8 elsewhere"""
     asked = [1, 2, 4, 8, 0, 3, 5, 16, -1]
     assert [vlib.variant_groups(0, n) for n in asked] == [1, 2, 4, 8, 8, 8, 8, 8, 8]
-    for unit in (1, 2):
+    for unit in (1, 2, 3, 4):
         assert [vlib.variant_groups(unit, n) for n in asked] == [8] * len(asked)
