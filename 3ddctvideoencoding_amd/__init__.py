@@ -38,6 +38,8 @@ DCT3D_OPT_QUANT_FORCE_TABLE = 11
 # the colour transform of the packed RGB24 stream calls and the rate probe (dct3d.h; rgb_to_ycbcr below)
 DCT3D_OPT_COLOUR = 12
 DCT3D_COLOUR_PLANES, DCT3D_COLOUR_YCBCR = 0, 1
+# 4:2:0 chroma subsampling on top of the colour transform (dct3d.h; Context.set_chroma, rgb_to_ycbcr420 below)
+DCT3D_CHROMA_444, DCT3D_CHROMA_420 = 0, 1
 
 # Every symbol include/dct3d.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -58,6 +60,7 @@ ABI_SYMBOLS = (
     "dct3d_distortion_frames", "dct3d_distortion_frames_dev",
     "dct3d_encode_eg_frames_vq", "dct3d_encode_eg_frames_vq_dev",
     "dct3d_decode_eg_frames_vq", "dct3d_decode_eg_frames_vq_dev",
+    "dct3d_ctx_set_chroma", "dct3d_ctx_get_chroma", "dct3d_chroma_size",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -155,6 +158,9 @@ def lib() -> C.CDLL:
         L.dct3d_encode_eg_frames_vq.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
         L.dct3d_decode_eg_frames_vq_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
         L.dct3d_decode_eg_frames_vq.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.dct3d_ctx_set_chroma.argtypes = [vp, i32]
+        L.dct3d_ctx_get_chroma.argtypes = [vp, C.POINTER(i32)]
+        L.dct3d_chroma_size.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
         _lib = L
     return _lib
 
@@ -280,6 +286,59 @@ def rgb_to_ycbcr(frames) -> np.ndarray:
 def ycbcr_to_rgb(frames) -> np.ndarray:
     """The inverse transform's definition: uint8 [.., 3] (Y, Cb, Cr) -> uint8 [.., 3] (R, G, B), clamped."""
     return np.clip(ycbcr_to_rgb_unclamped(frames), 0, 255).astype(np.uint8)
+
+
+def chroma_size(w: int, h: int):
+    """(cw, ch) of DCT3D_CHROMA_420's chroma planes for w x h frames: ((w + 1) // 2, (h + 1) // 2)."""
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0:
+        raise ValueError("a frame has at least one pixel")
+    return (w + 1) // 2, (h + 1) // 2
+
+
+def subsample_420(planes) -> np.ndarray:
+    """The definition of DCT3D_CHROMA_420's subsampling in numpy (dct3d.h): uint8 planes [.., H, W] -> uint8
+    [.., (H + 1) // 2, (W + 1) // 2].  The plane is padded to even width and height by repeating its last column and
+    row; then c[j, i] = (p[2j, 2i] + p[2j, 2i+1] + p[2j+1, 2i] + p[2j+1, 2i+1] + 2) >> 2."""
+    p = np.asarray(planes)
+    if p.ndim < 2 or p.shape[-1] < 1 or p.shape[-2] < 1:
+        raise ValueError("planes have shape [.., H, W]")
+    p = p.astype(np.int64)
+    if p.shape[-1] % 2:
+        p = np.concatenate((p, p[..., :, -1:]), axis=-1)
+    if p.shape[-2] % 2:
+        p = np.concatenate((p, p[..., -1:, :]), axis=-2)
+    s = p[..., 0::2, 0::2] + p[..., 0::2, 1::2] + p[..., 1::2, 0::2] + p[..., 1::2, 1::2]
+    return ((s + 2) >> 2).astype(np.uint8)
+
+
+def upsample_420(planes, w: int, h: int) -> np.ndarray:
+    """The definition of the upsampling: pixel replication, p[y, x] = c[y >> 1, x >> 1], cropped to w x h; planes
+    [.., (h + 1) // 2, (w + 1) // 2] -> [.., h, w], the dtype kept."""
+    c = np.asarray(planes)
+    if c.ndim < 2 or tuple(c.shape[-2:]) != chroma_size(w, h)[::-1]:
+        raise ValueError("the chroma planes of w x h frames have shape [.., (h + 1) // 2, (w + 1) // 2]")
+    return np.ascontiguousarray(np.repeat(np.repeat(c, 2, axis=-2), 2, axis=-1)[..., :h, :w])
+
+
+def rgb_to_ycbcr420(frames):
+    """uint8 frames [.., H, W, 3] (R, G, B) -> (Y [.., H, W], Cb, Cr [.., (H + 1) // 2, (W + 1) // 2]): the three
+    planes whose grey streams a packed RGB24 stream call writes under DCT3D_CHROMA_420: rgb_to_ycbcr, then
+    subsample_420 of its Cb and Cr planes."""
+    t = rgb_to_ycbcr(frames)
+    if t.ndim < 3:
+        raise ValueError("frames have shape [.., H, W, 3]")
+    return np.ascontiguousarray(t[..., 0]), subsample_420(t[..., 1]), subsample_420(t[..., 2])
+
+
+def ycbcr420_to_rgb(y, cb, cr) -> np.ndarray:
+    """The inverse: Y [.., H, W] and the chroma planes of rgb_to_ycbcr420 -> uint8 frames [.., H, W, 3]:
+    ycbcr_to_rgb of (Y, upsample_420(Cb), upsample_420(Cr))."""
+    y = np.asarray(y)
+    if y.ndim < 2:
+        raise ValueError("Y has shape [.., H, W]")
+    h, w = y.shape[-2:]
+    return ycbcr_to_rgb(np.stack((y, upsample_420(cb, w, h), upsample_420(cr, w, h)), axis=-1))
 
 
 RATE_MAX_TABLES = 32
@@ -426,6 +485,17 @@ class Context:
         """Test / diagnostic option (DCT3D_OPT_*): changes how later calls reach their (identical)
         results, e.g. to drive a rare path.  0 restores the default."""
         _check(lib().dct3d_ctx_set_option(self._h, option, float(value)), "dct3d_ctx_set_option")
+
+    def set_chroma(self, mode: int) -> None:
+        """DCT3D_CHROMA_444 (the default) or DCT3D_CHROMA_420: with the colour transform on, the packed RGB24 stream
+        calls and the rate probe code Cb and Cr at a quarter of the samples (rgb_to_ycbcr420)."""
+        _check(lib().dct3d_ctx_set_chroma(self._h, int(mode)), "dct3d_ctx_set_chroma")
+
+    def chroma(self) -> int:
+        """The context's chroma mode."""
+        m = C.c_int(0)
+        _check(lib().dct3d_ctx_get_chroma(self._h, C.byref(m)), "dct3d_ctx_get_chroma")
+        return m.value
 
     def set_quant(self, steps) -> None:
         """The context's quantiser table: one integer step in [1, 255] per s = kx + ky + kz (bw + bh + bd - 2

@@ -190,6 +190,10 @@ __device__ __forceinline__ uint32_t k1_code_off(uint32_t k) {
 // CT = 1 (dct3d_ycc.hip; DCT3D_OPT_COLOUR), with PX = 3: channel E.ch is plane Y, Cb or Cr of the
 // pixels' colour transform, computed where the channel's bytes are picked (ycc_pick8: the row loads and the exact
 // replay's reload, which therefore folds the bytes the main path saw).  Nothing else changes.
+// CT = 2 (dct3d_c420.hip; dct3d_ctx_set_chroma), with PX = 3 and E.ch = 1 | 2: the cubes are those of the
+// 4:2:0 subsampled Cb or Cr plane (P's cube fields: n_cubes, cubes_per_stack, nbx and the FastDivs), read from the
+// packed frames (P's address fields: width, height -- whatever EDGE --, plane, stack_stride) through c420_row8, in
+// the row loads and in the replay's reload alike.  EDGE = 1: the width or the height is no multiple of 16.
 template <int D, int PX = 1, int EDGE = 0, int QT = 0, int CT = 0, class... VQ>
 __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, EgFusedParams E, VQ... vq) {
     static_assert(sizeof...(VQ) == (QT == 2 ? 1 : 0), "the VqParams (vq_of) with QT = 2, and only then");
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(kBlock, 4) void encode_eg_kernel(EncodeParams P, Eg
         ReplayGeom R{P.raster, P.cubes_per_stack, P.nbx, P.width, P.plane, P.stack_stride,
                      E.ngroups, E.coef, E.group_of};
         if constexpr (PX != 1) R.ch = E.ch;
-        if constexpr (EDGE != 0) R.height = P.height;
+        if constexpr (EDGE != 0 || CT == 2) R.height = P.height;
         uint32_t nrep = 0;  // (counted by the PX / EDGE instantiations only)
         for (;;) {
             const unsigned long long who = __ballot((fm_lo | fm_hi) != 0u);

@@ -151,6 +151,71 @@ __device__ __forceinline__ uint2 channel_pick8(const uint2 (&w)[3], int ch) {
     if constexpr (CT == 1) return ycc_pick8(w, ch);
     else return rgb_pick8(w, ch);
 }
+// ---------------------------------------------------------------------------------------------
+// 4:2:0 chroma (CT = 2: dct3d_ctx_set_chroma, dct3d_c420.hip).  The cubes tile the subsampled plane
+// S(Cb) or S(Cr) of cw x chh = ceil(w / 2) x ceil(h / 2) samples, which exists nowhere in memory: sample (j, i)
+// is the box mean (sum of four + 2) >> 2 of plane ch at pixels (2 j + {0, 1}, 2 i + {0, 1}), each clamped into
+// the frame (the even pad), and the chroma coordinates are clamped to (chh - 1, cw - 1) before that (the padding
+// of the chroma plane).  Row y of chroma cube (by, bx) of one frame: a lane's 8 samples come from 16
+// packed pixels of 2 frame rows, 96 bytes, through ycc_pick8 (the 8-bit Cb / Cr of the transform) and then the
+// box sum.  EDGE = 0: w and h are multiples of 16, every load is aligned and inside.  EDGE = 1: a row whose 16
+// pixels end inside the frame loads them byte aligned; any other (the last cube column; w < 16) loads its
+// pixels one byte at a time, clamped.  No access leaves the frames.
+// ---------------------------------------------------------------------------------------------
+// horizontal pair sums of 4 bytes: bytes 0 + 1 in the low half, 2 + 3 in the high half
+__device__ __forceinline__ uint32_t c420_pairs(uint32_t x) { return (x & 0x00FF00FFu) + ((x >> 8) & 0x00FF00FFu); }
+// 8 pixels of a plane on two rows -> their 4 box means, one per byte
+__device__ __forceinline__ uint32_t c420_box4(uint2 r0, uint2 r1) {
+    const uint32_t lo = ((c420_pairs(r0.x) + c420_pairs(r1.x) + 0x00020002u) >> 2) & 0x00FF00FFu;
+    const uint32_t hi = ((c420_pairs(r0.y) + c420_pairs(r1.y) + 0x00020002u) >> 2) & 0x00FF00FFu;
+    return __builtin_amdgcn_perm(hi, lo, 0x06040200u);
+}
+// the 48 bytes of source pixels min(2 min(c0 + i, cw - 1) + d, width - 1), i < 8, d < 2, of the row at `row`
+__device__ __forceinline__ void c420_row_bytes(const uint8_t* row, uint32_t c0, uint32_t cw, uint32_t width,
+                                               uint2 (&a)[3], uint2 (&b)[3]) {
+    uint32_t d[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) d[i] = 0u;
+#pragma unroll
+    for (int t = 0; t < 48; t++) {
+        const uint32_t px = (uint32_t)(t / 3);
+        const uint32_t sx = min(2u * min(c0 + (px >> 1), cw - 1) + (px & 1u), width - 1);
+        d[t >> 2] |= (uint32_t)row[3 * (size_t)sx + t % 3] << (8 * (t & 3));
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        a[i] = make_uint2(d[2 * i], d[2 * i + 1]);
+        b[i] = make_uint2(d[6 + 2 * i], d[7 + 2 * i]);
+    }
+}
+// row y of chroma cube (by, bx) of the frame at `frame` (width x height packed pixels), plane ch (1 Cb, 2 Cr)
+template <int EDGE>
+__device__ __forceinline__ uint2 c420_row8(const uint8_t* frame, uint32_t width, uint32_t height, uint32_t by,
+                                           uint32_t bx, int y, int ch) {
+    uint2 a[2][3], b[2][3];  // [row][.]: pixels 0..7 and 8..15
+    if constexpr (!EDGE) {
+        const uint8_t* p = frame + 3 * ((size_t)(2 * (by * 8 + (uint32_t)y)) * width + bx * 16);
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            row_load<3, 0>(p + (size_t)r * 3 * width, width, a[r]);
+            row_load<3, 0>(p + (size_t)r * 3 * width + 24, width, b[r]);
+        }
+    } else {
+        const uint32_t cw = (width + 1) >> 1, chh = (height + 1) >> 1;
+        const uint32_t cy = min(by * 8 + (uint32_t)y, chh - 1);
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const uint8_t* row = frame + 3 * (size_t)min(2 * cy + (uint32_t)r, height - 1) * width;
+            if (bx * 16 + 16 <= width) {  // (width >= 16: row_load's byte-aligned 8-byte loads)
+                row_load<3, 1>(row + 3 * (size_t)(bx * 16), width, a[r]);
+                row_load<3, 1>(row + 3 * (size_t)(bx * 16) + 24, width, b[r]);
+            } else {
+                c420_row_bytes(row, bx * 8, cw, width, a[r], b[r]);
+            }
+        }
+    }
+    return make_uint2(c420_box4(ycc_pick8(a[0], ch), ycc_pick8(a[1], ch)), c420_box4(ycc_pick8(b[0], ch), ycc_pick8(b[1], ch)));
+}
 // Cube g of a packed RGB24 raster (stack s = g / cubes_per_stack) -> its cube in channel ch's block of
 // the output, layout [stack][channel][cube]; grey: g itself
 template <int PX>
@@ -213,7 +278,17 @@ __device__ __forceinline__ void load_channel_rows(const EncodeParams& P, uint32_
     } else {
 #pragma unroll
         for (int z = 0; z < N; z++) raw[z] = make_uint2(0u, 0u);
-        if (valid) {
+        if constexpr (CT == 2) {  // 4:2:0 chroma: P's cube fields are the chroma plane's, its address fields the frames'
+            if (valid) {
+                const CubePos c = cube_pos(P, g);
+                const uint8_t* f0 = P.raster + (size_t)c.s * P.stack_stride;
+#pragma unroll
+                for (int z = 0; z < N; z++) {
+                    raw[z] = c420_row8<EDGE>(f0 + (size_t)(ZM * h + z) * P.plane, P.width, P.height, c.by, c.bx, y, ch);
+                    asm volatile("" : "+v"(raw[z].x), "+v"(raw[z].y));
+                }
+            }
+        } else if (valid) {
             const RowSrc e = row_src<PX, EDGE>(P.raster, P.stack_stride, P.width, P.height, cube_pos(P, g), y);
 #pragma unroll
             for (int z = 0; z < N; z++) {
@@ -720,7 +795,9 @@ __device__ __forceinline__ ReplayIn replay_load(const ReplayGeom& R, uint32_t g,
         const uint32_t s = g / R.cubes_per_stack;
         const uint32_t r = g - s * R.cubes_per_stack;
         const uint32_t by = r / R.nbx, bx = r - by * R.nbx;
-        if constexpr (EDGE) {  // the main path's padded values (row_src, row_load, edge_fix)
+        if constexpr (CT == 2) {  // the main path's chroma samples (R.height: the frames', whatever EDGE)
+            in.px = c420_row8<EDGE>(R.raster + (size_t)s * R.stack_stride + (size_t)z * R.plane, R.width, R.height, by, bx, y, R.ch);
+        } else if constexpr (EDGE) {  // the main path's padded values (row_src, row_load, edge_fix)
             const RowSrc e = row_src<PX, 1>(R.raster, R.stack_stride, R.width, R.height, CubePos{s, r, by, bx}, y);
             uint2 w[PX];
             row_load<PX, 1>(e.p + (size_t)z * R.plane, R.width, w);

@@ -17,6 +17,8 @@ namespace dct3d {
 // that left it open.  Per cube and table one uint16 goes out (a cube costs < 2^15 bits: 512 codes of <= 27).
 // The wave's LDS region, free after the transform: the fold's scratch, the cubes' sums per table, the masks.
 // CT = 1 (dct3d_ycc.hip): the rows and the fold's reload are channel R.ch of the YCbCr planes (ycc_pick8).
+// CT = 2 (dct3d_c420.hip): the cubes of the 4:2:0 subsampled plane R.ch = 1 | 2 (c420_row8; P as
+// encode_eg_kernel's CT = 2), and cube_bits holds that plane alone: cube g at g.
 template <int D, int PX, int EDGE, int CT = 0>
 __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RateParams R) {
     constexpr int CS = 64 * D;
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
     // division and rounding per table that left it open.  (The distortion probe folds per table instead, before
     // that table's decode, which needs the value.)
     {
-        const ReplayGeom G = probe_replay_geom<PX, EDGE>(P, R.ch);
+        const ReplayGeom G = probe_replay_geom<PX, (CT == 2 ? 1 : EDGE)>(P, R.ch);  // (CT = 2: the height whatever EDGE)
         uint32_t nrep = 0;
         for (;;) {
             uint32_t any = fm[0];
@@ -125,8 +127,12 @@ __global__ __launch_bounds__(kBlock, 4) void rate_kernel(EncodeParams P, RatePar
 
     // lane 8 t + cc: cube cc's bits under table t (its place as the encode's [stack][channel][cube] blocks)
     const uint32_t ot = (uint32_t)lane >> 3, og = cube0 + ((uint32_t)lane & 7u);
-    if (ot < (uint32_t)nt && og < P.n_cubes)
-        R.cube_bits[(size_t)ot * R.table_stride + enc_out_cube<PX>(P, og, R.ch)] = (uint16_t)sums[lane];
+    if constexpr (CT == 2) {  // a chroma plane's cubes alone, [stack][cube] within a table
+        if (ot < (uint32_t)nt && og < P.n_cubes) R.cube_bits[(size_t)ot * R.table_stride + og] = (uint16_t)sums[lane];
+    } else {
+        if (ot < (uint32_t)nt && og < P.n_cubes)
+            R.cube_bits[(size_t)ot * R.table_stride + enc_out_cube<PX>(P, og, R.ch)] = (uint16_t)sums[lane];
+    }
 }
 
 }  // namespace dct3d

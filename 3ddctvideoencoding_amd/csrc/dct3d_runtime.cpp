@@ -24,6 +24,7 @@
 #include "dct3d_distortion.h"
 #include "dct3d_rate.h"
 #include "dct3d_vq.h"
+#include "dct3d_c420.h"
 
 using namespace dct3d;
 
@@ -150,6 +151,13 @@ struct dct3d_ctx {
     std::vector<double> vq_steps;
     VqParams vq_params = {};
     const VqParams* vq = nullptr;
+    // 4:2:0 chroma subsampling (dct3d_ctx_set_chroma): the mode, the stream decode's two chroma planes
+    // (S(Cb) then S(Cr), each [n_stacks * bd][ceil(h / 2)][ceil(w / 2)]: the grey stream decode writes them, the Y
+    // kernel reads them), and a vq call's second view of its block, whose FastDiv is the chroma plane's cubes per stack
+    int chroma = DCT3D_CHROMA_444;
+    DevBuf d_c420;
+    VqParams vq_params_c = {};
+    const VqParams* vq_c = nullptr;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -317,6 +325,14 @@ static Variant stream_variant_of(const dct3d_ctx* c, const Geom& g) {
 }
 // a call on packed frames that has no colour stage refuses the option (dct3d.h)
 static bool colour_refused(const dct3d_ctx* c, int px) { return c && c->opt_colour && px == 3; }
+// 4:2:0 acts on packed frames alone, on top of the colour transform: a packed call with the mode on and
+// the transform off is refused (c420_refused) before anything is queued.  c420_geom: the chroma plane's geometry
+// (grey, ceil(w / 2) x ceil(h / 2)) and its cubes per channel
+static bool c420_on(const dct3d_ctx* c, int px) { return c && c->chroma == DCT3D_CHROMA_420 && px == 3; }
+static bool c420_refused(const dct3d_ctx* c, int px) { return c420_on(c, px) && !c->opt_colour; }
+static bool c420_geom(const Geom& g, int n_stacks, Geom* gc, uint64_t* n_cubes) {
+    return make_geom(g.w / 2 + g.w % 2, g.h / 2 + g.h % 2, 1, n_stacks, true, gc, n_cubes);
+}
 static const double* qt_steps(const dct3d_ctx* c) { return (const double*)c->d_tabs64.p + kQtStepOff; }
 
 int dct3d_ctx_set_quant(dct3d_ctx* c, const int32_t* steps, int n) {
@@ -414,7 +430,7 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_egd_exit, &c->d_egd_status, &c->d_egd_in, &c->d_egd_raster, &c->d_egd_mark, &c->d_egd_desc,
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
                       &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums,
-                      &c->d_dist_steps, &c->d_dist_sse, &c->d_vq})
+                      &c->d_dist_steps, &c->d_dist_sse, &c->d_vq, &c->d_c420})
         b->release();
     if (c->h_rate) (void)hipHostFree(c->h_rate);
     if (c->vq_host) (void)hipHostFree(c->vq_host);
@@ -484,6 +500,25 @@ int dct3d_ctx_set_option(dct3d_ctx* c, int option, double value) {
             return DCT3D_OK;
         default: return DCT3D_EINVAL;
     }
+}
+
+int dct3d_ctx_set_chroma(dct3d_ctx* c, int mode) {
+    if (!c || (mode != DCT3D_CHROMA_444 && mode != DCT3D_CHROMA_420)) return DCT3D_EINVAL;
+    c->chroma = mode;
+    return DCT3D_OK;
+}
+
+int dct3d_ctx_get_chroma(const dct3d_ctx* c, int* mode) {
+    if (!c || !mode) return DCT3D_EINVAL;
+    *mode = c->chroma;
+    return DCT3D_OK;
+}
+
+int dct3d_chroma_size(int w, int h, int* cw, int* ch) {
+    if (w <= 0 || h <= 0 || !cw || !ch) return DCT3D_EINVAL;
+    *cw = w / 2 + w % 2;
+    *ch = h / 2 + h % 2;
+    return DCT3D_OK;
 }
 
 int dct3d_ctx_set_profiling(dct3d_ctx* c, int on) {
@@ -1037,12 +1072,26 @@ int dct3d_eg_encode_dev(dct3d_ctx* c, const int32_t* d_q, uint64_t n_cubes, uint
     return eg_run(c, d_q, n_cubes, carry_byte, carry_bits, (uint32_t*)d_out, out_cap, total_bits);
 }
 
+// 4:2:0: the encode kernels' cube fields from the chroma plane gc, their address fields (set_address_fields did
+// them) from the frames g, the height set whatever the edge (c420_row8 clamps by it)
+static void c420_cube_fields(EncodeParams& P, const Geom& g, const Geom& gc) {
+    P.cubes_per_stack = (uint32_t)gc.cps();
+    P.nbx = (uint32_t)(gc.wp / 8);
+    P.div_cps = fast_div(P.cubes_per_stack);
+    P.div_nbx = fast_div(P.nbx);
+    P.height = (uint32_t)g.h;
+}
+// the chroma loader's edge: a width or a height that is no multiple of 16
+static int c420_edge(const Geom& g) { return g.w % 16 || g.h % 16 ? 1 : 0; }
+
 // One fused launch chain on the context stream: encode_eg_kernel (transform, quantise, in-wave exact replay,
 // lane-level Exp-Golomb into slots) -> scan over segments -> eg_compact_kernel -> eg_stitch_kernel, for
 // channel ch of the n_cubes cubes of d_raster.  Returns once *total_bits is known.  A packed RGB24 call runs
 // one chain per channel back to back, reusing the slot, bits, offset and head / tail buffers.
+// gc (4:2:0, ch = 1 | 2): the chroma plane's geometry, n_cubes its cubes; the kernel reads the frames of g.
 static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g, int ch, uint64_t n_cubes,
-                           uint8_t carry_byte, int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits) {
+                           uint8_t carry_byte, int carry_bits, uint8_t* d_out, uint64_t out_cap, uint64_t* total_bits,
+                           const Geom* gc = nullptr) {
     const bool plain = g.px == 1 && !g.edge();  // dct3d_encode_eg_dev's geometry: its kernel
     int rc;
     const uint64_t n_seg = (n_cubes + 7) / 8, n_chunks = (n_seg + 4095) / 4096;
@@ -1059,6 +1108,7 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     if (rc) return rc;
     EncodeParams P;  // no int32 output; the replay tables travel in E
     fill_encode_params(c, P, d_raster, nullptr, g, n_cubes);
+    if (gc) c420_cube_fields(P, g, *gc);
     // (the new geometries' kernels count their exact replays; dct3d_encode_eg_dev's reports none)
     if (plain) P.replay_count = P.replay_clear = nullptr;
     EgFusedParams E;
@@ -1090,7 +1140,9 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     G.carry_byte = carry_byte;
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
-    if (launch_encode_eg(stream_variant_of(c, g), P, E, c->vq, c->stream)) return DCT3D_EKERNEL;
+    const Variant v = stream_variant_of(c, g);
+    if (gc ? launch_encode_eg_c420(v.D, c420_edge(g), v.qt, P, E, c->vq_c, c->stream) : launch_encode_eg(v, P, E, c->vq, c->stream))
+        return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
     if (ev) (void)hipEventRecord(ev[2], c->stream);
@@ -1198,6 +1250,11 @@ int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !d_out || !out_cap || !total_bits) return DCT3D_EINVAL;
     if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;  // the int32 intermediate has no colour stage
+    Geom gc = g;
+    uint64_t nc[3] = {n_cubes, n_cubes, n_cubes};  // cubes per channel (4:2:0: the chroma planes')
+    const bool c420 = c420_on(c, channels);
+    if (c420_refused(c, channels) || (c420 && !c420_geom(g, n_stacks, &gc, &nc[1]))) return DCT3D_EINVAL;
+    nc[2] = nc[1];
     if (eg_aligned(g))
         return dct3d_encode_eg_dev(c, d_frames, w, h, n_stacks, carry_byte[0], carry_bits[0], d_out[0], out_cap[0], total_bits);
     if (!d_frames && n_stacks) return DCT3D_EINVAL;
@@ -1208,12 +1265,13 @@ int dct3d_encode_eg_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int
     int rc, first = DCT3D_OK;  // every channel runs (each total_bits[ch] is set); the first error is returned
     for (int ch = 0; ch < channels; ch++) {
         total_bits[ch] = 0;
-        rc = n_cubes ? encode_eg_chain(c, d_frames, g, ch, n_cubes, carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch])
+        rc = n_cubes ? encode_eg_chain(c, d_frames, g, ch, nc[ch], carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch],
+                                       c420 && ch ? &gc : nullptr)
                      : dct3d_eg_encode_dev(c, nullptr, 0, carry_byte[ch], carry_bits[ch], d_out[ch], out_cap[ch], &total_bits[ch]);
         if (rc && !first) first = rc;
         if (rc && rc != DCT3D_ENOSPC) break;
     }
-    if (c->slot_used) count_slot_used(c, (uint64_t)channels * n_cubes * (uint64_t)c->plan.cs);
+    if (c->slot_used) count_slot_used(c, (channels == 3 ? nc[0] + nc[1] + nc[2] : n_cubes) * (uint64_t)c->plan.cs);
     return first;
 }
 
@@ -1224,6 +1282,7 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!carry_byte || !carry_bits || !total_bits) return DCT3D_EINVAL;
     if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;
+    if (c420_refused(c, channels)) return DCT3D_EINVAL;
     if (eg_aligned(g)) return dct3d_encode_eg(c, frames, w, h, n_stacks, carry_byte[0], carry_bits[0], total_bits);
     if (!frames && n_stacks) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
@@ -1326,11 +1385,77 @@ static int probe_grow_pinned(dct3d_ctx* c, size_t bytes) {
     return DCT3D_OK;
 }
 
+// The rate probe under 4:2:0 on frames in device memory: channel 0 as the colour transform's launch at
+// the frames' geometry, channels 1 and 2 as the chroma launches over the subsampled planes' cubes (gc), each plane's
+// cube bits in a block of its own ([table][stack][cube]: the layout is ragged, no caller's buffer is offered), the
+// sums per (table, stack) of each put together on the host.  bits: [n_tables][n_stacks][3].
+static int probe_c420_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
+                          int n_tables, uint64_t* bits) {
+    Geom gc;
+    uint64_t nc;
+    if (!c420_geom(g, n_stacks, &gc, &nc)) return DCT3D_EINVAL;
+    const uint64_t ny = g.cps() * (uint64_t)n_stacks;
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    call_begin(c);
+    if (!c->batch) c->last_units = 0;
+    if (ny == 0) return DCT3D_OK;
+    probe_tables(c, tables, n_tables, false);
+    const uint64_t ts = (uint64_t)n_tables * n_stacks;  // sums per plane (the Y launch's block: three times that)
+    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
+    const size_t y_cubes = (size_t)n_tables * 3 * ny, c_cubes = (size_t)n_tables * nc;
+    const size_t sum_bytes = 5 * ts * sizeof(uint64_t);
+    int rc;
+    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_rate_sums.grow(sum_bytes)) ||
+        (rc = c->d_rate_bits.grow((y_cubes + 2 * c_cubes) * sizeof(uint16_t))) || (rc = probe_grow_pinned(c, sum_bytes)))
+        return rc;
+    uint16_t* const cb_y = (uint16_t*)c->d_rate_bits.p;
+    uint16_t* const cb_c[2] = {cb_y + y_cubes, cb_y + y_cubes + c_cubes};
+    // (the Y launch fills channel 0's third of its [stack][channel][cube] block; the sums of the rest are dropped)
+    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemsetAsync(cb_y, 0, y_cubes * sizeof(uint16_t), c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    EncodeParams P, Pc;
+    fill_encode_params(c, P, d_frames, nullptr, g, ny);
+    fill_encode_params(c, Pc, d_frames, nullptr, g, nc);
+    c420_cube_fields(Pc, g, gc);
+    const Variant v = stream_variant_of(c, g);
+    hipEvent_t* ev = timer_begin(c);
+    rc = DCT3D_OK;
+    for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
+        for (int ch = 0; ch < 3 && !rc; ch++) {
+            RateParams R = {};
+            R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
+            R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
+            R.ch = ch;
+            R.table_stride = ch ? nc : 3 * ny;
+            R.cube_bits = (ch ? cb_c[ch - 1] : cb_y) + (size_t)t0 * R.table_stride;
+            if (ch ? launch_rate_c420(v.D, c420_edge(g), Pc, R, c->stream) : launch_rate_ycc(v.D, v.edge, P, R, c->stream))
+                rc = DCT3D_EKERNEL;
+            else c->slot_used = true;
+        }
+    uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
+    if (!rc && launch_rate_sum(cb_y, (uint32_t)g.cps(), 3 * ts, d_sums, c->stream)) rc = DCT3D_EKERNEL;
+    for (int k = 0; k < 2 && !rc; k++)
+        if (launch_rate_sum(cb_c[k], (uint32_t)gc.cps(), ts, d_sums + (3 + k) * ts, c->stream)) rc = DCT3D_EKERNEL;
+    timer_end(c, ev);
+    if (!rc && hipMemcpyAsync(c->h_rate, d_sums, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
+    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * (ny + 2 * nc) * (uint64_t)c->plan.cs);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < ts; i++) {
+        bits[3 * i] = c->h_rate[3 * i];
+        bits[3 * i + 1] = c->h_rate[3 * ts + i];
+        bits[3 * i + 2] = c->h_rate[4 * ts + i];
+    }
+    return DCT3D_OK;
+}
+
 // Both probes on frames in device memory (the arguments hold: rate_args_ok).  sse: the distortion probe (bits
 // optional; d_cube_sse the caller's per-cube buffer or nullptr); no sse: the rate probe (d_cube_bits likewise).
 static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
                      uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse, uint16_t* d_cube_bits) {
     const bool dist = sse != nullptr;
+    if (!dist && c420_on(c, g.px)) return probe_c420_dev(c, d_frames, g, n_stacks, tables, n_tables, bits);
     const int channels = g.px;
     const uint64_t n_cubes = g.cps() * (uint64_t)n_stacks;  // per channel
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
@@ -1443,6 +1568,8 @@ int dct3d_rate_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, i
     Geom g;
     uint64_t n_cubes;
     if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    // 4:2:0: the cube layout is ragged (the chroma planes have fewer cubes): only the totals are offered
+    if (c420_refused(c, channels) || (c420_on(c, channels) && d_cube_bits)) return DCT3D_EINVAL;
     return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, nullptr, bits, nullptr, d_cube_bits);
 }
 
@@ -1451,6 +1578,7 @@ int dct3d_rate_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int cha
     Geom g;
     uint64_t n_cubes;
     if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (c420_refused(c, channels)) return DCT3D_EINVAL;
     return probe_host(c, frames, g, n_stacks, tables, n_tables, nullptr, bits);
 }
 
@@ -1486,9 +1614,10 @@ constexpr int kEgRetry = 1000;
 // set >= 0 (a packed RGB24 stream decode: one front per channel, all three alive for the consumer): the front
 // keeps its marks in region `set` of three in d_egd_mark and its status words in d_egd_status3[set], zeroed
 // here; the other work buffers are reused from front to front in stream order.  set < 0: the grey calls' one
-// front, whose status words alternate between two slots.
+// front, whose status words alternate between two slots.  region_cubes: the cubes the mark regions are sized for
+// (0: n_cubes; the same for the three fronts of a call, so that the first front's allocation holds all three).
 static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint64_t start_bit, uint64_t n_cubes,
-                           EgDecParams& D, bool spec, int set = -1) {
+                           EgDecParams& D, bool spec, int set = -1, uint64_t region_cubes = 0) {
     const uint64_t limit = nbytes * 8;
     const uint64_t n_chunks = (limit - start_bit + kEgChunkBits - 1) / kEgChunkBits;
     const uint64_t n_scan = (n_chunks + 4095) / 4096;
@@ -1498,7 +1627,9 @@ static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     if (!rc) rc = c->d_eg_bsum.grow((n_scan + 1) * sizeof(uint64_t));
     const uint64_t n_marks = n_cubes * (uint64_t)c->plan.cs / 32;
     const uint64_t n_mark_groups = n_marks / kMarkGroup + 1;
-    const size_t mark_bytes = (n_mark_groups * sizeof(uint64_t) + (n_marks + 1) * sizeof(uint16_t) + 7) & ~(size_t)7;
+    // a region of the three: sized for region_cubes when the fronts' streams differ in length (4:2:0: the Y stream's)
+    const uint64_t r_marks = (region_cubes > n_cubes ? region_cubes : n_cubes) * (uint64_t)c->plan.cs / 32;
+    const size_t mark_bytes = ((r_marks / kMarkGroup + 1) * sizeof(uint64_t) + (r_marks + 1) * sizeof(uint16_t) + 7) & ~(size_t)7;
     if (!rc) rc = c->d_egd_mark.grow((set < 0 ? 1 : 3) * mark_bytes);
     if (rc) return rc;
     D.words = (const uint32_t*)d_bytes;
@@ -1756,6 +1887,92 @@ static int decode_eg_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint
         if (rc != kEgRetry || !spec) return rc == kEgRetry ? DCT3D_EDEVICE : rc;
     }
 }
+
+// The packed RGB24 stream decode under 4:2:0 of stacks [st0, st0 + ns) after the three fronts E (stream 0
+// over the frames' cubes, streams 1 and 2 over the chroma plane's: gc): (a) the grey stream decode of streams 1 and 2
+// at the chroma geometry into the context's two planes, sized for this range, and (b) the Y kernel, which reads them
+// and stores the frames at out_stack0 -- unless a front's verdict is bad: then nothing is stored (the planes may hold
+// anything).  Every pointer is rebased so that the kernels' global cube and stack indices land in the range's buffers.
+static int decode_c420_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, const Geom& gc, int st0, int ns,
+                             uint8_t* out_stack0) {
+    const int D = c->bd;
+    const size_t stack_c = (size_t)gc.plane() * D;  // bytes of a stack of one chroma plane
+    int rc;
+    if ((rc = c->d_c420.grow(2 * stack_c * ns))) return rc;
+    const uint64_t cps = g.cps(), cps_c = gc.cps();
+    uint8_t* const planes[2] = {(uint8_t*)c->d_c420.p - (size_t)st0 * stack_c,
+                                (uint8_t*)c->d_c420.p + (size_t)ns * stack_c - (size_t)st0 * stack_c};
+    const Variant v = stream_variant_of(c, g), vc = stream_variant_of(c, gc);
+    hipEvent_t* ev = timer_begin(c);
+    for (int ch = 1; ch < 3; ch++) {
+        DecodeParamsQ Pc;
+        fill_decode_params(c, Pc, nullptr, planes[ch - 1], gc, (st0 + ns) * cps_c);
+        Pc.cube_base = (uint32_t)(st0 * cps_c);
+        Pc.steps = qt_steps(c);
+        if (launch_decode_eg(vc, Pc, E[ch], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->vq_c, c->stream)) return DCT3D_EKERNEL;
+        count_slot_used(c, ns * cps_c * (uint64_t)c->plan.cs);
+    }
+    DecodeParamsQ P;
+    fill_decode_params(c, P, nullptr, out_stack0 - (size_t)st0 * g.plane() * D, g, (st0 + ns) * cps);
+    P.cube_base = (uint32_t)(st0 * cps);
+    P.height = (uint32_t)g.h;  // (the chroma fetch clamps by it whatever the edge)
+    P.steps = qt_steps(c);
+    EgDecRgbParams R;
+    for (int ch = 0; ch < 3; ch++)
+        R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
+    R.diag = E[0].diag;
+    if (launch_decode_eg_y420(v.D, v.edge, v.qt, P, R, C420Planes{planes[0], planes[1]}, c->vq, c->stream)) return DCT3D_EKERNEL;
+    timer_end(c, ev);
+    count_slot_used(c, ns * cps * (uint64_t)c->plan.cs);
+    return DCT3D_OK;
+}
+
+// The whole call: the three fronts, then the ranges -- to d_out (host_out == nullptr), or in chunks of stacks through
+// the pipeline to host_out, each chunk starting on a consumer group in both geometries (the lcm of their
+// eg_stack_align).  One counter slot for all launches (batch).  end_bit and the verdicts: as decode_eg_run's packed case.
+static int decode_c420_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint64_t* nbytes, const uint64_t* start_bit,
+                           const Geom& g, const Geom& gc, int n_stacks, uint64_t n_cubes, uint64_t nc, uint8_t* d_out,
+                           uint8_t* host_out, uint64_t* end_bit) {
+    const uint64_t cubes[3] = {n_cubes, nc, nc};
+    int rc;
+    for (int spec = 1;; spec = 0) {
+        EgDecParams E[3] = {};
+        for (int ch = 0; ch < 3; ch++)
+            if ((rc = eg_decode_front(c, d_bytes[ch], nbytes[ch], start_bit[ch], cubes[ch], E[ch], spec && !c->opt_eg_no_resolve, ch, n_cubes)))
+                return rc;
+        batch_begin(c);
+        if (host_out) {
+            const int ay = eg_stack_align(c, g), ac = eg_stack_align(c, gc);
+            int a = ay, b = ac;  // gcd
+            while (b) {
+                const int t = a % b;
+                a = b;
+                b = t;
+            }
+            rc = run_pipeline(c, n_stacks, 0, (size_t)g.plane() * c->bd, nullptr, host_out, [&](const void*, void* dout, int st0, int ns) {
+                return decode_c420_range(c, E, g, gc, st0, ns, (uint8_t*)dout);
+            }, ay / a * ac);
+        } else {
+            rc = decode_c420_range(c, E, g, gc, 0, n_stacks, d_out);
+        }
+        batch_end(c);
+        if (rc) return rc;
+        uint64_t w[18];
+        if (hipMemcpyAsync(c->h_status + 8, c->d_egd_status3.p, sizeof(w), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            stream_wait(c))
+            return DCT3D_EDEVICE;
+        memcpy(w, c->h_status + 8, sizeof(w));
+        int vd[3];
+        bool retry = false;
+        for (int ch = 0; ch < 3; ch++) retry |= (vd[ch] = egd_verdict(w + 6 * ch, E[ch].n_values, nullptr)) == kEgRetry;
+        rc = retry ? kEgRetry : DCT3D_OK;
+        for (int ch = 0; ch < 3 && !retry; ch++) {
+            if (!vd[ch]) end_bit[ch] = w[6 * ch + 1];
+            else if (!rc) rc = vd[ch];
+        }
+        if (rc != kEgRetry || !spec) return rc == kEgRetry ? DCT3D_EDEVICE : rc;
+    }
+}
 extern "C" {
 
 // Fused: device stream -> device raster.  On a corrupt stream the decode kernel skips itself; on a short
@@ -1801,6 +2018,10 @@ int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], con
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!d_bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
     if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;  // the int32 intermediate has no colour stage
+    Geom gc = g;
+    uint64_t nc = n_cubes;  // 4:2:0: the chroma planes' cubes
+    const bool c420 = c420_on(c, channels);
+    if (c420_refused(c, channels) || (c420 && !c420_geom(g, n_stacks, &gc, &nc))) return DCT3D_EINVAL;
     if (eg_aligned(g)) return dct3d_decode_eg_dev(c, d_bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, d_frames, end_bit);
     if (n_stacks && !d_frames) return DCT3D_EINVAL;
     for (int ch = 0; ch < channels; ch++)
@@ -1832,6 +2053,7 @@ int dct3d_decode_eg_frames_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], con
         if (first) return first;
         return decode_dev(c, (const int32_t*)c->d_eg_q.p, g, n_cubes, d_frames);
     }
+    if (c420) return decode_c420_run(c, d_bytes, nbytes, start_bit, g, gc, n_stacks, n_cubes, nc, d_frames, nullptr, end_bit);
     return decode_eg_run(c, d_bytes, nbytes, start_bit, g, n_stacks, n_cubes, d_frames, nullptr, end_bit);
 }
 
@@ -1845,6 +2067,7 @@ int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uin
     if (!c || !make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
     if (!bytes || !nbytes || !start_bit || !end_bit) return DCT3D_EINVAL;
     if (c->opt_eg_two_step && colour_refused(c, channels)) return DCT3D_EINVAL;
+    if (c420_refused(c, channels)) return DCT3D_EINVAL;
     int rc;
     if (eg_aligned(g)) return dct3d_decode_eg(c, bytes[0], nbytes[0], start_bit[0], w, h, n_stacks, frames, end_bit);
     if (n_stacks && !frames) return DCT3D_EINVAL;
@@ -1871,6 +2094,12 @@ int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uin
         if (hipMemcpyAsync(frames, c->d_egd_raster.p, out_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return DCT3D_EDEVICE;
         return hipStreamSynchronize(c->stream) == hipSuccess ? DCT3D_OK : DCT3D_EDEVICE;
     }
+    if (c420_on(c, channels)) {
+        Geom gc;
+        uint64_t nc;
+        if (!c420_geom(g, n_stacks, &gc, &nc)) return DCT3D_EINVAL;
+        return decode_c420_run(c, d_bytes, nbytes, sb, g, gc, n_stacks, n_cubes, nc, nullptr, frames, end_bit);
+    }
     return decode_eg_run(c, d_bytes, nbytes, sb, g, n_stacks, n_cubes, nullptr, frames, end_bit);
 }
 
@@ -1884,6 +2113,7 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
                     const uint8_t* stack_table) {
     if (!c || !tables || !stack_table || n_tables < 1 || n_tables > kVqMaxTables) return DCT3D_EINVAL;
     if (c->opt_eg_two_step) return DCT3D_EINVAL;  // the int32 intermediate has no table per stack (dct3d.h)
+    if (c420_refused(c, channels)) return DCT3D_EINVAL;  // (before the upload is queued)
     Geom g;
     uint64_t n_cubes;
     if (!make_geom(w, h, channels, n_stacks, true, &g, &n_cubes)) return DCT3D_EINVAL;
@@ -1905,7 +2135,14 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
     const size_t tab_bytes = c->vq_rows.size() * sizeof(float), step_bytes = c->vq_steps.size() * sizeof(double);
     const size_t map_off = kVqStepsBytes + sizeof(FastDiv);
     const size_t tab_off = (map_off + (size_t)n_stacks + 15) & ~(size_t)15;  // the rows: 16-byte aligned
-    const size_t blob_bytes = tab_off + tab_bytes;
+    // 4:2:0: the block twice, the second copy with the chroma plane's cubes per stack in its FastDiv (the chroma
+    // launches' view, c->vq_c: the grey decode's exact replay finds its stack through it)
+    Geom gc = g;
+    uint64_t nc = 0;
+    const bool c420 = c420_on(c, channels);
+    if (c420 && !c420_geom(g, n_stacks, &gc, &nc)) return DCT3D_EINVAL;
+    const size_t one_bytes = (tab_off + tab_bytes + 15) & ~(size_t)15;
+    const size_t blob_bytes = c420 ? 2 * one_bytes : tab_off + tab_bytes;
     int rc;
     if (c->vq_host_bytes < blob_bytes) {
         // (a call that returned has started its last kernel: the copy out of the old block is over)
@@ -1929,12 +2166,22 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
     memcpy(blob + kVqStepsBytes, &div, sizeof(div));
     memcpy(blob + map_off, stack_table, (size_t)n_stacks);
     memcpy(blob + tab_off, c->vq_rows.data(), tab_bytes);
+    if (c420) {
+        memcpy(blob + one_bytes, blob, tab_off + tab_bytes);
+        const FastDiv div_c = fast_div((uint32_t)gc.cps());
+        memcpy(blob + one_bytes + kVqStepsBytes, &div_c, sizeof(div_c));
+    }
     const size_t n16 = (blob_bytes + 15) / 16;  // (the pinned block has 4 KiB to spare behind blob_bytes)
     if ((rc = c->d_vq.grow(n16 * 16))) return rc;
     char* const d = (char*)c->d_vq.p;
     if (launch_vq_upload(c->vq_host_dev, d, (uint32_t)n16, c->stream)) return DCT3D_EKERNEL;
     c->vq_params = VqParams{(const float4*)(d + tab_off), (const double*)d, vq_map_behind((const double*)d)};
     c->vq = &c->vq_params;
+    if (c420) {
+        char* const d2 = d + one_bytes;
+        c->vq_params_c = VqParams{(const float4*)(d2 + tab_off), (const double*)d2, vq_map_behind((const double*)d2)};
+        c->vq_c = &c->vq_params_c;
+    }
     return DCT3D_OK;
 }
 // the call is over.  A call that ended before its kernels ran (an argument the base call refuses, a stream with
@@ -1942,7 +2189,7 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
 // rewrites, so the stream is waited for
 static int vq_end(dct3d_ctx* c, int rc) {
     if (c->vq && rc != DCT3D_OK) (void)stream_wait(c);
-    c->vq = nullptr;
+    c->vq = c->vq_c = nullptr;
     return rc;
 }
 extern "C" {

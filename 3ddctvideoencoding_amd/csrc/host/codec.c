@@ -368,6 +368,49 @@ static int ctx_apply_colour(dct3d_ctx *ctx, int ycc) {
     if (rc) printf("Error setting the colour transform: %s\n", dct3d_strerror(rc));
     return rc != 0;
 }
+static char g_chroma_text[16]; /* codec_set_chroma's text; "": none */
+
+int codec_set_chroma(const char *text) {
+    if (text && strlen(text) >= sizeof(g_chroma_text)) return 1;
+    snprintf(g_chroma_text, sizeof(g_chroma_text), "%s", text ? text : "");
+    return 0;
+}
+/* The chroma mode of a call on `channels` channels whose colour mode is ycc: codec_set_chroma's text, else
+ * DCT3D_CODEC_CHROMA ("420", "444" or the text).  *c420 = 1: Cb and Cr at a quarter of the samples.  1 after
+ * printing when the text is no "chroma=420|444", or 4:2:0 is asked of a call that cannot do it: grey or several
+ * devices (what names it), without ycc=1, the host Exp-Golomb path. */
+static int call_chroma(const char *what, int channels, int ycc, int *c420) {
+    const char *text = g_chroma_text[0] ? g_chroma_text : getenv("DCT3D_CODEC_CHROMA");
+    *c420 = 0;
+    if (!text || !text[0]) return 0;
+    const char *v = strncmp(text, "chroma=", 7) ? text : text + 7;
+    if (strcmp(v, "420") && strcmp(v, "444")) {
+        printf("Invalid chroma mode '%s': chroma=420 or chroma=444\n", text);
+        return 1;
+    }
+    if (!strcmp(v, "444")) return 0;
+    if (channels != 3) {
+        printf("chroma= applies to encode_rgb and decode_rgb on one device (%s)\n", what);
+        return 1;
+    }
+    if (host_eg_on()) {
+        printf("chroma=420 needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
+    if (!ycc) {
+        printf("chroma=420 needs ycc=1: it subsamples the Cb and Cr planes of the colour transform\n");
+        return 1;
+    }
+    *c420 = 1;
+    return 0;
+}
+/* the context of a call codes Cb and Cr at 4:2:0: 1 after printing on an error */
+static int ctx_apply_chroma(dct3d_ctx *ctx, int c420) {
+    if (!c420) return 0;
+    const int rc = dct3d_ctx_set_chroma(ctx, DCT3D_CHROMA_420);
+    if (rc) printf("Error setting the chroma mode: %s\n", dct3d_strerror(rc));
+    return rc != 0;
+}
 /* reads the call's map into ladder indices, one per stack: 1 after printing on an error */
 static int read_qmap(const char *path, int n_stacks, uint8_t *index) {
     int *q = (int *)malloc(sizeof(int) * (size_t)n_stacks);
@@ -655,7 +698,8 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
     }
     if (reject_targets("encode_multi") || reject_qmap("encode_multi")) return 1;
     int ycc;
-    if (call_colour("encode_multi", 1, 0, &ycc)) return 1;
+    int c420;
+    if (call_colour("encode_multi", 1, 0, &ycc) || call_chroma("encode_multi", 1, ycc, &c420)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -767,7 +811,8 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
     }
     if (reject_targets("decode_multi") || reject_qmap("decode_multi")) return 1;
     int ycc;
-    if (call_colour("decode_multi", 1, 0, &ycc)) return 1;
+    int c420;
+    if (call_colour("decode_multi", 1, 0, &ycc) || call_chroma("decode_multi", 1, ycc, &c420)) return 1;
     if (batch <= 0) batch = default_batch();
     FILE *in = fopen(inName, "rb");
     if (!in) {
@@ -912,6 +957,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     if (call_target(SEL_PSNR, &psnr_db, &psnr_set)) return 1;
     int ycc;
     if (call_colour("encode", channels, psnr_set, &ycc)) return 1;
+    int c420;
+    if (call_chroma("encode", channels, ycc, &c420)) return 1;
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
     const char *qmap_path = NULL;
     if (call_qmap(&qmap_path)) return 1;
@@ -938,6 +985,8 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         return 1;
     }
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    /* chroma=420: channels 1 and 2 are the subsampled planes, (width + 1) / 2 x (height + 1) / 2, padded likewise */
+    const int wpc = c420 ? ((width + 1) / 2 + 7) / 8 * 8 : wp, hpc = c420 ? ((height + 1) / 2 + 7) / 8 * 8 : hp;
     /* DCT3D_CODEC_HOST_EG=1: Exp-Golomb on the host from the quantised ints (A/B and tests); default: the
      * device Exp-Golomb stage, the same bytes */
     const int host_eg = host_eg_on();
@@ -964,7 +1013,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
         } else {
-            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc));
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc) || ctx_apply_chroma(ctx, c420));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth; /* of the frames as they are */
@@ -977,7 +1026,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         if (!host_eg) eg = (unsigned char *)malloc(eg_cap);
         int ok = fr && (host_eg ? q != NULL : eg != NULL);
         for (int ch = 0; ch < channels; ch++)
-            if (!(ent[ch] = dct3d_entropy_enc_create(wp, hp, depth, out[ch])) ||
+            if (!(ent[ch] = dct3d_entropy_enc_create(ch ? wpc : wp, ch ? hpc : hp, depth, out[ch])) ||
                 dct3d_entropy_enc_set_threads(ent[ch], deflate_threads, 0))
                 ok = 0;
         if (!ok) {
@@ -1082,6 +1131,8 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     if (reject_targets("decode")) return 1;
     int ycc;
     if (call_colour("decode", channels, 0, &ycc)) return 1;
+    int c420;
+    if (call_chroma("decode", channels, ycc, &c420)) return 1;
     const char *qmap_path = NULL;
     if (call_qmap(&qmap_path)) return 1;
     uint8_t *qmap = NULL;
@@ -1101,6 +1152,8 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     }
     if (batch <= 0) batch = default_batch();
     const int wp = (width + 7) / 8 * 8, hp = (height + 7) / 8 * 8;
+    /* chroma=420: channels 1 and 2 are the subsampled planes, (width + 1) / 2 x (height + 1) / 2, padded likewise */
+    const int wpc = c420 ? ((width + 1) / 2 + 7) / 8 * 8 : wp, hpc = c420 ? ((height + 1) / 2 + 7) / 8 * 8 : hp;
     const int host_eg = host_eg_on();
     FILE *in[3] = {NULL, NULL, NULL};
     dct3d_entropy_dec *ent[3] = {NULL, NULL, NULL};
@@ -1124,7 +1177,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
             printf("Error creating the device context: %s\n", dct3d_strerror(rc));
             status = 1;
         } else {
-            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc));
+            STAGE(t_ctx, status = ctx_apply_quant(ctx, depth) || ctx_apply_colour(ctx, ycc) || ctx_apply_chroma(ctx, c420));
         }
     }
     const size_t stack_bytes = (size_t)channels * width * height * depth;
@@ -1136,7 +1189,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
         if (host_eg) q = (int32_t *)malloc(channels * stack_px * batch * sizeof(int32_t));
         int ok = fr && (!host_eg || q);
         for (int ch = 0; ch < channels; ch++)
-            if (!(ent[ch] = dct3d_entropy_dec_create(wp, hp, depth, in[ch], NULL, 0))) ok = 0;
+            if (!(ent[ch] = dct3d_entropy_dec_create(ch ? wpc : wp, ch ? hpc : hp, depth, in[ch], NULL, 0))) ok = 0;
         if (!ok) {
             printf("Out of memory\n");
             status = 1;
@@ -1192,7 +1245,7 @@ static int decode_any(const char *inName, const char *outName, int width, int he
                     bits_per_value = 0.0;
                     for (int ch = 0; ch < channels; ch++) {
                         dct3d_entropy_dec_consume(ent[ch], eb[ch]);
-                        const double b = (double)(eb[ch] - (uint64_t)bit[ch]) / values;
+                        const double b = (double)(eb[ch] - (uint64_t)bit[ch]) / (ch ? (double)wpc * hpc * depth * nb : values);
                         if (b > bits_per_value) bits_per_value = b;
                     }
                 }

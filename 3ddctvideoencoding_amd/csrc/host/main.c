@@ -16,6 +16,8 @@
  *   a target and by a decode; not together with q= or several devices
  *   encode_rgb and decode_rgb take ycc=1 (codec.h, codec_set_colour): the three files hold the Y, Cb, Cr planes,
  *   the transform computed inside the device calls; not recorded in the file: decode with ycc=1 too; not with psnr=
+ *   ... and chroma=420 beside ycc=1 (codec.h, codec_set_chroma): .green / .blue hold the Cb and Cr planes at a quarter
+ *   of the samples, (width + 1) / 2 x (height + 1) / 2; not recorded either: decode with the same two tokens
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -63,6 +65,11 @@ static void usage(void) {
            "full-range BT.601 in 16-bit fixed point, computed inside the device calls) in place of R, G and B.  The file "
            "does not record it: decode with ycc=1 too.  rate= and qmap= price and code those planes; ycc=1 together with "
            "psnr=, on encode or decode, or with several devices is an error\n");
+    printf("encode_rgb and decode_rgb take chroma=420 together with ycc=1: the .green and .blue files hold the Cb and Cr "
+           "planes at a quarter of the samples, (width + 1) / 2 x (height + 1) / 2 (a 2 x 2 box mean on the way in, pixel "
+           "replication on the way back, inside the device calls); chroma=444 is the default.  The file does not record "
+           "it: decode with the same tokens.  rate= and qmap= price and code the subsampled planes; chroma=420 without "
+           "ycc=1, on encode or decode, or with several devices is an error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -116,13 +123,14 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0;
-    for (int a = 9; a < argc && a < 12 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0;
+    for (int a = 9; a < argc && a < 13 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
         const int is_rate = !strncmp(argv[a], "rate=", 5), is_psnr = !strncmp(argv[a], "psnr=", 5);
         const int is_qmap = !strncmp(argv[a], "qmap=", 5), is_ycc = !strncmp(argv[a], "ycc=", 4);
-        if (a >= 10 && (is_rate ? have_rate : is_psnr ? have_psnr : is_qmap ? have_qmap : is_ycc ? have_ycc : have_quant)) break; /* (a second argument counts only as another kind) */
+        const int is_chroma = !strncmp(argv[a], "chroma=", 7);
+        if (a >= 10 && (is_rate ? have_rate : is_psnr ? have_psnr : is_qmap ? have_qmap : is_ycc ? have_ycc : is_chroma ? have_chroma : have_quant)) break; /* (a second argument counts only as another kind) */
         if (is_ycc) {
             if (strcmp(argv[a], "ycc=0") && strcmp(argv[a], "ycc=1")) {
                 printf("Invalid colour mode '%s': ycc=0 or ycc=1\n", argv[a]);
@@ -134,6 +142,18 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             have_ycc = a;
+        } else if (is_chroma) {
+            if (strcmp(argv[a], "chroma=420") && strcmp(argv[a], "chroma=444")) {
+                printf("Invalid chroma mode '%s': chroma=420 or chroma=444\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (argv[a][9] == '0' && ((strcmp(argv[1], "encode_rgb") && strcmp(argv[1], "decode_rgb")) || n_dev > 1)) {
+                printf("chroma= applies to encode_rgb and decode_rgb on one device\n");
+                usage();
+                return 1;
+            }
+            have_chroma = a;
         } else if (is_qmap) {
             if (!argv[a][5]) {
                 printf("Invalid quality map '%s': qmap=<path>\n", argv[a]);
@@ -176,13 +196,18 @@ int main(int argc, char *argv[]) {
                "samples\n");
         return 1;
     }
+    if (have_chroma && argv[have_chroma][9] == '0' && !(have_ycc && argv[have_ycc][4] == '1') && !getenv("DCT3D_CODEC_YCC")) {
+        printf("chroma=420 needs ycc=1: it subsamples the Cb and Cr planes of the colour transform\n");
+        usage();
+        return 1;
+    }
     if (have_quant && have_qmap) {
         printf("q= and qmap= exclude each other\n");
         return 1;
     }
     if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate])) ||
         (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap])) ||
-        (have_ycc && codec_set_colour(argv[have_ycc]))) {
+        (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma]))) {
         printf("Argument too long\n");
         return 1;
     }

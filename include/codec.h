@@ -158,6 +158,19 @@ int codec_set_qmap(const char *text);
  *   too long to keep. */
 int codec_set_colour(const char *text);
 
+/* 4:2:0 chroma subsampling of the packed RGB24 calls on one device (encode_rgb_ex, decode_rgb_ex), on top of ycc=1:
+ * "chroma=420" codes the Cb and Cr planes at a quarter of the samples (dct3d.h, dct3d_ctx_set_chroma =
+ * DCT3D_CHROMA_420: a 2 x 2 box mean on the way in, pixel replication on the way back, both inside the device stream
+ * calls); "chroma=444" is none.  The .green / .blue files then hold the (width + 1) / 2 x (height + 1) / 2 planes,
+ * each the .bin of encode_ex for that plane.  The .bin does not record the mode: decode with the ycc= and the chroma=
+ * of the encode.  rate=, and rate= with qmap=, price and code the subsampled planes.
+ * Errors (a line printed, 1 returned, before any output file is made): a text that is neither "chroma=420" nor
+ * "chroma=444"; chroma=420 without ycc=1, on a grey call or a several-device call, or with DCT3D_CODEC_HOST_EG=1.
+ * codec_set_chroma: the mode of every later call of this process, as such a text; NULL or "": none.  It overrides
+ *   the environment variable DCT3D_CODEC_CHROMA ("420" or "444", or the text itself).  1 (nothing changes) if the
+ *   text is too long to keep. */
+int codec_set_chroma(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,44 @@ int dct3d_ctx_set_option(dct3d_ctx *ctx, int option, double value);
  * ------------------------------------------------------------------------------------------- */
 
 /* ---------------------------------------------------------------------------------------------
+ * 4:2:0 chroma subsampling (additive to ABI 9).  A mode of the context, not a
+ * DCT3D_OPT_* id, on top of DCT3D_OPT_COLOUR = DCT3D_COLOUR_YCBCR: with DCT3D_CHROMA_420 the Cb and Cr planes of
+ * a packed RGB24 stream call are coded at a quarter of the samples.  With T and T^-1 the colour transform above,
+ * on width x height frames, the mode is DEFINED by these integers:
+ *   chroma size   cw = (width + 1) / 2, ch = (height + 1) / 2 (dct3d_chroma_size).  No temporal subsampling: the
+ *                 block depth is the context's.
+ *   subsample S   per frame and chroma plane p: pad p to even width and height by repeating its last column and
+ *                 row, then c[j][i] = (p[2j][2i] + p[2j][2i+1] + p[2j+1][2i] + p[2j+1][2i+1] + 2) >> 2: a box
+ *                 filter on the 8-bit Cb / Cr values of T (S after T, not a transform of summed R, G, B).
+ *   upsample U    pixel replication, p[y][x] = c[y >> 1][x >> 1], cropped to width x height.
+ *   the streams   0: the Y plane, width x height; 1: S(Cb), cw x ch; 2: S(Cr), cw x ch -- each with its own edge
+ *                 padding (the next multiples of 8), its own cubes per stack, ceil(width / 8) ceil(height / 8) and
+ *                 ceil(cw / 8) ceil(ch / 8), and its own length.
+ * With channels == 3, the transform on and the mode on:
+ *   dct3d_encode_eg_frames[_dev], dct3d_encode_eg_frames_vq[_dev]  stream k, total_bits[k] and DCT3D_ENOSPC are
+ *       those of the grey call (channels == 1) on plane k of (Y, S(Cb), S(Cr)) of T(frames), under the same table
+ *       and carry; the map of a _vq call is per stack and shared by the three channels;
+ *   dct3d_decode_eg_frames[_dev], dct3d_decode_eg_frames_vq[_dev]  from three streams of those value counts, the
+ *       frames are T^-1 of (Y, U(Cb), U(Cr)) of the three grey decodes at (width, height), (cw, ch), (cw, ch);
+ *       end_bit[k] is the grey call's; a short or corrupt stream gives the code and end bits the 4:4:4 call gives
+ *       for the same fault in the same stream, and the frames stay untouched when any stream is bad;
+ *   dct3d_rate_frames[_dev]  bits[t][s][k] is the grey call's of plane k.  The per-cube layout is ragged: with a
+ *       non-NULL d_cube_bits dct3d_rate_frames_dev returns DCT3D_EINVAL; only the totals are offered;
+ *   dct3d_get_stats  n_units is the sum over the three grey calls.
+ * With channels == 1 the mode does nothing.  With channels == 3 and DCT3D_COLOUR_PLANES those calls return
+ * DCT3D_EINVAL before anything is queued.  The calls that refuse the colour option keep refusing it.
+ *
+ * dct3d_ctx_set_chroma: DCT3D_CHROMA_444 (the default) or DCT3D_CHROMA_420; a NULL context or any other value:
+ *   DCT3D_EINVAL, nothing changes.  A context that never sets DCT3D_CHROMA_420 launches what it launched before.
+ * dct3d_ctx_get_chroma: the mode.  dct3d_chroma_size: (cw, ch) of positive (w, h), no context needed.
+ * ------------------------------------------------------------------------------------------- */
+#define DCT3D_CHROMA_444 0
+#define DCT3D_CHROMA_420 1
+int dct3d_ctx_set_chroma(dct3d_ctx *ctx, int mode);
+int dct3d_ctx_get_chroma(const dct3d_ctx *ctx, int *mode);
+int dct3d_chroma_size(int w, int h, int *cw, int *ch);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantiser tables (additive to ABI 9).  A quantiser is one integer step per s = kx + ky + kz of a
  * coefficient's indices, 0 <= s <= bw + bh + bd - 3 (22 entries at 8x8x8, 18 at 8x8x4), each step in
  * [1, 255].  The reference codec's is step[s] = max(1, 5 s) (Encoder.java:75-89, Decoder.java:78-96),
