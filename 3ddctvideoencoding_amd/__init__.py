@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "dct3d_encode_eg_frames_vq", "dct3d_encode_eg_frames_vq_dev",
     "dct3d_decode_eg_frames_vq", "dct3d_decode_eg_frames_vq_dev",
     "dct3d_ctx_set_chroma", "dct3d_ctx_get_chroma", "dct3d_chroma_size",
+    "dct3d_encode_eg_frames_vqc", "dct3d_encode_eg_frames_vqc_dev",
+    "dct3d_decode_eg_frames_vqc", "dct3d_decode_eg_frames_vqc_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -158,6 +160,11 @@ def lib() -> C.CDLL:
         L.dct3d_encode_eg_frames_vq.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
         L.dct3d_decode_eg_frames_vq_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
         L.dct3d_decode_eg_frames_vq.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+        # (the _vq lists: table_map [n_stacks][channels] in the place of stack_table)
+        L.dct3d_encode_eg_frames_vqc_dev.argtypes = L.dct3d_encode_eg_frames_vq_dev.argtypes
+        L.dct3d_encode_eg_frames_vqc.argtypes = L.dct3d_encode_eg_frames_vq.argtypes
+        L.dct3d_decode_eg_frames_vqc_dev.argtypes = L.dct3d_decode_eg_frames_vq_dev.argtypes
+        L.dct3d_decode_eg_frames_vqc.argtypes = L.dct3d_decode_eg_frames_vq.argtypes
         L.dct3d_ctx_set_chroma.argtypes = [vp, i32]
         L.dct3d_ctx_get_chroma.argtypes = [vp, C.POINTER(i32)]
         L.dct3d_chroma_size.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -379,6 +386,29 @@ def pick_stack_qualities(bits, qualities, target_bits_per_stack) -> list:
         raise ValueError("bits must be [len(qualities), n_stacks, channels]")
     return [pick_quality({q: int(bits[t, s, :].astype(object).sum()) for t, q in enumerate(qualities)}, target_bits_per_stack)
             for s in range(bits.shape[1])]
+
+
+def pick_stack_channel_qualities(bits, qualities, target_bits_per_stack, chroma_rungs=0) -> list:
+    """One (q0, q1, q2) per stack for the per-(stack, channel) calls (encode_eg_frames_vqc): bits [T, n_stacks, 3]
+    as rate_frames returns them for the tables of `qualities` (T of them, in that order).  Candidate i codes
+    channel 0 under qualities[i] and channels 1 and 2 under qualities[j], j = min(i + chroma_rungs, T - 1), and
+    costs bits[i, s, 0] + bits[j, s, 1] + bits[j, s, 2]; stack s gets pick_quality's choice on these costs (the
+    smallest quality that fits target_bits_per_stack, else the largest quality).  Nothing assumed monotone."""
+    bits = np.asarray(bits)
+    qualities = [int(q) for q in qualities]
+    T = len(qualities)
+    if bits.ndim != 3 or bits.shape[0] != T or bits.shape[2] != 3:
+        raise ValueError("bits must be [len(qualities), n_stacks, 3]")
+    if int(chroma_rungs) != chroma_rungs or chroma_rungs < 0:
+        raise ValueError("chroma_rungs must be an integer >= 0")
+    j = [min(i + int(chroma_rungs), T - 1) for i in range(T)]
+    index = {q: i for i, q in enumerate(qualities)}
+    res = []
+    for s in range(bits.shape[1]):
+        q = pick_quality({qualities[i]: int(bits[i, s, 0]) + int(bits[j[i], s, 1]) + int(bits[j[i], s, 2]) for i in range(T)},
+                         target_bits_per_stack)
+        res.append((q, qualities[j[index[q]]], qualities[j[index[q]]]))
+    return res
 
 
 def pick_stack_qualities_psnr(sse, qualities, n_samples_per_stack, target_db) -> list:
@@ -836,31 +866,41 @@ class Context:
         return [int(t) for t in eb]
 
     # ---- the same four calls with a quantiser table per stack (include/dct3d.h) ----
-    def _vq_args(self, tables, stack_table, n_stacks: int, what: str):
-        """(int32 [T, n_steps], T, uint8 [n_stacks]) as the C-ABI takes them; a wrong shape is DCT3D_EINVAL"""
+    # (and, the _vqc names, per (stack, channel): DESIGN 4r.  Each pair shares one body: `what` is the C-ABI call,
+    # map_channels None for a map per stack, else the map's second dimension.)
+    def _vq_args(self, tables, stack_table, n_stacks: int, what: str, map_channels=None):
+        """(int32 [T, n_steps], T, uint8 [n_stacks] or [n_stacks, map_channels]) as the C-ABI takes them; a wrong
+        shape is DCT3D_EINVAL"""
         if tables is None or stack_table is None:
             raise Dct3dError(DCT3D_EINVAL, what)
         tb, T = self._rate_tables(tables)
         m = np.asarray(stack_table)
-        if m.ndim != 1 or m.size != n_stacks or np.any(m < 0) or np.any(m > 255) or np.any(m != np.floor(m)):
+        shape = (n_stacks,) if map_channels is None else (n_stacks, map_channels)
+        if m.shape != shape or np.any(m < 0) or np.any(m > 255) or np.any(m != np.floor(m)):
             raise Dct3dError(DCT3D_EINVAL, what)
         return tb, T, np.ascontiguousarray(m, np.uint8)
 
     def encode_eg_frames_vq(self, frames: np.ndarray, tables, stack_table, carry=None) -> list:
         """encode_eg_frames with stack s of every channel coded under tables[stack_table[s]] (a palette of 1..32
         tables, one uint8 entry per stack).  The context's quantiser is neither used nor changed."""
+        return self._encode_eg_frames_vq(frames, tables, stack_table, carry, "dct3d_encode_eg_frames_vq", False)
+
+    def encode_eg_frames_vqc(self, frames: np.ndarray, tables, table_map, carry=None) -> list:
+        """encode_eg_frames_vq with a table per (stack, channel): table_map [n_stacks, channels], stack s of channel
+        ch coded under tables[table_map[s, ch]] (under the colour transform: of plane ch, Y / Cb / Cr)"""
+        return self._encode_eg_frames_vq(frames, tables, table_map, carry, "dct3d_encode_eg_frames_vqc", True)
+
+    def _encode_eg_frames_vq(self, frames, tables, stack_table, carry, what, per_channel) -> list:
         frames = np.ascontiguousarray(frames, np.uint8)
         channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
-        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_encode_eg_frames_vq")
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, what, channels if per_channel else None)
         carry = list(carry) if carry is not None else [(0, 0)] * channels
         if len(carry) != channels:
             raise ValueError("one (carry_byte, carry_bits) per channel")
         cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
         cn = (C.c_int * channels)(*[n for _, n in carry])
         tb = (C.c_uint64 * channels)()
-        _check(lib().dct3d_encode_eg_frames_vq(self._h, _ptr(frames), W, H, channels, n_stacks, _ptr(tq), T,
-                                               _ptr(m), cb, cn, tb),
-               "dct3d_encode_eg_frames_vq")
+        _check(getattr(lib(), what)(self._h, _ptr(frames), W, H, channels, n_stacks, _ptr(tq), T, _ptr(m), cb, cn, tb), what)
         res = []
         for ch in range(channels):
             out = np.empty(eg_stream_bytes(tb[ch]), np.uint8)
@@ -871,10 +911,19 @@ class Context:
 
     def decode_eg_frames_vq(self, streams, width: int, height: int, n_stacks: int, tables, stack_table, start_bits=None):
         """decode_eg_frames under the same palette and map as encode_eg_frames_vq"""
+        return self._decode_eg_frames_vq(streams, width, height, n_stacks, tables, stack_table, start_bits,
+                                         "dct3d_decode_eg_frames_vq", False)
+
+    def decode_eg_frames_vqc(self, streams, width: int, height: int, n_stacks: int, tables, table_map, start_bits=None):
+        """decode_eg_frames under the same palette and [n_stacks, channels] map as encode_eg_frames_vqc"""
+        return self._decode_eg_frames_vq(streams, width, height, n_stacks, tables, table_map, start_bits,
+                                         "dct3d_decode_eg_frames_vqc", True)
+
+    def _decode_eg_frames_vq(self, streams, width, height, n_stacks, tables, stack_table, start_bits, what, per_channel):
         channels = len(streams)
         if channels not in (1, 3):
-            raise Dct3dError(DCT3D_EINVAL, "dct3d_decode_eg_frames_vq")
-        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_decode_eg_frames_vq")
+            raise Dct3dError(DCT3D_EINVAL, what)
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, what, channels if per_channel else None)
         start_bits = list(start_bits) if start_bits is not None else [0] * channels
         bufs = [np.frombuffer(b, np.uint8) for b in streams]
         ptrs = (C.c_void_p * channels)(*[_ptr(b) if b.size else None for b in bufs])
@@ -882,24 +931,36 @@ class Context:
         sb = (C.c_int * channels)(*start_bits)
         eb = (C.c_uint64 * channels)()
         out = np.empty((n_stacks * self.bd, height, width) + ((3,) if channels == 3 else ()), np.uint8)
-        _check(lib().dct3d_decode_eg_frames_vq(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T, _ptr(m),
-                                               _ptr(out), eb), "dct3d_decode_eg_frames_vq")
+        rc = getattr(lib(), what)(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T, _ptr(m), _ptr(out), eb)
+        if rc != DCT3D_OK:
+            raise Dct3dError(rc, what)
         return out, [int(e) for e in eb]
 
     def encode_eg_frames_vq_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables, stack_table,
                                 d_outs, out_caps, carry=None) -> list:
         """encode_eg_frames_dev with a table per stack; errors as there (.total_bits on DCT3D_ENOSPC)"""
-        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_encode_eg_frames_vq_dev")
+        return self._encode_eg_frames_vq_dev(d_frames, width, height, channels, n_stacks, tables, stack_table, d_outs,
+                                             out_caps, carry, "dct3d_encode_eg_frames_vq_dev", False)
+
+    def encode_eg_frames_vqc_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables, table_map,
+                                 d_outs, out_caps, carry=None) -> list:
+        """encode_eg_frames_vq_dev with table_map [n_stacks, channels]: a table per (stack, channel)"""
+        return self._encode_eg_frames_vq_dev(d_frames, width, height, channels, n_stacks, tables, table_map, d_outs,
+                                             out_caps, carry, "dct3d_encode_eg_frames_vqc_dev", True)
+
+    def _encode_eg_frames_vq_dev(self, d_frames, width, height, channels, n_stacks, tables, stack_table, d_outs, out_caps,
+                                 carry, what, per_channel) -> list:
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, what, channels if per_channel else None)
         carry = list(carry) if carry is not None else [(0, 0)] * channels
         cb = (C.c_uint8 * channels)(*[b for b, _ in carry])
         cn = (C.c_int * channels)(*[n for _, n in carry])
         outs = (C.c_void_p * channels)(*[_tptr(t) for t in d_outs])
         caps = (C.c_uint64 * channels)(*out_caps)
         tb = (C.c_uint64 * channels)()
-        rc = lib().dct3d_encode_eg_frames_vq_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks, _ptr(tq), T,
-                                                 _ptr(m), cb, cn, outs, caps, tb)
+        rc = getattr(lib(), what)(self._h, _tptr(d_frames), width, height, channels, n_stacks, _ptr(tq), T, _ptr(m), cb, cn,
+                                  outs, caps, tb)
         if rc != DCT3D_OK:
-            e = Dct3dError(rc, "dct3d_encode_eg_frames_vq_dev")
+            e = Dct3dError(rc, what)
             e.total_bits = [int(t) for t in tb]
             raise e
         return [int(t) for t in tb]
@@ -907,16 +968,27 @@ class Context:
     def decode_eg_frames_vq_dev(self, d_streams, nbytes, start_bits, width: int, height: int, n_stacks: int, tables,
                                 stack_table, d_frames) -> list:
         """decode_eg_frames_dev with a table per stack; errors as there (.end_bits of the good streams)"""
+        return self._decode_eg_frames_vq_dev(d_streams, nbytes, start_bits, width, height, n_stacks, tables, stack_table,
+                                             d_frames, "dct3d_decode_eg_frames_vq_dev", False)
+
+    def decode_eg_frames_vqc_dev(self, d_streams, nbytes, start_bits, width: int, height: int, n_stacks: int, tables,
+                                 table_map, d_frames) -> list:
+        """decode_eg_frames_vq_dev with table_map [n_stacks, channels]: a table per (stack, channel)"""
+        return self._decode_eg_frames_vq_dev(d_streams, nbytes, start_bits, width, height, n_stacks, tables, table_map,
+                                             d_frames, "dct3d_decode_eg_frames_vqc_dev", True)
+
+    def _decode_eg_frames_vq_dev(self, d_streams, nbytes, start_bits, width, height, n_stacks, tables, stack_table, d_frames,
+                                 what, per_channel) -> list:
         channels = len(d_streams)
-        tq, T, m = self._vq_args(tables, stack_table, n_stacks, "dct3d_decode_eg_frames_vq_dev")
+        tq, T, m = self._vq_args(tables, stack_table, n_stacks, what, channels if per_channel else None)
         ptrs = (C.c_void_p * channels)(*[_tptr(t) for t in d_streams])
         nb = (C.c_uint64 * channels)(*nbytes)
         sb = (C.c_uint64 * channels)(*start_bits)
         eb = (C.c_uint64 * channels)()
-        rc = lib().dct3d_decode_eg_frames_vq_dev(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T,
-                                                 _ptr(m), _tptr(d_frames), eb)
+        rc = getattr(lib(), what)(self._h, ptrs, nb, sb, width, height, channels, n_stacks, _ptr(tq), T, _ptr(m),
+                                  _tptr(d_frames), eb)
         if rc != DCT3D_OK:
-            e = Dct3dError(rc, "dct3d_decode_eg_frames_vq_dev")
+            e = Dct3dError(rc, what)
             e.end_bits = [int(t) for t in eb]
             raise e
         return [int(t) for t in eb]

@@ -16,6 +16,13 @@ namespace dct3d {
 // VqParams, as the kernel's trailing pack: empty for QT 0 and 1, whose parameters are the same with and without it.
 static_assert(kVqTabN == kTabN, "a palette table's rows as the encode kernels'");
 __device__ __forceinline__ const VqParams& vq_of(const VqParams& V) { return V; }  // the pack's one element
+// decode_eg_rgb_kernel's view for channel ch: the call's one block (_vq), or channel ch's (_vqc: VqcParams) -- scalar
+// arithmetic on kernel arguments and the channel loop's counter, no load
+__device__ __forceinline__ const VqParams& vq_channel(int, const VqParams& V) { return V; }
+__device__ __forceinline__ VqParams vq_channel(int ch, const VqcParams& V) {
+    const double* const st = (const double*)((const char*)V.steps + (uint32_t)ch * V.ch_stride);
+    return VqParams{V.tabs, st, vq_map_behind(st)};
+}
 
 // =============================================================================================
 // Fused encode + Exp-Golomb, K1 (dct3d_encode_eg_dev; encoder.c:206-274 up to the deflate)
@@ -835,9 +842,10 @@ __global__ __launch_bounds__(kBlock, 3) void decode_eg_rgb_kernel(typename Decod
         __builtin_amdgcn_s_setprio(0);  // the transform
         uint32_t outw[D][NW];
         if constexpr (QT == 2) {
-            // the steps of the lane's cube (all three channels of a stack share its table), looked up here and
-            // not earlier (the opaque lane: no register is held across the parse for it)
-            const VqParams& V = vq_of(vq...);
+            // the steps of the lane's cube (a _vq call: all three channels of a stack share its table; a _vqc call:
+            // under channel ch's map column, whose block lies ch * ch_stride bytes on), looked up here and not
+            // earlier (the opaque lane: no register is held across the parse for it)
+            const VqParams V = vq_channel(ch, vq...);
             int ql = lane;
             asm volatile("" : "+v"(ql));
             const double* const qs = vq_lane_steps<D>(V, P, min(cube0 + (uint32_t)dec_cube_of_lane<D>(ql), P.n_cubes - 1), ql);

@@ -245,12 +245,14 @@ int launch_decode(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
 // cube (a chunk of whole stacks).  Grey stream decode: groups_per_wave = 1, 2, 4 or 8 groups of CPW cubes per
 // wave, the next one's loads ahead, in the variant of grey multiples of 8 and the reference steps (every other
 // value, every other variant: 8).  Packed RGB24 stream decode: from three streams.  V: the call's palette and map
-// (dct3d_vq.h) for qt = 2, a table per stack; else nullptr.
+// (dct3d_vq.h) for qt = 2, a table per stack; else nullptr.  vq_ch_stride: VqcParams::ch_stride of a call with a
+// table per (stack, channel), else 0.
 struct VqParams;
 int launch_encode_eg(const Variant& v, const EncodeParams& P, const EgFusedParams& E, const VqParams* V, hipStream_t st);
 int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, const VqParams* V,
                      hipStream_t st);
-int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st);
+int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, uint32_t vq_ch_stride,
+                         hipStream_t st);
 template <class Unit> int launch_encode_in(const Variant& v, const EncodeParams& P, hipStream_t st);
 template <class Unit> int launch_decode_in(const Variant& v, const DecodeParamsQ& P, hipStream_t st);
 template <class Unit>
@@ -259,7 +261,8 @@ template <class Unit>
 int launch_decode_eg_in(const Variant& v, const DecodeParamsQ& P, const EgDecParams& E, int groups_per_wave, const VqParams* V,
                         hipStream_t st);
 template <class Unit>
-int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st);
+int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, uint32_t vq_ch_stride,
+                            hipStream_t st);
 int launch_eg_stitch(const EgParams& P, hipStream_t st);
 // scan of the segment bits + the lanes' words concatenated into the stream + stitch (P.n_cubes =
 // segments, P.bits = seg_bits)

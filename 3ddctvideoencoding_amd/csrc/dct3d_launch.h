@@ -77,17 +77,26 @@ int launch_decode_eg_in(const Variant& v, const DecodeParamsQ& P, const EgDecPar
     return rc;
 }
 
-// packed RGB24: three streams
+// packed RGB24: three streams.  vq_ch_stride != 0 (a _vqc call, qt = 2): the instances that take a block per channel
+// (VqcParams); the _vq calls keep theirs
 template <class Unit>
-int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st) {
+int launch_decode_eg_rgb_in(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V,
+                            uint32_t vq_ch_stride, hipStream_t st) {
     if (P.n_cubes == 0) return 0;
     int rc = -1;
     with_stream_variant(v, [&](auto d, auto p, auto e, auto q, auto ct) {
         if constexpr (p == 3 && Unit::holds(d, p, e, q, ct)) {
             if (q == 2 ? !V || !V->steps || !V->map : q && !P.steps) return;
             const dim3 grid(dec_grid(d, P.n_cubes - P.cube_base));
-            if constexpr (q == 2) hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, ct, VqParams>), grid, dim3(kBlock), 0, st, P, E, *V);
-            else hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, q, ct>), grid, dim3(kBlock), 0, st, P, E);
+            if constexpr (q == 2) {
+                if (vq_ch_stride)
+                    hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, ct, VqcParams>), grid, dim3(kBlock), 0, st, P, E,
+                                       VqcParams{*V, vq_ch_stride});
+                else
+                    hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, 2, ct, VqParams>), grid, dim3(kBlock), 0, st, P, E, *V);
+            } else {
+                hipLaunchKernelGGL((decode_eg_rgb_kernel<d, e, q, ct>), grid, dim3(kBlock), 0, st, P, E);
+            }
             rc = launched();
         }
     });

@@ -11,6 +11,6 @@ namespace dct3d {
 
 template int launch_encode_eg_in<StreamQuant>(const Variant&, const EncodeParams&, const EgFusedParams&, const VqParams*, hipStream_t);
 template int launch_decode_eg_in<StreamQuant>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, const VqParams*, hipStream_t);
-template int launch_decode_eg_rgb_in<StreamQuant>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, const VqParams*, hipStream_t);
+template int launch_decode_eg_rgb_in<StreamQuant>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, const VqParams*, uint32_t, hipStream_t);
 
 }  // namespace dct3d

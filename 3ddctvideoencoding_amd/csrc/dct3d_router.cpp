@@ -19,9 +19,10 @@ int launch_decode_eg(const Variant& v, const DecodeParamsQ& P, const EgDecParams
     return StreamUnits::route(v, [&](auto u) { return launch_decode_eg_in<decltype(u)>(v, P, E, groups_per_wave, V, st); });
 }
 // (no packed RGB24 variant is in StreamPlain, which builds no such ladder)
-int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, hipStream_t st) {
+int launch_decode_eg_rgb(const Variant& v, const DecodeParamsQ& P, const EgDecRgbParams& E, const VqParams* V, uint32_t vq_ch_stride,
+                         hipStream_t st) {
     using RgbUnits = Units<StreamFrames, StreamQuant, StreamVq, StreamYcc>;
-    return RgbUnits::route(v, [&](auto u) { return launch_decode_eg_rgb_in<decltype(u)>(v, P, E, V, st); });
+    return RgbUnits::route(v, [&](auto u) { return launch_decode_eg_rgb_in<decltype(u)>(v, P, E, V, vq_ch_stride, st); });
 }
 
 }  // namespace dct3d

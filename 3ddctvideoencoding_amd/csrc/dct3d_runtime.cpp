@@ -149,15 +149,17 @@ struct dct3d_ctx {
     std::vector<int32_t> vq_tables;
     std::vector<float> vq_rows;
     std::vector<double> vq_steps;
-    VqParams vq_params = {};
+    // (one view per channel: vq_ch[ch] is channel ch's block {steps, FastDiv, map column}, with the cubes per
+    // stack of that channel's plane in the FastDiv -- the chroma plane's under 4:2:0.  A _vq call's channels share
+    // a block where their planes' geometry is the same.  vq == vq_ch.)
+    VqParams vq_ch[3] = {};
     const VqParams* vq = nullptr;
+    uint32_t vq_ch_stride = 0;  // != 0: a _vqc call's 4:4:4 RGB decode, the bytes from one channel's block to the next
     // 4:2:0 chroma subsampling (dct3d_ctx_set_chroma): the mode, the stream decode's two chroma planes
     // (S(Cb) then S(Cr), each [n_stacks * bd][ceil(h / 2)][ceil(w / 2)]: the grey stream decode writes them, the Y
-    // kernel reads them), and a vq call's second view of its block, whose FastDiv is the chroma plane's cubes per stack
+    // kernel reads them)
     int chroma = DCT3D_CHROMA_444;
     DevBuf d_c420;
-    VqParams vq_params_c = {};
-    const VqParams* vq_c = nullptr;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -1141,7 +1143,8 @@ static int encode_eg_chain(dct3d_ctx* c, const uint8_t* d_raster, const Geom& g,
     uint64_t st[2] = {0, 0};
     hipEvent_t* ev = timer_begin(c);  // events 0-1 bracket K1, 2-3 the compaction
     const Variant v = stream_variant_of(c, g);
-    if (gc ? launch_encode_eg_c420(v.D, c420_edge(g), v.qt, P, E, c->vq_c, c->stream) : launch_encode_eg(v, P, E, c->vq, c->stream))
+    const VqParams* const vq = c->vq ? &c->vq_ch[ch] : nullptr;  // channel ch's map column
+    if (gc ? launch_encode_eg_c420(v.D, c420_edge(g), v.qt, P, E, vq, c->stream) : launch_encode_eg(v, P, E, vq, c->stream))
         return DCT3D_EKERNEL;
     if (!plain) c->slot_used = true;  // (the call flips the counter slot: count_slot_used)
     if (ev) (void)hipEventRecord(ev[1], c->stream);
@@ -1822,7 +1825,7 @@ static int decode_eg_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, in
         for (int ch = 0; ch < 3; ch++)
             R.s[ch] = EgDecStream{E[ch].words, E[ch].n_words, E[ch].n_values, E[ch].mark, E[ch].mark_base, E[ch].status};
         R.diag = E[0].diag;
-        lrc = launch_decode_eg_rgb(v, P, R, c->vq, c->stream);
+        lrc = launch_decode_eg_rgb(v, P, R, c->vq, c->vq_ch_stride, c->stream);
     } else {  // (the test option's groups per wave: where the variant's unit builds them.  A vq call's map is
               // indexed by the call's stacks: the chunks' cube indices are the call's)
         lrc = launch_decode_eg(v, P, E[0], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->vq, c->stream);
@@ -1909,7 +1912,8 @@ static int decode_c420_range(dct3d_ctx* c, const EgDecParams* E, const Geom& g, 
         fill_decode_params(c, Pc, nullptr, planes[ch - 1], gc, (st0 + ns) * cps_c);
         Pc.cube_base = (uint32_t)(st0 * cps_c);
         Pc.steps = qt_steps(c);
-        if (launch_decode_eg(vc, Pc, E[ch], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->vq_c, c->stream)) return DCT3D_EKERNEL;
+        if (launch_decode_eg(vc, Pc, E[ch], c->opt_eg_dec_groups ? c->opt_eg_dec_groups : 8, c->vq ? &c->vq_ch[ch] : nullptr, c->stream))
+            return DCT3D_EKERNEL;
         count_slot_used(c, ns * cps_c * (uint64_t)c->plan.cs);
     }
     DecodeParamsQ P;
@@ -2109,8 +2113,12 @@ int dct3d_decode_eg_frames(dct3d_ctx* c, const uint8_t* const bytes[], const uin
 // (probe_tables: encoder_tables per entry, no plan rebuild), and steps, map and rows queued to the device on the
 // context stream as one block laid out as VqParams says (launch_vq_upload, from the context's pinned copy).  From here to vq_end the stream calls' host bodies
 // launch the vq kernels.
+// per_channel (the _vqc calls): stack_table is [n_stacks][channels], else [n_stacks] for every channel.
+// The block holds one {steps, FastDiv, map column} per distinct (column, plane geometry) -- one for a _vq call, two
+// under 4:2:0 (the frames' and the chroma plane's cubes per stack), one per channel for a _vqc call of three
+// channels -- and the palette's rows once behind them; c->vq_ch[ch] is channel ch's view.
 static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, const int32_t* tables, int n_tables,
-                    const uint8_t* stack_table) {
+                    const uint8_t* stack_table, bool per_channel = false) {
     if (!c || !tables || !stack_table || n_tables < 1 || n_tables > kVqMaxTables) return DCT3D_EINVAL;
     if (c->opt_eg_two_step) return DCT3D_EINVAL;  // the int32 intermediate has no table per stack (dct3d.h)
     if (c420_refused(c, channels)) return DCT3D_EINVAL;  // (before the upload is queued)
@@ -2120,8 +2128,9 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
     const int n_steps = (int)c->plan.steps.size();
     for (int i = 0; i < n_tables * n_steps; i++)
         if (tables[i] < kMinStep || tables[i] > kMaxStep) return DCT3D_EINVAL;
-    for (int s = 0; s < n_stacks; s++)
-        if (stack_table[s] >= n_tables) return DCT3D_EINVAL;
+    const int map_w = per_channel ? channels : 1;  // entries per stack in stack_table
+    for (size_t i = 0; i < (size_t)n_stacks * map_w; i++)
+        if (stack_table[i] >= n_tables) return DCT3D_EINVAL;
     if (n_stacks == 0) return DCT3D_OK;  // (nothing to upload; the base call ends before any launch)
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     static_assert(kVqTabN == kRateTabN && kVqStepN == kDistStepN && kVqMaxTables == DCT3D_RATE_MAX_TABLES, "the probes' layouts");
@@ -2134,15 +2143,18 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
     }
     const size_t tab_bytes = c->vq_rows.size() * sizeof(float), step_bytes = c->vq_steps.size() * sizeof(double);
     const size_t map_off = kVqStepsBytes + sizeof(FastDiv);
-    const size_t tab_off = (map_off + (size_t)n_stacks + 15) & ~(size_t)15;  // the rows: 16-byte aligned
-    // 4:2:0: the block twice, the second copy with the chroma plane's cubes per stack in its FastDiv (the chroma
-    // launches' view, c->vq_c: the grey decode's exact replay finds its stack through it)
+    const size_t blk_bytes = (map_off + (size_t)n_stacks + 15) & ~(size_t)15;  // one {steps, FastDiv, map column}
+    // 4:2:0: the chroma channels' blocks have the chroma plane's cubes per stack in their FastDiv (the grey decode's
+    // exact replay finds its stack through it)
     Geom gc = g;
     uint64_t nc = 0;
     const bool c420 = c420_on(c, channels);
     if (c420 && !c420_geom(g, n_stacks, &gc, &nc)) return DCT3D_EINVAL;
-    const size_t one_bytes = (tab_off + tab_bytes + 15) & ~(size_t)15;
-    const size_t blob_bytes = c420 ? 2 * one_bytes : tab_off + tab_bytes;
+    const bool cols = per_channel && channels == 3;  // a column per channel
+    const int n_blk = cols ? 3 : c420 ? 2 : 1;
+    const int blk_of[3] = {0, n_blk > 1 ? 1 : 0, cols ? 2 : n_blk > 1 ? 1 : 0};
+    const size_t tab_off = (size_t)n_blk * blk_bytes;  // the rows: 16-byte aligned
+    const size_t blob_bytes = tab_off + tab_bytes;
     int rc;
     if (c->vq_host_bytes < blob_bytes) {
         // (a call that returned has started its last kernel: the copy out of the old block is over)
@@ -2161,27 +2173,28 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
         c->vq_host_bytes = blob_bytes + 4096;
     }
     uint8_t* const blob = c->vq_host;
-    memcpy(blob, c->vq_steps.data(), step_bytes);
-    const FastDiv div = fast_div((uint32_t)g.cps());
-    memcpy(blob + kVqStepsBytes, &div, sizeof(div));
-    memcpy(blob + map_off, stack_table, (size_t)n_stacks);
-    memcpy(blob + tab_off, c->vq_rows.data(), tab_bytes);
-    if (c420) {
-        memcpy(blob + one_bytes, blob, tab_off + tab_bytes);
-        const FastDiv div_c = fast_div((uint32_t)gc.cps());
-        memcpy(blob + one_bytes + kVqStepsBytes, &div_c, sizeof(div_c));
+    for (int b = 0; b < n_blk; b++) {
+        uint8_t* const blk = blob + (size_t)b * blk_bytes;
+        memcpy(blk, c->vq_steps.data(), step_bytes);
+        const FastDiv div = fast_div((uint32_t)(c420 && b ? gc.cps() : g.cps()));
+        memcpy(blk + kVqStepsBytes, &div, sizeof(div));
+        if (cols)  // column b of [n_stacks][3]
+            for (int s = 0; s < n_stacks; s++) blk[map_off + s] = stack_table[(size_t)s * 3 + b];
+        else
+            memcpy(blk + map_off, stack_table, (size_t)n_stacks);
     }
+    memcpy(blob + tab_off, c->vq_rows.data(), tab_bytes);
     const size_t n16 = (blob_bytes + 15) / 16;  // (the pinned block has 4 KiB to spare behind blob_bytes)
     if ((rc = c->d_vq.grow(n16 * 16))) return rc;
     char* const d = (char*)c->d_vq.p;
     if (launch_vq_upload(c->vq_host_dev, d, (uint32_t)n16, c->stream)) return DCT3D_EKERNEL;
-    c->vq_params = VqParams{(const float4*)(d + tab_off), (const double*)d, vq_map_behind((const double*)d)};
-    c->vq = &c->vq_params;
-    if (c420) {
-        char* const d2 = d + one_bytes;
-        c->vq_params_c = VqParams{(const float4*)(d2 + tab_off), (const double*)d2, vq_map_behind((const double*)d2)};
-        c->vq_c = &c->vq_params_c;
+    for (int ch = 0; ch < 3; ch++) {
+        const double* const st = (const double*)(d + (size_t)blk_of[ch] * blk_bytes);
+        c->vq_ch[ch] = VqParams{(const float4*)(d + tab_off), st, vq_map_behind(st)};
     }
+    // (decode_eg_rgb_kernel, the 4:4:4 decode of three channels, walks the blocks from channel 0's: VqcParams)
+    c->vq_ch_stride = cols && !c420 ? (uint32_t)blk_bytes : 0u;
+    c->vq = c->vq_ch;
     return DCT3D_OK;
 }
 // the call is over.  A call that ended before its kernels ran (an argument the base call refuses, a stream with
@@ -2189,7 +2202,8 @@ static int vq_begin(dct3d_ctx* c, int w, int h, int channels, int n_stacks, cons
 // rewrites, so the stream is waited for
 static int vq_end(dct3d_ctx* c, int rc) {
     if (c->vq && rc != DCT3D_OK) (void)stream_wait(c);
-    c->vq = c->vq_c = nullptr;
+    c->vq = nullptr;
+    c->vq_ch_stride = 0;
     return rc;
 }
 extern "C" {
@@ -2224,6 +2238,41 @@ int dct3d_decode_eg_frames_vq(dct3d_ctx* c, const uint8_t* const bytes[], const 
                               int w, int h, int channels, int n_stacks, const int32_t* tables, int n_tables,
                               const uint8_t* stack_table, uint8_t* frames, uint64_t end_bit[]) {
     const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, stack_table);
+    if (rc) return rc;
+    return vq_end(c, dct3d_decode_eg_frames(c, bytes, nbytes, start_bit, w, h, channels, n_stacks, frames, end_bit));
+}
+
+// ---- a table per (stack, channel): table_map[n_stacks][channels] (dct3d.h) ----
+int dct3d_encode_eg_frames_vqc_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                                   const int32_t* tables, int n_tables, const uint8_t* table_map,
+                                   const uint8_t carry_byte[], const int carry_bits[], uint8_t* const d_out[],
+                                   const uint64_t out_cap[], uint64_t total_bits[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, table_map, true);
+    if (rc) return rc;
+    return vq_end(c, dct3d_encode_eg_frames_dev(c, d_frames, w, h, channels, n_stacks, carry_byte, carry_bits, d_out, out_cap, total_bits));
+}
+
+int dct3d_encode_eg_frames_vqc(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                               const int32_t* tables, int n_tables, const uint8_t* table_map,
+                               const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, table_map, true);
+    if (rc) return rc;
+    return vq_end(c, dct3d_encode_eg_frames(c, frames, w, h, channels, n_stacks, carry_byte, carry_bits, total_bits));
+}
+
+int dct3d_decode_eg_frames_vqc_dev(dct3d_ctx* c, const uint8_t* const d_bytes[], const uint64_t nbytes[],
+                                   const uint64_t start_bit[], int w, int h, int channels, int n_stacks,
+                                   const int32_t* tables, int n_tables, const uint8_t* table_map, uint8_t* d_frames,
+                                   uint64_t end_bit[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, table_map, true);
+    if (rc) return rc;
+    return vq_end(c, dct3d_decode_eg_frames_dev(c, d_bytes, nbytes, start_bit, w, h, channels, n_stacks, d_frames, end_bit));
+}
+
+int dct3d_decode_eg_frames_vqc(dct3d_ctx* c, const uint8_t* const bytes[], const uint64_t nbytes[], const int start_bit[],
+                               int w, int h, int channels, int n_stacks, const int32_t* tables, int n_tables,
+                               const uint8_t* table_map, uint8_t* frames, uint64_t end_bit[]) {
+    const int rc = vq_begin(c, w, h, channels, n_stacks, tables, n_tables, table_map, true);
     if (rc) return rc;
     return vq_end(c, dct3d_decode_eg_frames(c, bytes, nbytes, start_bit, w, h, channels, n_stacks, frames, end_bit));
 }

@@ -23,6 +23,13 @@ struct VqParams {
     const double* steps;  // decode: [kVqMaxTables][kVqStepN] step_s (the first n_tables filled)
     const uint8_t* map;   // [n_stacks] table of each stack, < n_tables; == vq_map_behind(steps)
 };
+// A table per (stack, channel) (the _vqc calls): every channel has a block {steps, FastDiv, map column} of
+// its own and a launch is handed its channel's VqParams -- but for decode_eg_rgb_kernel, which walks the three
+// channels itself.  Its _vqc instances take this: channel ch's block begins ch * ch_stride bytes behind `steps`
+// (`map`: channel 0's column).  The _vq calls keep the VqParams instances, whose text is as it was.
+struct VqcParams : VqParams {
+    uint32_t ch_stride;
+};
 constexpr size_t kVqStepsBytes = (size_t)kVqMaxTables * kVqStepN * sizeof(double);
 __host__ __device__ inline const FastDiv* vq_div_behind(const double* steps) {
     return (const FastDiv*)((const char*)steps + kVqStepsBytes);

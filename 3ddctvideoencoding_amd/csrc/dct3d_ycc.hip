@@ -14,7 +14,7 @@ namespace dct3d {
 template int launch_encode_eg_in<StreamYcc>(const Variant&, const EncodeParams&, const EgFusedParams&, const VqParams*, hipStream_t);
 // (no grey variant is in StreamYcc: this ladder launches nothing and answers -1)
 template int launch_decode_eg_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecParams&, int, const VqParams*, hipStream_t);
-template int launch_decode_eg_rgb_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, const VqParams*, hipStream_t);
+template int launch_decode_eg_rgb_in<StreamYcc>(const Variant&, const DecodeParamsQ&, const EgDecRgbParams&, const VqParams*, uint32_t, hipStream_t);
 
 int launch_rate_ycc(int D, int edge, const EncodeParams& P, const RateParams& R, hipStream_t st) {
     return probe_dispatch(D, 3, edge, P, R, [&](auto d, auto, auto e) {

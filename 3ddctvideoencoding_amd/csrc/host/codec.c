@@ -325,6 +325,136 @@ static int reject_qmap(const char *what) {
     return 1;
 }
 
+/* ---- the per-(stack, channel) quality map of encode_rgb / decode_rgb (codec.h) ---------------------- */
+static char g_qmap3_text[4096]; /* codec_set_qmap3's text; "": none */
+static char g_cq_text[16];      /* codec_set_cq's text; "": none */
+
+int codec_set_qmap3(const char *text) {
+    if (text && strlen(text) >= sizeof(g_qmap3_text)) return 1;
+    snprintf(g_qmap3_text, sizeof(g_qmap3_text), "%s", text ? text : "");
+    return 0;
+}
+int codec_set_cq(const char *text) {
+    if (text && strlen(text) >= sizeof(g_cq_text)) return 1;
+    snprintf(g_cq_text, sizeof(g_cq_text), "%s", text ? text : "");
+    return 0;
+}
+
+int codec_parse_qmap3(const char *path, int n_stacks, int *qualities) {
+    if (!path || !path[0] || n_stacks <= 0 || !qualities) return 1;
+    FILE *f = fopen(path, "r");
+    if (!f) return 1;
+    int *q = (int *)malloc(sizeof(int) * 3 * (size_t)n_stacks);
+    int n = 0, bad = q == NULL;
+    char line[64];
+    while (!bad && fgets(line, sizeof(line), f)) {
+        size_t len = strlen(line);
+        if (len && line[len - 1] == '\n') line[--len] = '\0';
+        if (len && line[len - 1] == '\r') line[--len] = '\0';
+        if (n >= n_stacks) bad = 1; /* a line too many */
+        const char *p = line;
+        for (int k = 0; k < 3 && !bad; k++) { /* three numbers, one space between, nothing else */
+            char *end = NULL;
+            const long v = (*p >= '0' && *p <= '9') ? strtol(p, &end, 10) : -1;
+            if (v < 0 || ladder_index(v) < 0 || *end != (k < 2 ? ' ' : '\0')) bad = 1;
+            else {
+                q[3 * n + k] = (int)v;
+                p = end + 1;
+            }
+        }
+        if (!bad) n++;
+    }
+    fclose(f);
+    if (!bad && n != n_stacks) bad = 1;
+    if (!bad) memcpy(qualities, q, sizeof(int) * 3 * (size_t)n_stacks);
+    free(q);
+    return bad;
+}
+
+static const char *qmap3_text(void) { return g_qmap3_text[0] ? g_qmap3_text : getenv("DCT3D_CODEC_QMAP3"); }
+static const char *cq_text(void) { return g_cq_text[0] ? g_cq_text : getenv("DCT3D_CODEC_CQ"); }
+/* The three-column map of a call on `channels` channels: codec_set_qmap3's text, else DCT3D_CODEC_QMAP3; and the
+ * chroma offset cq=<k> (codec_set_cq, else DCT3D_CODEC_CQ).  *path = NULL: none given; *cq = k (0 without cq=).  1
+ * after printing when a text does not parse, the map stands beside a quantiser, a per-stack map or a PSNR target, on a
+ * grey call (what names it) or on the host Exp-Golomb path, or cq= stands without ycc=1 or without rate= and qmap3=. */
+static int call_qmap3(const char *what, int channels, int rate_set, int psnr_set, int ycc, const char **path, int *cq) {
+    const char *text = qmap3_text(), *ct = cq_text();
+    *path = NULL;
+    *cq = 0;
+    if (ct && ct[0]) {
+        const char *v = strncmp(ct, "cq=", 3) ? ct : ct + 3;
+        char *end = NULL;
+        const long k = (v[0] >= '0' && v[0] <= '9') ? strtol(v, &end, 10) : -1;
+        if (k < 0 || k > 15 || *end) {
+            printf("Invalid chroma offset '%s': cq=<0..15>, rungs of the ladder\n", ct);
+            return 1;
+        }
+        if (!ycc) {
+            printf("cq= needs ycc=1: it codes the Cb and Cr planes more coarsely than Y\n");
+            return 1;
+        }
+        if (!rate_set || !text || !text[0]) {
+            printf("cq= applies to an encode_rgb with rate= and qmap3= (%s)\n", what);
+            return 1;
+        }
+        *cq = (int)k;
+    }
+    if (!text || !text[0]) return 0;
+    if (strncmp(text, "qmap3=", 6) || !text[6]) {
+        printf("Invalid quality map '%s': qmap3=<path>\n", text);
+        return 1;
+    }
+    if (channels != 3) {
+        printf("qmap3= and cq= apply to encode_rgb and decode_rgb on one device (%s)\n", what);
+        return 1;
+    }
+    const char *qt = sel_text(SEL_QUANT), *mt = g_qmap_text[0] ? g_qmap_text : getenv("DCT3D_CODEC_QMAP");
+    if ((qt && qt[0]) || (mt && mt[0]) || psnr_set) {
+        printf("qmap3= excludes q=, qmap= and psnr= ('%s')\n", text);
+        return 1;
+    }
+    if (host_eg_on()) {
+        printf("qmap3= needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
+    *path = text + 6;
+    return 0;
+}
+/* the commands that take no three-column map: 1 after printing when one, or cq=, is given */
+static int reject_qmap3(const char *what) {
+    const char *text = qmap3_text(), *ct = cq_text();
+    if ((!text || !text[0]) && (!ct || !ct[0])) return 0;
+    printf("qmap3= and cq= apply to encode_rgb and decode_rgb on one device (%s)\n", what);
+    return 1;
+}
+/* the call's three-column map as ladder indices, [n_stacks][3]: 1 after printing on an error */
+static int read_qmap3(const char *path, int n_stacks, uint8_t *index) {
+    int *q = (int *)malloc(sizeof(int) * 3 * (size_t)n_stacks);
+    if (!q || codec_parse_qmap3(path, n_stacks, q)) {
+        printf("Invalid quality map file '%s': %d lines, one per stack, each three qualities of the ladder separated by "
+               "single spaces\n", path, n_stacks);
+        free(q);
+        return 1;
+    }
+    for (int i = 0; i < 3 * n_stacks; i++) index[i] = (uint8_t)ladder_index(q[i]);
+    free(q);
+    return 0;
+}
+static int write_qmap3(const char *path, int n_stacks, const uint8_t *index) {
+    FILE *f = fopen(path, "w");
+    if (!f) {
+        printf("Cannot open output file %s\n", path);
+        return 1;
+    }
+    for (int s = 0; s < n_stacks; s++)
+        fprintf(f, "%d %d %d\n", kRateLadder[index[3 * s]], kRateLadder[index[3 * s + 1]], kRateLadder[index[3 * s + 2]]);
+    if (fflush(f) || fclose(f)) {
+        printf("Error writing the quality map %s\n", path);
+        return 1;
+    }
+    return 0;
+}
+
 static char g_colour_text[16]; /* codec_set_colour's text; "": none */
 
 int codec_set_colour(const char *text) {
@@ -440,9 +570,12 @@ static int write_qmap(const char *path, int n_stacks, const uint8_t *index) {
 /* stack_pick (with a quality map): the rules per stack instead -- stack s's bits and squared error summed over the
  * channels, the rate target's budget that of `depth` frames, the PSNR over the stack's unpadded samples of all
  * channels (the zero-filled frames of a short last stack count); stack_pick[s] = the ladder index.  Prints
- * "qmap: stacks=<n> bits=<total>" and leaves the context's quantiser alone. */
+ * "qmap: stacks=<n> bits=<total>" and leaves the context's quantiser alone.
+ * cq >= 0 (a three-column map, rate target, three channels): stack_pick is [n_stacks][3]; candidate i of a stack codes
+ * channel 0 at rung i and channels 1 and 2 at rung j = min(i + cq, last), costs the three channels' bits under those
+ * rungs, and the rate rule picks among the candidates; stack_pick[s] = {i, j, j}.  Prints "qmap3: ...". */
 static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
-                           int channels, double target, int by_psnr, uint8_t *stack_pick) {
+                           int channels, double target, int by_psnr, uint8_t *stack_pick, int cq) {
     const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
     const size_t stack_bytes = (size_t)channels * width * height * depth;
     int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
@@ -484,6 +617,17 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
                 }
             }
             const double px = (double)width * (double)height * (double)depth;
+            if (cq >= 0) {
+                for (int i = 0; i < RATE_LADDER_N; i++) {
+                    const int j = i + cq < RATE_LADDER_N ? i + cq : RATE_LADDER_N - 1;
+                    sb[i] = bits[((size_t)i * nb + s) * 3] + bits[((size_t)j * nb + s) * 3 + 1] + bits[((size_t)j * nb + s) * 3 + 2];
+                }
+                const int p = pick_by_rate(sb, target * px), j = p + cq < RATE_LADDER_N ? p + cq : RATE_LADDER_N - 1;
+                stack_pick[3 * (s0 + s)] = (uint8_t)p;
+                stack_pick[3 * (s0 + s) + 1] = stack_pick[3 * (s0 + s) + 2] = (uint8_t)j;
+                map_bits += sb[p];
+                continue;
+            }
             const int p = by_psnr ? pick_by_psnr(se, px * (double)channels, target) : pick_by_rate(sb, target * px);
             stack_pick[s0 + s] = (uint8_t)p;
             map_bits += sb[p];
@@ -492,7 +636,7 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
     free(bits);
     if (status) return 1;
     if (stack_pick) {
-        printf("qmap: stacks=%d bits=%llu\n", n_stacks, (unsigned long long)map_bits);
+        printf("%s: stacks=%d bits=%llu\n", cq >= 0 ? "qmap3" : "qmap", n_stacks, (unsigned long long)map_bits);
     } else {
         int pick;
         if (by_psnr) {
@@ -696,7 +840,7 @@ int encode_multi(const char *inName, const char *outName, int width, int height,
                "of 8)\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_targets("encode_multi") || reject_qmap("encode_multi")) return 1;
+    if (reject_targets("encode_multi") || reject_qmap("encode_multi") || reject_qmap3("encode_multi")) return 1;
     int ycc;
     int c420;
     if (call_colour("encode_multi", 1, 0, &ycc) || call_chroma("encode_multi", 1, ycc, &c420)) return 1;
@@ -809,7 +953,7 @@ int decode_multi(const char *inName, const char *outName, int width, int height,
         printf("Invalid geometry: %dx%d, %d frames, block depth %d\n", width, height, frames, depth);
         return 1;
     }
-    if (reject_targets("decode_multi") || reject_qmap("decode_multi")) return 1;
+    if (reject_targets("decode_multi") || reject_qmap("decode_multi") || reject_qmap3("decode_multi")) return 1;
     int ycc;
     int c420;
     if (call_colour("decode_multi", 1, 0, &ycc) || call_chroma("decode_multi", 1, ycc, &c420)) return 1;
@@ -960,18 +1104,22 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     int c420;
     if (call_chroma("encode", channels, ycc, &c420)) return 1;
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
-    const char *qmap_path = NULL;
+    const char *qmap_path = NULL, *qmap3_path = NULL;
+    int cq = 0;
+    if (call_qmap3("encode", channels, rate_set, psnr_set, ycc, &qmap3_path, &cq)) return 1;
     if (call_qmap(&qmap_path)) return 1;
+    const int qw = qmap3_path ? 3 : 1; /* the map's entries per stack */
+    if (qmap3_path) qmap_path = qmap3_path;
     uint8_t *qmap = NULL;
     int32_t qmap_tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
     if (qmap_path) {
         const int ns = (frames + depth - 1) / depth;
-        qmap = (uint8_t *)calloc((size_t)ns, 1);
+        qmap = (uint8_t *)calloc((size_t)ns * qw, 1);
         if (!qmap) {
             printf("Out of memory\n");
             return 1;
         }
-        if (!rate_set && !psnr_set && read_qmap(qmap_path, ns, qmap)) {
+        if (!rate_set && !psnr_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
             free(qmap);
             return 1;
         }
@@ -1037,8 +1185,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     /* a rate target: the first pass picks the quality, the second encodes as q=<n> does */
     if (!status && (rate_set || psnr_set))
         STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
-                                              psnr_set ? psnr_db : rate_bpp, psnr_set, qmap));
-    if (!status && qmap && (rate_set || psnr_set)) status = write_qmap(qmap_path, n_stacks, qmap);
+                                              psnr_set ? psnr_db : rate_bpp, psnr_set, qmap, qw == 3 ? cq : -1));
+    if (!status && qmap && (rate_set || psnr_set))
+        status = qw == 3 ? write_qmap3(qmap_path, n_stacks, qmap) : write_qmap(qmap_path, n_stacks, qmap);
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
         size_t got = 0, r;
@@ -1069,7 +1218,10 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             int cbits[3] = {0, 0, 0};
             uint64_t tb[3] = {0, 0, 0};
             for (int ch = 0; ch < channels; ch++) dct3d_entropy_enc_carry(ent[ch], &cb[ch], &cbits[ch]);
-            if (qmap) /* stack s0 + s under the ladder's table qmap[s0 + s] */
+            if (qw == 3) /* stack s0 + s of channel ch under the ladder's table qmap[3 (s0 + s) + ch] */
+                STAGE(t_dev, rc = dct3d_encode_eg_frames_vqc(ctx, fr, width, height, channels, nb, qmap_tabs, RATE_LADDER_N,
+                                                             qmap + 3 * (size_t)s0, cb, cbits, tb));
+            else if (qmap) /* stack s0 + s under the ladder's table qmap[s0 + s] */
                 STAGE(t_dev, rc = dct3d_encode_eg_frames_vq(ctx, fr, width, height, channels, nb, qmap_tabs, RATE_LADDER_N,
                                                             qmap + s0, cb, cbits, tb));
             else
@@ -1133,18 +1285,22 @@ static int decode_any(const char *inName, const char *outName, int width, int he
     if (call_colour("decode", channels, 0, &ycc)) return 1;
     int c420;
     if (call_chroma("decode", channels, ycc, &c420)) return 1;
-    const char *qmap_path = NULL;
+    const char *qmap_path = NULL, *qmap3_path = NULL;
+    int cq = 0;
+    if (call_qmap3("decode", channels, 0, 0, ycc, &qmap3_path, &cq)) return 1; /* (cq=: an encode's, refused) */
     if (call_qmap(&qmap_path)) return 1;
+    const int qw = qmap3_path ? 3 : 1; /* the map's entries per stack */
+    if (qmap3_path) qmap_path = qmap3_path;
     uint8_t *qmap = NULL;
     int32_t qmap_tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
     if (qmap_path) { /* read before any file is made */
         const int ns = (frames + depth - 1) / depth;
-        qmap = (uint8_t *)calloc((size_t)ns, 1);
+        qmap = (uint8_t *)calloc((size_t)ns * qw, 1);
         if (!qmap) {
             printf("Out of memory\n");
             return 1;
         }
-        if (read_qmap(qmap_path, ns, qmap)) {
+        if (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap)) {
             free(qmap);
             return 1;
         }
@@ -1227,7 +1383,10 @@ static int decode_any(const char *inName, const char *outName, int width, int he
                     rc = DCT3D_EINVAL;
                     break;
                 }
-                if (qmap)
+                if (qw == 3)
+                    STAGE(t_dev, rc = dct3d_decode_eg_frames_vqc(ctx, p, len, bit, width, height, channels, nb, qmap_tabs,
+                                                                 RATE_LADDER_N, qmap + 3 * (size_t)s0, fr, eb));
+                else if (qmap)
                     STAGE(t_dev, rc = dct3d_decode_eg_frames_vq(ctx, p, len, bit, width, height, channels, nb, qmap_tabs,
                                                                 RATE_LADDER_N, qmap + s0, fr, eb));
                 else

@@ -18,6 +18,9 @@
  *   the transform computed inside the device calls; not recorded in the file: decode with ycc=1 too; not with psnr=
  *   ... and chroma=420 beside ycc=1 (codec.h, codec_set_chroma): .green / .blue hold the Cb and Cr planes at a quarter
  *   of the samples, (width + 1) / 2 x (height + 1) / 2; not recorded either: decode with the same two tokens
+ *   ... and qmap3=<path> (codec.h, codec_set_qmap3): three ladder qualities per stack and line, one per plane; written
+ *   by an encode_rgb that also has rate= (and cq=<k>: the chroma planes k rungs coarser), else read; not with qmap=,
+ *   q= or psnr=
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -70,6 +73,13 @@ static void usage(void) {
            "replication on the way back, inside the device calls); chroma=444 is the default.  The file does not record "
            "it: decode with the same tokens.  rate= and qmap= price and code the subsampled planes; chroma=420 without "
            "ycc=1, on encode or decode, or with several devices is an error\n");
+    printf("encode_rgb and decode_rgb take qmap3=<path>, a text file of three ladder qualities per stack (one line per "
+           "stack, single spaces between them): those of the .red, .green and .blue planes (Y, Cb, Cr with ycc=1).  "
+           "With rate= the first pass prices per stack the candidates 'plane 0 at rung i of the ladder, planes 1 and 2 at "
+           "rung min(i + k, 15)' (cq=<k>, 0..15, default 0; it needs ycc=1), picks the smallest rung that fits qmap='s "
+           "budget, WRITES the map and prints 'qmap3: stacks=<n> bits=<total>'; an encode without a target and a decode "
+           "READ it.  qmap3= together with qmap=, q= or psnr=, on encode or decode, with several devices, or a malformed "
+           "file is an error; so is cq= without ycc=1 or without rate= and qmap3=\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -123,13 +133,20 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0;
-    for (int a = 9; a < argc && a < 13 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0;
+    for (int a = 9; a < argc && a < 15 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
         const int is_rate = !strncmp(argv[a], "rate=", 5), is_psnr = !strncmp(argv[a], "psnr=", 5);
         const int is_qmap = !strncmp(argv[a], "qmap=", 5), is_ycc = !strncmp(argv[a], "ycc=", 4);
         const int is_chroma = !strncmp(argv[a], "chroma=", 7);
+        const int is_qmap3 = !strncmp(argv[a], "qmap3=", 6), is_cq = !strncmp(argv[a], "cq=", 3);
+        if (a >= 10 && (is_qmap3 ? have_qmap3 : is_cq ? have_cq : 0)) break;
+        if (is_qmap3 || is_cq) { /* collected here; the entry points check them (codec.c: call_qmap3, reject_qmap3) */
+            if (is_qmap3) have_qmap3 = a;
+            else have_cq = a;
+            continue;
+        }
         if (a >= 10 && (is_rate ? have_rate : is_psnr ? have_psnr : is_qmap ? have_qmap : is_ycc ? have_ycc : is_chroma ? have_chroma : have_quant)) break; /* (a second argument counts only as another kind) */
         if (is_ycc) {
             if (strcmp(argv[a], "ycc=0") && strcmp(argv[a], "ycc=1")) {
@@ -207,7 +224,8 @@ int main(int argc, char *argv[]) {
     }
     if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate])) ||
         (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap])) ||
-        (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma]))) {
+        (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma])) ||
+        (have_qmap3 && codec_set_qmap3(argv[have_qmap3])) || (have_cq && codec_set_cq(argv[have_cq]))) {
         printf("Argument too long\n");
         return 1;
     }
@@ -219,6 +237,7 @@ int main(int argc, char *argv[]) {
                          : decode_ex(argv[2], argv[3], width, height, frames, devs[0], depth, 0);
     if (!strcmp(argv[1], "encode_rgb") || !strcmp(argv[1], "decode_rgb")) {
         if (n_dev > 1) {
+            if (have_qmap3 || have_cq) printf("qmap3= and cq= apply to encode_rgb and decode_rgb on one device\n");
             printf("%s runs on one device\n", argv[1]);
             return 1;
         }

@@ -171,6 +171,33 @@ int codec_set_colour(const char *text);
  *   text is too long to keep. */
 int codec_set_chroma(const char *text);
 
+/* A quality per (stack, channel) of the packed RGB24 calls on one device (encode_rgb_ex, decode_rgb_ex):
+ * "qmap3=<path>" names a text file with one line per stack, in stack order, each three qualities of the ladder
+ * separated by single spaces: those of the .red, .green and .blue files' planes (R, G, B; with ycc=1 Y, Cb, Cr).  Stack
+ * s of plane ch is coded as q=<that quality> codes it (dct3d_encode_eg_frames_vqc / dct3d_decode_eg_frames_vqc, the
+ * ladder as the palette).  The map travels beside the .bin, as qmap='s does; a map of three equal columns gives the
+ * files of qmap= with that column.
+ *   encode with rate= AND qmap3= [cq=<k>]   the first pass prices every stack's candidates i = 0 .. 15: plane 0 at rung
+ *       i of the ladder, planes 1 and 2 at rung j = min(i + k, 15) (k in 0..15, 0 without cq=), the cost the three
+ *       planes' bits under those rungs; it picks the smallest rung whose cost fits qmap='s budget (bpp * width *
+ *       height * blockDepth bits), the largest when none does, WRITES the map (lines "q_i q_j q_j") and prints
+ *       "qmap3: stacks=<n> bits=<total>"; the second pass encodes with the map.
+ *   encode with qmap3= alone, decode with qmap3=   READ the map.
+ * Errors (a line printed, 1 returned, before any output file is made): qmap3= together with qmap=, a quantiser or
+ * psnr=; on a grey call or a several-device call; with DCT3D_CODEC_HOST_EG=1; a malformed file; cq= without ycc=1, or
+ * without rate= and qmap3=.
+ *
+ * codec_parse_qmap3: reads the file `path`: 0 and qualities[3 s + ch], or 1 (qualities untouched) if the file cannot
+ *   be read, has another line count, or holds a line that is not exactly three ladder qualities in decimal with one
+ *   space between them.
+ * codec_set_qmap3: the map of every later call of this process, as the text "qmap3=<path>"; NULL or "": none.  It
+ *   overrides the environment variable DCT3D_CODEC_QMAP3.  1 (nothing changes) if the text is too long to keep.  What it
+ *   excludes is refused by the call that finds both, as listed above: the rules live in one place.
+ * codec_set_cq: the chroma offset, as the text "cq=<k>"; NULL or "": none.  It overrides DCT3D_CODEC_CQ. */
+int codec_parse_qmap3(const char *path, int nStacks, int *qualities);
+int codec_set_qmap3(const char *text);
+int codec_set_cq(const char *text);
+
 #ifdef __cplusplus
 }
 #endif

@@ -569,6 +569,44 @@ int dct3d_decode_eg_frames_vq(dct3d_ctx *ctx, const uint8_t *const bytes[], cons
                               const int32_t *tables, int n_tables, const uint8_t *stack_table, uint8_t *frames,
                               uint64_t end_bit[]);
 
+/* ---------------------------------------------------------------------------------------------
+ * A quantiser table per (stack, channel) in the fused stream calls (additive to ABI 9; detect by symbol;
+ * DESIGN.md 4r).  The four _vq calls with `table_map` in the place of `stack_table`:
+ *   table_map    [n_stacks][channels], each entry < n_tables: stack s of channel ch is coded with
+ *                tables[table_map[s * channels + ch]].  Copied before the call returns.
+ * Write col(k) for the [n_stacks] column k of the map, and plane k for channel k of the frames
+ * (DCT3D_COLOUR_PLANES), plane k of rgb_to_ycbcr(frames) (DCT3D_COLOUR_YCBCR), or plane k of
+ * rgb_to_ycbcr420(frames) (DCT3D_CHROMA_420 on top).  Then
+ *   encode: stream k, total_bits[k] and the DCT3D_ENOSPC behaviour are those of the grey (channels == 1)
+ *       dct3d_encode_eg_frames_vq call on plane k with the same palette, col(k) and carry k;
+ *   decode: the frames are what the colour mode composes (the merge, T^-1, or ycbcr420_to_rgb) from the three
+ *       grey _vq decodes, each under its col(k); end_bit[k] is the grey call's; a short or corrupt stream gives
+ *       the _vq call's code and end bits and leaves the frames untouched.
+ * With all columns equal every output is the _vq call's with that column, byte for byte; with channels == 1
+ * the call is the _vq call.  Every value is certified or replayed exactly under the table of its own (stack,
+ * channel).  n_units is the sum over the three grey calls; the decode's n_flagged is their sum; the encode's
+ * equals the sum where all three planes are ragged and is at least the sum elsewhere (as the 4:2:0 calls').
+ * DCT3D_EINVAL: the _vq calls' cases, with a table_map entry >= n_tables in the place of the stack_table one
+ * (DCT3D_OPT_EG_TWO_STEP and three channels with 4:2:0 on but the colour transform off included); nothing is
+ * queued.  DCT3D_OPT_EG_FORCE_RETRY, DCT3D_OPT_EG_NO_RESOLVE and DCT3D_OPT_DEC_MARGIN act as on the base calls.
+ * dct3d_eg_fetch_channel serves dct3d_encode_eg_frames_vqc as it serves dct3d_encode_eg_frames.
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_encode_eg_frames_vqc_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                                   int n_stacks, const int32_t *tables, int n_tables, const uint8_t *table_map,
+                                   const uint8_t carry_byte[], const int carry_bits[], uint8_t *const d_out[],
+                                   const uint64_t out_cap[], uint64_t total_bits[]);
+int dct3d_encode_eg_frames_vqc(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                               int n_stacks, const int32_t *tables, int n_tables, const uint8_t *table_map,
+                               const uint8_t carry_byte[], const int carry_bits[], uint64_t total_bits[]);
+int dct3d_decode_eg_frames_vqc_dev(dct3d_ctx *ctx, const uint8_t *const d_bytes[], const uint64_t nbytes[],
+                                   const uint64_t start_bit[], int width, int height, int channels, int n_stacks,
+                                   const int32_t *tables, int n_tables, const uint8_t *table_map,
+                                   uint8_t *d_frames, uint64_t end_bit[]);
+int dct3d_decode_eg_frames_vqc(dct3d_ctx *ctx, const uint8_t *const bytes[], const uint64_t nbytes[],
+                               const int start_bit[], int width, int height, int channels, int n_stacks,
+                               const int32_t *tables, int n_tables, const uint8_t *table_map, uint8_t *frames,
+                               uint64_t end_bit[]);
+
 #ifdef __cplusplus
 }
 #endif
