@@ -40,6 +40,8 @@ DCT3D_OPT_COLOUR = 12
 DCT3D_COLOUR_PLANES, DCT3D_COLOUR_YCBCR = 0, 1
 # 4:2:0 chroma subsampling on top of the colour transform (dct3d.h; Context.set_chroma, rgb_to_ycbcr420 below)
 DCT3D_CHROMA_444, DCT3D_CHROMA_420 = 0, 1
+# bytes of decoded planes the RGB-domain distortion probe keeps per range of stacks (dct3d.h; or one stack's)
+DCT3D_RGB_PLANE_BUDGET = 64 << 20
 
 # Every symbol include/dct3d.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -63,6 +65,7 @@ ABI_SYMBOLS = (
     "dct3d_ctx_set_chroma", "dct3d_ctx_get_chroma", "dct3d_chroma_size",
     "dct3d_encode_eg_frames_vqc", "dct3d_encode_eg_frames_vqc_dev",
     "dct3d_decode_eg_frames_vqc", "dct3d_decode_eg_frames_vqc_dev",
+    "dct3d_distortion_rgb_frames", "dct3d_distortion_rgb_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -168,6 +171,8 @@ def lib() -> C.CDLL:
         L.dct3d_ctx_set_chroma.argtypes = [vp, i32]
         L.dct3d_ctx_get_chroma.argtypes = [vp, C.POINTER(i32)]
         L.dct3d_chroma_size.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        L.dct3d_distortion_rgb_frames_dev.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.dct3d_distortion_rgb_frames.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -421,6 +426,28 @@ def pick_stack_qualities_psnr(sse, qualities, n_samples_per_stack, target_db) ->
         raise ValueError("sse must be [len(qualities), n_stacks, channels]")
     return [pick_quality_psnr({q: int(sse[t, s, :].astype(object).sum()) for t, q in enumerate(qualities)},
                               n_samples_per_stack, target_db) for s in range(sse.shape[1])]
+
+
+def pick_stack_channel_qualities_psnr(sse, qualities, n_samples_per_stack, target_db, chroma_rungs=0) -> list:
+    """One (q0, q1, q2) per stack from the RGB-domain distortion probe: sse [T, n_stacks] as distortion_rgb_frames
+    returns it for the T candidates (qualities[i], qualities[j], qualities[j]), j = min(i + chroma_rungs, T - 1), in
+    that order.  Stack s gets pick_quality_psnr's choice on its errors over n_samples_per_stack samples (the three
+    bytes of one stack's unpadded pixels): the largest qualities[i] whose PSNR is >= target_db, else the smallest.
+    Mirrors pick_stack_channel_qualities; nothing assumed monotone."""
+    sse = np.asarray(sse)
+    qualities = [int(q) for q in qualities]
+    T = len(qualities)
+    if sse.ndim != 2 or sse.shape[0] != T:
+        raise ValueError("sse must be [len(qualities), n_stacks]")
+    if int(chroma_rungs) != chroma_rungs or chroma_rungs < 0:
+        raise ValueError("chroma_rungs must be an integer >= 0")
+    j = [min(i + int(chroma_rungs), T - 1) for i in range(T)]
+    index = {q: i for i, q in enumerate(qualities)}
+    res = []
+    for s in range(sse.shape[1]):
+        q = pick_quality_psnr({qualities[i]: int(sse[i, s]) for i in range(T)}, n_samples_per_stack, target_db)
+        res.append((q, qualities[j[index[q]]], qualities[j[index[q]]]))
+    return res
 
 
 def plan_query(block_w: int = 8, block_h: int = 8, block_d: int = 8, steps=None) -> dict:
@@ -1055,6 +1082,63 @@ class Context:
                                                  None if d_cube_sse is None else _tptr(d_cube_sse)),
                "dct3d_distortion_frames_dev")
         return (sse, bits) if want_bits else sse
+
+    # ---- RGB-domain distortion probe: the exact squared error in the RGB pixels under (Y, Cb, Cr) table triples ----
+    @staticmethod
+    def _rgb_candidates(candidates, T: int, what: str):
+        """candidates (None | [n][3] palette indices) -> (uint8 [n, 3] or None, n)"""
+        if candidates is None:
+            return None, T
+        cd = np.ascontiguousarray(candidates, np.int64)
+        if cd.ndim != 2 or cd.shape[1] != 3 or cd.shape[0] < 1 or (cd < 0).any() or (cd > 255).any():
+            raise Dct3dError(DCT3D_EINVAL, what)
+        return np.ascontiguousarray(cd, np.uint8), cd.shape[0]
+
+    def _rgb_result(self, sse, plane_sse, bits, want_planes, want_bits):
+        if not want_planes and not want_bits:
+            return sse
+        return (sse,) + ((plane_sse,) if want_planes else ()) + ((bits,) if want_bits else ())
+
+    def distortion_rgb_frames(self, frames: np.ndarray, tables=None, candidates=None, want_planes: bool = False,
+                              want_bits: bool = False):
+        """Packed RGB24 frames [n, H, W, 3] -> uint64 [n_cand, n_stacks]: the sum of (x - y)^2 over the unpadded pixels
+        of stack s and their three bytes, y = decode_eg_frames_vqc(encode_eg_frames_vqc(x)) with every row of the map
+        candidates[c] = (table of Y | R, of Cb | G, of Cr | B), indices into tables, in the context's colour and chroma
+        mode.  candidates None: candidate i = (i, i, i).  Exact; the context's quantiser and modes are neither used
+        (tables given) nor changed.  want_planes: also the planes' own errors, uint64 [T, n_stacks, 3]; want_bits: also
+        the bits, as rate_frames'.  Returns sse, or the tuple (sse[, plane_sse][, bits])."""
+        what = "dct3d_distortion_rgb_frames"
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        if channels != 3:
+            raise Dct3dError(DCT3D_EINVAL, what)
+        tb, T = self._rate_tables(tables)
+        cd, n = self._rgb_candidates(candidates, T, what)
+        sse = np.zeros((n, n_stacks), np.uint64)
+        plane_sse = np.zeros((T, n_stacks, 3), np.uint64) if want_planes else None
+        bits = np.zeros((T, n_stacks, 3), np.uint64) if want_bits else None
+        _check(lib().dct3d_distortion_rgb_frames(self._h, _ptr(frames), W, H, n_stacks, None if tb is None else _ptr(tb), T,
+                                                 None if cd is None else _ptr(cd), n, _ptr(sse),
+                                                 None if plane_sse is None else _ptr(plane_sse),
+                                                 None if bits is None else _ptr(bits)), what)
+        return self._rgb_result(sse, plane_sse, bits, want_planes, want_bits)
+
+    def distortion_rgb_frames_dev(self, d_frames, width: int, height: int, n_stacks: int, tables=None, candidates=None,
+                                  d_cube_sse=None, want_planes: bool = False, want_bits: bool = False):
+        """Device path of distortion_rgb_frames: packed RGB24 frames on the device; d_cube_sse (optional; a tensor or an
+        address) receives uint32 [n_cand, n_stacks, cubes per stack of the frames' grid], the same sum per cube."""
+        what = "dct3d_distortion_rgb_frames_dev"
+        tb, T = self._rate_tables(tables)
+        cd, n = self._rgb_candidates(candidates, T, what)
+        sse = np.zeros((n, n_stacks), np.uint64)
+        plane_sse = np.zeros((T, n_stacks, 3), np.uint64) if want_planes else None
+        bits = np.zeros((T, n_stacks, 3), np.uint64) if want_bits else None
+        _check(lib().dct3d_distortion_rgb_frames_dev(self._h, _tptr(d_frames), width, height, n_stacks,
+                                                     None if tb is None else _ptr(tb), T, None if cd is None else _ptr(cd), n,
+                                                     _ptr(sse), None if plane_sse is None else _ptr(plane_sse),
+                                                     None if bits is None else _ptr(bits),
+                                                     None if d_cube_sse is None else _tptr(d_cube_sse)), what)
+        return self._rgb_result(sse, plane_sse, bits, want_planes, want_bits)
 
     def fill_synthetic_dev(self, d_frames, width: int, height: int, n_frames: int,
                            seed: int = synthetic.DEFAULT_SEED, frame0: int = 0, kind: str = "ramp") -> None:

@@ -22,6 +22,7 @@
 #include "dct3d_kernels.h"
 #include "dct3d_plan.h"
 #include "dct3d_distortion.h"
+#include "dct3d_distortion_rgb.h"
 #include "dct3d_rate.h"
 #include "dct3d_vq.h"
 #include "dct3d_c420.h"
@@ -160,6 +161,11 @@ struct dct3d_ctx {
     // kernel reads them)
     int chroma = DCT3D_CHROMA_444;
     DevBuf d_c420;
+    // RGB-domain distortion probe (dct3d_distortion_rgb_frames*): the decoded planes of one range of
+    // stacks (pass 1 writes them, pass 2 reads them), the planes' per-cube squared errors and bits, the candidates'
+    // plane slots, the per-cube RGB errors when the caller keeps none
+    DevBuf d_rgb_planes, d_rgb_psse, d_rgb_pbits, d_rgb_slots, d_rgb_cube;
+    std::vector<int32_t> rgb_tables;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -432,7 +438,8 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_egd_exit, &c->d_egd_status, &c->d_egd_in, &c->d_egd_raster, &c->d_egd_mark, &c->d_egd_desc,
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
                       &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums,
-                      &c->d_dist_steps, &c->d_dist_sse, &c->d_vq, &c->d_c420})
+                      &c->d_dist_steps, &c->d_dist_sse, &c->d_vq, &c->d_c420, &c->d_rgb_planes, &c->d_rgb_psse,
+                      &c->d_rgb_pbits, &c->d_rgb_slots, &c->d_rgb_cube})
         b->release();
     if (c->h_rate) (void)hipHostFree(c->h_rate);
     if (c->vq_host) (void)hipHostFree(c->vq_host);
@@ -1603,6 +1610,298 @@ int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, i
     if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
     if (colour_refused(c, channels)) return DCT3D_EINVAL;
     return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits);
+}
+
+// ---- RGB-domain distortion probe: the exact squared error, in the RGB pixels, of the stream encode + decode
+//      under (Y, Cb, Cr) table triples, in all three colour modes (dct3d.h) ----
+}  // extern "C"
+// the decoded planes of one range of stacks stay under this many bytes (or one stack's): the size of the host-pointer
+// calls' staging chunk
+constexpr size_t kRgbPlaneBudget = DCT3D_RGB_PLANE_BUDGET;
+// the arguments of both calls (nothing is enqueued before they hold); packed RGB24 frames
+static bool rgb_args_ok(const dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables,
+                        int n_tables, const uint8_t* cand, int n_cand, const uint64_t* sse, Geom* g, uint64_t* n_cubes) {
+    if (!rate_args_ok(c, frames, w, h, 3, n_stacks, tables, n_tables, sse, g, n_cubes)) return false;
+    if (n_cand < 1 || n_cand > DCT3D_RATE_MAX_TABLES || (!cand && n_cand != n_tables)) return false;
+    if (cand)
+        for (int i = 0; i < 3 * n_cand; i++)
+            if (cand[i] >= n_tables) return false;
+    return !c420_refused(c, 3);
+}
+// candidate i = (i, i, i) where the caller gives no list
+static const uint8_t* rgb_cand(const uint8_t* cand, int n_cand, uint8_t (&own)[3 * DCT3D_RATE_MAX_TABLES]) {
+    if (cand) return cand;
+    for (int i = 0; i < 3 * n_cand; i++) own[i] = (uint8_t)(i / 3);
+    return own;
+}
+
+// Planes mode: the distortion probe itself; a candidate's error is the sum of its three planes' under their tables,
+// per stack on the host and per cube by a gather over the probe's per-cube buffer.
+static int probe_rgb_planes_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
+                                int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse,
+                                uint64_t* bits, uint32_t* d_cube_sse) {
+    const size_t n_runs = (size_t)n_tables * n_stacks * 3;
+    std::vector<uint64_t> ps(n_runs);
+    int rc = probe_dev(c, d_frames, g, n_stacks, tables, n_tables, ps.data(), bits, nullptr, nullptr);
+    if (rc || n_stacks == 0) return rc;
+    for (int i = 0; i < n_cand; i++)
+        for (int s = 0; s < n_stacks; s++) {
+            uint64_t v = 0;
+            for (int k = 0; k < 3; k++) v += ps[((size_t)cand[3 * i + k] * n_stacks + s) * 3 + k];
+            sse[(size_t)i * n_stacks + s] = v;
+        }
+    if (plane_sse) memcpy(plane_sse, ps.data(), n_runs * sizeof(uint64_t));
+    if (!d_cube_sse) return DCT3D_OK;
+    const uint64_t n_cubes = g.cps() * (uint64_t)n_stacks;
+    if ((rc = c->d_rgb_slots.grow((size_t)3 * n_cand))) return rc;
+    if (hipMemcpyAsync(c->d_rgb_slots.p, cand, (size_t)3 * n_cand, hipMemcpyHostToDevice, c->stream) != hipSuccess) return DCT3D_EDEVICE;
+    if (launch_distortion_rgb_gather((const uint32_t*)c->d_dist_sse.p, 3 * n_cubes, (const uint8_t*)c->d_rgb_slots.p, (uint32_t)n_cand,
+                                     (uint32_t)g.cps(), (uint32_t)n_stacks, d_cube_sse, n_cubes, c->stream))
+        rc = DCT3D_EKERNEL;
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;  // (the candidates' host copy is free again)
+    return rc;
+}
+
+// YCbCr and YCbCr + 4:2:0 on frames in device memory.  The stacks go in ranges whose decoded planes fit the budget;
+// per range, pass 1 per plane and kRateTables tables (launch_distortion_plane), the planes' sums, pass 2 over the
+// candidates (launch_distortion_rgb_combine).  A plane is coded under the tables some candidate uses for it, or
+// under all of them when plane_sse or bits is asked for.
+static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
+                             int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits,
+                             uint32_t* d_cube_sse) {
+    const bool c420 = c420_on(c, 3);
+    Geom gp[3];  // the planes' geometries (grey)
+    uint64_t nc_dummy;
+    if (!make_geom(g.w, g.h, 1, n_stacks, true, &gp[0], &nc_dummy)) return DCT3D_EINVAL;
+    if (c420 ? !c420_geom(g, n_stacks, &gp[1], &nc_dummy) : !make_geom(g.w, g.h, 1, n_stacks, true, &gp[1], &nc_dummy)) return DCT3D_EINVAL;
+    gp[2] = gp[1];
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    call_begin(c);
+    if (!c->batch) c->last_units = 0;
+    if (n_stacks == 0) return DCT3D_OK;
+    // each plane's tables, and where a candidate finds its plane
+    const bool all_pairs = plane_sse || bits;
+    std::vector<int> L[3];
+    int slot_of[3][DCT3D_RATE_MAX_TABLES];
+    for (int k = 0; k < 3; k++) {
+        for (int t = 0; t < n_tables; t++) slot_of[k][t] = -1;
+        if (all_pairs)
+            for (int t = 0; t < n_tables; t++) {
+                slot_of[k][t] = t;
+                L[k].push_back(t);
+            }
+        else
+            for (int i = 0; i < n_cand; i++) {
+                const int t = cand[3 * i + k];
+                if (slot_of[k][t] < 0) {
+                    slot_of[k][t] = (int)L[k].size();
+                    L[k].push_back(t);
+                }
+            }
+    }
+    const int n_steps = (int)c->plan.steps.size();
+    size_t toff[4] = {0, L[0].size(), L[0].size() + L[1].size(), L[0].size() + L[1].size() + L[2].size()};
+    const size_t NT = toff[3];
+    c->rgb_tables.resize(NT * n_steps + 3 * DCT3D_RATE_MAX_TABLES);  // (the tail: the candidates' slots, bytes)
+    for (int k = 0; k < 3; k++)
+        for (size_t i = 0; i < L[k].size(); i++)
+            for (int s = 0; s < n_steps; s++)
+                c->rgb_tables[(toff[k] + i) * n_steps + s] = tables ? tables[(size_t)L[k][i] * n_steps + s] : c->plan.steps[s];
+    uint8_t* const slots_host = (uint8_t*)(c->rgb_tables.data() + NT * n_steps);
+    for (int i = 0; i < n_cand; i++)
+        for (int k = 0; k < 3; k++) slots_host[3 * i + k] = (uint8_t)slot_of[k][cand[3 * i + k]];
+    probe_tables(c, c->rgb_tables.data(), (int)NT, true);
+
+    const int D = c->bd;
+    size_t cps[3], pframes[3];  // cubes per stack, bytes of one stack's frames of the plane
+    for (int k = 0; k < 3; k++) {
+        cps[k] = (size_t)gp[k].cps();
+        pframes[k] = (size_t)gp[k].w * gp[k].h * D;
+    }
+    size_t stack_planes = 0, stack_cubes = 0;
+    for (int k = 0; k < 3; k++) {
+        stack_planes += L[k].size() * pframes[k];
+        stack_cubes += L[k].size() * cps[k];
+    }
+    const int per = (int)std::max<size_t>(1, std::min<size_t>(kRgbPlaneBudget / stack_planes, (size_t)n_stacks));
+    const uint64_t out_stride = cps[0] * (uint64_t)n_stacks;
+    const size_t n_psums = NT * (size_t)n_stacks, n_rgb = (size_t)n_cand * n_stacks;
+    const size_t n_sums = n_psums * (bits ? 2 : 1) + n_rgb;
+    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
+    const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
+    int rc;
+    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_dist_steps.grow(step_bytes)) ||
+        (rc = c->d_rate_sums.grow(n_sums * sizeof(uint64_t))) || (rc = c->d_rgb_planes.grow(stack_planes * per)) ||
+        (rc = c->d_rgb_psse.grow(stack_cubes * per * sizeof(uint32_t))) ||
+        (bits && (rc = c->d_rgb_pbits.grow(stack_cubes * per * sizeof(uint16_t)))) ||
+        (rc = c->d_rgb_slots.grow((size_t)3 * n_cand)) ||
+        (!d_cube_sse && (rc = c->d_rgb_cube.grow((size_t)n_cand * out_stride * sizeof(uint32_t)))) ||
+        (rc = probe_grow_pinned(c, n_sums * sizeof(uint64_t))))
+        return rc;
+    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->d_rgb_slots.p, slots_host, (size_t)3 * n_cand, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    uint32_t* const cube_out = d_cube_sse ? d_cube_sse : (uint32_t*)c->d_rgb_cube.p;
+    uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
+    uint64_t* const d_rgb_sums = d_sums + n_psums * (bits ? 2 : 1);
+    const size_t stack_bytes = (size_t)g.plane() * D;
+    DecodeParams DP;
+    fill_decode_params(c, DP, nullptr, nullptr, g, 0);  // the decode's certificate constants, the test margin included
+    hipEvent_t* ev = timer_begin(c);
+    rc = DCT3D_OK;
+    for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
+        const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
+        const uint8_t* const fr = d_frames + (size_t)s0 * stack_bytes;
+        uint8_t* planes[3];
+        uint32_t* psse[3];
+        uint16_t* pbits[3];
+        planes[0] = (uint8_t*)c->d_rgb_planes.p;
+        psse[0] = (uint32_t*)c->d_rgb_psse.p;
+        pbits[0] = bits ? (uint16_t*)c->d_rgb_pbits.p : nullptr;
+        for (int k = 1; k < 3; k++) {
+            planes[k] = planes[k - 1] + L[k - 1].size() * pframes[k - 1] * ns;
+            psse[k] = psse[k - 1] + L[k - 1].size() * cps[k - 1] * ns;
+            pbits[k] = bits ? pbits[k - 1] + L[k - 1].size() * cps[k - 1] * ns : nullptr;
+        }
+        for (int k = 0; k < 3 && !rc; k++) {
+            const bool sub = c420 && k > 0;
+            const uint64_t ncu = cps[k] * (uint64_t)ns;
+            EncodeParams P;
+            fill_encode_params(c, P, fr, nullptr, g, ncu);
+            if (sub) c420_cube_fields(P, g, gp[k]);
+            DistPlaneParams R = {};
+            R.table_stride = ncu;
+            R.ch = k;
+            R.inv_coef_t = DP.inv_coef_t;
+            R.dec_G = DP.dec_G;
+            R.dec_E = DP.dec_E;
+            R.dec_l1_max = DP.dec_l1_max;
+            R.plane_stride = pframes[k] * ns;
+            R.pw = (uint32_t)gp[k].w;
+            R.ph = (uint32_t)gp[k].h;
+            const int nk = (int)L[k].size();
+            for (int t0 = 0; t0 < nk && !rc; t0 += kRateTables) {
+                R.n_tables = nk - t0 < kRateTables ? nk - t0 : kRateTables;
+                R.tabs = (const float4*)c->d_rate_tabs.p + (toff[k] + t0) * kRateTabN;
+                R.steps = (const double*)c->d_dist_steps.p + (toff[k] + t0) * kDistStepN;
+                R.cube_sse = psse[k] + (size_t)t0 * ncu;
+                R.cube_bits = bits ? pbits[k] + (size_t)t0 * ncu : nullptr;
+                R.planes = planes[k] + (size_t)t0 * R.plane_stride;
+                if (launch_distortion_plane(D, sub ? c420_edge(g) : (g.edge() ? 1 : 0), sub ? 2 : 1, P, R, c->stream)) rc = DCT3D_EKERNEL;
+                else c->slot_used = true;
+            }
+            // this range's sums of plane k: [table of L[k]][stack of the range]
+            uint64_t* const ds = d_sums + (size_t)s0 * NT + toff[k] * ns;
+            if (!rc && launch_distortion_sum(psse[k], (uint32_t)cps[k], (uint64_t)nk * ns, ds, c->stream)) rc = DCT3D_EKERNEL;
+            if (!rc && bits && launch_rate_sum(pbits[k], (uint32_t)cps[k], (uint64_t)nk * ns, ds + n_psums, c->stream)) rc = DCT3D_EKERNEL;
+        }
+        if (rc) break;
+        RgbCombineParams C = {};
+        C.frames = fr;
+        C.y = planes[0];
+        C.cb = planes[1];
+        C.cr = planes[2];
+        C.y_stride = pframes[0] * ns;
+        C.c_stride = pframes[1] * ns;
+        C.w = (uint32_t)g.w;
+        C.h = (uint32_t)g.h;
+        C.cw = (uint32_t)gp[1].w;
+        C.chh = (uint32_t)gp[1].h;
+        C.shift = c420 ? 1u : 0u;
+        C.nbx = (uint32_t)(g.wp / 8);
+        C.cubes_per_stack = (uint32_t)cps[0];
+        C.n_cubes = (uint32_t)(cps[0] * ns);
+        C.div_cps = fast_div(C.cubes_per_stack);
+        C.div_nbx = fast_div(C.nbx);
+        C.slots = (const uint8_t*)c->d_rgb_slots.p;
+        C.n_cand = (uint32_t)n_cand;
+        C.cube_sse = cube_out + (size_t)s0 * cps[0];
+        C.cand_stride = out_stride;
+        if (launch_distortion_rgb_combine(D, C, c->stream)) rc = DCT3D_EKERNEL;
+    }
+    if (!rc && launch_distortion_sum(cube_out, (uint32_t)cps[0], n_rgb, d_rgb_sums, c->stream)) rc = DCT3D_EKERNEL;
+    timer_end(c, ev);
+    if (!rc && hipMemcpyAsync(c->h_rate, d_sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;  // synchronous on return (as probe_dev)
+    if (c->slot_used) count_slot_used(c, (uint64_t)stack_cubes * n_stacks * (uint64_t)c->plan.cs);
+    if (rc) return rc;
+    memcpy(sse, c->h_rate + (d_rgb_sums - d_sums), n_rgb * sizeof(uint64_t));
+    if (all_pairs)  // every (table, plane) pair was coded: slot t of plane k is table t
+        for (int s0 = 0; s0 < n_stacks; s0 += per) {
+            const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
+            for (int k = 0; k < 3; k++)
+                for (int t = 0; t < n_tables; t++)
+                    for (int s = 0; s < ns; s++) {
+                        const size_t src = (size_t)s0 * NT + toff[k] * ns + (size_t)t * ns + s;
+                        const size_t dst = ((size_t)t * n_stacks + s0 + s) * 3 + k;
+                        if (plane_sse) plane_sse[dst] = c->h_rate[src];
+                        if (bits) bits[dst] = c->h_rate[n_psums + src];
+                    }
+        }
+    return DCT3D_OK;
+}
+
+static int probe_rgb_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                         const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits, uint32_t* d_cube_sse) {
+    return c->opt_colour ? probe_rgb_ycc_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, plane_sse, bits, d_cube_sse)
+                         : probe_rgb_planes_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, plane_sse, bits, d_cube_sse);
+}
+
+// Frames in host memory: chunks of whole stacks, as probe_host
+static int probe_rgb_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                          const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits) {
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    const size_t stack_bytes = (size_t)g.plane() * c->bd;
+    constexpr size_t kChunkBytes = (size_t)64 << 20;
+    const int per = (int)std::max<size_t>(1, std::min<size_t>(kChunkBytes / stack_bytes, (size_t)(n_stacks > 0 ? n_stacks : 1)));
+    int rc;
+    if ((rc = c->h_in.grow(stack_bytes * per))) return rc;
+    const size_t pl = (size_t)n_tables * per * 3;
+    std::vector<uint64_t> part((size_t)n_cand * per + 2 * pl);
+    c->last_units = 0;
+    batch_begin(c);
+    rc = DCT3D_OK;
+    for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
+        const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
+        if (hipMemcpyAsync(c->h_in.p, frames + (size_t)s0 * stack_bytes, (size_t)ns * stack_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            rc = DCT3D_EDEVICE;
+            break;
+        }
+        uint64_t* const pr = part.data();
+        uint64_t* const pp = plane_sse ? pr + (size_t)n_cand * per : nullptr;
+        uint64_t* const pb = bits ? pr + (size_t)n_cand * per + pl : nullptr;
+        rc = probe_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, pr, pp, pb, nullptr);
+        if (rc) break;
+        for (int i = 0; i < n_cand; i++) memcpy(sse + (size_t)i * n_stacks + s0, pr + (size_t)i * ns, ns * sizeof(uint64_t));
+        for (int t = 0; t < n_tables; t++) {
+            const size_t dst = ((size_t)t * n_stacks + s0) * 3, src = (size_t)t * ns * 3;
+            if (plane_sse) memcpy(plane_sse + dst, pp + src, (size_t)ns * 3 * sizeof(uint64_t));
+            if (bits) memcpy(bits + dst, pb + src, (size_t)ns * 3 * sizeof(uint64_t));
+        }
+    }
+    batch_end(c);
+    return rc;
+}
+extern "C" {
+
+int dct3d_distortion_rgb_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int n_stacks, const int32_t* tables,
+                                    int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse,
+                                    uint64_t* bits, uint32_t* d_cube_sse) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rgb_args_ok(c, d_frames, w, h, n_stacks, tables, n_tables, cand, n_cand, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
+    return probe_rgb_dev(c, d_frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, plane_sse, bits, d_cube_sse);
+}
+
+int dct3d_distortion_rgb_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables,
+                                int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rgb_args_ok(c, frames, w, h, n_stacks, tables, n_tables, cand, n_cand, sse, &g, &n_cubes)) return DCT3D_EINVAL;
+    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
+    return probe_rgb_host(c, frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, plane_sse, bits);
 }
 
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,

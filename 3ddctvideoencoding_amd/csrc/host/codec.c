@@ -156,7 +156,8 @@ static int parse_positive(const char *text, const char *prefix, double *value) {
  * one (set or in the environment) beside an entry before it in this list refuses. */
 static char g_rate_text[64]; /* codec_set_rate's text; "": none */
 static char g_psnr_text[64]; /* codec_set_psnr's text; "": none */
-enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_N };
+static char g_psnr_rgb_text[64]; /* codec_set_psnr_rgb's text; "": none */
+enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_PSNR_RGB, SEL_N };
 static const struct {
     const char *prefix, *env, *noun, *unit;
     char *text;
@@ -165,11 +166,13 @@ static const struct {
     {"q=", "DCT3D_CODEC_QUANT", "quantiser", NULL, g_quant_text, sizeof(g_quant_text)},
     {"rate=", "DCT3D_CODEC_RATE", "rate target", "bits per pixel", g_rate_text, sizeof(g_rate_text)},
     {"psnr=", "DCT3D_CODEC_PSNR", "PSNR target", "dB", g_psnr_text, sizeof(g_psnr_text)},
+    {"psnr_rgb=", "DCT3D_CODEC_PSNR_RGB", "RGB PSNR target", "dB", g_psnr_rgb_text, sizeof(g_psnr_rgb_text)},
 };
 static const char *sel_text(int i) { return kSel[i].text[0] ? kSel[i].text : getenv(kSel[i].env); }
 
 int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, kSel[SEL_RATE].prefix, bpp); }
 int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR].prefix, db); }
+int codec_parse_psnr_rgb(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR_RGB].prefix, db); }
 
 static int set_target(int i, const char *text) {
     if (text && strlen(text) >= kSel[i].cap) return 1;
@@ -180,6 +183,7 @@ static int set_target(int i, const char *text) {
 }
 int codec_set_rate(const char *text) { return set_target(SEL_RATE, text); }
 int codec_set_psnr(const char *text) { return set_target(SEL_PSNR, text); }
+int codec_set_psnr_rgb(const char *text) { return set_target(SEL_PSNR_RGB, text); }
 
 /* Target i of a call: codec_set_*'s text, else the environment variable.  *set = 0: none given.  1 after printing
  * when the text does not parse or a quantiser or an earlier target is given too. */
@@ -377,7 +381,8 @@ static const char *cq_text(void) { return g_cq_text[0] ? g_cq_text : getenv("DCT
  * chroma offset cq=<k> (codec_set_cq, else DCT3D_CODEC_CQ).  *path = NULL: none given; *cq = k (0 without cq=).  1
  * after printing when a text does not parse, the map stands beside a quantiser, a per-stack map or a PSNR target, on a
  * grey call (what names it) or on the host Exp-Golomb path, or cq= stands without ycc=1 or without rate= and qmap3=. */
-static int call_qmap3(const char *what, int channels, int rate_set, int psnr_set, int ycc, const char **path, int *cq) {
+static int call_qmap3(const char *what, int channels, int writes_map, int psnr_set, int ycc, const char **path, int *cq) {
+    /* (writes_map: the call has a target whose first pass writes the map -- rate=, or psnr_rgb=) */
     const char *text = qmap3_text(), *ct = cq_text();
     *path = NULL;
     *cq = 0;
@@ -393,7 +398,7 @@ static int call_qmap3(const char *what, int channels, int rate_set, int psnr_set
             printf("cq= needs ycc=1: it codes the Cb and Cr planes more coarsely than Y\n");
             return 1;
         }
-        if (!rate_set || !text || !text[0]) {
+        if (!writes_map || !text || !text[0]) {
             printf("cq= applies to an encode_rgb with rate= and qmap3= (%s)\n", what);
             return 1;
         }
@@ -647,6 +652,91 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
             pick = pick_by_rate(tot, target * (double)width * (double)height * (double)frames);
             printf("rate: q=%d bits=%llu\n", kRateLadder[pick], (unsigned long long)tot[pick]);
         }
+        const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
+        if (rc) {
+            printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
+            return 1;
+        }
+    }
+    if (fseek(in, 0, SEEK_SET)) {
+        printf("Cannot rewind the input file for the second pass\n");
+        return 1;
+    }
+    return 0;
+}
+
+/* The first pass of an encode_rgb with an RGB-domain PSNR target (psnr_rgb=<dB>; codec.h): the RGB-domain
+ * distortion probe (dct3d_distortion_rgb_frames) per batch over the ladder, candidate i = (rung i, rung j, rung j), j =
+ * min(i + cq, last) (cq: with a three-column map; else 0), in the context's colour and chroma mode; the squared
+ * errors of the pixels and the candidates' bits summed over the file.  PSNR = 10 log10(255^2 3 w h frames / sse), the
+ * zero-filled frames of a short last stack counting as frames; the pick is pick_by_psnr's.  Without a map it prints
+ * "psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB> bits=<total>" and sets the context's quantiser to the pick.  stack_pick
+ * ([n_stacks], or [n_stacks][3] with qw == 3): the rule per stack over the stack's pixels instead; prints "qmap: ..."
+ * or "qmap3: ..." as the rate target does.  Rewinds the input.  1 after printing on an error. */
+static int psnr_rgb_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
+                               double target, uint8_t *stack_pick, int qw, int cq) {
+    const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
+    const size_t stack_bytes = (size_t)3 * width * height * depth;
+    int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
+    uint8_t cand[3 * RATE_LADDER_N];
+    int jof[RATE_LADDER_N];
+    uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N], map_bits = 0;
+    ladder_tables(depth, tabs);
+    for (int i = 0; i < RATE_LADDER_N; i++) {
+        tot[i] = err[i] = 0;
+        jof[i] = i + cq < RATE_LADDER_N ? i + cq : RATE_LADDER_N - 1;
+        cand[3 * i] = (uint8_t)i;
+        cand[3 * i + 1] = cand[3 * i + 2] = (uint8_t)jof[i];
+    }
+    const size_t n_sse = (size_t)RATE_LADDER_N * batch, n_bits = n_sse * 3;
+    uint64_t *sse = (uint64_t *)malloc(sizeof(uint64_t) * (n_sse + n_bits)), *bits = sse ? sse + n_sse : NULL;
+    if (!sse) {
+        printf("Out of memory\n");
+        return 1;
+    }
+    int status = 0;
+    for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
+        const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;
+        size_t got = 0, r;
+        const size_t want = stack_bytes * nb;
+        while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
+        if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as the encode's */
+        const int rc = dct3d_distortion_rgb_frames(ctx, fr, width, height, nb, tabs, RATE_LADDER_N, cand, RATE_LADDER_N, sse,
+                                                   NULL, bits);
+        if (rc) {
+            printf("Error running the RGB distortion probe: %s\n", dct3d_strerror(rc));
+            status = 1;
+            break;
+        }
+        for (int s = 0; s < nb; s++) {
+            uint64_t sb[RATE_LADDER_N], se[RATE_LADDER_N];
+            for (int i = 0; i < RATE_LADDER_N; i++) {
+                const int j = jof[i];
+                se[i] = sse[(size_t)i * nb + s];
+                sb[i] = bits[((size_t)i * nb + s) * 3] + bits[((size_t)j * nb + s) * 3 + 1] + bits[((size_t)j * nb + s) * 3 + 2];
+                err[i] += se[i];
+                tot[i] += sb[i];
+            }
+            if (!stack_pick) continue;
+            const int p = pick_by_psnr(se, 3.0 * (double)width * (double)height * (double)depth, target);
+            if (qw == 3) {
+                stack_pick[3 * (s0 + s)] = (uint8_t)p;
+                stack_pick[3 * (s0 + s) + 1] = stack_pick[3 * (s0 + s) + 2] = (uint8_t)jof[p];
+            } else {
+                stack_pick[s0 + s] = (uint8_t)p;
+            }
+            map_bits += sb[p];
+        }
+    }
+    free(sse);
+    if (status) return 1;
+    if (stack_pick) {
+        printf("%s: stacks=%d bits=%llu\n", qw == 3 ? "qmap3" : "qmap", n_stacks, (unsigned long long)map_bits);
+    } else {
+        const double n_samples = 3.0 * (double)width * (double)height * (double)n_stacks * (double)depth;
+        const int pick = pick_by_psnr(err, n_samples, target);
+        printf("psnr_rgb: q=%d,%d,%d psnr=%.3f bits=%llu\n", kRateLadder[pick], kRateLadder[jof[pick]], kRateLadder[jof[pick]],
+               psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
         const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
         if (rc) {
             printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
@@ -1099,6 +1189,18 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     double psnr_db = 0.0;
     int psnr_set = 0;
     if (call_target(SEL_PSNR, &psnr_db, &psnr_set)) return 1;
+    /* the RGB-domain PSNR target: packed RGB24 on the device stream calls alone -- refused before any file is made */
+    double prgb_db = 0.0;
+    int prgb_set = 0;
+    if (call_target(SEL_PSNR_RGB, &prgb_db, &prgb_set)) return 1;
+    if (prgb_set && channels != 3) {
+        printf("psnr_rgb= applies to encode_rgb on one device (encode): a grey encode takes psnr=\n");
+        return 1;
+    }
+    if (prgb_set && host_eg_on()) {
+        printf("psnr_rgb= needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
     int ycc;
     if (call_colour("encode", channels, psnr_set, &ycc)) return 1;
     int c420;
@@ -1106,7 +1208,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
     const char *qmap_path = NULL, *qmap3_path = NULL;
     int cq = 0;
-    if (call_qmap3("encode", channels, rate_set, psnr_set, ycc, &qmap3_path, &cq)) return 1;
+    if (call_qmap3("encode", channels, rate_set || prgb_set, psnr_set, ycc, &qmap3_path, &cq)) return 1;
     if (call_qmap(&qmap_path)) return 1;
     const int qw = qmap3_path ? 3 : 1; /* the map's entries per stack */
     if (qmap3_path) qmap_path = qmap3_path;
@@ -1119,7 +1221,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             printf("Out of memory\n");
             return 1;
         }
-        if (!rate_set && !psnr_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
+        if (!rate_set && !psnr_set && !prgb_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
             free(qmap);
             return 1;
         }
@@ -1186,7 +1288,9 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     if (!status && (rate_set || psnr_set))
         STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
                                               psnr_set ? psnr_db : rate_bpp, psnr_set, qmap, qw == 3 ? cq : -1));
-    if (!status && qmap && (rate_set || psnr_set))
+    if (!status && prgb_set)
+        STAGE(t_dev, status = psnr_rgb_first_pass(ctx, in, fr, width, height, frames, depth, batch, prgb_db, qmap, qw, qw == 3 ? cq : 0));
+    if (!status && qmap && (rate_set || psnr_set || prgb_set))
         status = qw == 3 ? write_qmap3(qmap_path, n_stacks, qmap) : write_qmap(qmap_path, n_stacks, qmap);
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;

@@ -21,6 +21,9 @@
  *   ... and qmap3=<path> (codec.h, codec_set_qmap3): three ladder qualities per stack and line, one per plane; written
  *   by an encode_rgb that also has rate= (and cq=<k>: the chroma planes k rungs coarser), else read; not with qmap=,
  *   q= or psnr=
+ *   encode_rgb takes psnr_rgb=<dB> (codec.h, codec_parse_psnr_rgb) in the quantiser's place, in every colour mode: the
+ *   first pass measures the squared error in the RGB pixels (the RGB-domain distortion probe) and prints
+ *   "psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB> bits=<total>"; with qmap= or qmap3= [cq=<k>] it writes the map
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -80,6 +83,14 @@ static void usage(void) {
            "budget, WRITES the map and prints 'qmap3: stacks=<n> bits=<total>'; an encode without a target and a decode "
            "READ it.  qmap3= together with qmap=, q= or psnr=, on encode or decode, with several devices, or a malformed "
            "file is an error; so is cq= without ycc=1 or without rate= and qmap3=\n");
+    printf("encode_rgb on one device takes psnr_rgb=<dB> in the quantiser's place, with or without ycc=1 and chroma=420: "
+           "the first pass measures, per rung of the ladder, the exact squared error of encode + decode in the RGB pixels "
+           "(all three bytes of every unpadded pixel), picks the largest q whose PSNR is >= <dB> (1 when none reaches it) "
+           "and prints 'psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB> bits=<total>'; the second pass encodes as q=<n>.  With "
+           "qmap=<path> the rule is applied per stack and the map is WRITTEN; with qmap3=<path> [cq=<k>] the candidates "
+           "are 'plane 0 at rung i, planes 1 and 2 at rung min(i + k, 15)' and the three-column map is written.  "
+           "psnr_rgb= on a decode, on a grey command, together with q=, rate= or psnr=, or with several devices is an "
+           "error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -133,7 +144,7 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0;
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0, have_prgb = 0;
     for (int a = 9; a < argc && a < 15 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
@@ -141,6 +152,22 @@ int main(int argc, char *argv[]) {
         const int is_qmap = !strncmp(argv[a], "qmap=", 5), is_ycc = !strncmp(argv[a], "ycc=", 4);
         const int is_chroma = !strncmp(argv[a], "chroma=", 7);
         const int is_qmap3 = !strncmp(argv[a], "qmap3=", 6), is_cq = !strncmp(argv[a], "cq=", 3);
+        const int is_prgb = !strncmp(argv[a], "psnr_rgb=", 9);
+        if (is_prgb) { /* the RGB-domain PSNR target: refused here before any file is made */
+            if (have_prgb) break;
+            if (codec_parse_psnr_rgb(argv[a], &v)) {
+                printf("Invalid psnr_rgb target '%s': psnr_rgb=<dB>, a positive number\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (strcmp(argv[1], "encode_rgb") || n_dev > 1) {
+                printf("psnr_rgb= applies to encode_rgb on one device: decode with the q=<n> or the map that the encode "
+                       "printed or wrote\n");
+                return 1;
+            }
+            have_prgb = a;
+            continue;
+        }
         if (a >= 10 && (is_qmap3 ? have_qmap3 : is_cq ? have_cq : 0)) break;
         if (is_qmap3 || is_cq) { /* collected here; the entry points check them (codec.c: call_qmap3, reject_qmap3) */
             if (is_qmap3) have_qmap3 = a;
@@ -208,6 +235,10 @@ int main(int argc, char *argv[]) {
         printf("%s and %s exclude each other\n", have_quant ? "q=" : "rate=", have_psnr ? "psnr=" : "rate=");
         return 1;
     }
+    if (have_prgb && (have_quant || have_rate || have_psnr)) {
+        printf("%s and psnr_rgb= exclude each other\n", have_quant ? "q=" : have_rate ? "rate=" : "psnr=");
+        return 1;
+    }
     if (have_ycc && argv[have_ycc][4] == '1' && have_psnr) {
         printf("ycc=1 and psnr= exclude each other: the distortion probe would measure the Y, Cb, Cr planes, not the RGB "
                "samples\n");
@@ -225,7 +256,8 @@ int main(int argc, char *argv[]) {
     if ((have_quant && codec_set_quant(argv[have_quant])) || (have_rate && codec_set_rate(argv[have_rate])) ||
         (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap])) ||
         (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma])) ||
-        (have_qmap3 && codec_set_qmap3(argv[have_qmap3])) || (have_cq && codec_set_cq(argv[have_cq]))) {
+        (have_qmap3 && codec_set_qmap3(argv[have_qmap3])) || (have_cq && codec_set_cq(argv[have_cq])) ||
+        (have_prgb && codec_set_psnr_rgb(argv[have_prgb]))) {
         printf("Argument too long\n");
         return 1;
     }

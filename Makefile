@@ -17,7 +17,7 @@ CFLAGS   := -O2 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude -std=c11 -D_
 DEV_SRCS  := $(CSRC)/dct3d_kernels.hip $(CSRC)/dct3d_kernels_f.hip $(CSRC)/dct3d_eg.hip $(CSRC)/dct3d_rgb.hip \
              $(CSRC)/dct3d_edge.hip $(CSRC)/dct3d_eg_frames.hip $(CSRC)/dct3d_quant.hip $(CSRC)/dct3d_quant_eg.hip \
              $(CSRC)/dct3d_rate.hip $(CSRC)/dct3d_distortion.hip $(CSRC)/dct3d_vq_enc.hip $(CSRC)/dct3d_vq_dec.hip \
-             $(CSRC)/dct3d_ycc.hip $(CSRC)/dct3d_c420.hip
+             $(CSRC)/dct3d_ycc.hip $(CSRC)/dct3d_c420.hip $(CSRC)/dct3d_distortion_rgb.hip
 DIAG_SRCS := $(CSRC)/dct3d_diag.hip
 HOST_SRCS := $(CSRC)/dct3d_plan.cpp $(CSRC)/dct3d_runtime.cpp $(CSRC)/dct3d_router.cpp
 HDRS      := $(wildcard $(CSRC)/*.h) include/dct3d.h include/dct3d_diag.h

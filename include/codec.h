@@ -119,6 +119,24 @@ int codec_set_rate(const char *text);
 int codec_parse_psnr(const char *text, double *db);
 int codec_set_psnr(const char *text);
 
+/* An RGB-domain PSNR target in place of a quantiser (encode_rgb_ex on one device, in every colour mode: planes,
+ * ycc=1, ycc=1 chroma=420): "psnr_rgb=<dB>", a positive decimal number.  The first pass runs the RGB-domain distortion
+ * probe (dct3d_distortion_rgb_frames) per batch over the rate target's ladder, candidate i = (rung i, rung j, rung j)
+ * with j = min(i + k, 15) (k: cq=<k> beside qmap3=, else 0), and sums the squared errors of the pixels and the
+ * candidates' bits over the file.  PSNR = 10 log10(255^2 * 3 * width * height * frames / sse), the zero-filled frames
+ * of a short last stack counting as frames; the pick is the PSNR target's rule (the largest q whose PSNR is >= <dB>,
+ * the smallest when none reaches it).  It prints one line "psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB, 3 decimals>
+ * bits=<total>"; the second pass encodes as q=<n> does, byte for byte.  With qmap=<path> the rule is applied per
+ * stack with one quality for all planes and the map is written as rate= writes it; with qmap3=<path> [cq=<k>] per
+ * stack with the triples (i, j, j).  With ycc=0 the numbers are psnr=<dB>'s.
+ * codec_parse_psnr_rgb: 0 and *db for "psnr_rgb=<positive number>"; 1 (*db untouched) on anything else.
+ * codec_set_psnr_rgb: the target of every later encode call of this process; NULL or "": none.  It overrides the
+ *   environment variable DCT3D_CODEC_PSNR_RGB.  It excludes a quantiser, a rate target and a PSNR target as those
+ *   exclude each other.  A call refuses it, before any file is made, on a decode, on a grey encode, on several
+ *   devices and with DCT3D_CODEC_HOST_EG=1. */
+int codec_parse_psnr_rgb(const char *text, double *db);
+int codec_set_psnr_rgb(const char *text);
+
 /* A quality per stack (the single-device calls: encode, encode_ex, encode_rgb_ex and their decodes): "qmap=<path>"
  * names a text file with one line per stack, in stack order, each a quality of the ladder above; stack s of every
  * channel is coded as q=<that quality> codes it (dct3d_encode_eg_frames_vq / dct3d_decode_eg_frames_vq, the ladder

@@ -533,6 +533,43 @@ int dct3d_distortion_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, in
                             int n_stacks, const int32_t *tables, int n_tables, uint64_t *sse, uint64_t *bits);
 
 /* ---------------------------------------------------------------------------------------------
+ * RGB-domain distortion probe (additive to ABI 9; detect by symbol): the exact squared error, in
+ * the RGB pixels, of the packed RGB24 stream encode + decode under a list of (Y, Cb, Cr) table triples, in all
+ * three colour modes of the context: planes, DCT3D_COLOUR_YCBCR, and DCT3D_CHROMA_420 on top.  Let y_c be what
+ * dct3d_decode_eg_frames_vqc(dct3d_encode_eg_frames_vqc(x)) returns when every row of the [n_stacks][3] map is
+ * cand[c], in the context's colour and chroma mode.
+ *   frames, width, height, n_stacks   packed RGB24 frames of any size, as dct3d_rate_frames* with channels == 3.
+ *   tables, n_tables   the palette, as dct3d_rate_frames* (NULL with n_tables == 1: the context's table).
+ *   cand      host, [n_cand][3] palette indices (Y | R, Cb | G, Cr | B), 1 <= n_cand <= DCT3D_RATE_MAX_TABLES;
+ *             NULL: n_cand == n_tables and candidate i = (i, i, i).
+ *   sse       host, [n_cand][n_stacks], required: sse[c][s] = sum (x - y_c)^2, as integers, over the unpadded
+ *             pixels of stack s and their three bytes.
+ *   plane_sse host, [n_tables][n_stacks][3], or NULL: the error of plane k under tables[t] in the plane's own
+ *             domain, over the plane's own unpadded samples (ceil(w / 2) x ceil(h / 2) for chroma under 4:2:0);
+ *             in planes mode exactly dct3d_distortion_frames' sse.
+ *   bits      host, the same shape, or NULL: exactly dct3d_rate_frames' result in the same mode.
+ *   d_cube_sse    optional device memory, uint32 [n_cand][n_stacks][C] (C: the padded cubes per stack of the
+ *             frames' grid): sse per 8 x 8 x D cube over its pixels inside the frame (512 x 3 x 255^2 < 2^32).
+ * When plane_sse or bits is asked for, every (table, plane) pair is coded; otherwise (YCbCr modes) only the pairs
+ * some candidate uses.  The results are exact; the call writes no stream, neither reads (tables != NULL) nor
+ * changes the context's quantiser, colour or chroma mode, honours DCT3D_OPT_DEC_MARGIN as the decode calls do and
+ * is synchronous on return; the host-pointer call moves the frames in chunks of whole stacks, as
+ * dct3d_rate_frames does.  In the YCbCr modes the decoded planes of a range of stacks live in a buffer the context
+ * owns (DCT3D_RGB_PLANE_BUDGET bytes at most, or one stack's): the call walks the stacks in ranges.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_rate_frames with sse in the place of bits, n_cand outside
+ * 1..DCT3D_RATE_MAX_TABLES, a candidate index >= n_tables, cand == NULL with n_cand != n_tables, 4:2:0 set
+ * without the colour transform.
+ * Statistics: n_units = padded coefficients x tables of every launch; n_flagged as the distortion probe counts.
+ * ------------------------------------------------------------------------------------------- */
+#define DCT3D_RGB_PLANE_BUDGET (64u << 20)
+int dct3d_distortion_rgb_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int n_stacks,
+                                    const int32_t *tables, int n_tables, const uint8_t *cand, int n_cand,
+                                    uint64_t *sse, uint64_t *plane_sse, uint64_t *bits, uint32_t *d_cube_sse);
+int dct3d_distortion_rgb_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int n_stacks,
+                                const int32_t *tables, int n_tables, const uint8_t *cand, int n_cand,
+                                uint64_t *sse, uint64_t *plane_sse, uint64_t *bits);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-stack quantiser tables in the fused stream calls (additive to ABI 9; detect by symbol).
  * The four dct3d_*_eg_frames* calls with three more host arguments, copied before the call returns:
  *   tables       [n_tables][bw + bh + bd - 2] steps, each in [1, 255]: a palette of 1 <= n_tables <=
