@@ -1,7 +1,9 @@
-"""Shared by test_cert_common.py (CPU), test_gpu_certificates.py and test_gpu_probe_certificates.py (GPU): what the
+"""Shared by test_cert_common.py (CPU), test_gpu_certificates.py, test_gpu_probe_certificates.py and
+test_gpu_distortion_rgb_certificates.py (GPU): what the
 host emulations of the kernels' arithmetic predict for the counts dct3d_get_stats reports -- which coefficients the
 fp32 encode certificate leaves open, which lanes the decode certificate flags, how the 8x8x8 second certificate splits
-the open ones, and what the rate and distortion probes count under several tables.
+the open ones, what the rate and distortion probes count under several tables, and what the RGB-domain distortion
+probe counts per plane of the colour transform and coded table.
 
 The emulations are tests/native/emulate_encode.cpp and emulate_decode_quant.cpp, built here as test_emulation.py
 builds them (g++ -O2 -ffp-contract=off -fno-fast-math, into a temporary directory).  With contraction off on both
@@ -452,3 +454,177 @@ def sum_partials(values, lanes):
 # a cube costs 1,981,851 (8x8x8) / 990,577 (8x8x4) on average, the least 8-lane partial is 1.0019 / 1.0035 x 2^32
 # (one block row less: 0.9982 / 0.9998).
 BIG_SUM = {8: (2560, 1744), 4: (3840, 2328)}
+
+
+# ---- the RGB-domain distortion probe in the colour modes (test_gpu_distortion_rgb_certificates.py) ---------------------
+# distortion_plane_kernel (dct3d_distortion_rgb.hip) is a copy of distortion_kernel's certificate loop with a forward
+# transform, a reload source, a table loop and a fold count of its own; probe_rgb_ycc_dev decides on the host which
+# (table, plane) pairs are coded at all.  The prediction treats every plane of the colour transform as a grey clip.
+
+COLOUR_MODES = ("planes", "ycc", "c420")
+
+
+class ColourCase:
+    """packed RGB24 content("uniform", depth, 3, w, h, stacks) in one colour mode of a context.  band: the frame rows
+    of one band -- one block row (8), in c420 mode 16: two Y block rows over one chroma block row, so that a crop at a
+    band's start has the whole frame's Y and chroma cubes.  rich: the shape claims richness under q1."""
+
+    def __init__(self, mode, depth, w, h, stacks, rich=False):
+        assert mode in COLOUR_MODES
+        self.mode, self.depth, self.w, self.h, self.stacks, self.rich = mode, depth, w, h, stacks, rich
+        self.band = 16 if mode == "c420" else 8
+        self.nb = (h + self.band - 1) // self.band
+        self.rgb = Case("uniform", depth, 3, w, h, stacks)  # planes mode: the plane probe's case
+        self.id = f"{mode}-{w}x{h}x{stacks}-d{depth}"
+
+    def frames(self):
+        return self.rgb.frames()
+
+    def __repr__(self):
+        return self.id
+
+
+@functools.lru_cache(maxsize=None)
+def colour_planes(c):
+    """the case's three planes as grey clips [F, ph, pw]: R, G, B | rgb_to_ycbcr's | rgb_to_ycbcr420's (the chroma
+    at chroma_size); never modified"""
+    p, fr = qc.pkg(), c.frames()
+    if c.mode == "c420":
+        pl = list(p.rgb_to_ycbcr420(fr))
+    else:
+        t = fr if c.mode == "planes" else p.rgb_to_ycbcr(fr)
+        pl = [t[..., k] for k in range(3)]
+    pl = tuple(np.ascontiguousarray(a, np.uint8) for a in pl)
+    if c.mode == "c420":
+        assert pl[1].shape[1:] == qc.pkg().chroma_size(c.w, c.h)[::-1]
+    for a in pl:
+        a.setflags(write=False)
+    return pl
+
+
+def colour_plane_cubes(c, k):
+    """(padded cubes per stack, block rows) of plane k"""
+    _, ph, pw = colour_planes(c)[k].shape
+    return ((pw + 7) // 8) * ((ph + 7) // 8), (ph + 7) // 8
+
+
+@functools.lru_cache(maxsize=None)
+def colour_plane_dct(c, k):
+    d = dct_cubes(colour_planes(c)[k], c.depth)
+    d.setflags(write=False)
+    return d
+
+
+def colour_plane_q_ref(c, k, name):
+    """the reference's coefficients of plane k under table `name`"""
+    return qc.pkg().quantize_ref(colour_plane_dct(c, k), steps_of(table(name, c.depth), c.depth))
+
+
+@functools.lru_cache(maxsize=None)
+def colour_plane_open(c, k, name, shift=0):
+    """(the emulation's q, its open mask) of plane k under table `name`, kept per (case, plane, table)"""
+    q, op, _ = encode_emulate(colour_planes(c)[k], c.depth, table(name, c.depth), 1, shift)
+    q.setflags(write=False)
+    op.setflags(write=False)
+    return q, op
+
+
+@functools.lru_cache(maxsize=None)
+def colour_plane_lanes(c, k, name):
+    """the lanes the decode certificate flags on the reference's coefficients of plane k, one mask per margin of
+    PROBE_MARGINS (probe_decode_lanes on the plane; the preconditions are asserted inside)"""
+    return tuple(decode_emulate_margins(colour_plane_q_ref(c, k, name), c.depth, table(name, c.depth), PROBE_MARGINS)[0])
+
+
+def _plane_bands(c, k, mask):
+    """per-unit mask of plane k [cube, ...] -> int64 [nb + 1]: the count per band of the frames, then the plane's.
+    Block row r of the plane lies in the frame rows from 8 r (chroma of c420: 16 r) on."""
+    _, nby = colour_plane_cubes(c, k)
+    rows = mask.reshape(c.stacks, nby, -1).sum(axis=(0, 2)).astype(np.int64)
+    sub = 2 if (c.mode == "c420" and k > 0) else 1
+    v = np.zeros(c.nb, np.int64)
+    np.add.at(v, (8 * sub * np.arange(nby)) // c.band, rows)
+    return with_total(v)
+
+
+@functools.lru_cache(maxsize=None)
+def colour_open_counts(c, k, name, shift=0):
+    v = _plane_bands(c, k, colour_plane_open(c, k, name, shift)[1])
+    v.setflags(write=False)
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def colour_lane_counts(c, k, name, margin):
+    v = _plane_bands(c, k, colour_plane_lanes(c, k, name)[PROBE_MARGINS.index(margin)])
+    v.setflags(write=False)
+    return v
+
+
+def coded_tables(n_tables, cand, all_pairs):
+    """probe_rgb_ycc_dev's lists L[k]: the tables plane k is coded under, in the order of their first use -- the
+    distinct tables some candidate names for plane k; every table when the planes' errors or the bits are asked for
+    (all_pairs) or no candidates are given (candidate i = (i, i, i))"""
+    if cand is None or all_pairs:
+        return [list(range(n_tables)) for _ in range(3)]
+    L = [[], [], []]
+    for cd in cand:
+        for k in range(3):
+            if cd[k] not in L[k]:
+                L[k].append(int(cd[k]))
+    return L
+
+
+def colour_distortion_counts(c, names, cand, margin, all_pairs=False, shift=0):
+    """n_flagged of one distortion_rgb_frames[_dev] call, int64 [nb + 1] (per band, then the whole raster).
+    ycc, c420: the sum over the planes k and the tables of L[k] of (the open coefficients + 32 x the lanes the decode
+    tile replays): a table several candidates name is coded and counted once, a table no candidate names for the plane
+    not at all.  planes: the plane probe under every table, whatever the candidates say."""
+    if c.mode == "planes":
+        return distortion_probe_counts(c.rgb, names, margin, shift)
+    L = coded_tables(len(names), cand, all_pairs)
+    return sum(colour_open_counts(c, k, names[t], shift) + 32 * colour_lane_counts(c, k, names[t], margin)
+               for k in range(3) for t in L[k])
+
+
+def colour_rate_counts(c, names, shift=0):
+    """n_flagged of rate_frames_dev in ycc or c420 mode: the rate probe's rule, every table on every plane"""
+    return sum(colour_open_counts(c, k, n, shift) for k in range(3) for n in names)
+
+
+def colour_units(c, names, cand, all_pairs=False, rows=None):
+    """n_units of the call on the frames cropped to `rows` frame rows (None: whole): per plane |L[k]| x padded cubes
+    x 64 depth x stacks (planes mode: every table)"""
+    p = qc.pkg()
+    h = c.h if rows is None else rows
+    sizes = [(c.w, h)] + [p.chroma_size(c.w, h) if c.mode == "c420" else (c.w, h)] * 2
+    L = coded_tables(len(names), None if c.mode == "planes" else cand, all_pairs)
+    return sum(len(L[k]) * ((pw + 7) // 8) * ((ph + 7) // 8) for k, (pw, ph) in enumerate(sizes)) * 64 * c.depth * c.stacks
+
+
+def colour_rich(c, names, cand, all_pairs=False):
+    """a (case, table set) is rich: is_rich of the summed per-band open counts of the coded pairs, and every plane
+    has >= 12 open coefficients under some table of the set"""
+    L = coded_tables(len(names), cand, all_pairs)
+    total = sum(colour_open_counts(c, k, names[t]) for k in range(3) for t in L[k])
+    return is_rich(total[:-1]) and all(max(int(colour_open_counts(c, k, n)[-1]) for n in names) >= 12 for k in range(3))
+
+
+# (w, h, stacks, rich under q1); planes mode runs at two of them: its kernel is the plane probe's
+COLOUR_SHAPES = ((200, 72, 2, True), (208, 80, 2, True), (244, 54, 2, True), (1366, 24, 1, True), (24, 16, 5, False),
+                 (13, 11, 1, False), (1, 1, 1, False))
+COLOUR_PROBE_CASES = [ColourCase(m, d, w, h, st, rich) for d in (8, 4) for m in ("ycc", "c420")
+                      for (w, h, st, rich) in COLOUR_SHAPES] + \
+                     [ColourCase("planes", d, w, h, st) for d in (8, 4) for (w, h, st) in ((200, 72, 2), (13, 11, 1))]
+# name -> (table names, candidates or None, ask for the planes' errors).  subsets: each plane a different proper
+# subset of the four, table 3 coded for no plane; planes4: the same with every pair coded
+_SUBSETS = ((0, 1, 2), (2, 1, 0), (0, 1, 0))
+COLOUR_SETS = {
+    "q1": (("q1",), ((0, 0, 0),), False),
+    "ref": (("ref",), ((0, 0, 0),), False),
+    "subsets": (TABLES, _SUBSETS, False),
+    "planes4": (TABLES, _SUBSETS, True),
+    "eleven": (PROBE_TABLES, None, False),
+    "repeat": (("q1", "q12", "seeded"), ((0, 1, 2), (2, 2, 0), (0, 1, 2)), False),
+}
+COLOUR_RICH_SETS = ("q1", "planes4", "eleven")  # the sets that code q1 on all three planes

@@ -10,7 +10,10 @@
     predicted count of every rich case: that mutation cannot pass the GPU module unseen;
   * the same for the rate and distortion probes' predictions (test_gpu_probe_certificates.py): soundness under the
     probe-only tables, the decode preconditions at every margin used, a set's count as the sum of its tables', and
-    the shifted threshold seen by every rich set."""
+    the shifted threshold seen by every rich set;
+  * the same for the RGB-domain distortion probe's predictions (test_gpu_distortion_rgb_certificates.py), per plane of
+    the colour transform: and the rule for which (table, plane) pairs a call codes, and that a band's crop has the
+    whole frame's cubes."""
 import numpy as np
 import pytest
 
@@ -202,6 +205,116 @@ def test_probe_reference_is_ref_frames():
         for n in ("ref", "all255", "qt7"):
             T = cc.steps_of(cc.table(n, c.depth), c.depth)
             assert np.array_equal(cc.case_q_ref(c, n), qc.ref_frames(c.frames(), T, c.depth)[0])
+
+
+# ---- the RGB-domain distortion probe's predictions (test_gpu_distortion_rgb_certificates.py) -------------------------
+
+def test_colour_cases_are_the_listed_ones():
+    ids = [c.id for c in cc.COLOUR_PROBE_CASES]
+    assert len(ids) == len(set(ids)) == 32
+    shapes = ("200x72x2", "208x80x2", "244x54x2", "1366x24x1", "24x16x5", "13x11x1", "1x1x1")
+    for d in (8, 4):
+        want = [f"{m}-{s}-d{d}" for m in ("ycc", "c420") for s in shapes] + [f"planes-{s}-d{d}" for s in ("200x72x2", "13x11x1")]
+        assert set(want) == {i for i in ids if i.endswith(f"d{d}")}
+    for c in cc.COLOUR_PROBE_CASES:
+        assert c.rich == (c.mode != "planes" and (c.w, c.h) in ((200, 72), (208, 80), (244, 54), (1366, 24)))
+    assert set(cc.COLOUR_SETS) == {"q1", "ref", "subsets", "planes4", "eleven", "repeat"}
+    names, cand, _ = cc.COLOUR_SETS["subsets"]
+    L = cc.coded_tables(len(names), cand, False)
+    assert [sorted(x) for x in L] == [[0, 2], [1], [0, 2]] and len({tuple(sorted(x)) for x in L}) >= 2
+    assert all(3 not in x and len(x) < 4 for x in L)  # proper subsets; table 3 is coded for no plane
+    assert cc.coded_tables(4, cand, True) == [[0, 1, 2, 3]] * 3 == cc.coded_tables(4, None, False)
+
+
+def test_coded_tables_of_the_repeated_candidates():
+    """the L[k] rule restated in Python on test_gpu_distortion_rgb.py's repeated-candidate set: a table several
+    candidates name is listed once, in the order of its first use"""
+    from test_gpu_distortion_rgb import SETS
+    names, cand, want = SETS["repeat"]
+    assert (names, tuple(cand), want) == cc.COLOUR_SETS["repeat"]
+    L = cc.coded_tables(len(names), cand, want)
+    assert [[names[t] for t in x] for x in L] == [["q1", "seeded"], ["q12", "seeded"], ["seeded", "q1"]]
+
+
+def test_colour_bands_of_a_crop_are_the_whole_frames():
+    """a crop that starts at a multiple of the band has the whole frame's cubes in every plane (c420: 16 rows are two
+    Y block rows over one chroma block row; the last band of a ragged height is shorter), so the whole raster's masks
+    give the per-band predictions"""
+    import oracle
+    for c in cc.COLOUR_PROBE_CASES:
+        if (c.w, c.h) not in ((244, 54), (13, 11)) or c.depth != 4:
+            continue
+        whole = cc.colour_planes(c)
+        for b in range(c.nb):
+            crop = cc.ColourCase(c.mode, c.depth, c.w, min(c.band, c.h - b * c.band), c.stacks)
+            crop.frames = lambda b=b: np.ascontiguousarray(c.frames()[:, b * c.band:(b + 1) * c.band])
+            for k, pl in enumerate(cc.colour_planes(crop)):
+                sub = 2 if (c.mode == "c420" and k > 0) else 1
+                nby = cc.colour_plane_cubes(c, k)[1]
+                rows = [r for r in range(nby) if (8 * sub * r) // c.band == b]
+                got = oracle.to_cubes(cc.raster_of(pl, c.depth), 8, 8, c.depth).reshape((c.stacks, len(rows), -1, c.depth, 8, 8))
+                want = oracle.to_cubes(cc.raster_of(whole[k], c.depth), 8, 8, c.depth).reshape((c.stacks, nby, -1, c.depth, 8, 8))
+                assert np.array_equal(got, want[:, rows]), f"{c.id} band {b} plane {k}"
+            assert cc.colour_units(crop, ("q1",), ((0, 0, 0),)) == cc.colour_units(c, ("q1",), ((0, 0, 0),), rows=crop.h)
+
+
+@pytest.mark.parametrize("c", cc.COLOUR_PROBE_CASES, ids=repr)
+def test_colour_probe_predictions(c):
+    """per colour case and plane: under every table of the sets the emulation is sound (what it leaves closed is the
+    reference's q) and decode_emulate's preconditions hold at each of PROBE_MARGINS, with no lane flagged at margin 0
+    under ref, q1, q12 and seeded (under quant_table(64) at 8x8x4 the flat chroma planes do flag lanes at margin 0:
+    the prediction carries them); richness where claimed; a set's prediction is the sum over its coded pairs, and
+    the thresholds read at s + 1 change the prediction of every rich (case, set)."""
+    if c.mode == "planes":
+        for s, (names, cand, planes) in cc.COLOUR_SETS.items():
+            for m in cc.PROBE_MARGINS:
+                assert np.array_equal(cc.colour_distortion_counts(c, names, cand, m, planes),
+                                      cc.distortion_probe_counts(c.rgb, names, m))
+            assert cc.colour_units(c, names, cand, planes) == len(names) * cc.raster_of(c.frames(), c.depth).size
+        return
+    for k in range(3):
+        ncubes, nby = cc.colour_plane_cubes(c, k)
+        for n in cc.PROBE_TABLES:
+            q, op = cc.colour_plane_open(c, k, n)
+            assert q.shape[0] == ncubes * c.stacks
+            bad = (q != cc.colour_plane_q_ref(c, k, n)) & ~op
+            assert not bad.any(), f"plane {k} {n}: {int(bad.sum())} closed coefficients differ"
+            assert not op[:, 0, 0, 0].any()
+            lanes = cc.colour_plane_lanes(c, k, n)  # (asserts the preconditions)
+            if n in cc.TABLES:
+                assert not lanes[0].any(), f"{c.id} plane {k} {n}: a lane flagged at margin 0: another seed"
+            v = cc.colour_open_counts(c, k, n)
+            assert v.shape == (c.nb + 1,) and v[-1] == v[:-1].sum() == op.sum()
+            for m in cc.PROBE_MARGINS:
+                assert cc.colour_lane_counts(c, k, n, m)[-1] == lanes[cc.PROBE_MARGINS.index(m)].sum()
+        if c.rich:
+            assert cc.colour_open_counts(c, k, "q1")[-1] >= 12, f"{c.id} plane {k}"
+    for s, (names, cand, planes) in cc.COLOUR_SETS.items():
+        for all_pairs in sorted({planes, True}):  # (asking for the bits codes every pair)
+            L = cc.coded_tables(len(names), cand, all_pairs)
+            rate = sum(cc.colour_open_counts(c, k, names[t]) for k in range(3) for t in L[k])
+            for i, m in enumerate(cc.PROBE_MARGINS):
+                dist = cc.colour_distortion_counts(c, names, cand, m, all_pairs)
+                assert dist.shape == (c.nb + 1,) and dist[-1] == dist[:-1].sum()
+                assert dist[-1] == rate[-1] + 32 * sum(int(cc.colour_plane_lanes(c, k, names[t])[i].sum())
+                                                       for k in range(3) for t in L[k])
+            if all_pairs:
+                assert np.array_equal(rate, cc.colour_rate_counts(c, names))
+            if names[0] in cc.TABLES and len(names) <= 4:
+                assert np.array_equal(cc.colour_distortion_counts(c, names, cand, 0.0, all_pairs), rate)  # margin 0: the encode term
+            units = cc.colour_units(c, names, cand, all_pairs)
+            assert units == sum(len(L[k]) * cc.colour_plane_cubes(c, k)[0] for k in range(3)) * 64 * c.depth * c.stacks
+        if c.rich and s in cc.COLOUR_RICH_SETS:
+            assert cc.colour_rich(c, names, cand, planes), f"{c.id} {s} is not rich"
+            for m in (0.0, cc.MARGINS[0]):
+                pred = cc.colour_distortion_counts(c, names, cand, m, planes)
+                shifted = cc.colour_distortion_counts(c, names, cand, m, planes, shift=1)
+                assert shifted[-1] != pred[-1] and not np.array_equal(shifted, pred), f"{c.id} {s}: no sight of thr[s + 1]"
+        print(f"{c.id} {s}: units {cc.colour_units(c, names, cand, planes)}, flagged at {cc.PROBE_MARGINS}: "
+              f"{[int(cc.colour_distortion_counts(c, names, cand, m, planes)[-1]) for m in cc.PROBE_MARGINS]}")
+    if c.rich:
+        rate = cc.colour_rate_counts(c, cc.TABLES)
+        assert cc.is_rich(rate[:-1]) and cc.colour_rate_counts(c, cc.TABLES, shift=1)[-1] != rate[-1]
 
 
 def test_sum_partials_is_the_sum_kernels_partition():

@@ -64,6 +64,10 @@ def frames_of(content, depth, w, h, stacks):
     p = qc.pkg()
     if content == "rare":
         fr = _rare_content(p, depth, 3)
+    elif content.startswith("cert"):  # "cert<H>@<y0>": rows y0 .. y0 + h of cert_common's colour content of H rows
+        import cert_common as cc
+        H, y0 = (int(v) for v in content[4:].split("@"))
+        fr = cc.content("uniform", depth, 3, w, H, stacks)[:, y0:y0 + h]
     elif content.startswith("chk"):
         n = int(content[3:])
         z, y, x = np.ogrid[:stacks * depth, :h, :w]
@@ -127,9 +131,11 @@ def ref_planes(content, depth, w, h, stacks, mode, names, what):
                      for n in names])
 
 
-def probe_dev(ctx, content, depth, w, h, stacks, names, cand, want):
+def probe_dev(ctx, content, depth, w, h, stacks, names, cand, want, want_bits=None):
     """distortion_rgb_frames_dev with guard bands around d_cube_sse and the frames at the end of their allocation
-    -> (sse, plane_sse or None, bits or None, cube sse [n_cand, stacks, C])"""
+    -> (sse, plane_sse or None, bits or None, cube sse [n_cand, stacks, C]).  want: the planes' errors and, unless
+    want_bits says otherwise, the bits"""
+    want_bits = want if want_bits is None else want_bits
     import torch
     p = qc.pkg()
     wp, hp = p.padded_size(w, h)
@@ -142,12 +148,14 @@ def probe_dev(ctx, content, depth, w, h, stacks, names, cand, want):
     d_fr = store[4096:]
     d_fr.copy_(torch.from_numpy(np.array(fr)).reshape(-1))
     res = ctx.distortion_rgb_frames_dev(d_fr, w, h, stacks, [_table(depth, x) for x in names], cand, mid,
-                                        want_planes=want, want_bits=want)
+                                        want_planes=want, want_bits=want_bits)
     got, intact = qc.bands_intact(buf, n, 0xA5)
     assert intact, "a write outside d_cube_sse"
     assert np.array_equal(d_fr.cpu().numpy(), fr.reshape(-1)), "the frames were written"
     cubes = got.view(np.uint32).reshape(n_cand, stacks, C)
-    return (res + (cubes,)) if want else (res, None, None, cubes)
+    if want and want_bits:
+        return res + (cubes,)
+    return (res[0], res[1], None, cubes) if want else (res[0], None, res[1], cubes) if want_bits else (res, None, None, cubes)
 
 
 def check_case(ctx, pkg, content, depth, w, h, stacks, mode, set_name):
