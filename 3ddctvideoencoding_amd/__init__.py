@@ -42,6 +42,9 @@ DCT3D_COLOUR_PLANES, DCT3D_COLOUR_YCBCR = 0, 1
 DCT3D_CHROMA_444, DCT3D_CHROMA_420 = 0, 1
 # bytes of decoded planes the RGB-domain distortion probe keeps per range of stacks (dct3d.h; or one stack's)
 DCT3D_RGB_PLANE_BUDGET = 64 << 20
+# bytes of 4 x 4 block records the SSIM probe keeps per range of stacks (dct3d.h; or one stack's): per stack and
+# channel D ceil(w / 4) ceil(h / 4) (8 n_tables + 4)
+DCT3D_SSIM_BLOCK_BUDGET = 16 << 20
 
 # Every symbol include/dct3d.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -66,6 +69,7 @@ ABI_SYMBOLS = (
     "dct3d_encode_eg_frames_vqc", "dct3d_encode_eg_frames_vqc_dev",
     "dct3d_decode_eg_frames_vqc", "dct3d_decode_eg_frames_vqc_dev",
     "dct3d_distortion_rgb_frames", "dct3d_distortion_rgb_frames_dev",
+    "dct3d_ssim_frames", "dct3d_ssim_frames_dev", "dct3d_ssim_windows",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -173,6 +177,9 @@ def lib() -> C.CDLL:
         L.dct3d_chroma_size.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
         L.dct3d_distortion_rgb_frames_dev.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]
         L.dct3d_distortion_rgb_frames.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]
+        L.dct3d_ssim_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+        L.dct3d_ssim_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.dct3d_ssim_windows.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
         _lib = L
     return _lib
 
@@ -379,6 +386,92 @@ def pick_quality_psnr(sse_per_quality: dict, n_samples, target_db) -> int:
         raise ValueError("no qualities to pick from")
     ok = [q for q, e in sse_per_quality.items() if psnr_db(e, n_samples) >= target_db]
     return int(max(ok)) if ok else int(min(sse_per_quality))
+
+
+def ssim_windows(w: int, h: int) -> tuple:
+    """(nwx, nwy): the SSIM probe's windows of a w x h plane (dct3d_ssim_windows): 8 x 8 windows at a stride of 4
+    over the 4 x 4 block grid, nwx = max(ceil(w / 4) - 1, 1)."""
+    nwx, nwy = C.c_int(), C.c_int()
+    _check(lib().dct3d_ssim_windows(int(w), int(h), C.byref(nwx), C.byref(nwy)), "dct3d_ssim_windows")
+    return nwx.value, nwy.value
+
+
+def ssim_windows_ref(x, y, _parts: bool = False) -> np.ndarray:
+    """The SSIM probe's definition (include/dct3d.h) in numpy: uint8 planes x (the source) and y (the decoded
+    frames) [.., H, W] -> int64 [.., nwy, nwx], v = floor(s 2^24) of every window.  Blocks: the 4 x 4 grid's integer
+    moments n, Sx, Sy, Sxx, Syy, Sxy over the samples inside the plane.  Window (i, j): the sums over blocks
+    i .. min(i + 1, nbx - 1) by j .. min(j + 1, nby - 1).  In int64
+        A = 20000 Sx Sy + 65025 n^2                  B = 20000 (n Sxy - Sx Sy) + 585225 n^2
+        C = 10000 (Sx^2 + Sy^2) + 65025 n^2          D = 10000 (n Sxx - Sx^2 + n Syy - Sy^2) + 585225 n^2
+    and in fp64 s = fl(fl(A B) / fl(C D)): two multiplications and one division of exactly converted integers.
+    (_parts: the tuple (v, A, B, C, D) instead, for the tests of the bounds.)"""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.dtype != np.uint8 or y.dtype != np.uint8 or x.shape != y.shape or x.ndim < 2:
+        raise ValueError("x and y are uint8 planes [.., H, W] of one shape")
+    h, w = x.shape[-2:]
+    if h < 1 or w < 1:
+        raise ValueError("empty planes")
+    nbx, nby = (w + 3) // 4, (h + 3) // 4
+    nwx, nwy = max(nbx - 1, 1), max(nby - 1, 1)
+    lead = x.shape[:-2]
+
+    def blocks(a):  # the 4 x 4 blocks' sums of a [.., H, W] (zero outside the plane)
+        p = np.zeros(lead + (4 * nby, 4 * nbx), np.int64)
+        p[..., :h, :w] = a
+        return p.reshape(lead + (nby, 4, nbx, 4)).sum(axis=(-3, -1))
+
+    def windows(b):  # blocks -> windows: the 1, 2 or 4 blocks of each
+        r = b[..., :nwy, :nwx].copy()
+        if nbx > 1:
+            r += b[..., :nwy, 1:nwx + 1]
+        if nby > 1:
+            r += b[..., 1:nwy + 1, :nwx]
+        if nbx > 1 and nby > 1:
+            r += b[..., 1:nwy + 1, 1:nwx + 1]
+        return r
+
+    xi, yi = x.astype(np.int64), y.astype(np.int64)
+    n = windows(blocks(np.ones(x.shape, np.int64)))
+    Sx, Sy = windows(blocks(xi)), windows(blocks(yi))
+    Sxx, Syy, Sxy = windows(blocks(xi * xi)), windows(blocks(yi * yi)), windows(blocks(xi * yi))
+    n2 = n * n
+    A = 20000 * Sx * Sy + 65025 * n2
+    B = 20000 * (n * Sxy - Sx * Sy) + 585225 * n2
+    Cc = 10000 * (Sx * Sx + Sy * Sy) + 65025 * n2
+    D = 10000 * (n * Sxx - Sx * Sx + n * Syy - Sy * Sy) + 585225 * n2
+    s = (A.astype(np.float64) * B.astype(np.float64)) / (Cc.astype(np.float64) * D.astype(np.float64))
+    v = np.floor(s * 16777216.0).astype(np.int64)
+    return (v, A, B, Cc, D) if _parts else v
+
+
+def ssim_mean(total, n_windows) -> float:
+    """The mean SSIM of n_windows windows whose v sum to total (ssim_frames' numbers, summed as needed):
+    total / (2^24 n_windows)."""
+    if int(n_windows) < 1:
+        raise ValueError("n_windows must be >= 1")
+    return float(int(total)) / (16777216.0 * float(int(n_windows)))
+
+
+def pick_quality_ssim(ssim_per_quality: dict, n_windows, target) -> int:
+    """The rule of the codec's ssim= argument: the largest quality (the coarsest quantiser) whose mean SSIM is >=
+    target; if none reaches it, the smallest quality of the dict.  Nothing is assumed about how the SSIM varies with
+    the quality."""
+    if not ssim_per_quality:
+        raise ValueError("no qualities to pick from")
+    ok = [q for q, t in ssim_per_quality.items() if ssim_mean(t, n_windows) >= target]
+    return int(max(ok)) if ok else int(min(ssim_per_quality))
+
+
+def pick_stack_qualities_ssim(ssim, qualities, n_windows_per_stack, target) -> list:
+    """pick_quality_ssim per stack: ssim [T, n_stacks, channels] as ssim_frames returns it for the tables of
+    `qualities`; stack s gets pick_quality_ssim of its sums added over the channels, over n_windows_per_stack windows
+    (all channels' windows of one stack)."""
+    ssim = np.asarray(ssim)
+    qualities = [int(q) for q in qualities]
+    if ssim.ndim != 3 or ssim.shape[0] != len(qualities):
+        raise ValueError("ssim must be [len(qualities), n_stacks, channels]")
+    return [pick_quality_ssim({q: int(ssim[t, s, :].astype(object).sum()) for t, q in enumerate(qualities)},
+                              n_windows_per_stack, target) for s in range(ssim.shape[1])]
 
 
 def pick_stack_qualities(bits, qualities, target_bits_per_stack) -> list:
@@ -1082,6 +1175,44 @@ class Context:
                                                  None if d_cube_sse is None else _tptr(d_cube_sse)),
                "dct3d_distortion_frames_dev")
         return (sse, bits) if want_bits else sse
+
+    # ---- SSIM probe: the exact 8 x 8 / stride 4 windowed SSIM of encode + decode under several tables ----
+    @staticmethod
+    def _ssim_result(ssim, sse, bits):
+        if sse is None and bits is None:
+            return ssim
+        return (ssim,) + (() if sse is None else (sse,)) + (() if bits is None else (bits,))
+
+    def ssim_frames(self, frames: np.ndarray, tables=None, want_sse: bool = False, want_bits: bool = False):
+        """u8 frames as encode_frames' -> int64 [T, n_stacks, channels]: the sum of v = floor(s 2^24) over the windows
+        of the D frames of stack s, channel ch (ssim_windows_ref states s), y = decode_frames(encode_frames(x)) under
+        tables[t] (None: the context's table, T = 1); ssim_mean turns sums into means.  Exact; the context's quantiser
+        is neither used (tables given) nor changed.  want_sse / want_bits: the tuple (ssim[, sse][, bits]), sse and
+        bits exactly distortion_frames'."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        tb, T = self._rate_tables(tables)
+        ssim = np.zeros((T, n_stacks, channels), np.int64)
+        sse = np.zeros((T, n_stacks, channels), np.uint64) if want_sse else None
+        bits = np.zeros((T, n_stacks, channels), np.uint64) if want_bits else None
+        _check(lib().dct3d_ssim_frames(self._h, _ptr(frames), W, H, channels, n_stacks, None if tb is None else _ptr(tb), T,
+                                       _ptr(ssim), None if sse is None else _ptr(sse), None if bits is None else _ptr(bits)),
+               "dct3d_ssim_frames")
+        return self._ssim_result(ssim, sse, bits)
+
+    def ssim_frames_dev(self, d_frames, width: int, height: int, channels: int, n_stacks: int, tables=None,
+                        d_window_ssim=None, want_sse: bool = False, want_bits: bool = False):
+        """Device path of ssim_frames: u8 frames on the device; d_window_ssim (optional; a tensor or an address)
+        receives int32 [T, n_stacks, channels, D, nwy, nwx], the v of every window."""
+        tb, T = self._rate_tables(tables)
+        ssim = np.zeros((T, n_stacks, channels), np.int64)
+        sse = np.zeros((T, n_stacks, channels), np.uint64) if want_sse else None
+        bits = np.zeros((T, n_stacks, channels), np.uint64) if want_bits else None
+        _check(lib().dct3d_ssim_frames_dev(self._h, _tptr(d_frames), width, height, channels, n_stacks,
+                                           None if tb is None else _ptr(tb), T, _ptr(ssim),
+                                           None if sse is None else _ptr(sse), None if bits is None else _ptr(bits),
+                                           None if d_window_ssim is None else _tptr(d_window_ssim)), "dct3d_ssim_frames_dev")
+        return self._ssim_result(ssim, sse, bits)
 
     # ---- RGB-domain distortion probe: the exact squared error in the RGB pixels under (Y, Cb, Cr) table triples ----
     @staticmethod

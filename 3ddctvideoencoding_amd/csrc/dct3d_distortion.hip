@@ -4,9 +4,12 @@
 // expects its staged input, runs the certified fp64 decode tile with the bytes kept in registers, and compares
 // them with the rows it started from.  No coefficient and no decoded raster exists in memory.  A translation
 // unit of its own: no other kernel's code object changes with it.
+// The SSIM probe (dct3d_ssim_frames*) is an arm of the same kernel -- the moments of the frames' 4 x 4
+// blocks from the same bytes -- and two small kernels that turn the blocks' records into the windows' values.
 #include "dct3d_distortion.h"
 #include "dct3d_probe_dev.h"
 #include "dct3d_decode_dev.h"
+#include <type_traits>
 
 namespace dct3d {
 
@@ -145,8 +148,18 @@ __device__ __forceinline__ void e16_forward(const uint2 (&raw)[4], char* wl, int
 // The wave's LDS region: the decode's region (first the forward transform's transposes, then per table the
 // staged integers, the decode's own transposes and replay scratch), the int16 copy of the staged integers
 // (ReloadQ16), the fold's scratch, the cubes' bits.
-template <int D, int PX, int EDGE>
-__global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, DistParams R) {
+// SSIM = 1 (the SSIM probe): a word of the decode side is one row of a 4 x 4 block of one frame, the
+// block's four rows are the lanes dk ^ 1, dk ^ 2.  Per table the lane takes Sy, Syy and Sxy of each word, the four
+// rows add up as two packed words (quad permutes), and the lane of the block's first row stores the record.
+template <int SSIM>
+using DistKernelParams = std::conditional_t<SSIM != 0, SsimParams, DistParams>;
+// the sum over the lane's quad partner x (1 | 2): both are quad permutes
+template <int X>
+__device__ __forceinline__ uint32_t quad_add(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, X == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false);
+}
+template <int D, int PX, int EDGE, int SSIM = 0>
+__global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, DistKernelParams<SSIM> R) {
     using G = DecGeom<D>;
     constexpr int CS = 64 * D, CPW = G::CPW;
     constexpr int NXC = (D == 8) ? 4 : 8, NW = NXC / 4;
@@ -224,6 +237,26 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
             for (int wd = 0; wd < NW; wd++) {
                 sw[z][wd] &= bmask[wd];
                 saa = __builtin_amdgcn_udot4(sw[z][wd], sw[z][wd], saa, false);
+            }
+    }
+    // SSIM: the lane's blocks (word wd of frame z at blk0 + z * blkz + wd) and, once, the source's moments
+    [[maybe_unused]] size_t blk0 = 0, blkz = 0;
+    [[maybe_unused]] bool bst[NW] = {};
+    if constexpr (SSIM) {
+        const CubePos cp = cube_pos(P, min(cube0 + (uint32_t)dc, P.n_cubes - 1u));
+        const uint32_t by4 = cp.by * 2 + ((uint32_t)dy >> 2), bx4 = cp.bx * 2 + ((uint32_t)dx0 >> 2);
+        blkz = (size_t)R.nby * R.nbx;
+        blk0 = ((size_t)cp.s * D * R.nby + by4) * R.nbx + bx4;
+#pragma unroll
+        for (int wd = 0; wd < NW; wd++) bst[wd] = dvalid && (dk & 3) == 0 && by4 < R.nby && bx4 + wd < R.nbx;
+#pragma unroll
+        for (int z = 0; z < D; z++)
+#pragma unroll
+            for (int wd = 0; wd < NW; wd++) {
+                uint32_t m = __builtin_amdgcn_udot4(sw[z][wd], 0x01010101u, 0u, false) |
+                             (__builtin_amdgcn_udot4(sw[z][wd], sw[z][wd], 0u, false) << 12);
+                m = quad_add<2>(quad_add<1>(m));
+                if (bst[wd]) R.blk_x[blk0 + z * blkz + wd] = m;
             }
     }
 
@@ -322,15 +355,25 @@ __global__ __launch_bounds__(kBlock, 2) void distortion_kernel(EncodeParams P, D
 #pragma unroll
             for (int wd = 0; wd < NW; wd++) {
                 const uint32_t y = outw[z][wd] & bmask[wd];
-                sbb = __builtin_amdgcn_udot4(y, y, sbb, false);
-                sab = __builtin_amdgcn_udot4(sw[z][wd], y, sab, false);
+                if constexpr (SSIM) {
+                    const uint32_t syy = __builtin_amdgcn_udot4(y, y, 0u, false);
+                    const uint32_t sxy = __builtin_amdgcn_udot4(sw[z][wd], y, 0u, false);
+                    sbb += syy;
+                    sab += sxy;
+                    const uint32_t lo = quad_add<2>(quad_add<1>(__builtin_amdgcn_udot4(y, 0x01010101u, 0u, false) | (syy << 12)));
+                    const uint32_t hi = quad_add<2>(quad_add<1>(sxy));
+                    if (bst[wd]) R.blk_y[(size_t)t * R.blk_stride + blk0 + z * blkz + wd] = ((uint64_t)hi << 32) | lo;
+                } else {
+                    sbb = __builtin_amdgcn_udot4(y, y, sbb, false);
+                    sab = __builtin_amdgcn_udot4(sw[z][wd], y, sab, false);
+                }
             }
         uint32_t sse = saa + sbb - 2u * sab;  // < 2^32 for the cube: 512 x 255^2
         sse += __shfl_xor(sse, 1, 64);
         sse += __shfl_xor(sse, 2, 64);
         if constexpr (D == 8) sse += __shfl_xor(sse, 4, 64);
         sse += __shfl_xor(sse, 16, 64);
-        if (dk == 0 && dh == 0 && dvalid) R.cube_sse[(size_t)t * R.table_stride + ocube] = sse;
+        if (dk == 0 && dh == 0 && dvalid && (!SSIM || R.cube_sse)) R.cube_sse[(size_t)t * R.table_stride + ocube] = sse;
         wave_lds_sync();  // the next table rewrites the staging
     }
     if (nrep && lane == 0 && P.replay_count) atomicAdd(P.replay_count + (blockIdx.x & (kCountSpread - 1)), nrep);
@@ -352,10 +395,82 @@ int launch_distortion(int D, int px, int edge, const EncodeParams& P, const Dist
     });
 }
 
+int launch_distortion_ssim(int D, int px, int edge, const EncodeParams& P, const SsimParams& R, hipStream_t st) {
+    return probe_dispatch(D, px, edge, P, R, [&](auto d, auto p, auto e) {
+        const dim3 grid(grid_blocks(P.n_cubes, DecGeom<decltype(d)::value>::CPW));
+        hipLaunchKernelGGL((distortion_kernel<decltype(d)::value, decltype(p)::value, decltype(e)::value, 1>), grid, dim3(kBlock), 0, st, P, R);
+    });
+}
+
 int launch_distortion_sum(const uint32_t* cube_sse, uint32_t run, uint64_t n_runs, uint64_t* out, hipStream_t st) {
     if (n_runs == 0) return 0;
     if (n_runs > 0x7FFFFFFFull) return -1;
     hipLaunchKernelGGL(distortion_sum_kernel, dim3((uint32_t)n_runs), dim3(kBlock), 0, st, cube_sse, run, out);
+    return launched();
+}
+
+// ---- the SSIM probe's windows (dct3d.h states the definition) ----
+// One thread per window of (table blockIdx.z, stack blockIdx.y): the moments of its 1, 2 or 4 blocks, n from the
+// geometry, A, B, C, D in int64, s = fl(fl(A B) / fl(C D)), v = floor(s 2^24); the block's sum of v
+__global__ __launch_bounds__(kBlock) void ssim_window_kernel(SsimWinParams W) {
+    const uint32_t t = blockIdx.z, s = blockIdx.y;
+    const uint32_t per_frame = W.nwx * W.nwy, per_stack = per_frame * W.depth;
+    const uint64_t* const by_ = W.blk_y + (size_t)t * W.blk_stride;
+    int64_t sum = 0;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < per_stack; i += W.bpr * kBlock) {
+        const uint32_t z = i / per_frame, r = i - z * per_frame;
+        const uint32_t j = r / W.nwx, x = r - j * W.nwx;
+        const uint32_t x1 = min(x + 1u, W.nbx - 1u), j1 = min(j + 1u, W.nby - 1u);
+        const size_t f0 = ((size_t)s * W.depth + z) * W.nby;
+        int64_t Sx = 0, Sy = 0, Sxx = 0, Syy = 0, Sxy = 0;
+        for (uint32_t bj = j; bj <= j1; bj++)
+            for (uint32_t bi = x; bi <= x1; bi++) {
+                const size_t b = (f0 + bj) * W.nbx + bi;
+                const uint64_t my = by_[b];
+                const uint32_t mx = W.blk_x[b];
+                Sx += mx & 0xFFFu;
+                Sxx += mx >> 12;
+                Sy += (uint32_t)my & 0xFFFu;
+                Syy += (uint32_t)my >> 12;
+                Sxy += (uint32_t)(my >> 32);
+            }
+        const int64_t n = (int64_t)(min(4u * x + 8u, W.w) - 4u * x) * (int64_t)(min(4u * j + 8u, W.h) - 4u * j);
+        const int64_t n2 = n * n, xy = Sx * Sy, xx = Sx * Sx, yy = Sy * Sy;
+        const int64_t A = 20000 * xy + 65025 * n2;
+        const int64_t B = 20000 * (n * Sxy - xy) + 585225 * n2;
+        const int64_t Cc = 10000 * (xx + yy) + 65025 * n2;
+        const int64_t Dd = 10000 * (n * Sxx - xx + n * Syy - yy) + 585225 * n2;
+        const double q = __ddiv_rn(__dmul_rn((double)A, (double)B), __dmul_rn((double)Cc, (double)Dd));
+        const int32_t v = (int32_t)floor(__dmul_rn(q, 16777216.0));
+        if (W.win) W.win[(size_t)t * W.win_t + (size_t)s * W.win_s + i] = v;
+        sum += v;
+    }
+    const uint64_t r = probe_block_sum((uint64_t)sum);
+    if (threadIdx.x == 0) W.part[((size_t)t * W.ns + s) * W.bpr + blockIdx.x] = (int64_t)r;
+}
+
+// One block per (stack blockIdx.x, table blockIdx.y): the sum of its bpr partial sums
+__global__ __launch_bounds__(kBlock) void ssim_sum_kernel(const int64_t* part, uint32_t bpr, int64_t* out, uint64_t out_t,
+                                                          uint64_t out_s) {
+    const int64_t* p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * bpr;
+    uint64_t s = 0;
+    for (uint32_t i = threadIdx.x; i < bpr; i += kBlock) s += (uint64_t)p[i];
+    const uint64_t r = probe_block_sum(s);
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * out_t + (size_t)blockIdx.x * out_s] = (int64_t)r;
+}
+
+int launch_ssim_window(const SsimWinParams& W, hipStream_t st) {
+    if (W.ns == 0 || W.n_tables == 0) return 0;
+    if (W.ns > 65535u || W.n_tables > 65535u || W.bpr == 0) return -1;
+    hipLaunchKernelGGL(ssim_window_kernel, dim3(W.bpr, W.ns, W.n_tables), dim3(kBlock), 0, st, W);
+    return launched();
+}
+
+int launch_ssim_sum(const int64_t* part, uint32_t bpr, uint32_t ns, uint32_t n_tables, int64_t* out, uint64_t out_t,
+                    uint64_t out_s, hipStream_t st) {
+    if (ns == 0 || n_tables == 0) return 0;
+    if (n_tables > 65535u) return -1;
+    hipLaunchKernelGGL(ssim_sum_kernel, dim3(ns, n_tables), dim3(kBlock), 0, st, part, bpr, out, out_t, out_s);
     return launched();
 }
 

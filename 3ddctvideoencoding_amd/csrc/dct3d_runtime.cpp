@@ -166,6 +166,9 @@ struct dct3d_ctx {
     // plane slots, the per-cube RGB errors when the caller keeps none
     DevBuf d_rgb_planes, d_rgb_psse, d_rgb_pbits, d_rgb_slots, d_rgb_cube;
     std::vector<int32_t> rgb_tables;
+    // SSIM probe (dct3d_ssim_frames*): the 4 x 4 blocks' moments of one range of stacks and one channel
+    // (per table the uint64 records, then the source's uint32 records) and the window kernel's partial sums
+    DevBuf d_ssim_blk, d_ssim_part;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -439,7 +442,7 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
                       &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums,
                       &c->d_dist_steps, &c->d_dist_sse, &c->d_vq, &c->d_c420, &c->d_rgb_planes, &c->d_rgb_psse,
-                      &c->d_rgb_pbits, &c->d_rgb_slots, &c->d_rgb_cube})
+                      &c->d_rgb_pbits, &c->d_rgb_slots, &c->d_rgb_cube, &c->d_ssim_blk, &c->d_ssim_part})
         b->release();
     if (c->h_rate) (void)hipHostFree(c->h_rate);
     if (c->vq_host) (void)hipHostFree(c->vq_host);
@@ -1537,10 +1540,125 @@ static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n
     return DCT3D_OK;
 }
 
-// Both probes on frames in host memory: the frames go up in chunks of whole stacks (one staging buffer of 64 MiB
+// The SSIM probe on frames in device memory (the arguments hold: rate_args_ok).  The distortion probe's
+// launches with the block-moment arm, over ranges of stacks whose block records fit kSsimBlockBudget (or one stack
+// at a time); per range and channel the records, then the windows of all tables and their sums.  sse and bits
+// (optional) as probe_dev leaves them.
+constexpr size_t kSsimBlockBudget = DCT3D_SSIM_BLOCK_BUDGET;
+static int ssim_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                    int64_t* ssim, uint64_t* sse, uint64_t* bits, int32_t* d_win) {
+    const int channels = g.px, D = c->bd;
+    const uint64_t cps = g.cps(), n_cubes = cps * (uint64_t)n_stacks;  // per channel
+    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
+    call_begin(c);
+    if (!c->batch) c->last_units = 0;
+    if (n_cubes == 0) return DCT3D_OK;
+    probe_tables(c, tables, n_tables, true);
+    const uint32_t nbx = ((uint32_t)g.w + 3) / 4, nby = ((uint32_t)g.h + 3) / 4;
+    const uint32_t nwx = nbx > 1 ? nbx - 1 : 1, nwy = nby > 1 ? nby - 1 : 1;
+    const uint64_t blk_per_stack = (uint64_t)D * nbx * nby, win_per_stack = (uint64_t)D * nwx * nwy;
+    if (win_per_stack >= (1ull << 32)) return DCT3D_EINVAL;
+    const uint64_t rec_per_stack = blk_per_stack * (8ull * n_tables + 4);  // bytes (dct3d.h)
+    const int rs = (int)std::max<uint64_t>(1, std::min<uint64_t>({kSsimBlockBudget / rec_per_stack, (uint64_t)n_stacks, 65535ull}));
+    const uint64_t blk_stride = blk_per_stack * rs;
+    const uint32_t bpr = (uint32_t)std::min<uint64_t>((win_per_stack + kSsimWinPerBlock - 1) / kSsimWinPerBlock, kSsimMaxBpr);
+    const uint64_t stride = (uint64_t)channels * n_cubes;              // cubes of one table
+    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;  // sums: the SSIM, then the squared errors, then the bits
+    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
+    const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
+    const size_t sum_bytes = (1 + (sse ? 1 : 0) + (bits ? 1 : 0)) * n_runs * sizeof(uint64_t);
+    int rc;
+    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_dist_steps.grow(step_bytes)) || (rc = c->d_rate_sums.grow(sum_bytes)) ||
+        (sse && (rc = c->d_dist_sse.grow((size_t)n_tables * stride * sizeof(uint32_t)))) ||
+        (bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))) ||
+        (rc = c->d_ssim_blk.grow((size_t)rec_per_stack * rs)) ||
+        (rc = c->d_ssim_part.grow((size_t)n_tables * rs * bpr * sizeof(int64_t))) || (rc = probe_grow_pinned(c, sum_bytes)))
+        return rc;
+    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return DCT3D_EDEVICE;
+    uint32_t* const cube_sse = sse ? (uint32_t*)c->d_dist_sse.p : nullptr;
+    uint16_t* const cube_bits = bits ? (uint16_t*)c->d_rate_bits.p : nullptr;
+    uint64_t* const blk_y = (uint64_t*)c->d_ssim_blk.p;
+    uint32_t* const blk_x = (uint32_t*)(blk_y + (size_t)n_tables * blk_stride);
+    int64_t* const d_ssim_sums = (int64_t*)c->d_rate_sums.p;
+    uint64_t* const d_sse_sums = (uint64_t*)c->d_rate_sums.p + n_runs;
+    uint64_t* const d_bit_sums = d_sse_sums + (sse ? n_runs : 0);
+    const Variant v = stream_variant_of(c, g);
+    hipEvent_t* ev = timer_begin(c);
+    rc = DCT3D_OK;
+    for (int s0 = 0; s0 < n_stacks && !rc; s0 += rs) {
+        const int ns = n_stacks - s0 < rs ? n_stacks - s0 : rs;
+        EncodeParams P;
+        fill_encode_params(c, P, d_frames + (size_t)s0 * g.plane() * D, nullptr, g, cps * ns);
+        DecodeParams DP;
+        fill_decode_params(c, DP, nullptr, nullptr, g, cps * ns);
+        SsimParams R = {};
+        R.table_stride = stride;
+        R.inv_coef_t = DP.inv_coef_t;
+        R.dec_G = DP.dec_G;
+        R.dec_E = DP.dec_E;
+        R.dec_l1_max = DP.dec_l1_max;
+        R.blk_x = blk_x;
+        R.blk_stride = blk_stride;
+        R.nbx = nbx;
+        R.nby = nby;
+        const size_t cube_off = (size_t)s0 * channels * cps;  // the range's first cube in a table's block
+        for (int ch = 0; ch < channels && !rc; ch++) {
+            // kRateTables tables per launch (as probe_dev); every launch writes the source's records (the same)
+            for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables) {
+                R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
+                R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
+                R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
+                R.ch = ch;
+                R.cube_bits = cube_bits ? cube_bits + (size_t)t0 * stride + cube_off : nullptr;
+                R.cube_sse = cube_sse ? cube_sse + (size_t)t0 * stride + cube_off : nullptr;
+                R.blk_y = blk_y + (size_t)t0 * blk_stride;
+                if (launch_distortion_ssim(v.D, v.px, v.edge, P, R, c->stream)) rc = DCT3D_EKERNEL;
+                else c->slot_used = true;
+            }
+            SsimWinParams W = {};
+            W.blk_y = blk_y;
+            W.blk_x = blk_x;
+            W.blk_stride = blk_stride;
+            W.win_t = (uint64_t)n_stacks * channels * win_per_stack;
+            W.win_s = (uint64_t)channels * win_per_stack;
+            W.win = d_win ? d_win + ((size_t)s0 * channels + ch) * win_per_stack : nullptr;
+            W.part = (int64_t*)c->d_ssim_part.p;
+            W.w = (uint32_t)g.w;
+            W.h = (uint32_t)g.h;
+            W.nbx = nbx;
+            W.nby = nby;
+            W.nwx = nwx;
+            W.nwy = nwy;
+            W.depth = (uint32_t)D;
+            W.ns = (uint32_t)ns;
+            W.n_tables = (uint32_t)n_tables;
+            W.bpr = bpr;
+            if (!rc && (launch_ssim_window(W, c->stream) ||
+                        launch_ssim_sum(W.part, bpr, W.ns, W.n_tables, d_ssim_sums + ((size_t)s0 * channels + ch),
+                                        (uint64_t)n_stacks * channels, (uint64_t)channels, c->stream)))
+                rc = DCT3D_EKERNEL;
+        }
+    }
+    if (!rc && sse && launch_distortion_sum(cube_sse, (uint32_t)cps, n_runs, d_sse_sums, c->stream)) rc = DCT3D_EKERNEL;
+    if (!rc && bits && launch_rate_sum(cube_bits, (uint32_t)cps, n_runs, d_bit_sums, c->stream)) rc = DCT3D_EKERNEL;
+    timer_end(c, ev);
+    if (!rc && hipMemcpyAsync(c->h_rate, c->d_rate_sums.p, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
+    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
+    if (rc) return rc;
+    memcpy(ssim, c->h_rate, n_runs * sizeof(int64_t));
+    if (sse) memcpy(sse, c->h_rate + n_runs, n_runs * sizeof(uint64_t));
+    if (bits) memcpy(bits, c->h_rate + (d_bit_sums - (uint64_t*)c->d_rate_sums.p), n_runs * sizeof(uint64_t));
+    return DCT3D_OK;
+}
+
+// The probes on frames in host memory: the frames go up in chunks of whole stacks (one staging buffer of 64 MiB
 // at most, or one stack), each chunk's sums land at its stacks' places; the chunks' statistics add up (batch).
+// ssim: the SSIM probe (sse and bits optional); else as probe_dev.
 static int probe_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                      uint64_t* sse, uint64_t* bits) {
+                      uint64_t* sse, uint64_t* bits, int64_t* ssim = nullptr) {
     const int channels = g.px;
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     const size_t stack_bytes = (size_t)g.plane() * c->bd;  // the unpadded frames of one stack
@@ -1548,7 +1666,7 @@ static int probe_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_
     const int per = stack_bytes ? (int)std::max<size_t>(1, std::min<size_t>(kChunkBytes / stack_bytes, (size_t)(n_stacks > 0 ? n_stacks : 1))) : 1;
     int rc;
     if ((rc = c->h_in.grow(stack_bytes * per ? stack_bytes * per : 1))) return rc;
-    std::vector<uint64_t> part((size_t)2 * n_tables * per * channels);
+    std::vector<uint64_t> part((size_t)3 * n_tables * per * channels);
     c->last_units = 0;  // (no stack: no chunk)
     batch_begin(c);
     rc = DCT3D_OK;
@@ -1561,9 +1679,12 @@ static int probe_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_
         }
         uint64_t* const ps = sse ? part.data() : nullptr;
         uint64_t* const pb = bits ? part.data() + (sse ? (size_t)n_tables * run : 0) : nullptr;
-        rc = probe_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, ps, pb, nullptr, nullptr);
+        int64_t* const pm = (int64_t*)part.data() + (size_t)2 * n_tables * per * channels;
+        rc = ssim ? ssim_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, pm, ps, pb, nullptr)
+                  : probe_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, ps, pb, nullptr, nullptr);
         for (int t = 0; t < n_tables && !rc; t++) {
             const size_t dst = ((size_t)t * n_stacks + s0) * channels;
+            if (ssim) memcpy(ssim + dst, pm + (size_t)t * run, run * sizeof(int64_t));
             if (sse) memcpy(sse + dst, ps + (size_t)t * run, run * sizeof(uint64_t));
             if (bits) memcpy(bits + dst, pb + (size_t)t * run, run * sizeof(uint64_t));
         }
@@ -1610,6 +1731,34 @@ int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, i
     if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
     if (colour_refused(c, channels)) return DCT3D_EINVAL;
     return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits);
+}
+
+// ---- SSIM probe: the exact 8 x 8 / stride 4 windowed SSIM of encode + decode under several tables, from the
+//      distortion probe's transform and decode tile per cube (dct3d.h states the definition) ----
+int dct3d_ssim_windows(int w, int h, int* nwx, int* nwy) {
+    if (w < 1 || h < 1 || !nwx || !nwy) return DCT3D_EINVAL;
+    const int nbx = w / 4 + (w % 4 != 0), nby = h / 4 + (h % 4 != 0);
+    *nwx = nbx > 1 ? nbx - 1 : 1;
+    *nwy = nby > 1 ? nby - 1 : 1;
+    return DCT3D_OK;
+}
+
+int dct3d_ssim_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
+                          const int32_t* tables, int n_tables, int64_t* ssim, uint64_t* sse, uint64_t* bits, int32_t* d_window_ssim) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (colour_refused(c, channels) || c420_refused(c, channels)) return DCT3D_EINVAL;
+    return ssim_dev(c, d_frames, g, n_stacks, tables, n_tables, ssim, sse, bits, d_window_ssim);
+}
+
+int dct3d_ssim_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
+                      const int32_t* tables, int n_tables, int64_t* ssim, uint64_t* sse, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (colour_refused(c, channels) || c420_refused(c, channels)) return DCT3D_EINVAL;
+    return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits, ssim);
 }
 
 // ---- RGB-domain distortion probe: the exact squared error, in the RGB pixels, of the stream encode + decode

@@ -157,22 +157,35 @@ static int parse_positive(const char *text, const char *prefix, double *value) {
 static char g_rate_text[64]; /* codec_set_rate's text; "": none */
 static char g_psnr_text[64]; /* codec_set_psnr's text; "": none */
 static char g_psnr_rgb_text[64]; /* codec_set_psnr_rgb's text; "": none */
-enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_PSNR_RGB, SEL_N };
+static char g_ssim_text[64]; /* codec_set_ssim's text; "": none */
+enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_PSNR_RGB, SEL_SSIM, SEL_N };
 static const struct {
-    const char *prefix, *env, *noun, *unit;
+    const char *prefix, *env, *noun, *unit, *range;
     char *text;
     size_t cap;
 } kSel[SEL_N] = {
-    {"q=", "DCT3D_CODEC_QUANT", "quantiser", NULL, g_quant_text, sizeof(g_quant_text)},
-    {"rate=", "DCT3D_CODEC_RATE", "rate target", "bits per pixel", g_rate_text, sizeof(g_rate_text)},
-    {"psnr=", "DCT3D_CODEC_PSNR", "PSNR target", "dB", g_psnr_text, sizeof(g_psnr_text)},
-    {"psnr_rgb=", "DCT3D_CODEC_PSNR_RGB", "RGB PSNR target", "dB", g_psnr_rgb_text, sizeof(g_psnr_rgb_text)},
+    {"q=", "DCT3D_CODEC_QUANT", "quantiser", NULL, NULL, g_quant_text, sizeof(g_quant_text)},
+    {"rate=", "DCT3D_CODEC_RATE", "rate target", "bits per pixel", "a positive number", g_rate_text, sizeof(g_rate_text)},
+    {"psnr=", "DCT3D_CODEC_PSNR", "PSNR target", "dB", "a positive number", g_psnr_text, sizeof(g_psnr_text)},
+    {"psnr_rgb=", "DCT3D_CODEC_PSNR_RGB", "RGB PSNR target", "dB", "a positive number", g_psnr_rgb_text, sizeof(g_psnr_rgb_text)},
+    {"ssim=", "DCT3D_CODEC_SSIM", "SSIM target", "target", "a decimal in (0, 1]", g_ssim_text, sizeof(g_ssim_text)},
 };
 static const char *sel_text(int i) { return kSel[i].text[0] ? kSel[i].text : getenv(kSel[i].env); }
 
 int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, kSel[SEL_RATE].prefix, bpp); }
 int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR].prefix, db); }
 int codec_parse_psnr_rgb(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR_RGB].prefix, db); }
+/* a plain decimal in (0, 1] */
+int codec_parse_ssim(const char *text, double *target) {
+    double v;
+    if (!target || parse_positive(text, kSel[SEL_SSIM].prefix, &v) || v > 1.0) return 1;
+    *target = v;
+    return 0;
+}
+/* target i's text -> its value: 1 when it does not parse */
+static int parse_target(int i, const char *text, double *value) {
+    return i == SEL_SSIM ? codec_parse_ssim(text, value) : parse_positive(text, kSel[i].prefix, value);
+}
 
 static int set_target(int i, const char *text) {
     if (text && strlen(text) >= kSel[i].cap) return 1;
@@ -184,6 +197,7 @@ static int set_target(int i, const char *text) {
 int codec_set_rate(const char *text) { return set_target(SEL_RATE, text); }
 int codec_set_psnr(const char *text) { return set_target(SEL_PSNR, text); }
 int codec_set_psnr_rgb(const char *text) { return set_target(SEL_PSNR_RGB, text); }
+int codec_set_ssim(const char *text) { return set_target(SEL_SSIM, text); }
 
 /* Target i of a call: codec_set_*'s text, else the environment variable.  *set = 0: none given.  1 after printing
  * when the text does not parse or a quantiser or an earlier target is given too. */
@@ -198,9 +212,9 @@ static int call_target(int i, double *value, int *set) {
             return 1;
         }
     }
-    if (parse_positive(text, kSel[i].prefix, value)) {
-        printf("Invalid %.*s target '%s': %s<%s>, a positive number\n", (int)strlen(kSel[i].prefix) - 1, kSel[i].prefix,
-               text, kSel[i].prefix, kSel[i].unit);
+    if (parse_target(i, text, value)) {
+        printf("Invalid %.*s target '%s': %s<%s>, %s\n", (int)strlen(kSel[i].prefix) - 1, kSel[i].prefix, text,
+               kSel[i].prefix, kSel[i].unit, kSel[i].range);
         return 1;
     }
     return 0;
@@ -225,11 +239,15 @@ static int reject_targets(const char *what) {
  * bits fit bpp * width * height * frames (unpadded pixels, all channels together, Exp-Golomb bits before the
  * deflate), or the largest when none fits.  Prints "rate: q=<n> bits=<total>", sets the context's quantiser to
  * q=<n> and rewinds the input.  1 after printing on an error.
- * by_psnr: the first pass of an encode with a PSNR target instead: the distortion probe (dct3d_distortion_frames)
+ * METRIC_PSNR: the first pass of an encode with a PSNR target instead: the distortion probe (dct3d_distortion_frames)
  * per batch over the same ladder, the squared errors and the bits summed over the file and the channels; the PSNR
  * of a quality is taken over all unpadded samples of all channels together (the zero-filled frames of a short last
  * stack count as frames); the pick is the largest quality whose PSNR is >= target, or the smallest when none
- * reaches it.  Prints "psnr: q=<n> psnr=<dB> bits=<total>". */
+ * reaches it.  Prints "psnr: q=<n> psnr=<dB> bits=<total>".
+ * METRIC_SSIM: an SSIM target (ssim=<target>): the SSIM probe (dct3d_ssim_frames) in the distortion probe's place, its
+ * sums added over the file and the channels, the mean over all windows (dct3d_ssim_windows per frame and channel; the
+ * zero-filled frames count); psnr='s rule on the means.  Prints "ssim: q=<n> ssim=<6 decimals> bits=<total>". */
+enum { METRIC_RATE, METRIC_PSNR, METRIC_SSIM }; /* what the first pass measures and picks by */
 static const int kRateLadder[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64};
 #define RATE_LADDER_N ((int)(sizeof(kRateLadder) / sizeof(kRateLadder[0])))
 static double psnr_of(uint64_t sse, double n_samples) {
@@ -256,6 +274,14 @@ static int pick_by_psnr(const uint64_t *err, double n_samples, double target_db)
     int pick = 0; /* none reaches the target: the smallest quality (the ladder ascends) */
     for (int i = 0; i < RATE_LADDER_N; i++)
         if (psnr_of(err[i], n_samples) >= target_db) pick = i; /* the largest that reaches it, whatever the order */
+    return pick;
+}
+/* the SSIM probe's sums: the mean over n_windows windows, and psnr='s rule on it */
+static double ssim_of(int64_t sum, double n_windows) { return (double)sum / (16777216.0 * n_windows); }
+static int pick_by_ssim(const int64_t *sum, double n_windows, double target) {
+    int pick = 0;
+    for (int i = 0; i < RATE_LADDER_N; i++)
+        if (ssim_of(sum[i], n_windows) >= target) pick = i;
     return pick;
 }
 
@@ -470,7 +496,7 @@ int codec_set_colour(const char *text) {
 /* The colour mode of a call on `channels` channels: codec_set_colour's text, else DCT3D_CODEC_YCC ("1", "0" or the
  * text).  *ycc = 1: the Y, Cb, Cr planes.  1 after printing when the text is no "ycc=0|1", or the mode is on for a
  * call that has no colour stage: grey (what names it), a PSNR target, the host Exp-Golomb path. */
-static int call_colour(const char *what, int channels, int psnr_set, int *ycc) {
+static int call_colour(const char *what, int channels, int target_sel, int *ycc) { /* (target_sel: 0 | SEL_PSNR | SEL_SSIM) */
     const char *text = g_colour_text[0] ? g_colour_text : getenv("DCT3D_CODEC_YCC");
     *ycc = 0;
     if (!text || !text[0]) return 0;
@@ -484,7 +510,11 @@ static int call_colour(const char *what, int channels, int psnr_set, int *ycc) {
         printf("ycc= applies to encode_rgb and decode_rgb on one device (%s)\n", what);
         return 1;
     }
-    if (psnr_set) {
+    if (target_sel == SEL_SSIM) {
+        printf("ycc=1 and ssim= exclude each other: the SSIM probe measures the R, G, B planes (luma SSIM is not built)\n");
+        return 1;
+    }
+    if (target_sel == SEL_PSNR) {
         printf("ycc=1 and psnr= exclude each other: the distortion probe would measure the Y, Cb, Cr planes, not the "
                "RGB samples\n");
         return 1;
@@ -580,17 +610,24 @@ static int write_qmap(const char *path, int n_stacks, const uint8_t *index) {
  * channel 0 at rung i and channels 1 and 2 at rung j = min(i + cq, last), costs the three channels' bits under those
  * rungs, and the rate rule picks among the candidates; stack_pick[s] = {i, j, j}.  Prints "qmap3: ...". */
 static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
-                           int channels, double target, int by_psnr, uint8_t *stack_pick, int cq) {
+                           int channels, double target, int metric, uint8_t *stack_pick, int cq) {
     const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
     const size_t stack_bytes = (size_t)channels * width * height * depth;
     int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
     uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N], map_bits = 0;
     ladder_tables(depth, tabs);
-    for (int i = 0; i < RATE_LADDER_N; i++) tot[i] = err[i] = 0;
+    int64_t sim[RATE_LADDER_N]; /* METRIC_SSIM: the sums of v over the file */
+    int nwx = 1, nwy = 1;
+    if (metric == METRIC_SSIM) (void)dct3d_ssim_windows(width, height, &nwx, &nwy);
+    const double n_win = (double)nwx * (double)nwy; /* windows of one frame and channel */
+    for (int i = 0; i < RATE_LADDER_N; i++) tot[i] = err[i] = 0, sim[i] = 0;
     const size_t n_sums = (size_t)RATE_LADDER_N * batch * channels;
     uint64_t *bits = (uint64_t *)malloc(sizeof(uint64_t) * n_sums * 2), *sse = bits ? bits + n_sums : NULL;
-    if (!bits) {
+    int64_t *ssim = (int64_t *)malloc(sizeof(int64_t) * (metric == METRIC_SSIM ? n_sums : 1));
+    if (!bits || !ssim) {
         printf("Out of memory\n");
+        free(bits);
+        free(ssim);
         return 1;
     }
     int status = 0;
@@ -600,25 +637,30 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
         const size_t want = stack_bytes * nb;
         while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
         if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as the encode's */
-        const int rc = by_psnr ? dct3d_distortion_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, sse, bits)
-                               : dct3d_rate_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, bits);
+        const int rc = metric == METRIC_SSIM ? dct3d_ssim_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, ssim, NULL, bits)
+                       : metric == METRIC_PSNR ? dct3d_distortion_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, sse, bits)
+                                               : dct3d_rate_frames(ctx, fr, width, height, channels, nb, tabs, RATE_LADDER_N, bits);
         if (rc) {
-            printf("Error running the %s probe: %s\n", by_psnr ? "distortion" : "rate", dct3d_strerror(rc));
+            printf("Error running the %s probe: %s\n", metric == METRIC_SSIM ? "SSIM" : metric == METRIC_PSNR ? "distortion" : "rate",
+                   dct3d_strerror(rc));
             status = 1;
             break;
         }
         for (int i = 0; i < RATE_LADDER_N; i++)
             for (int k = 0; k < nb * channels; k++) {
                 tot[i] += bits[(size_t)i * nb * channels + k];
-                if (by_psnr) err[i] += sse[(size_t)i * nb * channels + k];
+                if (metric == METRIC_PSNR) err[i] += sse[(size_t)i * nb * channels + k];
+                if (metric == METRIC_SSIM) sim[i] += ssim[(size_t)i * nb * channels + k];
             }
         for (int s = 0; stack_pick && s < nb; s++) { /* the same rules on this stack's sums */
             uint64_t sb[RATE_LADDER_N], se[RATE_LADDER_N];
+            int64_t sm[RATE_LADDER_N];
             for (int i = 0; i < RATE_LADDER_N; i++) {
-                sb[i] = se[i] = 0;
+                sb[i] = se[i] = 0, sm[i] = 0;
                 for (int ch = 0; ch < channels; ch++) {
                     sb[i] += bits[((size_t)i * nb + s) * channels + ch];
-                    if (by_psnr) se[i] += sse[((size_t)i * nb + s) * channels + ch];
+                    if (metric == METRIC_PSNR) se[i] += sse[((size_t)i * nb + s) * channels + ch];
+                    if (metric == METRIC_SSIM) sm[i] += ssim[((size_t)i * nb + s) * channels + ch];
                 }
             }
             const double px = (double)width * (double)height * (double)depth;
@@ -633,18 +675,25 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
                 map_bits += sb[p];
                 continue;
             }
-            const int p = by_psnr ? pick_by_psnr(se, px * (double)channels, target) : pick_by_rate(sb, target * px);
+            const int p = metric == METRIC_SSIM ? pick_by_ssim(sm, n_win * (double)depth * (double)channels, target)
+                          : metric == METRIC_PSNR ? pick_by_psnr(se, px * (double)channels, target)
+                                                  : pick_by_rate(sb, target * px);
             stack_pick[s0 + s] = (uint8_t)p;
             map_bits += sb[p];
         }
     }
     free(bits);
+    free(ssim);
     if (status) return 1;
     if (stack_pick) {
         printf("%s: stacks=%d bits=%llu\n", cq >= 0 ? "qmap3" : "qmap", n_stacks, (unsigned long long)map_bits);
     } else {
         int pick;
-        if (by_psnr) {
+        if (metric == METRIC_SSIM) {
+            const double n_windows = n_win * (double)channels * (double)n_stacks * (double)depth;
+            pick = pick_by_ssim(sim, n_windows, target);
+            printf("ssim: q=%d ssim=%.6f bits=%llu\n", kRateLadder[pick], ssim_of(sim[pick], n_windows), (unsigned long long)tot[pick]);
+        } else if (metric == METRIC_PSNR) {
             const double n_samples = (double)width * (double)height * (double)channels * (double)n_stacks * (double)depth;
             pick = pick_by_psnr(err, n_samples, target);
             printf("psnr: q=%d psnr=%.3f bits=%llu\n", kRateLadder[pick], psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
@@ -1201,14 +1250,18 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         printf("psnr_rgb= needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
         return 1;
     }
+    /* the SSIM target: psnr='s place and passes, the SSIM probe's numbers */
+    double ssim_target = 0.0;
+    int ssim_set = 0;
+    if (call_target(SEL_SSIM, &ssim_target, &ssim_set)) return 1;
     int ycc;
-    if (call_colour("encode", channels, psnr_set, &ycc)) return 1;
+    if (call_colour("encode", channels, ssim_set ? SEL_SSIM : psnr_set ? SEL_PSNR : 0, &ycc)) return 1;
     int c420;
     if (call_chroma("encode", channels, ycc, &c420)) return 1;
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
     const char *qmap_path = NULL, *qmap3_path = NULL;
     int cq = 0;
-    if (call_qmap3("encode", channels, rate_set || prgb_set, psnr_set, ycc, &qmap3_path, &cq)) return 1;
+    if (call_qmap3("encode", channels, rate_set || prgb_set, psnr_set || ssim_set, ycc, &qmap3_path, &cq)) return 1;
     if (call_qmap(&qmap_path)) return 1;
     const int qw = qmap3_path ? 3 : 1; /* the map's entries per stack */
     if (qmap3_path) qmap_path = qmap3_path;
@@ -1221,7 +1274,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             printf("Out of memory\n");
             return 1;
         }
-        if (!rate_set && !psnr_set && !prgb_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
+        if (!rate_set && !psnr_set && !ssim_set && !prgb_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
             free(qmap);
             return 1;
         }
@@ -1285,12 +1338,13 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         }
     }
     /* a rate target: the first pass picks the quality, the second encodes as q=<n> does */
-    if (!status && (rate_set || psnr_set))
+    if (!status && (rate_set || psnr_set || ssim_set))
         STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
-                                              psnr_set ? psnr_db : rate_bpp, psnr_set, qmap, qw == 3 ? cq : -1));
+                                              ssim_set ? ssim_target : psnr_set ? psnr_db : rate_bpp,
+                                              ssim_set ? METRIC_SSIM : psnr_set ? METRIC_PSNR : METRIC_RATE, qmap, qw == 3 ? cq : -1));
     if (!status && prgb_set)
         STAGE(t_dev, status = psnr_rgb_first_pass(ctx, in, fr, width, height, frames, depth, batch, prgb_db, qmap, qw, qw == 3 ? cq : 0));
-    if (!status && qmap && (rate_set || psnr_set || prgb_set))
+    if (!status && qmap && (rate_set || psnr_set || ssim_set || prgb_set))
         status = qw == 3 ? write_qmap3(qmap_path, n_stacks, qmap) : write_qmap(qmap_path, n_stacks, qmap);
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;

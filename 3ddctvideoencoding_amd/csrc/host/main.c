@@ -24,6 +24,9 @@
  *   encode_rgb takes psnr_rgb=<dB> (codec.h, codec_parse_psnr_rgb) in the quantiser's place, in every colour mode: the
  *   first pass measures the squared error in the RGB pixels (the RGB-domain distortion probe) and prints
  *   "psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB> bits=<total>"; with qmap= or qmap3= [cq=<k>] it writes the map
+ *   the single-device encodes take ssim=<target in (0, 1]> (codec.h, codec_parse_ssim) in the quantiser's place: the
+ *   first pass picks the largest q whose mean SSIM (the SSIM probe) reaches the target and prints
+ *   "ssim: q=<n> ssim=<mean> bits=<total>"; with qmap= it writes the map; not with ycc=1 or chroma=420
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -91,6 +94,13 @@ static void usage(void) {
            "are 'plane 0 at rung i, planes 1 and 2 at rung min(i + k, 15)' and the three-column map is written.  "
            "psnr_rgb= on a decode, on a grey command, together with q=, rate= or psnr=, or with several devices is an "
            "error\n");
+    printf("encode and encode_rgb on one device take ssim=<target>, a decimal in (0, 1], in the quantiser's place: the "
+           "first pass measures, per rung of the ladder, the exact SSIM of encode + decode (8 x 8 windows at a stride of "
+           "4 over every frame of every plane), takes each q's mean over all windows, picks the largest q whose mean is "
+           ">= <target> (1 when none reaches it) and prints 'ssim: q=<n> ssim=<mean> bits=<total>'; the second pass "
+           "encodes as q=<n>.  With qmap=<path> the rule is applied per stack and the map is WRITTEN.  ssim= on a "
+           "decode, together with q=, rate=, psnr= or psnr_rgb=, with ycc=1 or chroma=420, or with several devices is an "
+           "error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -144,7 +154,7 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0, have_prgb = 0;
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0, have_prgb = 0, have_ssim = 0;
     for (int a = 9; a < argc && a < 15 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
@@ -166,6 +176,20 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             have_prgb = a;
+            continue;
+        }
+        if (!strncmp(argv[a], "ssim=", 5)) { /* the SSIM target: refused here before any file is made */
+            if (have_ssim) break;
+            if (codec_parse_ssim(argv[a], &v)) {
+                printf("Invalid ssim target '%s': ssim=<target>, a decimal in (0, 1]\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (argv[1][0] != 'e' || n_dev > 1) {
+                printf("ssim= applies to encode and encode_rgb on one device: decode with the q=<n> that the encode printed\n");
+                return 1;
+            }
+            have_ssim = a;
             continue;
         }
         if (a >= 10 && (is_qmap3 ? have_qmap3 : is_cq ? have_cq : 0)) break;
@@ -239,6 +263,15 @@ int main(int argc, char *argv[]) {
         printf("%s and psnr_rgb= exclude each other\n", have_quant ? "q=" : have_rate ? "rate=" : "psnr=");
         return 1;
     }
+    if (have_ssim && (have_quant || have_rate || have_psnr || have_prgb)) {
+        printf("%s and ssim= exclude each other\n", have_quant ? "q=" : have_rate ? "rate=" : have_psnr ? "psnr=" : "psnr_rgb=");
+        return 1;
+    }
+    if (have_ssim && ((have_ycc && argv[have_ycc][4] == '1') || (have_chroma && argv[have_chroma][9] == '0'))) {
+        printf("%s and ssim= exclude each other: the SSIM probe measures the R, G, B planes (luma SSIM is not built)\n",
+               have_ycc && argv[have_ycc][4] == '1' ? "ycc=1" : "chroma=420");
+        return 1;
+    }
     if (have_ycc && argv[have_ycc][4] == '1' && have_psnr) {
         printf("ycc=1 and psnr= exclude each other: the distortion probe would measure the Y, Cb, Cr planes, not the RGB "
                "samples\n");
@@ -257,7 +290,7 @@ int main(int argc, char *argv[]) {
         (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap])) ||
         (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma])) ||
         (have_qmap3 && codec_set_qmap3(argv[have_qmap3])) || (have_cq && codec_set_cq(argv[have_cq])) ||
-        (have_prgb && codec_set_psnr_rgb(argv[have_prgb]))) {
+        (have_prgb && codec_set_psnr_rgb(argv[have_prgb])) || (have_ssim && codec_set_ssim(argv[have_ssim]))) {
         printf("Argument too long\n");
         return 1;
     }

@@ -137,6 +137,22 @@ int codec_set_psnr(const char *text);
 int codec_parse_psnr_rgb(const char *text, double *db);
 int codec_set_psnr_rgb(const char *text);
 
+/* An SSIM target in place of a quantiser (the single-device encodes, grey or R, G, B planes): "ssim=<target>", a plain
+ * decimal in (0, 1].  It takes psnr='s two passes with the SSIM probe (dct3d_ssim_frames; dct3d.h states the SSIM:
+ * 8 x 8 windows at a stride of 4, exact) in the distortion probe's place: the sums of the ladder's q are added over
+ * the file and the channels, a q's mean SSIM is sum / (2^24 * windows) over all windows (dct3d_ssim_windows per frame
+ * and channel; the zero-filled frames of a short last stack count as frames), the pick is the largest q whose mean is
+ * >= the target (the smallest q when none reaches it).  It prints one line "ssim: q=<n> ssim=<mean, 6 decimals>
+ * bits=<total>"; the second pass encodes as q=<n> does, byte for byte.  With qmap=<path> the rule is applied per stack
+ * (the mean over the stack's windows of all channels) and the map is written, as for psnr= with qmap=.
+ * codec_parse_ssim: 0 and *target for "ssim=<decimal in (0, 1]>"; 1 (*target untouched) on anything else.
+ * codec_set_ssim: the target of every later encode call of this process; NULL or "": none.  It overrides the
+ *   environment variable DCT3D_CODEC_SSIM.  It excludes a quantiser, a rate target and both PSNR targets as those
+ *   exclude each other.  A call refuses it, before any file is made, on a decode, on several devices, with ycc=1 and
+ *   with chroma=420 (luma SSIM in the YCbCr modes is not built). */
+int codec_parse_ssim(const char *text, double *target);
+int codec_set_ssim(const char *text);
+
 /* A quality per stack (the single-device calls: encode, encode_ex, encode_rgb_ex and their decodes): "qmap=<path>"
  * names a text file with one line per stack, in stack order, each a quality of the ladder above; stack s of every
  * channel is coded as q=<that quality> codes it (dct3d_encode_eg_frames_vq / dct3d_decode_eg_frames_vq, the ladder

@@ -570,6 +570,50 @@ int dct3d_distortion_rgb_frames(dct3d_ctx *ctx, const uint8_t *frames, int width
                                 uint64_t *sse, uint64_t *plane_sse, uint64_t *bits);
 
 /* ---------------------------------------------------------------------------------------------
+ * SSIM probe (additive to ABI 9; detect by symbol): the exact windowed SSIM of encode + decode
+ * under several quantiser tables, from the distortion probe's one row load and one forward transform per cube.
+ *
+ * Definition.  Take one plane of one frame, w x h; x is the source, y what
+ * dct3d_decode_frames(dct3d_encode_frames(x)) returns under the table.  Only samples inside the frame count
+ * (padded columns and rows are coded, not counted, as in dct3d_distortion_frames).
+ *   Blocks.  The 4 x 4 grid has nbx = ceil(w / 4) columns and nby = ceil(h / 4) rows; block (bx, by) has the
+ *   integer moments n (1 .. 16), Sx, Sy, Sxx, Syy, Sxy over its samples inside the frame.
+ *   Windows.  nwx = max(nbx - 1, 1) by nwy = max(nby - 1, 1) windows (dct3d_ssim_windows); window (i, j) sums the
+ *   moments of blocks i .. min(i + 1, nbx - 1) by j .. min(j + 1, nby - 1): 8 x 8 windows at a stride of 4, with
+ *   fewer than 64 samples at the right and bottom edges and in frames under 5 samples wide or high.
+ *   Value.  In int64, with c1 = 6.5025 and c2 = 58.5225 scaled by 10^4:
+ *     A = 20000 Sx Sy + 65025 n^2                          B = 20000 (n Sxy - Sx Sy) + 585225 n^2
+ *     C = 10000 (Sx^2 + Sy^2) + 65025 n^2                  D = 10000 (n Sxx - Sx^2 + n Syy - Sy^2) + 585225 n^2
+ *   (every term below 2^43 in magnitude; C, D > 0).  The window's SSIM in fp64 is s = fl(fl(A B) / fl(C D)): two
+ *   IEEE multiplications and one IEEE division of exactly converted integers, no addition, nothing to contract.
+ *   |s| <= 1, and s == 1 for x == y.  The window's number is v = floor(s 2^24), an int32 in [-2^24, 2^24].
+ *   Result.  ssim[t][s][ch] is the int64 sum of v over the windows of the D frames of stack s, plane ch, under
+ *   tables[t]; the mean SSIM is sum / (2^24 D nwx nwy).  Exact; there is no estimate mode.
+ *
+ *   frames, width, height, channels, n_stacks, tables, n_tables   as dct3d_distortion_frames*.
+ *   ssim      host, int64 [n_tables][n_stacks][channels], required.
+ *   sse, bits host, the same shape, or NULL: exactly dct3d_distortion_frames' numbers for the same arguments.
+ *   d_window_ssim   optional device memory, int32 [n_tables][n_stacks][channels][D][nwy][nwx]: the v of every window.
+ * The call writes no stream, neither reads (tables != NULL) nor changes the context's quantiser, honours
+ * DCT3D_OPT_DEC_MARGIN as dct3d_decode_frames does, and is synchronous on return; the host-pointer call moves the
+ * frames in chunks of whole stacks, as dct3d_rate_frames does.  The blocks' moments live in a buffer the context
+ * owns: per stack and channel D nbx nby (8 n_tables + 4) bytes, DCT3D_SSIM_BLOCK_BUDGET bytes at most (or one
+ * stack's); the call walks the stacks in ranges and the channels reuse the buffer.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_distortion_frames with ssim in the place of sse; with channels == 3,
+ * DCT3D_OPT_COLOUR other than planes or DCT3D_CHROMA_420 set on the context (luma SSIM in the YCbCr modes is
+ * not built).  dct3d_ssim_windows: DCT3D_EINVAL for w < 1, h < 1 or a NULL result.
+ * Statistics: as dct3d_distortion_frames counts them.
+ * ------------------------------------------------------------------------------------------- */
+#define DCT3D_SSIM_BLOCK_BUDGET (16u << 20)
+int dct3d_ssim_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int channels,
+                          int n_stacks, const int32_t *tables, int n_tables,
+                          int64_t *ssim, uint64_t *sse, uint64_t *bits, int32_t *d_window_ssim);
+int dct3d_ssim_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int channels,
+                      int n_stacks, const int32_t *tables, int n_tables,
+                      int64_t *ssim, uint64_t *sse, uint64_t *bits);
+int dct3d_ssim_windows(int w, int h, int *nwx, int *nwy);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-stack quantiser tables in the fused stream calls (additive to ABI 9; detect by symbol).
  * The four dct3d_*_eg_frames* calls with three more host arguments, copied before the call returns:
  *   tables       [n_tables][bw + bh + bd - 2] steps, each in [1, 255]: a palette of 1 <= n_tables <=
