@@ -70,6 +70,7 @@ ABI_SYMBOLS = (
     "dct3d_decode_eg_frames_vqc", "dct3d_decode_eg_frames_vqc_dev",
     "dct3d_distortion_rgb_frames", "dct3d_distortion_rgb_frames_dev",
     "dct3d_ssim_frames", "dct3d_ssim_frames_dev", "dct3d_ssim_windows",
+    "dct3d_ssim_rgb_frames", "dct3d_ssim_rgb_frames_dev",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -180,6 +181,8 @@ def lib() -> C.CDLL:
         L.dct3d_ssim_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
         L.dct3d_ssim_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
         L.dct3d_ssim_windows.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        L.dct3d_ssim_rgb_frames_dev.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        L.dct3d_ssim_rgb_frames.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -539,6 +542,28 @@ def pick_stack_channel_qualities_psnr(sse, qualities, n_samples_per_stack, targe
     res = []
     for s in range(sse.shape[1]):
         q = pick_quality_psnr({qualities[i]: int(sse[i, s]) for i in range(T)}, n_samples_per_stack, target_db)
+        res.append((q, qualities[j[index[q]]], qualities[j[index[q]]]))
+    return res
+
+
+def pick_stack_channel_qualities_ssim(ssim, qualities, n_windows_per_stack, target, chroma_rungs=0) -> list:
+    """One (q0, q1, q2) per stack from the RGB and luma SSIM probe: ssim [T, n_stacks, 3] as ssim_rgb_frames returns
+    it for the T candidates (qualities[i], qualities[j], qualities[j]), j = min(i + chroma_rungs, T - 1), in that order.
+    Stack s gets pick_quality_ssim's choice on its sums added over R, G and B, over n_windows_per_stack windows (the
+    three planes' windows of one stack): the largest qualities[i] whose mean SSIM is >= target, else the smallest.
+    Mirrors pick_stack_channel_qualities_psnr; nothing assumed monotone."""
+    ssim = np.asarray(ssim)
+    qualities = [int(q) for q in qualities]
+    T = len(qualities)
+    if ssim.ndim != 3 or ssim.shape[0] != T or ssim.shape[2] != 3:
+        raise ValueError("ssim must be [len(qualities), n_stacks, 3]")
+    if int(chroma_rungs) != chroma_rungs or chroma_rungs < 0:
+        raise ValueError("chroma_rungs must be an integer >= 0")
+    j = [min(i + int(chroma_rungs), T - 1) for i in range(T)]
+    index = {q: i for i, q in enumerate(qualities)}
+    res = []
+    for s in range(ssim.shape[1]):
+        q = pick_quality_ssim({qualities[i]: sum(int(v) for v in ssim[i, s, :]) for i in range(T)}, n_windows_per_stack, target)
         res.append((q, qualities[j[index[q]]], qualities[j[index[q]]]))
     return res
 
@@ -1270,6 +1295,55 @@ class Context:
                                                      None if bits is None else _ptr(bits),
                                                      None if d_cube_sse is None else _tptr(d_cube_sse)), what)
         return self._rgb_result(sse, plane_sse, bits, want_planes, want_bits)
+
+    # ---- RGB and luma SSIM probe: the SSIM probe's sums on the RGB bytes (and the luma) under table triples ----
+    @staticmethod
+    def _ssim_rgb_result(ssim, ssim_y, sse, bits):
+        rest = tuple(a for a in (ssim_y, sse, bits) if a is not None)
+        return (ssim,) + rest if rest else ssim
+
+    def ssim_rgb_frames(self, frames: np.ndarray, tables=None, candidates=None, want_luma: bool = False,
+                        want_sse: bool = False, want_bits: bool = False):
+        """Packed RGB24 frames [n, H, W, 3] -> int64 [n_cand, n_stacks, 3]: the sum of v (ssim_windows_ref) over the
+        windows of the D frames of stack s between plane k (R, G, B) of x and of
+        y = decode_eg_frames_vqc(encode_eg_frames_vqc(x)) with every row of the map candidates[c], as
+        distortion_rgb_frames takes them, in the context's colour and chroma mode.  want_luma (YCbCr modes): also int64
+        [n_cand, n_stacks], the sums between the luma of rgb_to_ycbcr(x) and the decoded Y plane; want_sse: also
+        distortion_rgb_frames' sse; want_bits: also its bits.  Returns ssim, or the tuple (ssim[, ssim_y][, sse][, bits])."""
+        what = "dct3d_ssim_rgb_frames"
+        frames = np.ascontiguousarray(frames, np.uint8)
+        channels, n_stacks, H, W = self._frames_shape(frames, self.bd)
+        if channels != 3:
+            raise Dct3dError(DCT3D_EINVAL, what)
+        tb, T = self._rate_tables(tables)
+        cd, n = self._rgb_candidates(candidates, T, what)
+        ssim = np.zeros((n, n_stacks, 3), np.int64)
+        ssim_y = np.zeros((n, n_stacks), np.int64) if want_luma else None
+        sse = np.zeros((n, n_stacks), np.uint64) if want_sse else None
+        bits = np.zeros((T, n_stacks, 3), np.uint64) if want_bits else None
+        _check(lib().dct3d_ssim_rgb_frames(self._h, _ptr(frames), W, H, n_stacks, None if tb is None else _ptr(tb), T,
+                                           None if cd is None else _ptr(cd), n, _ptr(ssim),
+                                           None if ssim_y is None else _ptr(ssim_y), None if sse is None else _ptr(sse),
+                                           None if bits is None else _ptr(bits)), what)
+        return self._ssim_rgb_result(ssim, ssim_y, sse, bits)
+
+    def ssim_rgb_frames_dev(self, d_frames, width: int, height: int, n_stacks: int, tables=None, candidates=None,
+                            d_window_ssim=None, want_luma: bool = False, want_sse: bool = False, want_bits: bool = False):
+        """Device path of ssim_rgb_frames: packed RGB24 frames on the device; d_window_ssim (optional; a tensor or an
+        address) receives int32 [n_cand, 3, n_stacks, D, nwy, nwx], the v of every window."""
+        what = "dct3d_ssim_rgb_frames_dev"
+        tb, T = self._rate_tables(tables)
+        cd, n = self._rgb_candidates(candidates, T, what)
+        ssim = np.zeros((n, n_stacks, 3), np.int64)
+        ssim_y = np.zeros((n, n_stacks), np.int64) if want_luma else None
+        sse = np.zeros((n, n_stacks), np.uint64) if want_sse else None
+        bits = np.zeros((T, n_stacks, 3), np.uint64) if want_bits else None
+        _check(lib().dct3d_ssim_rgb_frames_dev(self._h, _tptr(d_frames), width, height, n_stacks,
+                                               None if tb is None else _ptr(tb), T, None if cd is None else _ptr(cd), n,
+                                               _ptr(ssim), None if ssim_y is None else _ptr(ssim_y),
+                                               None if sse is None else _ptr(sse), None if bits is None else _ptr(bits),
+                                               None if d_window_ssim is None else _tptr(d_window_ssim)), what)
+        return self._ssim_rgb_result(ssim, ssim_y, sse, bits)
 
     def fill_synthetic_dev(self, d_frames, width: int, height: int, n_frames: int,
                            seed: int = synthetic.DEFAULT_SEED, frame0: int = 0, kind: str = "ramp") -> None:

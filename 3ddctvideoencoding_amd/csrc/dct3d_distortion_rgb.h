@@ -36,6 +36,20 @@ struct RgbCombineParams {
 };
 int launch_distortion_rgb_combine(int D, const RgbCombineParams& C, hipStream_t st);
 
+// The RGB and luma SSIM probe's pass 2: C as above (cube_sse and cand_stride unused) and, in the SSIM
+// probe's record formats (SsimParams), the 4 x 4 blocks' moments of planes R, G, B (and, luma = 1, plane 3: the
+// source's luma against the decoded Y) between the source pixels and the candidate's decoded pixels.  Block
+// (frame f of C's stacks, by, bx) at i = (f * nby4 + by) * nbx4 + bx: blk_y[(k * n_cand + c) * blk_stride + i],
+// blk_x[k * blk_stride + i] (candidate 0's threads write it).
+struct SsimRgbParams {
+    RgbCombineParams C;
+    uint64_t* blk_y;
+    uint32_t* blk_x;
+    uint64_t blk_stride;   // >= frames x nby4 x nbx4
+    uint32_t nbx4, nby4;   // ceil(w / 4), ceil(h / 4)
+};
+int launch_ssim_rgb_block(int D, int luma, const SsimRgbParams& S, hipStream_t st);
+
 // Planes mode: out[c * out_stride + s * cps + g] = sum over k < 3 of in[slots[c][k] * in_stride + (3 s + k) * cps + g]
 // (in: the distortion probe's per-cube buffer of one table, [stack][channel][cube])
 int launch_distortion_rgb_gather(const uint32_t* in, uint64_t in_stride, const uint8_t* slots, uint32_t n_cand, uint32_t cps,

@@ -167,8 +167,12 @@ struct dct3d_ctx {
     DevBuf d_rgb_planes, d_rgb_psse, d_rgb_pbits, d_rgb_slots, d_rgb_cube;
     std::vector<int32_t> rgb_tables;
     // SSIM probe (dct3d_ssim_frames*): the 4 x 4 blocks' moments of one range of stacks and one channel
-    // (per table the uint64 records, then the source's uint32 records) and the window kernel's partial sums
+    // (per table the uint64 records, then the source's uint32 records) and the window kernel's partial sums; the RGB
+    // and luma SSIM probe keeps a range's records of all its planes there ([plane][candidate], then [plane])
     DevBuf d_ssim_blk, d_ssim_part;
+    // RGB and luma SSIM probe (dct3d_ssim_rgb_frames*), planes mode with d_window_ssim: the plane
+    // probe's windows, which the caller's [candidate][plane] layout is copied out of
+    DevBuf d_ssim_win;
 };
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
@@ -442,7 +446,7 @@ void dct3d_ctx_destroy(dct3d_ctx* c) {
                       &c->d_egf_slot, &c->d_eg_out_x[0], &c->d_eg_out_x[1], &c->d_egd_in_x[0], &c->d_egd_in_x[1],
                       &c->d_eg_q_ch, &c->d_egd_status3, &c->d_rate_tabs, &c->d_rate_bits, &c->d_rate_sums,
                       &c->d_dist_steps, &c->d_dist_sse, &c->d_vq, &c->d_c420, &c->d_rgb_planes, &c->d_rgb_psse,
-                      &c->d_rgb_pbits, &c->d_rgb_slots, &c->d_rgb_cube, &c->d_ssim_blk, &c->d_ssim_part})
+                      &c->d_rgb_pbits, &c->d_rgb_slots, &c->d_rgb_cube, &c->d_ssim_blk, &c->d_ssim_part, &c->d_ssim_win})
         b->release();
     if (c->h_rate) (void)hipHostFree(c->h_rate);
     if (c->vq_host) (void)hipHostFree(c->vq_host);
@@ -1815,9 +1819,17 @@ static int probe_rgb_planes_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geo
 // per range, pass 1 per plane and kRateTables tables (launch_distortion_plane), the planes' sums, pass 2 over the
 // candidates (launch_distortion_rgb_combine).  A plane is coded under the tables some candidate uses for it, or
 // under all of them when plane_sse or bits is asked for.
+// sm (the RGB and luma SSIM probe; sse is optional then): pass 2 is launch_ssim_rgb_block -- the 4 x 4
+// blocks' moments of R, G, B (and luma) per candidate in d_ssim_blk -- and per plane the SSIM probe's windows and
+// sums; the combine kernel runs as well when sse is asked for.  The ranges fit kSsimBlockBudget too.
+struct SsimRgbOut {
+    int64_t* ssim;    // [n_cand][n_stacks][3]
+    int64_t* ssim_y;  // [n_cand][n_stacks] or nullptr
+    int32_t* d_win;   // device [n_cand][3][n_stacks][D][nwy][nwx] or nullptr
+};
 static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
                              int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits,
-                             uint32_t* d_cube_sse) {
+                             uint32_t* d_cube_sse, const SsimRgbOut* sm = nullptr) {
     const bool c420 = c420_on(c, 3);
     Geom gp[3];  // the planes' geometries (grey)
     uint64_t nc_dummy;
@@ -1872,10 +1884,23 @@ static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& 
         stack_planes += L[k].size() * pframes[k];
         stack_cubes += L[k].size() * cps[k];
     }
-    const int per = (int)std::max<size_t>(1, std::min<size_t>(kRgbPlaneBudget / stack_planes, (size_t)n_stacks));
+    size_t per_z = std::min<size_t>(kRgbPlaneBudget / stack_planes, (size_t)n_stacks);
+    // the SSIM records of a stack: the blocks of its D frames, per plane 8 bytes per candidate and 4 for the source
+    const uint32_t nbx4 = ((uint32_t)g.w + 3) / 4, nby4 = ((uint32_t)g.h + 3) / 4;
+    const uint32_t nwx = nbx4 > 1 ? nbx4 - 1 : 1, nwy = nby4 > 1 ? nby4 - 1 : 1;
+    const uint64_t blk_per_stack = (uint64_t)D * nbx4 * nby4, win_per_stack = (uint64_t)D * nwx * nwy;
+    const int n_sp = sm ? (sm->ssim_y ? 4 : 3) : 0;  // the planes of the records
+    const uint64_t rec_per_stack = blk_per_stack * (8ull * n_cand + 4) * n_sp;
+    if (sm) {
+        if (win_per_stack >= (1ull << 32)) return DCT3D_EINVAL;
+        per_z = std::min<size_t>({per_z, (size_t)(kSsimBlockBudget / rec_per_stack), (size_t)65535});
+    }
+    const int per = (int)std::max<size_t>(1, per_z);
+    const uint32_t bpr = (uint32_t)std::min<uint64_t>((win_per_stack + kSsimWinPerBlock - 1) / kSsimWinPerBlock, kSsimMaxBpr);
     const uint64_t out_stride = cps[0] * (uint64_t)n_stacks;
     const size_t n_psums = NT * (size_t)n_stacks, n_rgb = (size_t)n_cand * n_stacks;
-    const size_t n_sums = n_psums * (bits ? 2 : 1) + n_rgb;
+    // the sums: the planes' errors [and bits], the candidates' errors, [the candidates' SSIM of R, G, B, of the luma]
+    const size_t n_sums = n_psums * (bits ? 2 : 1) + n_rgb * (1 + (size_t)n_sp);
     const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
     const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
     int rc;
@@ -1884,7 +1909,9 @@ static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& 
         (rc = c->d_rgb_psse.grow(stack_cubes * per * sizeof(uint32_t))) ||
         (bits && (rc = c->d_rgb_pbits.grow(stack_cubes * per * sizeof(uint16_t)))) ||
         (rc = c->d_rgb_slots.grow((size_t)3 * n_cand)) ||
-        (!d_cube_sse && (rc = c->d_rgb_cube.grow((size_t)n_cand * out_stride * sizeof(uint32_t)))) ||
+        (sse && !d_cube_sse && (rc = c->d_rgb_cube.grow((size_t)n_cand * out_stride * sizeof(uint32_t)))) ||
+        (sm && ((rc = c->d_ssim_blk.grow((size_t)rec_per_stack * per)) ||
+                (rc = c->d_ssim_part.grow((size_t)n_cand * per * bpr * sizeof(int64_t))))) ||
         (rc = probe_grow_pinned(c, n_sums * sizeof(uint64_t))))
         return rc;
     if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -1894,6 +1921,7 @@ static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& 
     uint32_t* const cube_out = d_cube_sse ? d_cube_sse : (uint32_t*)c->d_rgb_cube.p;
     uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
     uint64_t* const d_rgb_sums = d_sums + n_psums * (bits ? 2 : 1);
+    int64_t* const d_ssim_sums = (int64_t*)(d_rgb_sums + n_rgb);
     const size_t stack_bytes = (size_t)g.plane() * D;
     DecodeParams DP;
     fill_decode_params(c, DP, nullptr, nullptr, g, 0);  // the decode's certificate constants, the test margin included
@@ -1967,15 +1995,56 @@ static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& 
         C.n_cand = (uint32_t)n_cand;
         C.cube_sse = cube_out + (size_t)s0 * cps[0];
         C.cand_stride = out_stride;
-        if (launch_distortion_rgb_combine(D, C, c->stream)) rc = DCT3D_EKERNEL;
+        if (sse && launch_distortion_rgb_combine(D, C, c->stream)) rc = DCT3D_EKERNEL;
+        if (!sm || rc) continue;
+        // the range's block records, then per plane the windows of all candidates and their sums per (candidate, stack)
+        SsimRgbParams S = {};
+        S.C = C;
+        S.C.cube_sse = nullptr;
+        S.blk_stride = blk_per_stack * ns;
+        S.blk_y = (uint64_t*)c->d_ssim_blk.p;
+        S.blk_x = (uint32_t*)(S.blk_y + (size_t)n_sp * n_cand * S.blk_stride);
+        S.nbx4 = nbx4;
+        S.nby4 = nby4;
+        if (launch_ssim_rgb_block(D, n_sp == 4, S, c->stream)) rc = DCT3D_EKERNEL;
+        for (int k = 0; k < n_sp && !rc; k++) {
+            SsimWinParams W = {};
+            W.blk_y = S.blk_y + (size_t)k * n_cand * S.blk_stride;
+            W.blk_x = S.blk_x + (size_t)k * S.blk_stride;
+            W.blk_stride = S.blk_stride;
+            W.win_t = 3ull * n_stacks * win_per_stack;
+            W.win_s = win_per_stack;
+            W.win = sm->d_win && k < 3 ? sm->d_win + ((size_t)k * n_stacks + s0) * win_per_stack : nullptr;
+            W.part = (int64_t*)c->d_ssim_part.p;
+            W.w = (uint32_t)g.w;
+            W.h = (uint32_t)g.h;
+            W.nbx = nbx4;
+            W.nby = nby4;
+            W.nwx = nwx;
+            W.nwy = nwy;
+            W.depth = (uint32_t)D;
+            W.ns = (uint32_t)ns;
+            W.n_tables = (uint32_t)n_cand;
+            W.bpr = bpr;
+            // ssim[c][s][k] at (c * n_stacks + s) * 3 + k; ssim_y[c][s] behind them
+            int64_t* const out = k < 3 ? d_ssim_sums + (size_t)s0 * 3 + k : d_ssim_sums + 3 * n_rgb + s0;
+            if (launch_ssim_window(W, c->stream) ||
+                launch_ssim_sum(W.part, bpr, W.ns, W.n_tables, out, k < 3 ? 3ull * n_stacks : (uint64_t)n_stacks, k < 3 ? 3 : 1, c->stream))
+                rc = DCT3D_EKERNEL;
+        }
     }
-    if (!rc && launch_distortion_sum(cube_out, (uint32_t)cps[0], n_rgb, d_rgb_sums, c->stream)) rc = DCT3D_EKERNEL;
+    if (!rc && sse && launch_distortion_sum(cube_out, (uint32_t)cps[0], n_rgb, d_rgb_sums, c->stream)) rc = DCT3D_EKERNEL;
     timer_end(c, ev);
     if (!rc && hipMemcpyAsync(c->h_rate, d_sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
     if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;  // synchronous on return (as probe_dev)
     if (c->slot_used) count_slot_used(c, (uint64_t)stack_cubes * n_stacks * (uint64_t)c->plan.cs);
     if (rc) return rc;
-    memcpy(sse, c->h_rate + (d_rgb_sums - d_sums), n_rgb * sizeof(uint64_t));
+    if (sse) memcpy(sse, c->h_rate + (d_rgb_sums - d_sums), n_rgb * sizeof(uint64_t));
+    if (sm) {
+        const uint64_t* const hs = c->h_rate + ((uint64_t*)d_ssim_sums - d_sums);
+        memcpy(sm->ssim, hs, 3 * n_rgb * sizeof(int64_t));
+        if (sm->ssim_y) memcpy(sm->ssim_y, hs + 3 * n_rgb, n_rgb * sizeof(int64_t));
+    }
     if (all_pairs)  // every (table, plane) pair was coded: slot t of plane k is table t
         for (int s0 = 0; s0 < n_stacks; s0 += per) {
             const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
@@ -1997,9 +2066,74 @@ static int probe_rgb_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, i
                          : probe_rgb_planes_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, plane_sse, bits, d_cube_sse);
 }
 
-// Frames in host memory: chunks of whole stacks, as probe_host
+// The RGB and luma SSIM probe in planes mode: the SSIM probe itself (ssim_dev) on the tables some candidate uses (all
+// of them when bits is asked for); a candidate's numbers are its three planes' under their tables, put together on
+// the host, and its windows strided copies out of the plane probe's.
+static int ssim_rgb_planes_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
+                               int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* bits, const SsimRgbOut& sm) {
+    int slot[DCT3D_RATE_MAX_TABLES];
+    std::vector<int> used;
+    for (int t = 0; t < n_tables; t++) slot[t] = bits ? t : -1;
+    if (bits)
+        for (int t = 0; t < n_tables; t++) used.push_back(t);
+    else
+        for (int i = 0; i < 3 * n_cand; i++)
+            if (slot[cand[i]] < 0) {
+                slot[cand[i]] = (int)used.size();
+                used.push_back(cand[i]);
+            }
+    const int nu = (int)used.size(), n_steps = (int)c->plan.steps.size();
+    const int32_t* tb = tables;
+    if (tables && !bits) {
+        c->rgb_tables.resize((size_t)nu * n_steps);
+        for (int i = 0; i < nu; i++) memcpy(&c->rgb_tables[(size_t)i * n_steps], tables + (size_t)used[i] * n_steps, n_steps * sizeof(int32_t));
+        tb = c->rgb_tables.data();
+    }
+    int nwx, nwy;
+    (void)dct3d_ssim_windows(g.w, g.h, &nwx, &nwy);
+    const size_t wps = (size_t)c->bd * nwx * nwy, n_runs = (size_t)nu * n_stacks * 3;
+    int rc;
+    if (sm.d_win && (rc = c->d_ssim_win.grow(n_runs * wps * sizeof(int32_t) + 4))) return rc;
+    std::vector<int64_t> pm(n_runs);
+    std::vector<uint64_t> ps(sse ? n_runs : 0);
+    rc = ssim_dev(c, d_frames, g, n_stacks, tb, nu, pm.data(), sse ? ps.data() : nullptr, bits, sm.d_win ? (int32_t*)c->d_ssim_win.p : nullptr);
+    if (rc || n_stacks == 0) return rc;
+    for (int i = 0; i < n_cand; i++)
+        for (int s = 0; s < n_stacks; s++) {
+            uint64_t v = 0;
+            for (int k = 0; k < 3; k++) {
+                const size_t at = ((size_t)slot[cand[3 * i + k]] * n_stacks + s) * 3 + k;
+                sm.ssim[((size_t)i * n_stacks + s) * 3 + k] = pm[at];
+                if (sse) v += ps[at];
+            }
+            if (sse) sse[(size_t)i * n_stacks + s] = v;
+        }
+    if (!sm.d_win) return DCT3D_OK;
+    // [table][stack][plane][windows] -> [candidate][plane][stack][windows]: one strided copy per (candidate, plane)
+    for (int i = 0; i < n_cand && !rc; i++)
+        for (int k = 0; k < 3 && !rc; k++) {
+            const int32_t* const from = (const int32_t*)c->d_ssim_win.p + ((size_t)slot[cand[3 * i + k]] * n_stacks * 3 + k) * wps;
+            int32_t* const to = sm.d_win + ((size_t)i * 3 + k) * n_stacks * wps;
+            if (hipMemcpy2DAsync(to, wps * sizeof(int32_t), from, 3 * wps * sizeof(int32_t), wps * sizeof(int32_t), (size_t)n_stacks,
+                                 hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                rc = DCT3D_EDEVICE;
+        }
+    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
+    return rc;
+}
+
+// (the arguments hold: rgb_args_ok; no luma in planes mode)
+static int ssim_rgb_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
+                        const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* bits, const SsimRgbOut& sm) {
+    return c->opt_colour ? probe_rgb_ycc_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, nullptr, bits, nullptr, &sm)
+                         : ssim_rgb_planes_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, bits, sm);
+}
+
+// Frames in host memory: chunks of whole stacks, as probe_host.  sm: the RGB and luma SSIM probe (sse optional,
+// no plane_sse)
 static int probe_rgb_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                          const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits) {
+                          const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits,
+                          const SsimRgbOut* sm = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
     const size_t stack_bytes = (size_t)g.plane() * c->bd;
     constexpr size_t kChunkBytes = (size_t)64 << 20;
@@ -2008,6 +2142,7 @@ static int probe_rgb_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, in
     if ((rc = c->h_in.grow(stack_bytes * per))) return rc;
     const size_t pl = (size_t)n_tables * per * 3;
     std::vector<uint64_t> part((size_t)n_cand * per + 2 * pl);
+    std::vector<int64_t> spart(sm ? (size_t)4 * n_cand * per : 0);  // a chunk's ssim [n_cand][ns][3], then ssim_y [n_cand][ns]
     c->last_units = 0;
     batch_begin(c);
     rc = DCT3D_OK;
@@ -2020,9 +2155,18 @@ static int probe_rgb_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, in
         uint64_t* const pr = part.data();
         uint64_t* const pp = plane_sse ? pr + (size_t)n_cand * per : nullptr;
         uint64_t* const pb = bits ? pr + (size_t)n_cand * per + pl : nullptr;
-        rc = probe_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, pr, pp, pb, nullptr);
+        if (sm) {
+            const SsimRgbOut chunk = {spart.data(), sm->ssim_y ? spart.data() + (size_t)3 * n_cand * ns : nullptr, nullptr};
+            rc = ssim_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, sse ? pr : nullptr, pb, chunk);
+            for (int i = 0; i < n_cand && !rc; i++) {
+                memcpy(sm->ssim + ((size_t)i * n_stacks + s0) * 3, chunk.ssim + (size_t)i * ns * 3, (size_t)ns * 3 * sizeof(int64_t));
+                if (sm->ssim_y) memcpy(sm->ssim_y + (size_t)i * n_stacks + s0, chunk.ssim_y + (size_t)i * ns, ns * sizeof(int64_t));
+            }
+        } else {
+            rc = probe_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, pr, pp, pb, nullptr);
+        }
         if (rc) break;
-        for (int i = 0; i < n_cand; i++) memcpy(sse + (size_t)i * n_stacks + s0, pr + (size_t)i * ns, ns * sizeof(uint64_t));
+        for (int i = 0; i < n_cand && sse; i++) memcpy(sse + (size_t)i * n_stacks + s0, pr + (size_t)i * ns, ns * sizeof(uint64_t));
         for (int t = 0; t < n_tables; t++) {
             const size_t dst = ((size_t)t * n_stacks + s0) * 3, src = (size_t)t * ns * 3;
             if (plane_sse) memcpy(plane_sse + dst, pp + src, (size_t)ns * 3 * sizeof(uint64_t));
@@ -2051,6 +2195,31 @@ int dct3d_distortion_rgb_frames(dct3d_ctx* c, const uint8_t* frames, int w, int 
     if (!rgb_args_ok(c, frames, w, h, n_stacks, tables, n_tables, cand, n_cand, sse, &g, &n_cubes)) return DCT3D_EINVAL;
     uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
     return probe_rgb_host(c, frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, plane_sse, bits);
+}
+
+// ---- RGB and luma SSIM probe: the SSIM probe's numbers on the RGB bytes (and the luma plane) of the stream encode
+//      + decode under (Y, Cb, Cr) table triples, in all three colour modes (dct3d.h) ----
+int dct3d_ssim_rgb_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int n_stacks, const int32_t* tables,
+                              int n_tables, const uint8_t* cand, int n_cand, int64_t* ssim, int64_t* ssim_y, uint64_t* sse,
+                              uint64_t* bits, int32_t* d_window_ssim) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rgb_args_ok(c, d_frames, w, h, n_stacks, tables, n_tables, cand, n_cand, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (ssim_y && !c->opt_colour) return DCT3D_EINVAL;  // planes mode has no luma plane
+    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
+    return ssim_rgb_dev(c, d_frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, bits,
+                        SsimRgbOut{ssim, ssim_y, d_window_ssim});
+}
+
+int dct3d_ssim_rgb_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables, int n_tables,
+                          const uint8_t* cand, int n_cand, int64_t* ssim, int64_t* ssim_y, uint64_t* sse, uint64_t* bits) {
+    Geom g;
+    uint64_t n_cubes;
+    if (!rgb_args_ok(c, frames, w, h, n_stacks, tables, n_tables, cand, n_cand, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
+    if (ssim_y && !c->opt_colour) return DCT3D_EINVAL;
+    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
+    const SsimRgbOut sm = {ssim, ssim_y, nullptr};
+    return probe_rgb_host(c, frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, nullptr, bits, &sm);
 }
 
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,

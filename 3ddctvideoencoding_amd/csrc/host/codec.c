@@ -158,7 +158,8 @@ static char g_rate_text[64]; /* codec_set_rate's text; "": none */
 static char g_psnr_text[64]; /* codec_set_psnr's text; "": none */
 static char g_psnr_rgb_text[64]; /* codec_set_psnr_rgb's text; "": none */
 static char g_ssim_text[64]; /* codec_set_ssim's text; "": none */
-enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_PSNR_RGB, SEL_SSIM, SEL_N };
+static char g_ssim_rgb_text[64]; /* codec_set_ssim_rgb's text; "": none */
+enum { SEL_QUANT, SEL_RATE, SEL_PSNR, SEL_PSNR_RGB, SEL_SSIM, SEL_SSIM_RGB, SEL_N };
 static const struct {
     const char *prefix, *env, *noun, *unit, *range;
     char *text;
@@ -169,22 +170,25 @@ static const struct {
     {"psnr=", "DCT3D_CODEC_PSNR", "PSNR target", "dB", "a positive number", g_psnr_text, sizeof(g_psnr_text)},
     {"psnr_rgb=", "DCT3D_CODEC_PSNR_RGB", "RGB PSNR target", "dB", "a positive number", g_psnr_rgb_text, sizeof(g_psnr_rgb_text)},
     {"ssim=", "DCT3D_CODEC_SSIM", "SSIM target", "target", "a decimal in (0, 1]", g_ssim_text, sizeof(g_ssim_text)},
+    {"ssim_rgb=", "DCT3D_CODEC_SSIM_RGB", "RGB SSIM target", "target", "a decimal in (0, 1]", g_ssim_rgb_text, sizeof(g_ssim_rgb_text)},
 };
 static const char *sel_text(int i) { return kSel[i].text[0] ? kSel[i].text : getenv(kSel[i].env); }
 
 int codec_parse_rate(const char *text, double *bpp) { return parse_positive(text, kSel[SEL_RATE].prefix, bpp); }
 int codec_parse_psnr(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR].prefix, db); }
 int codec_parse_psnr_rgb(const char *text, double *db) { return parse_positive(text, kSel[SEL_PSNR_RGB].prefix, db); }
-/* a plain decimal in (0, 1] */
-int codec_parse_ssim(const char *text, double *target) {
+/* a plain decimal in (0, 1] behind the prefix */
+static int parse_unit(const char *text, const char *prefix, double *target) {
     double v;
-    if (!target || parse_positive(text, kSel[SEL_SSIM].prefix, &v) || v > 1.0) return 1;
+    if (!target || parse_positive(text, prefix, &v) || v > 1.0) return 1;
     *target = v;
     return 0;
 }
+int codec_parse_ssim(const char *text, double *target) { return parse_unit(text, kSel[SEL_SSIM].prefix, target); }
+int codec_parse_ssim_rgb(const char *text, double *target) { return parse_unit(text, kSel[SEL_SSIM_RGB].prefix, target); }
 /* target i's text -> its value: 1 when it does not parse */
 static int parse_target(int i, const char *text, double *value) {
-    return i == SEL_SSIM ? codec_parse_ssim(text, value) : parse_positive(text, kSel[i].prefix, value);
+    return i == SEL_SSIM || i == SEL_SSIM_RGB ? parse_unit(text, kSel[i].prefix, value) : parse_positive(text, kSel[i].prefix, value);
 }
 
 static int set_target(int i, const char *text) {
@@ -198,6 +202,7 @@ int codec_set_rate(const char *text) { return set_target(SEL_RATE, text); }
 int codec_set_psnr(const char *text) { return set_target(SEL_PSNR, text); }
 int codec_set_psnr_rgb(const char *text) { return set_target(SEL_PSNR_RGB, text); }
 int codec_set_ssim(const char *text) { return set_target(SEL_SSIM, text); }
+int codec_set_ssim_rgb(const char *text) { return set_target(SEL_SSIM_RGB, text); }
 
 /* Target i of a call: codec_set_*'s text, else the environment variable.  *set = 0: none given.  1 after printing
  * when the text does not parse or a quantiser or an earlier target is given too. */
@@ -722,25 +727,38 @@ static int rate_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int
  * "psnr_rgb: q=<qY>,<qCb>,<qCr> psnr=<dB> bits=<total>" and sets the context's quantiser to the pick.  stack_pick
  * ([n_stacks], or [n_stacks][3] with qw == 3): the rule per stack over the stack's pixels instead; prints "qmap: ..."
  * or "qmap3: ..." as the rate target does.  Rewinds the input.  1 after printing on an error. */
+/* metric == METRIC_SSIM: an RGB SSIM target instead (ssim_rgb=<target>; codec.h): the RGB and luma SSIM probe
+ * (dct3d_ssim_rgb_frames) in the probe's place, the same candidates; the sums of R, G and B added, the mean over all
+ * windows of the three planes (dct3d_ssim_windows per frame and plane; the zero-filled frames count); the pick is
+ * pick_by_ssim's.  luma (the YCbCr modes): the luma sums are taken too.  Prints "ssim_rgb: q=<qY>,<qCb>,<qCr>
+ * ssim=<6 decimals> [ssim_y=<6 decimals> ]bits=<total>". */
 static int psnr_rgb_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width, int height, int frames, int depth, int batch,
-                               double target, uint8_t *stack_pick, int qw, int cq) {
+                               double target, int metric, int luma, uint8_t *stack_pick, int qw, int cq) {
     const int n = depth + 14, n_stacks = (frames + depth - 1) / depth;
     const size_t stack_bytes = (size_t)3 * width * height * depth;
     int32_t tabs[RATE_LADDER_N * QUANT_MAX_STEPS];
     uint8_t cand[3 * RATE_LADDER_N];
     int jof[RATE_LADDER_N];
     uint64_t tot[RATE_LADDER_N], err[RATE_LADDER_N], map_bits = 0;
+    int64_t sim[RATE_LADDER_N], sim_y[RATE_LADDER_N]; /* METRIC_SSIM: the sums of v over the file */
+    int nwx = 1, nwy = 1;
+    if (metric == METRIC_SSIM) (void)dct3d_ssim_windows(width, height, &nwx, &nwy);
+    const double n_win = (double)nwx * (double)nwy; /* windows of one frame and plane */
     ladder_tables(depth, tabs);
     for (int i = 0; i < RATE_LADDER_N; i++) {
         tot[i] = err[i] = 0;
+        sim[i] = sim_y[i] = 0;
         jof[i] = i + cq < RATE_LADDER_N ? i + cq : RATE_LADDER_N - 1;
         cand[3 * i] = (uint8_t)i;
         cand[3 * i + 1] = cand[3 * i + 2] = (uint8_t)jof[i];
     }
     const size_t n_sse = (size_t)RATE_LADDER_N * batch, n_bits = n_sse * 3;
     uint64_t *sse = (uint64_t *)malloc(sizeof(uint64_t) * (n_sse + n_bits)), *bits = sse ? sse + n_sse : NULL;
-    if (!sse) {
+    int64_t *ssim = (int64_t *)malloc(sizeof(int64_t) * (metric == METRIC_SSIM ? 4 * n_sse : 1)), *ssim_y = ssim ? ssim + 3 * n_sse : NULL;
+    if (!sse || !ssim) {
         printf("Out of memory\n");
+        free(sse);
+        free(ssim);
         return 1;
     }
     int status = 0;
@@ -750,24 +768,36 @@ static int psnr_rgb_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width,
         const size_t want = stack_bytes * nb;
         while (got < want && (r = fread(fr + got, 1, want - got, in)) > 0) got += r;
         if (got < want) memset(fr + got, 0, want - got); /* a short last stack is zero-filled, as the encode's */
-        const int rc = dct3d_distortion_rgb_frames(ctx, fr, width, height, nb, tabs, RATE_LADDER_N, cand, RATE_LADDER_N, sse,
-                                                   NULL, bits);
+        const int rc = metric == METRIC_SSIM
+                           ? dct3d_ssim_rgb_frames(ctx, fr, width, height, nb, tabs, RATE_LADDER_N, cand, RATE_LADDER_N, ssim,
+                                                   luma ? ssim_y : NULL, NULL, bits)
+                           : dct3d_distortion_rgb_frames(ctx, fr, width, height, nb, tabs, RATE_LADDER_N, cand, RATE_LADDER_N, sse,
+                                                         NULL, bits);
         if (rc) {
-            printf("Error running the RGB distortion probe: %s\n", dct3d_strerror(rc));
+            printf("Error running the RGB %s probe: %s\n", metric == METRIC_SSIM ? "SSIM" : "distortion", dct3d_strerror(rc));
             status = 1;
             break;
         }
         for (int s = 0; s < nb; s++) {
             uint64_t sb[RATE_LADDER_N], se[RATE_LADDER_N];
+            int64_t sm[RATE_LADDER_N];
             for (int i = 0; i < RATE_LADDER_N; i++) {
                 const int j = jof[i];
-                se[i] = sse[(size_t)i * nb + s];
+                se[i] = 0, sm[i] = 0;
+                if (metric == METRIC_SSIM) {
+                    for (int k = 0; k < 3; k++) sm[i] += ssim[((size_t)i * nb + s) * 3 + k];
+                    if (luma) sim_y[i] += ssim_y[(size_t)i * nb + s];
+                } else {
+                    se[i] = sse[(size_t)i * nb + s];
+                }
                 sb[i] = bits[((size_t)i * nb + s) * 3] + bits[((size_t)j * nb + s) * 3 + 1] + bits[((size_t)j * nb + s) * 3 + 2];
                 err[i] += se[i];
+                sim[i] += sm[i];
                 tot[i] += sb[i];
             }
             if (!stack_pick) continue;
-            const int p = pick_by_psnr(se, 3.0 * (double)width * (double)height * (double)depth, target);
+            const int p = metric == METRIC_SSIM ? pick_by_ssim(sm, 3.0 * n_win * (double)depth, target)
+                                                : pick_by_psnr(se, 3.0 * (double)width * (double)height * (double)depth, target);
             if (qw == 3) {
                 stack_pick[3 * (s0 + s)] = (uint8_t)p;
                 stack_pick[3 * (s0 + s) + 1] = stack_pick[3 * (s0 + s) + 2] = (uint8_t)jof[p];
@@ -778,14 +808,22 @@ static int psnr_rgb_first_pass(dct3d_ctx *ctx, FILE *in, uint8_t *fr, int width,
         }
     }
     free(sse);
+    free(ssim);
     if (status) return 1;
     if (stack_pick) {
         printf("%s: stacks=%d bits=%llu\n", qw == 3 ? "qmap3" : "qmap", n_stacks, (unsigned long long)map_bits);
     } else {
         const double n_samples = 3.0 * (double)width * (double)height * (double)n_stacks * (double)depth;
-        const int pick = pick_by_psnr(err, n_samples, target);
-        printf("psnr_rgb: q=%d,%d,%d psnr=%.3f bits=%llu\n", kRateLadder[pick], kRateLadder[jof[pick]], kRateLadder[jof[pick]],
-               psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
+        const double n_windows = n_win * (double)n_stacks * (double)depth; /* of one plane */
+        const int pick = metric == METRIC_SSIM ? pick_by_ssim(sim, 3.0 * n_windows, target) : pick_by_psnr(err, n_samples, target);
+        if (metric == METRIC_SSIM) {
+            printf("ssim_rgb: q=%d,%d,%d ssim=%.6f ", kRateLadder[pick], kRateLadder[jof[pick]], kRateLadder[jof[pick]],
+                   ssim_of(sim[pick], 3.0 * n_windows));
+            if (luma) printf("ssim_y=%.6f ", ssim_of(sim_y[pick], n_windows));
+            printf("bits=%llu\n", (unsigned long long)tot[pick]);
+        } else
+            printf("psnr_rgb: q=%d,%d,%d psnr=%.3f bits=%llu\n", kRateLadder[pick], kRateLadder[jof[pick]], kRateLadder[jof[pick]],
+                   psnr_of(err[pick], n_samples), (unsigned long long)tot[pick]);
         const int rc = dct3d_ctx_set_quant(ctx, tabs + pick * n, n);
         if (rc) {
             printf("Error setting the quantiser: %s\n", dct3d_strerror(rc));
@@ -1254,6 +1292,18 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     double ssim_target = 0.0;
     int ssim_set = 0;
     if (call_target(SEL_SSIM, &ssim_target, &ssim_set)) return 1;
+    /* the RGB SSIM target: psnr_rgb='s place, passes and conditions, the RGB and luma SSIM probe's numbers */
+    double srgb_target = 0.0;
+    int srgb_set = 0;
+    if (call_target(SEL_SSIM_RGB, &srgb_target, &srgb_set)) return 1;
+    if (srgb_set && channels != 3) {
+        printf("ssim_rgb= applies to encode_rgb on one device (encode): a grey encode takes ssim=\n");
+        return 1;
+    }
+    if (srgb_set && host_eg_on()) {
+        printf("ssim_rgb= needs the device stream calls (DCT3D_CODEC_HOST_EG=1 is set)\n");
+        return 1;
+    }
     int ycc;
     if (call_colour("encode", channels, ssim_set ? SEL_SSIM : psnr_set ? SEL_PSNR : 0, &ycc)) return 1;
     int c420;
@@ -1261,7 +1311,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
     /* a quality map: written by the first pass of a rate or PSNR target, else read -- before any file is made */
     const char *qmap_path = NULL, *qmap3_path = NULL;
     int cq = 0;
-    if (call_qmap3("encode", channels, rate_set || prgb_set, psnr_set || ssim_set, ycc, &qmap3_path, &cq)) return 1;
+    if (call_qmap3("encode", channels, rate_set || prgb_set || srgb_set, psnr_set || ssim_set, ycc, &qmap3_path, &cq)) return 1;
     if (call_qmap(&qmap_path)) return 1;
     const int qw = qmap3_path ? 3 : 1; /* the map's entries per stack */
     if (qmap3_path) qmap_path = qmap3_path;
@@ -1274,7 +1324,7 @@ static int encode_any(const char *inName, const char *outName, int width, int he
             printf("Out of memory\n");
             return 1;
         }
-        if (!rate_set && !psnr_set && !ssim_set && !prgb_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
+        if (!rate_set && !psnr_set && !ssim_set && !prgb_set && !srgb_set && (qw == 3 ? read_qmap3(qmap_path, ns, qmap) : read_qmap(qmap_path, ns, qmap))) {
             free(qmap);
             return 1;
         }
@@ -1342,9 +1392,10 @@ static int encode_any(const char *inName, const char *outName, int width, int he
         STAGE(t_dev, status = rate_first_pass(ctx, in, fr, width, height, frames, depth, batch, channels,
                                               ssim_set ? ssim_target : psnr_set ? psnr_db : rate_bpp,
                                               ssim_set ? METRIC_SSIM : psnr_set ? METRIC_PSNR : METRIC_RATE, qmap, qw == 3 ? cq : -1));
-    if (!status && prgb_set)
-        STAGE(t_dev, status = psnr_rgb_first_pass(ctx, in, fr, width, height, frames, depth, batch, prgb_db, qmap, qw, qw == 3 ? cq : 0));
-    if (!status && qmap && (rate_set || psnr_set || ssim_set || prgb_set))
+    if (!status && (prgb_set || srgb_set))
+        STAGE(t_dev, status = psnr_rgb_first_pass(ctx, in, fr, width, height, frames, depth, batch, srgb_set ? srgb_target : prgb_db,
+                                                  srgb_set ? METRIC_SSIM : METRIC_PSNR, ycc, qmap, qw, qw == 3 ? cq : 0));
+    if (!status && qmap && (rate_set || psnr_set || ssim_set || prgb_set || srgb_set))
         status = qw == 3 ? write_qmap3(qmap_path, n_stacks, qmap) : write_qmap(qmap_path, n_stacks, qmap);
     for (int s0 = 0; !status && s0 < n_stacks; s0 += batch) {
         const int nb = (n_stacks - s0) < batch ? (n_stacks - s0) : batch;

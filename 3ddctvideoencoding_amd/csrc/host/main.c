@@ -27,6 +27,9 @@
  *   the single-device encodes take ssim=<target in (0, 1]> (codec.h, codec_parse_ssim) in the quantiser's place: the
  *   first pass picks the largest q whose mean SSIM (the SSIM probe) reaches the target and prints
  *   "ssim: q=<n> ssim=<mean> bits=<total>"; with qmap= it writes the map; not with ycc=1 or chroma=420
+ *   encode_rgb takes ssim_rgb=<target in (0, 1]> (codec.h, codec_parse_ssim_rgb) in the quantiser's place, in every
+ *   colour mode: psnr_rgb='s passes with the RGB and luma SSIM probe; prints "ssim_rgb: q=<qY>,<qCb>,<qCr> ssim=<mean>
+ *   [ssim_y=<mean>] bits=<total>"; with qmap= or qmap3= [cq=<k>] it writes the map
  *   width and height: any size >= 1 on one device (a size that is no multiple of 8 is padded by repeating the
  *   last column and row inside the device transform, and cropped on the way back); multiples of 8 on several
  * (list_platforms is accepted as an alias of list_devices.)  device_index may be a comma-separated list
@@ -101,6 +104,14 @@ static void usage(void) {
            "encodes as q=<n>.  With qmap=<path> the rule is applied per stack and the map is WRITTEN.  ssim= on a "
            "decode, together with q=, rate=, psnr= or psnr_rgb=, with ycc=1 or chroma=420, or with several devices is an "
            "error\n");
+    printf("encode_rgb on one device takes ssim_rgb=<target>, a decimal in (0, 1], in the quantiser's place, with or "
+           "without ycc=1 and chroma=420: the first pass measures, per rung of the ladder, the exact SSIM of encode + "
+           "decode on the R, G and B bytes the decode writes (and, with ycc=1, on the luma plane), picks the largest q "
+           "whose mean over the windows of R, G and B is >= <target> (1 when none reaches it) and prints 'ssim_rgb: "
+           "q=<qY>,<qCb>,<qCr> ssim=<mean> ssim_y=<mean> bits=<total>' (no ssim_y= without ycc=1); the second pass encodes "
+           "as q=<n>.  With qmap=<path> the rule is applied per stack and the map is WRITTEN; with qmap3=<path> [cq=<k>] "
+           "the candidates are psnr_rgb='s triples and the three-column map is written.  ssim_rgb= on a decode, on a grey "
+           "command, together with q=, rate=, psnr=, psnr_rgb= or ssim=, or with several devices is an error\n");
     printf("<width> and <height> may be any size >= 1: a size that is no multiple of 8 is padded by repeating the "
            "last column and row (the stream is that of the padded video) and cropped again by decode; with "
            "several devices they must be multiples of 8\n");
@@ -154,7 +165,7 @@ int main(int argc, char *argv[]) {
     }
     if (n_dev == 0) devs[n_dev++] = 1;
     const int depth = argc > 8 ? atoi(argv[8]) : DCT_BLOCK_DEPTH;
-    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0, have_prgb = 0, have_ssim = 0;
+    int have_quant = 0, have_rate = 0, have_psnr = 0, have_qmap = 0, have_ycc = 0, have_chroma = 0, have_qmap3 = 0, have_cq = 0, have_prgb = 0, have_ssim = 0, have_srgb = 0;
     for (int a = 9; a < argc && a < 15 && (depth == 8 || depth == 4); a++) { /* (any other depth: the entry point reports the geometry) */
         int32_t steps[32];
         double v;
@@ -176,6 +187,21 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             have_prgb = a;
+            continue;
+        }
+        if (!strncmp(argv[a], "ssim_rgb=", 9)) { /* the RGB SSIM target: refused here before any file is made */
+            if (have_srgb) break;
+            if (codec_parse_ssim_rgb(argv[a], &v)) {
+                printf("Invalid ssim_rgb target '%s': ssim_rgb=<target>, a decimal in (0, 1]\n", argv[a]);
+                usage();
+                return 1;
+            }
+            if (strcmp(argv[1], "encode_rgb") || n_dev > 1) {
+                printf("ssim_rgb= applies to encode_rgb on one device: decode with the q=<n> or the map that the encode "
+                       "printed or wrote\n");
+                return 1;
+            }
+            have_srgb = a;
             continue;
         }
         if (!strncmp(argv[a], "ssim=", 5)) { /* the SSIM target: refused here before any file is made */
@@ -267,6 +293,11 @@ int main(int argc, char *argv[]) {
         printf("%s and ssim= exclude each other\n", have_quant ? "q=" : have_rate ? "rate=" : have_psnr ? "psnr=" : "psnr_rgb=");
         return 1;
     }
+    if (have_srgb && (have_quant || have_rate || have_psnr || have_prgb || have_ssim)) {
+        printf("%s and ssim_rgb= exclude each other\n",
+               have_quant ? "q=" : have_rate ? "rate=" : have_psnr ? "psnr=" : have_prgb ? "psnr_rgb=" : "ssim=");
+        return 1;
+    }
     if (have_ssim && ((have_ycc && argv[have_ycc][4] == '1') || (have_chroma && argv[have_chroma][9] == '0'))) {
         printf("%s and ssim= exclude each other: the SSIM probe measures the R, G, B planes (luma SSIM is not built)\n",
                have_ycc && argv[have_ycc][4] == '1' ? "ycc=1" : "chroma=420");
@@ -290,7 +321,8 @@ int main(int argc, char *argv[]) {
         (have_psnr && codec_set_psnr(argv[have_psnr])) || (have_qmap && codec_set_qmap(argv[have_qmap])) ||
         (have_ycc && codec_set_colour(argv[have_ycc])) || (have_chroma && codec_set_chroma(argv[have_chroma])) ||
         (have_qmap3 && codec_set_qmap3(argv[have_qmap3])) || (have_cq && codec_set_cq(argv[have_cq])) ||
-        (have_prgb && codec_set_psnr_rgb(argv[have_prgb])) || (have_ssim && codec_set_ssim(argv[have_ssim]))) {
+        (have_prgb && codec_set_psnr_rgb(argv[have_prgb])) || (have_ssim && codec_set_ssim(argv[have_ssim])) ||
+        (have_srgb && codec_set_ssim_rgb(argv[have_srgb]))) {
         printf("Argument too long\n");
         return 1;
     }

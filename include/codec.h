@@ -153,6 +153,23 @@ int codec_set_psnr_rgb(const char *text);
 int codec_parse_ssim(const char *text, double *target);
 int codec_set_ssim(const char *text);
 
+/* An RGB SSIM target in place of a quantiser (encode_rgb_ex on one device, in every colour mode: planes, ycc=1, ycc=1
+ * chroma=420): "ssim_rgb=<target>", a plain decimal in (0, 1].  It is psnr_rgb='s first pass with the RGB and luma SSIM
+ * probe (dct3d_ssim_rgb_frames) in the probe's place: candidate i = (rung i, rung j, rung j), j = min(i + k, 15) (k:
+ * cq=<k> beside qmap3=, else 0); the sums are added over the file and over R, G and B, the mean is taken over all
+ * windows of the three planes (dct3d_ssim_windows per frame and plane; the zero-filled frames of a short last stack
+ * count as frames), the pick is ssim='s rule.  It prints one line "ssim_rgb: q=<qY>,<qCb>,<qCr> ssim=<mean, 6 decimals>
+ * ssim_y=<mean, 6 decimals> bits=<total>", ssim_y= (the luma plane's mean under the pick) only in the YCbCr modes; the
+ * second pass encodes as q=<n> does, byte for byte.  With qmap=<path> the rule is applied per stack with one quality for
+ * all planes, with qmap3=<path> [cq=<k>] per stack with the triples; the maps are written as psnr_rgb= writes them.
+ * codec_parse_ssim_rgb: 0 and *target for "ssim_rgb=<decimal in (0, 1]>"; 1 (*target untouched) on anything else.
+ * codec_set_ssim_rgb: the target of every later encode call of this process; NULL or "": none.  It overrides the
+ *   environment variable DCT3D_CODEC_SSIM_RGB.  It excludes a quantiser and every other target as those exclude each
+ *   other.  A call refuses it, before any file is made, on a decode, on a grey encode, on several devices and with
+ *   DCT3D_CODEC_HOST_EG=1. */
+int codec_parse_ssim_rgb(const char *text, double *target);
+int codec_set_ssim_rgb(const char *text);
+
 /* A quality per stack (the single-device calls: encode, encode_ex, encode_rgb_ex and their decodes): "qmap=<path>"
  * names a text file with one line per stack, in stack order, each a quality of the ladder above; stack s of every
  * channel is coded as q=<that quality> codes it (dct3d_encode_eg_frames_vq / dct3d_decode_eg_frames_vq, the ladder

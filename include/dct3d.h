@@ -614,6 +614,38 @@ int dct3d_ssim_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int heig
 int dct3d_ssim_windows(int w, int h, int *nwx, int *nwy);
 
 /* ---------------------------------------------------------------------------------------------
+ * RGB and luma SSIM probe (additive to ABI 9; detect by symbol): the SSIM above, taken on the RGB
+ * bytes the packed RGB24 stream decode would write, under a list of (Y, Cb, Cr) table triples, in all three colour
+ * modes of the context: planes, DCT3D_COLOUR_YCBCR, and DCT3D_CHROMA_420 on top.  The arguments are
+ * dct3d_distortion_rgb_frames*'; y_c is, as there, what dct3d_decode_eg_frames_vqc(dct3d_encode_eg_frames_vqc(x))
+ * returns when every row of the map is cand[c].
+ *   ssim      host, int64 [n_cand][n_stacks][3], required: ssim[c][s][k] is the sum of v (the definition above) over
+ *             the dct3d_ssim_windows(width, height) windows of the D frames of stack s, between plane k (R, G, B)
+ *             of x and plane k of y_c.
+ *   ssim_y    host, int64 [n_cand][n_stacks], or NULL (YCbCr modes only): the same sum between the luma plane of
+ *             the colour transform of x (the plane the encode codes) and the decoded Y plane under
+ *             tables[cand[c][0]].
+ *   sse       host, [n_cand][n_stacks], or NULL: exactly dct3d_distortion_rgb_frames' sse.
+ *   bits      host, [n_tables][n_stacks][3], or NULL: exactly dct3d_distortion_rgb_frames' bits.
+ *   d_window_ssim   optional device memory, int32 [n_cand][3][n_stacks][D][nwy][nwx]: the v of every window.
+ * Exact; the call writes no stream, neither reads (tables != NULL) nor changes the context's quantiser, colour or
+ * chroma mode, honours DCT3D_OPT_DEC_MARGIN and is synchronous on return; the host-pointer call moves the frames in
+ * chunks of whole stacks.  The blocks' moments of a range of stacks live in the SSIM probe's buffer: per stack
+ * D nbx nby (8 n_cand + 4) P bytes, P = 3, or 4 with ssim_y; the call walks the stacks in ranges that fit both
+ * DCT3D_RGB_PLANE_BUDGET (the decoded planes) and DCT3D_SSIM_BLOCK_BUDGET (the records), or one stack at a time.
+ * When bits is asked for, every (table, plane) pair is coded; otherwise only the pairs some candidate uses.
+ * Errors.  DCT3D_EINVAL: the cases of dct3d_distortion_rgb_frames with ssim in the place of sse; ssim_y != NULL in
+ * planes mode (there is no luma plane).
+ * Statistics: as dct3d_distortion_rgb_frames counts them, over the pairs that are coded.
+ * ------------------------------------------------------------------------------------------- */
+int dct3d_ssim_rgb_frames_dev(dct3d_ctx *ctx, const uint8_t *d_frames, int width, int height, int n_stacks,
+                              const int32_t *tables, int n_tables, const uint8_t *cand, int n_cand,
+                              int64_t *ssim, int64_t *ssim_y, uint64_t *sse, uint64_t *bits, int32_t *d_window_ssim);
+int dct3d_ssim_rgb_frames(dct3d_ctx *ctx, const uint8_t *frames, int width, int height, int n_stacks,
+                          const int32_t *tables, int n_tables, const uint8_t *cand, int n_cand,
+                          int64_t *ssim, int64_t *ssim_y, uint64_t *sse, uint64_t *bits);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-stack quantiser tables in the fused stream calls (additive to ABI 9; detect by symbol).
  * The four dct3d_*_eg_frames* calls with three more host arguments, copied before the call returns:
  *   tables       [n_tables][bw + bh + bd - 2] steps, each in [1, 255]: a palette of 1 <= n_tables <=
