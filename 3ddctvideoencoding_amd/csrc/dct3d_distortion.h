@@ -1,5 +1,5 @@
 // dct3d_distortion.h -- the distortion probe's kernel parameters and launchers (dct3d_distortion.hip; DESIGN
-// 4j), shared with the C-ABI runtime.
+// 4j), shared with the probes' host unit (dct3d_probes.cpp).
 #pragma once
 #include "dct3d_rate.h"
 

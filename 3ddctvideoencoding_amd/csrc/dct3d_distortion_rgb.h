@@ -1,5 +1,6 @@
 // dct3d_distortion_rgb.h -- the RGB-domain distortion probe's kernel parameters and launchers
-// (dct3d_distortion_rgb.hip; dct3d_distortion_rgb_frames*), shared with the C-ABI runtime.
+// (dct3d_distortion_rgb.hip; dct3d_distortion_rgb_frames*), shared with the probes' host unit
+// (dct3d_probes.cpp).
 #pragma once
 #include "dct3d_distortion.h"
 

@@ -1,5 +1,5 @@
 // dct3d_rate.h -- the rate probe's kernel parameters and launchers (dct3d_rate.hip), shared with
-// the C-ABI runtime.
+// the probes' host unit (dct3d_probes.cpp).
 #pragma once
 #include "dct3d_kernels.h"
 

@@ -18,16 +18,12 @@
 #include <thread>
 #include <new>
 
-#include "../../include/dct3d.h"
-#include "dct3d_kernels.h"
-#include "dct3d_plan.h"
-#include "dct3d_distortion.h"
-#include "dct3d_distortion_rgb.h"
-#include "dct3d_rate.h"
-#include "dct3d_vq.h"
+#include "dct3d_ctx.h"
 #include "dct3d_c420.h"
+#include "dct3d_distortion.h"
 
 using namespace dct3d;
+using namespace dct3d::rt;
 
 namespace {
 
@@ -38,142 +34,7 @@ constexpr size_t kEgdStatusBytes = 6 * sizeof(uint64_t);
 // hand-off tags, [8, 26) the three fronts' words of a packed RGB24 stream decode
 constexpr size_t kHostStatusBytes = (8 + 18) * sizeof(uint64_t);
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int grow(size_t need) {
-        if (need <= bytes) return DCT3D_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        if (hipMalloc(&p, need) != hipSuccess) return DCT3D_ENOMEM;
-        bytes = need;
-        return DCT3D_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
 }  // namespace
-
-struct dct3d_ctx {
-    int device = 0;
-    int bw = 8, bh = 8, bd = 8;
-    Plan plan;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    bool profiling = false;
-    // ring of event quadruples (main kernel begin/end, auxiliary launch begin/end); resolved lazily
-    static constexpr int kRing = 256;
-    hipEvent_t ev[kRing][4] = {};
-    int ring_head = 0, ring_pending = 0;
-    uint64_t n_timed = 0;
-    double kernel_ms = 0.0, aux_ms = 0.0;
-    // plan tables on device
-    DevBuf d_ngroups, d_coef, d_group_of, d_inv_coef, d_tabs, d_tabs64;
-    // test / diagnostic options (dct3d_ctx_set_option): how later calls reach their results
-    double opt_dec_margin = 0.0;    // added to the decode margin
-    bool opt_enc_no_recheck = false, opt_eg_two_step = false,
-         opt_eg_no_resolve = false;
-    bool opt_eg_force_retry = false;
-    bool opt_eg_fused_front = false;
-    int opt_eg_dec_groups = 0;  // fused stream decode: groups per wave (0: the default, 8)
-    int opt_colour = 0;            // DCT3D_OPT_COLOUR: 1 = the packed RGB24 stream calls and the rate probe code Y, Cb, Cr
-    bool opt_quant_force = false;  // the table kernels even for the reference table (DCT3D_OPT_QUANT_FORCE_TABLE)
-    // certify-or-replay state
-    uint64_t last_units = 0;
-    bool last_valid = false;
-    // in-wave replay (encode, decode): two counter slots that alternate between calls; each launch zeroes
-    // the other slot for the next call, so a call needs no reset copy (zeroed once at creation).
-    // Slot j (2 kCountSpread words at j * 2 kCountSpread): Java-fold replays, then second-certificate
-    // settlements, each spread over kCountSpread words (dct3d_kernels.h).
-    DevBuf d_enc_counts;
-    int enc_slot = 0;
-    int last_count_slot = -1;  // >= 0: the last call's statistics are in d_enc_counts[slot]
-    bool slot_used = false;    // a counting kernel of the current call was enqueued into enc_slot
-    bool batch = false;        // a host entry point's chunks: one slot for the whole call (batch_end flips it)
-    uint64_t batch_units = 0;
-    hipEvent_t ev_switch = nullptr;  // orders a dct3d_ctx_set_stream switch after the old stream's work
-    // host-pointer entry point staging
-    DevBuf h_in, h_out, h_aux;
-    // Exp-Golomb stage: diagonal order, per-cube bits / offsets, chunk sums, status, device stream
-    DevBuf d_diag, d_eg_bits, d_eg_off, d_eg_bsum, d_eg_status, d_eg_out, d_eg_q, d_eg_ht;
-    // fused encode + Exp-Golomb: per-segment slots and lane bit counts
-    DevBuf d_egf_slot;
-    // Exp-Golomb decode: chunk exits (two passes' worth), decode status, staged stream / raster
-    // (d_egd_status: the decode's four status words, then the scan's two -- one read-back per call)
-    DevBuf d_egd_exit, d_egd_status, d_egd_in, d_egd_raster, d_egd_mark, d_egd_desc;
-    // d_egd_status holds two slots of the words; calls alternate between them, and the fused decode's
-    // consumer zeroes the other slot for the next call (clean: known zero, no memset needed)
-    int egd_slot = 0;
-    bool egd_clean[2] = {true, true};
-    // the same for the encode stream's two status words (d_eg_status: two slots of 16 bytes)
-    int eg_slot = 0;
-    bool eg_clean[2] = {true, true};
-    // pinned host words the entropy stages' status lands in (one DMA read-back, not a pageable copy)
-    uint64_t* h_status = nullptr;
-    uint64_t* h_status_dev = nullptr;  // its device-side address (decode_eg_kernel writes the words there)
-    uint64_t egd_seq = 0;              // stream-decode calls so far: decode_eg_kernel's hand-off tag (h_status[6])
-    uint64_t eg_seq = 0;               // stream-encode calls so far: eg_stitch_kernel's hand-off tag (h_status[7])
-    // host-pointer pipeline: copy streams, slot events, double-buffered slots
-    hipStream_t s_up = nullptr, s_down = nullptr;
-    hipEvent_t pe_in[2] = {}, pe_done[2] = {};
-    DevBuf p_in[2], p_out[2];
-    uint64_t eg_last_bytes = 0;
-    // frames of any size / packed RGB24 through the fused Exp-Golomb calls (dct3d_*_eg_frames*): channels 1
-    // and 2 of the host calls' device streams (channel 0: d_eg_out / d_egd_in), a gathered channel for the
-    // two-step option, and the three fronts' status words (3 x 6; their marks share d_egd_mark)
-    DevBuf d_eg_out_x[2], d_egd_in_x[2], d_eg_q_ch, d_egd_status3;
-    uint64_t eg_last_bytes_x[2] = {0, 0};
-    // rate probe (dct3d_rate_frames*): the candidate tables' rows (host copy, device), the per-cube bits when
-    // the caller keeps none, the per-(table, stack, channel) sums and their pinned host copy
-    std::vector<float> rate_tabs_host;
-    DevBuf d_rate_tabs, d_rate_bits, d_rate_sums;
-    uint64_t* h_rate = nullptr;
-    size_t h_rate_bytes = 0;
-    // distortion probe (dct3d_distortion_frames*): the tables' fp64 steps (host copy, device) and the per-cube
-    // squared errors when the caller keeps none; the rows, bits, sums and pinned copy are the rate probe's
-    std::vector<double> dist_steps_host;
-    DevBuf d_dist_steps, d_dist_sse;
-    // per-stack quantiser tables (dct3d_*_eg_frames_vq*): the call's fp64 steps, map and palette rows in one
-    // device buffer and its host copy (VqParams' layout), and -- while such a call runs the stream calls' host
-    // bodies -- the kernels' view of them (else nullptr)
-    // (the host copy is pinned: the upload is one asynchronous DMA, no staging and no wait; the palette's rows
-    // and steps are kept from call to call and rebuilt only when the tables change)
-    DevBuf d_vq;
-    uint8_t* vq_host = nullptr;
-    uint8_t* vq_host_dev = nullptr;  // its device-side address (launch_vq_upload reads it)
-    size_t vq_host_bytes = 0;
-    std::vector<int32_t> vq_tables;
-    std::vector<float> vq_rows;
-    std::vector<double> vq_steps;
-    // (one view per channel: vq_ch[ch] is channel ch's block {steps, FastDiv, map column}, with the cubes per
-    // stack of that channel's plane in the FastDiv -- the chroma plane's under 4:2:0.  A _vq call's channels share
-    // a block where their planes' geometry is the same.  vq == vq_ch.)
-    VqParams vq_ch[3] = {};
-    const VqParams* vq = nullptr;
-    uint32_t vq_ch_stride = 0;  // != 0: a _vqc call's 4:4:4 RGB decode, the bytes from one channel's block to the next
-    // 4:2:0 chroma subsampling (dct3d_ctx_set_chroma): the mode, the stream decode's two chroma planes
-    // (S(Cb) then S(Cr), each [n_stacks * bd][ceil(h / 2)][ceil(w / 2)]: the grey stream decode writes them, the Y
-    // kernel reads them)
-    int chroma = DCT3D_CHROMA_444;
-    DevBuf d_c420;
-    // RGB-domain distortion probe (dct3d_distortion_rgb_frames*): the decoded planes of one range of
-    // stacks (pass 1 writes them, pass 2 reads them), the planes' per-cube squared errors and bits, the candidates'
-    // plane slots, the per-cube RGB errors when the caller keeps none
-    DevBuf d_rgb_planes, d_rgb_psse, d_rgb_pbits, d_rgb_slots, d_rgb_cube;
-    std::vector<int32_t> rgb_tables;
-    // SSIM probe (dct3d_ssim_frames*): the 4 x 4 blocks' moments of one range of stacks and one channel
-    // (per table the uint64 records, then the source's uint32 records) and the window kernel's partial sums; the RGB
-    // and luma SSIM probe keeps a range's records of all its planes there ([plane][candidate], then [plane])
-    DevBuf d_ssim_blk, d_ssim_part;
-    // RGB and luma SSIM probe (dct3d_ssim_rgb_frames*), planes mode with d_window_ssim: the plane
-    // probe's windows, which the caller's [candidate][plane] layout is copied out of
-    DevBuf d_ssim_win;
-};
 
 // diagonal-slice order (CubeUtils.c:5-46): x + y + z ascending; y outer, z middle, x inner
 static int diagonal_order(int bw, int bh, int bd, uint16_t* out) {
@@ -210,7 +71,7 @@ const char* dct3d_strerror(int code) {
 // The end of a synchronous call: the stream polled for a while before blocking (a blocking wait took
 // ~15-40 us to return after the stream's last kernel, profiles/r06/gaps/), so that the caller's next
 // call reaches the device sooner.
-static int stream_wait(dct3d_ctx* c) {
+extern "C++" int rt::stream_wait(dct3d_ctx* c) {
     for (int i = 0; i < 20000; i++) {
         const hipError_t e = hipStreamQuery(c->stream);
         if (e == hipSuccess) return DCT3D_OK;
@@ -332,20 +193,20 @@ static Variant variant_of(const dct3d_ctx* c, const Geom& g) {
 // the stream kernels' and the rate probe's: the colour transform acts on packed RGB24 alone; qt = 2 while a vq
 // call is open (vq_begin .. vq_end: a table per stack, c->vq; the one place that turns it into a variant.  No
 // probe runs inside one, and probe_dev reads no qt)
-static Variant stream_variant_of(const dct3d_ctx* c, const Geom& g) {
+extern "C++" Variant rt::stream_variant_of(const dct3d_ctx* c, const Geom& g) {
     Variant v = variant_of(c, g);
     if (c->vq) v.qt = 2;
     v.colour = (c->opt_colour && g.px == 3) ? 1 : 0;
     return v;
 }
 // a call on packed frames that has no colour stage refuses the option (dct3d.h)
-static bool colour_refused(const dct3d_ctx* c, int px) { return c && c->opt_colour && px == 3; }
+extern "C++" bool rt::colour_refused(const dct3d_ctx* c, int px) { return c && c->opt_colour && px == 3; }
 // 4:2:0 acts on packed frames alone, on top of the colour transform: a packed call with the mode on and
 // the transform off is refused (c420_refused) before anything is queued.  c420_geom: the chroma plane's geometry
 // (grey, ceil(w / 2) x ceil(h / 2)) and its cubes per channel
-static bool c420_on(const dct3d_ctx* c, int px) { return c && c->chroma == DCT3D_CHROMA_420 && px == 3; }
-static bool c420_refused(const dct3d_ctx* c, int px) { return c420_on(c, px) && !c->opt_colour; }
-static bool c420_geom(const Geom& g, int n_stacks, Geom* gc, uint64_t* n_cubes) {
+extern "C++" bool rt::c420_on(const dct3d_ctx* c, int px) { return c && c->chroma == DCT3D_CHROMA_420 && px == 3; }
+extern "C++" bool rt::c420_refused(const dct3d_ctx* c, int px) { return c420_on(c, px) && !c->opt_colour; }
+extern "C++" bool rt::c420_geom(const Geom& g, int n_stacks, Geom* gc, uint64_t* n_cubes) {
     return make_geom(g.w / 2 + g.w % 2, g.h / 2 + g.h % 2, 1, n_stacks, true, gc, n_cubes);
 }
 static const double* qt_steps(const dct3d_ctx* c) { return (const double*)c->d_tabs64.p + kQtStepOff; }
@@ -576,12 +437,12 @@ static hipEvent_t* timing_slot(dct3d_ctx* c) {
     return e;
 }
 // A call of one launch: events 0-1 bracket it, the second pair brackets nothing.
-static hipEvent_t* timer_begin(dct3d_ctx* c) {
+extern "C++" hipEvent_t* rt::timer_begin(dct3d_ctx* c) {
     hipEvent_t* ev = timing_slot(c);
     if (ev) (void)hipEventRecord(ev[0], c->stream);
     return ev;
 }
-static void timer_end(dct3d_ctx* c, hipEvent_t* ev) {
+extern "C++" void rt::timer_end(dct3d_ctx* c, hipEvent_t* ev) {
     if (!ev) return;
     for (int i = 1; i < 4; i++) (void)hipEventRecord(ev[i], c->stream);
 }
@@ -633,7 +494,7 @@ static void set_dec_replay(dct3d_ctx* c, DecodeParams& P) {
 // slot flips at the end of the call -- of every chunk together inside a host entry point's pipeline
 // (batch), and whenever a counting kernel was enqueued, even if a later step of the call failed (the
 // next call must start on the slot this one's launches zeroed).
-static void count_slot_used(dct3d_ctx* c, uint64_t units) {
+extern "C++" void rt::count_slot_used(dct3d_ctx* c, uint64_t units) {
     c->slot_used = true;
     if (c->batch) {
         c->batch_units += units;
@@ -647,20 +508,20 @@ static void count_slot_used(dct3d_ctx* c, uint64_t units) {
 }
 // The start of a call on the device: the last call's statistics no longer stand (inside a host entry point's
 // pipeline the call is one chunk of many: batch_begin did it).
-static void call_begin(dct3d_ctx* c) {
+extern "C++" void rt::call_begin(dct3d_ctx* c) {
     if (c->batch) return;
     c->last_valid = false;
     c->last_count_slot = -1;
     c->slot_used = false;
 }
-static void batch_begin(dct3d_ctx* c) {
+extern "C++" void rt::batch_begin(dct3d_ctx* c) {
     c->batch = true;
     c->batch_units = 0;
     c->slot_used = false;
     c->last_valid = false;
     c->last_count_slot = -1;
 }
-static void batch_end(dct3d_ctx* c) {
+extern "C++" void rt::batch_end(dct3d_ctx* c) {
     c->batch = false;
     if (!c->slot_used) return;
     c->last_count_slot = c->enc_slot;
@@ -685,7 +546,7 @@ static int forward_f64_raster(dct3d_ctx* c, const uint8_t* d_raster, int w, int 
 
 // The encode and decode kernels' parameters for the cubes [0, n_cubes) of geometry g (packed RGB24: n_cubes
 // counts RGB cubes); the address fields: set_address_fields (dct3d_geom.h).
-static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_raster, int32_t* d_q, const Geom& g,
+extern "C++" void rt::fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_raster, int32_t* d_q, const Geom& g,
                                uint64_t n_cubes) {
     memset(&P, 0, sizeof(P));
     P.raster = d_raster;
@@ -703,7 +564,7 @@ static void fill_encode_params(dct3d_ctx* c, EncodeParams& P, const uint8_t* d_r
     P.tab64 = (const double*)c->d_tabs64.p;
     P.recheck = c->opt_enc_no_recheck ? 0u : 1u;
 }
-static void fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q, uint8_t* d_raster, const Geom& g,
+extern "C++" void rt::fill_decode_params(dct3d_ctx* c, DecodeParams& P, const int32_t* d_q, uint8_t* d_raster, const Geom& g,
                                uint64_t n_cubes) {
     P.in = d_q;
     P.out = d_raster;
@@ -1090,7 +951,7 @@ int dct3d_eg_encode_dev(dct3d_ctx* c, const int32_t* d_q, uint64_t n_cubes, uint
 
 // 4:2:0: the encode kernels' cube fields from the chroma plane gc, their address fields (set_address_fields did
 // them) from the frames g, the height set whatever the edge (c420_row8 clamps by it)
-static void c420_cube_fields(EncodeParams& P, const Geom& g, const Geom& gc) {
+extern "C++" void rt::c420_cube_fields(EncodeParams& P, const Geom& g, const Geom& gc) {
     P.cubes_per_stack = (uint32_t)gc.cps();
     P.nbx = (uint32_t)(gc.wp / 8);
     P.div_cps = fast_div(P.cubes_per_stack);
@@ -1098,7 +959,7 @@ static void c420_cube_fields(EncodeParams& P, const Geom& g, const Geom& gc) {
     P.height = (uint32_t)g.h;
 }
 // the chroma loader's edge: a width or a height that is no multiple of 16
-static int c420_edge(const Geom& g) { return g.w % 16 || g.h % 16 ? 1 : 0; }
+extern "C++" int rt::c420_edge(const Geom& g) { return g.w % 16 || g.h % 16 ? 1 : 0; }
 
 // One fused launch chain on the context stream: encode_eg_kernel (transform, quantise, in-wave exact replay,
 // lane-level Exp-Golomb into slots) -> scan over segments -> eg_compact_kernel -> eg_stitch_kernel, for
@@ -1346,880 +1207,6 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
         eg_last_bytes(c, ch) = (tb[ch] + 7) / 8;
     }
     return DCT3D_OK;
-}
-
-// ---- rate probe: the streams' exact sizes under several tables, one transform per cube (dct3d.h) ----
-}  // extern "C"
-// the arguments of both rate calls (nothing is enqueued before they hold)
-static bool rate_args_ok(const dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                         const int32_t* tables, int n_tables, const uint64_t* bits, Geom* g, uint64_t* n_cubes) {
-    if (!c || !make_geom(w, h, channels, n_stacks, true, g, n_cubes)) return false;
-    if (n_tables < 1 || n_tables > DCT3D_RATE_MAX_TABLES || (!tables && n_tables != 1) || !bits) return false;
-    if (!frames && n_stacks) return false;
-    const int n_steps = (int)c->plan.steps.size();
-    if (tables)
-        for (int i = 0; i < n_tables * n_steps; i++)
-            if (tables[i] < kMinStep || tables[i] > kMaxStep) return false;
-    return true;
-}
-// Each table's {1 / step, G, 0.5 - E, step} rows from the context's one plan (encoder_tables: the rows
-// dct3d_plan_query_quant reports for that table), as the encode kernels' LDS copy holds them (enc_tables); with
-// want_steps its steps in fp64 too (as the decode kernels' table)
-static void probe_tables(dct3d_ctx* c, const int32_t* tables, int n_tables, bool want_steps) {
-    static_assert(kRateTabN <= kMaxS && kDistStepN == kMaxS, "a table's rows and steps");
-    const int n_steps = (int)c->plan.steps.size();
-    c->rate_tabs_host.resize((size_t)n_tables * kRateTabN * 4);
-    c->dist_steps_host.resize(want_steps ? (size_t)n_tables * kDistStepN : 0);
-    for (int t = 0; t < n_tables; t++) {
-        int32_t st[kMaxS];
-        float rstep[kMaxS], G[kMaxS], E[kMaxS];
-        for (int s = 0; s < kMaxS; s++) {
-            st[s] = s < n_steps ? (tables ? tables[(size_t)t * n_steps + s] : c->plan.steps[s]) : reference_step(s);
-            if (want_steps) c->dist_steps_host[(size_t)t * kDistStepN + s] = (double)st[s];
-        }
-        encoder_tables(c->plan, st, rstep, G, E);
-        float* row = c->rate_tabs_host.data() + (size_t)t * kRateTabN * 4;
-        for (int s = 0; s < kRateTabN; s++, row += 4) {
-            row[0] = rstep[s];
-            row[1] = G[s];
-            row[2] = 0.5f - E[s];
-            row[3] = (float)st[s];
-        }
-    }
-}
-
-// the pinned buffer the probes' sums come back in
-static int probe_grow_pinned(dct3d_ctx* c, size_t bytes) {
-    if (c->h_rate_bytes >= bytes) return DCT3D_OK;
-    if (c->h_rate) (void)hipHostFree(c->h_rate);
-    c->h_rate = nullptr;
-    c->h_rate_bytes = 0;
-    if (hipHostMalloc((void**)&c->h_rate, bytes, hipHostMallocDefault) != hipSuccess) {
-        c->h_rate = nullptr;
-        return DCT3D_ENOMEM;
-    }
-    c->h_rate_bytes = bytes;
-    return DCT3D_OK;
-}
-
-// The rate probe under 4:2:0 on frames in device memory: channel 0 as the colour transform's launch at
-// the frames' geometry, channels 1 and 2 as the chroma launches over the subsampled planes' cubes (gc), each plane's
-// cube bits in a block of its own ([table][stack][cube]: the layout is ragged, no caller's buffer is offered), the
-// sums per (table, stack) of each put together on the host.  bits: [n_tables][n_stacks][3].
-static int probe_c420_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
-                          int n_tables, uint64_t* bits) {
-    Geom gc;
-    uint64_t nc;
-    if (!c420_geom(g, n_stacks, &gc, &nc)) return DCT3D_EINVAL;
-    const uint64_t ny = g.cps() * (uint64_t)n_stacks;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    if (!c->batch) c->last_units = 0;
-    if (ny == 0) return DCT3D_OK;
-    probe_tables(c, tables, n_tables, false);
-    const uint64_t ts = (uint64_t)n_tables * n_stacks;  // sums per plane (the Y launch's block: three times that)
-    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
-    const size_t y_cubes = (size_t)n_tables * 3 * ny, c_cubes = (size_t)n_tables * nc;
-    const size_t sum_bytes = 5 * ts * sizeof(uint64_t);
-    int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_rate_sums.grow(sum_bytes)) ||
-        (rc = c->d_rate_bits.grow((y_cubes + 2 * c_cubes) * sizeof(uint16_t))) || (rc = probe_grow_pinned(c, sum_bytes)))
-        return rc;
-    uint16_t* const cb_y = (uint16_t*)c->d_rate_bits.p;
-    uint16_t* const cb_c[2] = {cb_y + y_cubes, cb_y + y_cubes + c_cubes};
-    // (the Y launch fills channel 0's third of its [stack][channel][cube] block; the sums of the rest are dropped)
-    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemsetAsync(cb_y, 0, y_cubes * sizeof(uint16_t), c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
-    EncodeParams P, Pc;
-    fill_encode_params(c, P, d_frames, nullptr, g, ny);
-    fill_encode_params(c, Pc, d_frames, nullptr, g, nc);
-    c420_cube_fields(Pc, g, gc);
-    const Variant v = stream_variant_of(c, g);
-    hipEvent_t* ev = timer_begin(c);
-    rc = DCT3D_OK;
-    for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
-        for (int ch = 0; ch < 3 && !rc; ch++) {
-            RateParams R = {};
-            R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
-            R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
-            R.ch = ch;
-            R.table_stride = ch ? nc : 3 * ny;
-            R.cube_bits = (ch ? cb_c[ch - 1] : cb_y) + (size_t)t0 * R.table_stride;
-            if (ch ? launch_rate_c420(v.D, c420_edge(g), Pc, R, c->stream) : launch_rate_ycc(v.D, v.edge, P, R, c->stream))
-                rc = DCT3D_EKERNEL;
-            else c->slot_used = true;
-        }
-    uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
-    if (!rc && launch_rate_sum(cb_y, (uint32_t)g.cps(), 3 * ts, d_sums, c->stream)) rc = DCT3D_EKERNEL;
-    for (int k = 0; k < 2 && !rc; k++)
-        if (launch_rate_sum(cb_c[k], (uint32_t)gc.cps(), ts, d_sums + (3 + k) * ts, c->stream)) rc = DCT3D_EKERNEL;
-    timer_end(c, ev);
-    if (!rc && hipMemcpyAsync(c->h_rate, d_sums, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
-    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * (ny + 2 * nc) * (uint64_t)c->plan.cs);
-    if (rc) return rc;
-    for (uint64_t i = 0; i < ts; i++) {
-        bits[3 * i] = c->h_rate[3 * i];
-        bits[3 * i + 1] = c->h_rate[3 * ts + i];
-        bits[3 * i + 2] = c->h_rate[4 * ts + i];
-    }
-    return DCT3D_OK;
-}
-
-// Both probes on frames in device memory (the arguments hold: rate_args_ok).  sse: the distortion probe (bits
-// optional; d_cube_sse the caller's per-cube buffer or nullptr); no sse: the rate probe (d_cube_bits likewise).
-static int probe_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                     uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse, uint16_t* d_cube_bits) {
-    const bool dist = sse != nullptr;
-    if (!dist && c420_on(c, g.px)) return probe_c420_dev(c, d_frames, g, n_stacks, tables, n_tables, bits);
-    const int channels = g.px;
-    const uint64_t n_cubes = g.cps() * (uint64_t)n_stacks;  // per channel
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    if (!c->batch) c->last_units = 0;
-    if (n_cubes == 0) return DCT3D_OK;
-    probe_tables(c, tables, n_tables, dist);
-    const uint64_t stride = (uint64_t)channels * n_cubes;              // cubes of one table
-    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;  // sums (the squared errors, then the bits)
-    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
-    const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
-    const size_t sum_bytes = ((dist ? 1 : 0) + (bits ? 1 : 0)) * n_runs * sizeof(uint64_t);
-    int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (dist && (rc = c->d_dist_steps.grow(step_bytes))) ||
-        (rc = c->d_rate_sums.grow(sum_bytes)) ||
-        (dist && !d_cube_sse && (rc = c->d_dist_sse.grow((size_t)n_tables * stride * sizeof(uint32_t)))) ||
-        (bits && !d_cube_bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))) ||
-        (rc = probe_grow_pinned(c, sum_bytes)))
-        return rc;
-    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        (dist && hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess))
-        return DCT3D_EDEVICE;
-    uint32_t* const cube_sse = d_cube_sse ? d_cube_sse : (uint32_t*)c->d_dist_sse.p;
-    uint16_t* const cube_bits = d_cube_bits ? d_cube_bits : bits ? (uint16_t*)c->d_rate_bits.p : nullptr;
-    EncodeParams P;
-    fill_encode_params(c, P, d_frames, nullptr, g, n_cubes);
-    DistParams R = {};
-    R.table_stride = stride;
-    if (dist) {  // the decode's certificate constants and the replay's table, the test margin included
-        DecodeParams DP;
-        fill_decode_params(c, DP, nullptr, nullptr, g, n_cubes);
-        R.inv_coef_t = DP.inv_coef_t;
-        R.dec_G = DP.dec_G;
-        R.dec_E = DP.dec_E;
-        R.dec_l1_max = DP.dec_l1_max;
-    }
-    const Variant v = stream_variant_of(c, g);  // (the probes read tables of their own: no qt; colour: the rate probe)
-    hipEvent_t* ev = timer_begin(c);
-    rc = DCT3D_OK;
-    // kRateTables tables per launch, one launch per channel (as the stream encode's chains)
-    for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables)
-        for (int ch = 0; ch < channels && !rc; ch++) {
-            R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
-            R.cube_bits = cube_bits ? cube_bits + (size_t)t0 * stride : nullptr;
-            R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
-            R.ch = ch;
-            if (dist) {
-                R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
-                R.cube_sse = cube_sse + (size_t)t0 * stride;
-            }
-            if (dist       ? launch_distortion(v.D, v.px, v.edge, P, R, c->stream)
-                : v.colour ? launch_rate_ycc(v.D, v.edge, P, R, c->stream)
-                           : launch_rate(v.D, v.px, v.edge, P, R, c->stream))
-                rc = DCT3D_EKERNEL;
-            else c->slot_used = true;
-        }
-    uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
-    uint64_t* const d_bit_sums = d_sums + (dist ? n_runs : 0);
-    if (!rc && dist && launch_distortion_sum(cube_sse, (uint32_t)g.cps(), n_runs, d_sums, c->stream)) rc = DCT3D_EKERNEL;
-    if (!rc && bits && launch_rate_sum(cube_bits, (uint32_t)g.cps(), n_runs, d_bit_sums, c->stream)) rc = DCT3D_EKERNEL;
-    timer_end(c, ev);
-    if (!rc && hipMemcpyAsync(c->h_rate, d_sums, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
-    // synchronous on return (the sums are a host result; the tables' host copies and buffers are free again)
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
-    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
-    if (rc) return rc;
-    if (dist) memcpy(sse, c->h_rate, n_runs * sizeof(uint64_t));
-    if (bits) memcpy(bits, c->h_rate + (d_bit_sums - d_sums), n_runs * sizeof(uint64_t));
-    return DCT3D_OK;
-}
-
-// The SSIM probe on frames in device memory (the arguments hold: rate_args_ok).  The distortion probe's
-// launches with the block-moment arm, over ranges of stacks whose block records fit kSsimBlockBudget (or one stack
-// at a time); per range and channel the records, then the windows of all tables and their sums.  sse and bits
-// (optional) as probe_dev leaves them.
-constexpr size_t kSsimBlockBudget = DCT3D_SSIM_BLOCK_BUDGET;
-static int ssim_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                    int64_t* ssim, uint64_t* sse, uint64_t* bits, int32_t* d_win) {
-    const int channels = g.px, D = c->bd;
-    const uint64_t cps = g.cps(), n_cubes = cps * (uint64_t)n_stacks;  // per channel
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    if (!c->batch) c->last_units = 0;
-    if (n_cubes == 0) return DCT3D_OK;
-    probe_tables(c, tables, n_tables, true);
-    const uint32_t nbx = ((uint32_t)g.w + 3) / 4, nby = ((uint32_t)g.h + 3) / 4;
-    const uint32_t nwx = nbx > 1 ? nbx - 1 : 1, nwy = nby > 1 ? nby - 1 : 1;
-    const uint64_t blk_per_stack = (uint64_t)D * nbx * nby, win_per_stack = (uint64_t)D * nwx * nwy;
-    if (win_per_stack >= (1ull << 32)) return DCT3D_EINVAL;
-    const uint64_t rec_per_stack = blk_per_stack * (8ull * n_tables + 4);  // bytes (dct3d.h)
-    const int rs = (int)std::max<uint64_t>(1, std::min<uint64_t>({kSsimBlockBudget / rec_per_stack, (uint64_t)n_stacks, 65535ull}));
-    const uint64_t blk_stride = blk_per_stack * rs;
-    const uint32_t bpr = (uint32_t)std::min<uint64_t>((win_per_stack + kSsimWinPerBlock - 1) / kSsimWinPerBlock, kSsimMaxBpr);
-    const uint64_t stride = (uint64_t)channels * n_cubes;              // cubes of one table
-    const uint64_t n_runs = (uint64_t)n_tables * n_stacks * channels;  // sums: the SSIM, then the squared errors, then the bits
-    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
-    const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
-    const size_t sum_bytes = (1 + (sse ? 1 : 0) + (bits ? 1 : 0)) * n_runs * sizeof(uint64_t);
-    int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_dist_steps.grow(step_bytes)) || (rc = c->d_rate_sums.grow(sum_bytes)) ||
-        (sse && (rc = c->d_dist_sse.grow((size_t)n_tables * stride * sizeof(uint32_t)))) ||
-        (bits && (rc = c->d_rate_bits.grow((size_t)n_tables * stride * sizeof(uint16_t)))) ||
-        (rc = c->d_ssim_blk.grow((size_t)rec_per_stack * rs)) ||
-        (rc = c->d_ssim_part.grow((size_t)n_tables * rs * bpr * sizeof(int64_t))) || (rc = probe_grow_pinned(c, sum_bytes)))
-        return rc;
-    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
-    uint32_t* const cube_sse = sse ? (uint32_t*)c->d_dist_sse.p : nullptr;
-    uint16_t* const cube_bits = bits ? (uint16_t*)c->d_rate_bits.p : nullptr;
-    uint64_t* const blk_y = (uint64_t*)c->d_ssim_blk.p;
-    uint32_t* const blk_x = (uint32_t*)(blk_y + (size_t)n_tables * blk_stride);
-    int64_t* const d_ssim_sums = (int64_t*)c->d_rate_sums.p;
-    uint64_t* const d_sse_sums = (uint64_t*)c->d_rate_sums.p + n_runs;
-    uint64_t* const d_bit_sums = d_sse_sums + (sse ? n_runs : 0);
-    const Variant v = stream_variant_of(c, g);
-    hipEvent_t* ev = timer_begin(c);
-    rc = DCT3D_OK;
-    for (int s0 = 0; s0 < n_stacks && !rc; s0 += rs) {
-        const int ns = n_stacks - s0 < rs ? n_stacks - s0 : rs;
-        EncodeParams P;
-        fill_encode_params(c, P, d_frames + (size_t)s0 * g.plane() * D, nullptr, g, cps * ns);
-        DecodeParams DP;
-        fill_decode_params(c, DP, nullptr, nullptr, g, cps * ns);
-        SsimParams R = {};
-        R.table_stride = stride;
-        R.inv_coef_t = DP.inv_coef_t;
-        R.dec_G = DP.dec_G;
-        R.dec_E = DP.dec_E;
-        R.dec_l1_max = DP.dec_l1_max;
-        R.blk_x = blk_x;
-        R.blk_stride = blk_stride;
-        R.nbx = nbx;
-        R.nby = nby;
-        const size_t cube_off = (size_t)s0 * channels * cps;  // the range's first cube in a table's block
-        for (int ch = 0; ch < channels && !rc; ch++) {
-            // kRateTables tables per launch (as probe_dev); every launch writes the source's records (the same)
-            for (int t0 = 0; t0 < n_tables && !rc; t0 += kRateTables) {
-                R.tabs = (const float4*)c->d_rate_tabs.p + (size_t)t0 * kRateTabN;
-                R.steps = (const double*)c->d_dist_steps.p + (size_t)t0 * kDistStepN;
-                R.n_tables = n_tables - t0 < kRateTables ? n_tables - t0 : kRateTables;
-                R.ch = ch;
-                R.cube_bits = cube_bits ? cube_bits + (size_t)t0 * stride + cube_off : nullptr;
-                R.cube_sse = cube_sse ? cube_sse + (size_t)t0 * stride + cube_off : nullptr;
-                R.blk_y = blk_y + (size_t)t0 * blk_stride;
-                if (launch_distortion_ssim(v.D, v.px, v.edge, P, R, c->stream)) rc = DCT3D_EKERNEL;
-                else c->slot_used = true;
-            }
-            SsimWinParams W = {};
-            W.blk_y = blk_y;
-            W.blk_x = blk_x;
-            W.blk_stride = blk_stride;
-            W.win_t = (uint64_t)n_stacks * channels * win_per_stack;
-            W.win_s = (uint64_t)channels * win_per_stack;
-            W.win = d_win ? d_win + ((size_t)s0 * channels + ch) * win_per_stack : nullptr;
-            W.part = (int64_t*)c->d_ssim_part.p;
-            W.w = (uint32_t)g.w;
-            W.h = (uint32_t)g.h;
-            W.nbx = nbx;
-            W.nby = nby;
-            W.nwx = nwx;
-            W.nwy = nwy;
-            W.depth = (uint32_t)D;
-            W.ns = (uint32_t)ns;
-            W.n_tables = (uint32_t)n_tables;
-            W.bpr = bpr;
-            if (!rc && (launch_ssim_window(W, c->stream) ||
-                        launch_ssim_sum(W.part, bpr, W.ns, W.n_tables, d_ssim_sums + ((size_t)s0 * channels + ch),
-                                        (uint64_t)n_stacks * channels, (uint64_t)channels, c->stream)))
-                rc = DCT3D_EKERNEL;
-        }
-    }
-    if (!rc && sse && launch_distortion_sum(cube_sse, (uint32_t)cps, n_runs, d_sse_sums, c->stream)) rc = DCT3D_EKERNEL;
-    if (!rc && bits && launch_rate_sum(cube_bits, (uint32_t)cps, n_runs, d_bit_sums, c->stream)) rc = DCT3D_EKERNEL;
-    timer_end(c, ev);
-    if (!rc && hipMemcpyAsync(c->h_rate, c->d_rate_sums.p, sum_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
-    if (c->slot_used) count_slot_used(c, (uint64_t)n_tables * stride * (uint64_t)c->plan.cs);
-    if (rc) return rc;
-    memcpy(ssim, c->h_rate, n_runs * sizeof(int64_t));
-    if (sse) memcpy(sse, c->h_rate + n_runs, n_runs * sizeof(uint64_t));
-    if (bits) memcpy(bits, c->h_rate + (d_bit_sums - (uint64_t*)c->d_rate_sums.p), n_runs * sizeof(uint64_t));
-    return DCT3D_OK;
-}
-
-// The probes on frames in host memory: the frames go up in chunks of whole stacks (one staging buffer of 64 MiB
-// at most, or one stack), each chunk's sums land at its stacks' places; the chunks' statistics add up (batch).
-// ssim: the SSIM probe (sse and bits optional); else as probe_dev.
-static int probe_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                      uint64_t* sse, uint64_t* bits, int64_t* ssim = nullptr) {
-    const int channels = g.px;
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    const size_t stack_bytes = (size_t)g.plane() * c->bd;  // the unpadded frames of one stack
-    constexpr size_t kChunkBytes = (size_t)64 << 20;       // (as the host-pointer pipeline's chunks)
-    const int per = stack_bytes ? (int)std::max<size_t>(1, std::min<size_t>(kChunkBytes / stack_bytes, (size_t)(n_stacks > 0 ? n_stacks : 1))) : 1;
-    int rc;
-    if ((rc = c->h_in.grow(stack_bytes * per ? stack_bytes * per : 1))) return rc;
-    std::vector<uint64_t> part((size_t)3 * n_tables * per * channels);
-    c->last_units = 0;  // (no stack: no chunk)
-    batch_begin(c);
-    rc = DCT3D_OK;
-    for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
-        const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
-        const size_t run = (size_t)ns * channels;
-        if (hipMemcpyAsync(c->h_in.p, frames + (size_t)s0 * stack_bytes, (size_t)ns * stack_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            rc = DCT3D_EDEVICE;
-            break;
-        }
-        uint64_t* const ps = sse ? part.data() : nullptr;
-        uint64_t* const pb = bits ? part.data() + (sse ? (size_t)n_tables * run : 0) : nullptr;
-        int64_t* const pm = (int64_t*)part.data() + (size_t)2 * n_tables * per * channels;
-        rc = ssim ? ssim_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, pm, ps, pb, nullptr)
-                  : probe_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, ps, pb, nullptr, nullptr);
-        for (int t = 0; t < n_tables && !rc; t++) {
-            const size_t dst = ((size_t)t * n_stacks + s0) * channels;
-            if (ssim) memcpy(ssim + dst, pm + (size_t)t * run, run * sizeof(int64_t));
-            if (sse) memcpy(sse + dst, ps + (size_t)t * run, run * sizeof(uint64_t));
-            if (bits) memcpy(bits + dst, pb + (size_t)t * run, run * sizeof(uint64_t));
-        }
-    }
-    batch_end(c);
-    return rc;
-}
-extern "C" {
-
-int dct3d_rate_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
-                          const int32_t* tables, int n_tables, uint64_t* bits, uint16_t* d_cube_bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
-    // 4:2:0: the cube layout is ragged (the chroma planes have fewer cubes): only the totals are offered
-    if (c420_refused(c, channels) || (c420_on(c, channels) && d_cube_bits)) return DCT3D_EINVAL;
-    return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, nullptr, bits, nullptr, d_cube_bits);
-}
-
-int dct3d_rate_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                      const int32_t* tables, int n_tables, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, bits, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (c420_refused(c, channels)) return DCT3D_EINVAL;
-    return probe_host(c, frames, g, n_stacks, tables, n_tables, nullptr, bits);
-}
-
-// ---- distortion probe: the exact squared error of encode + decode under several tables, one transform per
-//      cube and one certified decode tile per cube and table (dct3d.h) ----
-int dct3d_distortion_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
-                                const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits, uint32_t* d_cube_sse) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (colour_refused(c, channels)) return DCT3D_EINVAL;
-    return probe_dev(c, d_frames, g, n_stacks, tables, n_tables, sse, bits, d_cube_sse, nullptr);
-}
-
-int dct3d_distortion_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                            const int32_t* tables, int n_tables, uint64_t* sse, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, sse, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (colour_refused(c, channels)) return DCT3D_EINVAL;
-    return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits);
-}
-
-// ---- SSIM probe: the exact 8 x 8 / stride 4 windowed SSIM of encode + decode under several tables, from the
-//      distortion probe's transform and decode tile per cube (dct3d.h states the definition) ----
-int dct3d_ssim_windows(int w, int h, int* nwx, int* nwy) {
-    if (w < 1 || h < 1 || !nwx || !nwy) return DCT3D_EINVAL;
-    const int nbx = w / 4 + (w % 4 != 0), nby = h / 4 + (h % 4 != 0);
-    *nwx = nbx > 1 ? nbx - 1 : 1;
-    *nwy = nby > 1 ? nby - 1 : 1;
-    return DCT3D_OK;
-}
-
-int dct3d_ssim_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int channels, int n_stacks,
-                          const int32_t* tables, int n_tables, int64_t* ssim, uint64_t* sse, uint64_t* bits, int32_t* d_window_ssim) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, d_frames, w, h, channels, n_stacks, tables, n_tables, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (colour_refused(c, channels) || c420_refused(c, channels)) return DCT3D_EINVAL;
-    return ssim_dev(c, d_frames, g, n_stacks, tables, n_tables, ssim, sse, bits, d_window_ssim);
-}
-
-int dct3d_ssim_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int channels, int n_stacks,
-                      const int32_t* tables, int n_tables, int64_t* ssim, uint64_t* sse, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rate_args_ok(c, frames, w, h, channels, n_stacks, tables, n_tables, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (colour_refused(c, channels) || c420_refused(c, channels)) return DCT3D_EINVAL;
-    return probe_host(c, frames, g, n_stacks, tables, n_tables, sse, bits, ssim);
-}
-
-// ---- RGB-domain distortion probe: the exact squared error, in the RGB pixels, of the stream encode + decode
-//      under (Y, Cb, Cr) table triples, in all three colour modes (dct3d.h) ----
-}  // extern "C"
-// the decoded planes of one range of stacks stay under this many bytes (or one stack's): the size of the host-pointer
-// calls' staging chunk
-constexpr size_t kRgbPlaneBudget = DCT3D_RGB_PLANE_BUDGET;
-// the arguments of both calls (nothing is enqueued before they hold); packed RGB24 frames
-static bool rgb_args_ok(const dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables,
-                        int n_tables, const uint8_t* cand, int n_cand, const uint64_t* sse, Geom* g, uint64_t* n_cubes) {
-    if (!rate_args_ok(c, frames, w, h, 3, n_stacks, tables, n_tables, sse, g, n_cubes)) return false;
-    if (n_cand < 1 || n_cand > DCT3D_RATE_MAX_TABLES || (!cand && n_cand != n_tables)) return false;
-    if (cand)
-        for (int i = 0; i < 3 * n_cand; i++)
-            if (cand[i] >= n_tables) return false;
-    return !c420_refused(c, 3);
-}
-// candidate i = (i, i, i) where the caller gives no list
-static const uint8_t* rgb_cand(const uint8_t* cand, int n_cand, uint8_t (&own)[3 * DCT3D_RATE_MAX_TABLES]) {
-    if (cand) return cand;
-    for (int i = 0; i < 3 * n_cand; i++) own[i] = (uint8_t)(i / 3);
-    return own;
-}
-
-// Planes mode: the distortion probe itself; a candidate's error is the sum of its three planes' under their tables,
-// per stack on the host and per cube by a gather over the probe's per-cube buffer.
-static int probe_rgb_planes_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
-                                int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse,
-                                uint64_t* bits, uint32_t* d_cube_sse) {
-    const size_t n_runs = (size_t)n_tables * n_stacks * 3;
-    std::vector<uint64_t> ps(n_runs);
-    int rc = probe_dev(c, d_frames, g, n_stacks, tables, n_tables, ps.data(), bits, nullptr, nullptr);
-    if (rc || n_stacks == 0) return rc;
-    for (int i = 0; i < n_cand; i++)
-        for (int s = 0; s < n_stacks; s++) {
-            uint64_t v = 0;
-            for (int k = 0; k < 3; k++) v += ps[((size_t)cand[3 * i + k] * n_stacks + s) * 3 + k];
-            sse[(size_t)i * n_stacks + s] = v;
-        }
-    if (plane_sse) memcpy(plane_sse, ps.data(), n_runs * sizeof(uint64_t));
-    if (!d_cube_sse) return DCT3D_OK;
-    const uint64_t n_cubes = g.cps() * (uint64_t)n_stacks;
-    if ((rc = c->d_rgb_slots.grow((size_t)3 * n_cand))) return rc;
-    if (hipMemcpyAsync(c->d_rgb_slots.p, cand, (size_t)3 * n_cand, hipMemcpyHostToDevice, c->stream) != hipSuccess) return DCT3D_EDEVICE;
-    if (launch_distortion_rgb_gather((const uint32_t*)c->d_dist_sse.p, 3 * n_cubes, (const uint8_t*)c->d_rgb_slots.p, (uint32_t)n_cand,
-                                     (uint32_t)g.cps(), (uint32_t)n_stacks, d_cube_sse, n_cubes, c->stream))
-        rc = DCT3D_EKERNEL;
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;  // (the candidates' host copy is free again)
-    return rc;
-}
-
-// YCbCr and YCbCr + 4:2:0 on frames in device memory.  The stacks go in ranges whose decoded planes fit the budget;
-// per range, pass 1 per plane and kRateTables tables (launch_distortion_plane), the planes' sums, pass 2 over the
-// candidates (launch_distortion_rgb_combine).  A plane is coded under the tables some candidate uses for it, or
-// under all of them when plane_sse or bits is asked for.
-// sm (the RGB and luma SSIM probe; sse is optional then): pass 2 is launch_ssim_rgb_block -- the 4 x 4
-// blocks' moments of R, G, B (and luma) per candidate in d_ssim_blk -- and per plane the SSIM probe's windows and
-// sums; the combine kernel runs as well when sse is asked for.  The ranges fit kSsimBlockBudget too.
-struct SsimRgbOut {
-    int64_t* ssim;    // [n_cand][n_stacks][3]
-    int64_t* ssim_y;  // [n_cand][n_stacks] or nullptr
-    int32_t* d_win;   // device [n_cand][3][n_stacks][D][nwy][nwx] or nullptr
-};
-static int probe_rgb_ycc_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
-                             int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits,
-                             uint32_t* d_cube_sse, const SsimRgbOut* sm = nullptr) {
-    const bool c420 = c420_on(c, 3);
-    Geom gp[3];  // the planes' geometries (grey)
-    uint64_t nc_dummy;
-    if (!make_geom(g.w, g.h, 1, n_stacks, true, &gp[0], &nc_dummy)) return DCT3D_EINVAL;
-    if (c420 ? !c420_geom(g, n_stacks, &gp[1], &nc_dummy) : !make_geom(g.w, g.h, 1, n_stacks, true, &gp[1], &nc_dummy)) return DCT3D_EINVAL;
-    gp[2] = gp[1];
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    call_begin(c);
-    if (!c->batch) c->last_units = 0;
-    if (n_stacks == 0) return DCT3D_OK;
-    // each plane's tables, and where a candidate finds its plane
-    const bool all_pairs = plane_sse || bits;
-    std::vector<int> L[3];
-    int slot_of[3][DCT3D_RATE_MAX_TABLES];
-    for (int k = 0; k < 3; k++) {
-        for (int t = 0; t < n_tables; t++) slot_of[k][t] = -1;
-        if (all_pairs)
-            for (int t = 0; t < n_tables; t++) {
-                slot_of[k][t] = t;
-                L[k].push_back(t);
-            }
-        else
-            for (int i = 0; i < n_cand; i++) {
-                const int t = cand[3 * i + k];
-                if (slot_of[k][t] < 0) {
-                    slot_of[k][t] = (int)L[k].size();
-                    L[k].push_back(t);
-                }
-            }
-    }
-    const int n_steps = (int)c->plan.steps.size();
-    size_t toff[4] = {0, L[0].size(), L[0].size() + L[1].size(), L[0].size() + L[1].size() + L[2].size()};
-    const size_t NT = toff[3];
-    c->rgb_tables.resize(NT * n_steps + 3 * DCT3D_RATE_MAX_TABLES);  // (the tail: the candidates' slots, bytes)
-    for (int k = 0; k < 3; k++)
-        for (size_t i = 0; i < L[k].size(); i++)
-            for (int s = 0; s < n_steps; s++)
-                c->rgb_tables[(toff[k] + i) * n_steps + s] = tables ? tables[(size_t)L[k][i] * n_steps + s] : c->plan.steps[s];
-    uint8_t* const slots_host = (uint8_t*)(c->rgb_tables.data() + NT * n_steps);
-    for (int i = 0; i < n_cand; i++)
-        for (int k = 0; k < 3; k++) slots_host[3 * i + k] = (uint8_t)slot_of[k][cand[3 * i + k]];
-    probe_tables(c, c->rgb_tables.data(), (int)NT, true);
-
-    const int D = c->bd;
-    size_t cps[3], pframes[3];  // cubes per stack, bytes of one stack's frames of the plane
-    for (int k = 0; k < 3; k++) {
-        cps[k] = (size_t)gp[k].cps();
-        pframes[k] = (size_t)gp[k].w * gp[k].h * D;
-    }
-    size_t stack_planes = 0, stack_cubes = 0;
-    for (int k = 0; k < 3; k++) {
-        stack_planes += L[k].size() * pframes[k];
-        stack_cubes += L[k].size() * cps[k];
-    }
-    size_t per_z = std::min<size_t>(kRgbPlaneBudget / stack_planes, (size_t)n_stacks);
-    // the SSIM records of a stack: the blocks of its D frames, per plane 8 bytes per candidate and 4 for the source
-    const uint32_t nbx4 = ((uint32_t)g.w + 3) / 4, nby4 = ((uint32_t)g.h + 3) / 4;
-    const uint32_t nwx = nbx4 > 1 ? nbx4 - 1 : 1, nwy = nby4 > 1 ? nby4 - 1 : 1;
-    const uint64_t blk_per_stack = (uint64_t)D * nbx4 * nby4, win_per_stack = (uint64_t)D * nwx * nwy;
-    const int n_sp = sm ? (sm->ssim_y ? 4 : 3) : 0;  // the planes of the records
-    const uint64_t rec_per_stack = blk_per_stack * (8ull * n_cand + 4) * n_sp;
-    if (sm) {
-        if (win_per_stack >= (1ull << 32)) return DCT3D_EINVAL;
-        per_z = std::min<size_t>({per_z, (size_t)(kSsimBlockBudget / rec_per_stack), (size_t)65535});
-    }
-    const int per = (int)std::max<size_t>(1, per_z);
-    const uint32_t bpr = (uint32_t)std::min<uint64_t>((win_per_stack + kSsimWinPerBlock - 1) / kSsimWinPerBlock, kSsimMaxBpr);
-    const uint64_t out_stride = cps[0] * (uint64_t)n_stacks;
-    const size_t n_psums = NT * (size_t)n_stacks, n_rgb = (size_t)n_cand * n_stacks;
-    // the sums: the planes' errors [and bits], the candidates' errors, [the candidates' SSIM of R, G, B, of the luma]
-    const size_t n_sums = n_psums * (bits ? 2 : 1) + n_rgb * (1 + (size_t)n_sp);
-    const size_t tab_bytes = c->rate_tabs_host.size() * sizeof(float);
-    const size_t step_bytes = c->dist_steps_host.size() * sizeof(double);
-    int rc;
-    if ((rc = c->d_rate_tabs.grow(tab_bytes)) || (rc = c->d_dist_steps.grow(step_bytes)) ||
-        (rc = c->d_rate_sums.grow(n_sums * sizeof(uint64_t))) || (rc = c->d_rgb_planes.grow(stack_planes * per)) ||
-        (rc = c->d_rgb_psse.grow(stack_cubes * per * sizeof(uint32_t))) ||
-        (bits && (rc = c->d_rgb_pbits.grow(stack_cubes * per * sizeof(uint16_t)))) ||
-        (rc = c->d_rgb_slots.grow((size_t)3 * n_cand)) ||
-        (sse && !d_cube_sse && (rc = c->d_rgb_cube.grow((size_t)n_cand * out_stride * sizeof(uint32_t)))) ||
-        (sm && ((rc = c->d_ssim_blk.grow((size_t)rec_per_stack * per)) ||
-                (rc = c->d_ssim_part.grow((size_t)n_cand * per * bpr * sizeof(int64_t))))) ||
-        (rc = probe_grow_pinned(c, n_sums * sizeof(uint64_t))))
-        return rc;
-    if (hipMemcpyAsync(c->d_rate_tabs.p, c->rate_tabs_host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->d_dist_steps.p, c->dist_steps_host.data(), step_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->d_rgb_slots.p, slots_host, (size_t)3 * n_cand, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return DCT3D_EDEVICE;
-    uint32_t* const cube_out = d_cube_sse ? d_cube_sse : (uint32_t*)c->d_rgb_cube.p;
-    uint64_t* const d_sums = (uint64_t*)c->d_rate_sums.p;
-    uint64_t* const d_rgb_sums = d_sums + n_psums * (bits ? 2 : 1);
-    int64_t* const d_ssim_sums = (int64_t*)(d_rgb_sums + n_rgb);
-    const size_t stack_bytes = (size_t)g.plane() * D;
-    DecodeParams DP;
-    fill_decode_params(c, DP, nullptr, nullptr, g, 0);  // the decode's certificate constants, the test margin included
-    hipEvent_t* ev = timer_begin(c);
-    rc = DCT3D_OK;
-    for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
-        const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
-        const uint8_t* const fr = d_frames + (size_t)s0 * stack_bytes;
-        uint8_t* planes[3];
-        uint32_t* psse[3];
-        uint16_t* pbits[3];
-        planes[0] = (uint8_t*)c->d_rgb_planes.p;
-        psse[0] = (uint32_t*)c->d_rgb_psse.p;
-        pbits[0] = bits ? (uint16_t*)c->d_rgb_pbits.p : nullptr;
-        for (int k = 1; k < 3; k++) {
-            planes[k] = planes[k - 1] + L[k - 1].size() * pframes[k - 1] * ns;
-            psse[k] = psse[k - 1] + L[k - 1].size() * cps[k - 1] * ns;
-            pbits[k] = bits ? pbits[k - 1] + L[k - 1].size() * cps[k - 1] * ns : nullptr;
-        }
-        for (int k = 0; k < 3 && !rc; k++) {
-            const bool sub = c420 && k > 0;
-            const uint64_t ncu = cps[k] * (uint64_t)ns;
-            EncodeParams P;
-            fill_encode_params(c, P, fr, nullptr, g, ncu);
-            if (sub) c420_cube_fields(P, g, gp[k]);
-            DistPlaneParams R = {};
-            R.table_stride = ncu;
-            R.ch = k;
-            R.inv_coef_t = DP.inv_coef_t;
-            R.dec_G = DP.dec_G;
-            R.dec_E = DP.dec_E;
-            R.dec_l1_max = DP.dec_l1_max;
-            R.plane_stride = pframes[k] * ns;
-            R.pw = (uint32_t)gp[k].w;
-            R.ph = (uint32_t)gp[k].h;
-            const int nk = (int)L[k].size();
-            for (int t0 = 0; t0 < nk && !rc; t0 += kRateTables) {
-                R.n_tables = nk - t0 < kRateTables ? nk - t0 : kRateTables;
-                R.tabs = (const float4*)c->d_rate_tabs.p + (toff[k] + t0) * kRateTabN;
-                R.steps = (const double*)c->d_dist_steps.p + (toff[k] + t0) * kDistStepN;
-                R.cube_sse = psse[k] + (size_t)t0 * ncu;
-                R.cube_bits = bits ? pbits[k] + (size_t)t0 * ncu : nullptr;
-                R.planes = planes[k] + (size_t)t0 * R.plane_stride;
-                if (launch_distortion_plane(D, sub ? c420_edge(g) : (g.edge() ? 1 : 0), sub ? 2 : 1, P, R, c->stream)) rc = DCT3D_EKERNEL;
-                else c->slot_used = true;
-            }
-            // this range's sums of plane k: [table of L[k]][stack of the range]
-            uint64_t* const ds = d_sums + (size_t)s0 * NT + toff[k] * ns;
-            if (!rc && launch_distortion_sum(psse[k], (uint32_t)cps[k], (uint64_t)nk * ns, ds, c->stream)) rc = DCT3D_EKERNEL;
-            if (!rc && bits && launch_rate_sum(pbits[k], (uint32_t)cps[k], (uint64_t)nk * ns, ds + n_psums, c->stream)) rc = DCT3D_EKERNEL;
-        }
-        if (rc) break;
-        RgbCombineParams C = {};
-        C.frames = fr;
-        C.y = planes[0];
-        C.cb = planes[1];
-        C.cr = planes[2];
-        C.y_stride = pframes[0] * ns;
-        C.c_stride = pframes[1] * ns;
-        C.w = (uint32_t)g.w;
-        C.h = (uint32_t)g.h;
-        C.cw = (uint32_t)gp[1].w;
-        C.chh = (uint32_t)gp[1].h;
-        C.shift = c420 ? 1u : 0u;
-        C.nbx = (uint32_t)(g.wp / 8);
-        C.cubes_per_stack = (uint32_t)cps[0];
-        C.n_cubes = (uint32_t)(cps[0] * ns);
-        C.div_cps = fast_div(C.cubes_per_stack);
-        C.div_nbx = fast_div(C.nbx);
-        C.slots = (const uint8_t*)c->d_rgb_slots.p;
-        C.n_cand = (uint32_t)n_cand;
-        C.cube_sse = cube_out + (size_t)s0 * cps[0];
-        C.cand_stride = out_stride;
-        if (sse && launch_distortion_rgb_combine(D, C, c->stream)) rc = DCT3D_EKERNEL;
-        if (!sm || rc) continue;
-        // the range's block records, then per plane the windows of all candidates and their sums per (candidate, stack)
-        SsimRgbParams S = {};
-        S.C = C;
-        S.C.cube_sse = nullptr;
-        S.blk_stride = blk_per_stack * ns;
-        S.blk_y = (uint64_t*)c->d_ssim_blk.p;
-        S.blk_x = (uint32_t*)(S.blk_y + (size_t)n_sp * n_cand * S.blk_stride);
-        S.nbx4 = nbx4;
-        S.nby4 = nby4;
-        if (launch_ssim_rgb_block(D, n_sp == 4, S, c->stream)) rc = DCT3D_EKERNEL;
-        for (int k = 0; k < n_sp && !rc; k++) {
-            SsimWinParams W = {};
-            W.blk_y = S.blk_y + (size_t)k * n_cand * S.blk_stride;
-            W.blk_x = S.blk_x + (size_t)k * S.blk_stride;
-            W.blk_stride = S.blk_stride;
-            W.win_t = 3ull * n_stacks * win_per_stack;
-            W.win_s = win_per_stack;
-            W.win = sm->d_win && k < 3 ? sm->d_win + ((size_t)k * n_stacks + s0) * win_per_stack : nullptr;
-            W.part = (int64_t*)c->d_ssim_part.p;
-            W.w = (uint32_t)g.w;
-            W.h = (uint32_t)g.h;
-            W.nbx = nbx4;
-            W.nby = nby4;
-            W.nwx = nwx;
-            W.nwy = nwy;
-            W.depth = (uint32_t)D;
-            W.ns = (uint32_t)ns;
-            W.n_tables = (uint32_t)n_cand;
-            W.bpr = bpr;
-            // ssim[c][s][k] at (c * n_stacks + s) * 3 + k; ssim_y[c][s] behind them
-            int64_t* const out = k < 3 ? d_ssim_sums + (size_t)s0 * 3 + k : d_ssim_sums + 3 * n_rgb + s0;
-            if (launch_ssim_window(W, c->stream) ||
-                launch_ssim_sum(W.part, bpr, W.ns, W.n_tables, out, k < 3 ? 3ull * n_stacks : (uint64_t)n_stacks, k < 3 ? 3 : 1, c->stream))
-                rc = DCT3D_EKERNEL;
-        }
-    }
-    if (!rc && sse && launch_distortion_sum(cube_out, (uint32_t)cps[0], n_rgb, d_rgb_sums, c->stream)) rc = DCT3D_EKERNEL;
-    timer_end(c, ev);
-    if (!rc && hipMemcpyAsync(c->h_rate, d_sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = DCT3D_EDEVICE;
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;  // synchronous on return (as probe_dev)
-    if (c->slot_used) count_slot_used(c, (uint64_t)stack_cubes * n_stacks * (uint64_t)c->plan.cs);
-    if (rc) return rc;
-    if (sse) memcpy(sse, c->h_rate + (d_rgb_sums - d_sums), n_rgb * sizeof(uint64_t));
-    if (sm) {
-        const uint64_t* const hs = c->h_rate + ((uint64_t*)d_ssim_sums - d_sums);
-        memcpy(sm->ssim, hs, 3 * n_rgb * sizeof(int64_t));
-        if (sm->ssim_y) memcpy(sm->ssim_y, hs + 3 * n_rgb, n_rgb * sizeof(int64_t));
-    }
-    if (all_pairs)  // every (table, plane) pair was coded: slot t of plane k is table t
-        for (int s0 = 0; s0 < n_stacks; s0 += per) {
-            const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
-            for (int k = 0; k < 3; k++)
-                for (int t = 0; t < n_tables; t++)
-                    for (int s = 0; s < ns; s++) {
-                        const size_t src = (size_t)s0 * NT + toff[k] * ns + (size_t)t * ns + s;
-                        const size_t dst = ((size_t)t * n_stacks + s0 + s) * 3 + k;
-                        if (plane_sse) plane_sse[dst] = c->h_rate[src];
-                        if (bits) bits[dst] = c->h_rate[n_psums + src];
-                    }
-        }
-    return DCT3D_OK;
-}
-
-static int probe_rgb_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                         const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits, uint32_t* d_cube_sse) {
-    return c->opt_colour ? probe_rgb_ycc_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, plane_sse, bits, d_cube_sse)
-                         : probe_rgb_planes_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, plane_sse, bits, d_cube_sse);
-}
-
-// The RGB and luma SSIM probe in planes mode: the SSIM probe itself (ssim_dev) on the tables some candidate uses (all
-// of them when bits is asked for); a candidate's numbers are its three planes' under their tables, put together on
-// the host, and its windows strided copies out of the plane probe's.
-static int ssim_rgb_planes_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables,
-                               int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* bits, const SsimRgbOut& sm) {
-    int slot[DCT3D_RATE_MAX_TABLES];
-    std::vector<int> used;
-    for (int t = 0; t < n_tables; t++) slot[t] = bits ? t : -1;
-    if (bits)
-        for (int t = 0; t < n_tables; t++) used.push_back(t);
-    else
-        for (int i = 0; i < 3 * n_cand; i++)
-            if (slot[cand[i]] < 0) {
-                slot[cand[i]] = (int)used.size();
-                used.push_back(cand[i]);
-            }
-    const int nu = (int)used.size(), n_steps = (int)c->plan.steps.size();
-    const int32_t* tb = tables;
-    if (tables && !bits) {
-        c->rgb_tables.resize((size_t)nu * n_steps);
-        for (int i = 0; i < nu; i++) memcpy(&c->rgb_tables[(size_t)i * n_steps], tables + (size_t)used[i] * n_steps, n_steps * sizeof(int32_t));
-        tb = c->rgb_tables.data();
-    }
-    int nwx, nwy;
-    (void)dct3d_ssim_windows(g.w, g.h, &nwx, &nwy);
-    const size_t wps = (size_t)c->bd * nwx * nwy, n_runs = (size_t)nu * n_stacks * 3;
-    int rc;
-    if (sm.d_win && (rc = c->d_ssim_win.grow(n_runs * wps * sizeof(int32_t) + 4))) return rc;
-    std::vector<int64_t> pm(n_runs);
-    std::vector<uint64_t> ps(sse ? n_runs : 0);
-    rc = ssim_dev(c, d_frames, g, n_stacks, tb, nu, pm.data(), sse ? ps.data() : nullptr, bits, sm.d_win ? (int32_t*)c->d_ssim_win.p : nullptr);
-    if (rc || n_stacks == 0) return rc;
-    for (int i = 0; i < n_cand; i++)
-        for (int s = 0; s < n_stacks; s++) {
-            uint64_t v = 0;
-            for (int k = 0; k < 3; k++) {
-                const size_t at = ((size_t)slot[cand[3 * i + k]] * n_stacks + s) * 3 + k;
-                sm.ssim[((size_t)i * n_stacks + s) * 3 + k] = pm[at];
-                if (sse) v += ps[at];
-            }
-            if (sse) sse[(size_t)i * n_stacks + s] = v;
-        }
-    if (!sm.d_win) return DCT3D_OK;
-    // [table][stack][plane][windows] -> [candidate][plane][stack][windows]: one strided copy per (candidate, plane)
-    for (int i = 0; i < n_cand && !rc; i++)
-        for (int k = 0; k < 3 && !rc; k++) {
-            const int32_t* const from = (const int32_t*)c->d_ssim_win.p + ((size_t)slot[cand[3 * i + k]] * n_stacks * 3 + k) * wps;
-            int32_t* const to = sm.d_win + ((size_t)i * 3 + k) * n_stacks * wps;
-            if (hipMemcpy2DAsync(to, wps * sizeof(int32_t), from, 3 * wps * sizeof(int32_t), wps * sizeof(int32_t), (size_t)n_stacks,
-                                 hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-                rc = DCT3D_EDEVICE;
-        }
-    if (stream_wait(c) && !rc) rc = DCT3D_EDEVICE;
-    return rc;
-}
-
-// (the arguments hold: rgb_args_ok; no luma in planes mode)
-static int ssim_rgb_dev(dct3d_ctx* c, const uint8_t* d_frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                        const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* bits, const SsimRgbOut& sm) {
-    return c->opt_colour ? probe_rgb_ycc_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, nullptr, bits, nullptr, &sm)
-                         : ssim_rgb_planes_dev(c, d_frames, g, n_stacks, tables, n_tables, cand, n_cand, sse, bits, sm);
-}
-
-// Frames in host memory: chunks of whole stacks, as probe_host.  sm: the RGB and luma SSIM probe (sse optional,
-// no plane_sse)
-static int probe_rgb_host(dct3d_ctx* c, const uint8_t* frames, const Geom& g, int n_stacks, const int32_t* tables, int n_tables,
-                          const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits,
-                          const SsimRgbOut* sm = nullptr) {
-    if (hipSetDevice(c->device) != hipSuccess) return DCT3D_EDEVICE;
-    const size_t stack_bytes = (size_t)g.plane() * c->bd;
-    constexpr size_t kChunkBytes = (size_t)64 << 20;
-    const int per = (int)std::max<size_t>(1, std::min<size_t>(kChunkBytes / stack_bytes, (size_t)(n_stacks > 0 ? n_stacks : 1)));
-    int rc;
-    if ((rc = c->h_in.grow(stack_bytes * per))) return rc;
-    const size_t pl = (size_t)n_tables * per * 3;
-    std::vector<uint64_t> part((size_t)n_cand * per + 2 * pl);
-    std::vector<int64_t> spart(sm ? (size_t)4 * n_cand * per : 0);  // a chunk's ssim [n_cand][ns][3], then ssim_y [n_cand][ns]
-    c->last_units = 0;
-    batch_begin(c);
-    rc = DCT3D_OK;
-    for (int s0 = 0; s0 < n_stacks && !rc; s0 += per) {
-        const int ns = n_stacks - s0 < per ? n_stacks - s0 : per;
-        if (hipMemcpyAsync(c->h_in.p, frames + (size_t)s0 * stack_bytes, (size_t)ns * stack_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            rc = DCT3D_EDEVICE;
-            break;
-        }
-        uint64_t* const pr = part.data();
-        uint64_t* const pp = plane_sse ? pr + (size_t)n_cand * per : nullptr;
-        uint64_t* const pb = bits ? pr + (size_t)n_cand * per + pl : nullptr;
-        if (sm) {
-            const SsimRgbOut chunk = {spart.data(), sm->ssim_y ? spart.data() + (size_t)3 * n_cand * ns : nullptr, nullptr};
-            rc = ssim_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, sse ? pr : nullptr, pb, chunk);
-            for (int i = 0; i < n_cand && !rc; i++) {
-                memcpy(sm->ssim + ((size_t)i * n_stacks + s0) * 3, chunk.ssim + (size_t)i * ns * 3, (size_t)ns * 3 * sizeof(int64_t));
-                if (sm->ssim_y) memcpy(sm->ssim_y + (size_t)i * n_stacks + s0, chunk.ssim_y + (size_t)i * ns, ns * sizeof(int64_t));
-            }
-        } else {
-            rc = probe_rgb_dev(c, (const uint8_t*)c->h_in.p, g, ns, tables, n_tables, cand, n_cand, pr, pp, pb, nullptr);
-        }
-        if (rc) break;
-        for (int i = 0; i < n_cand && sse; i++) memcpy(sse + (size_t)i * n_stacks + s0, pr + (size_t)i * ns, ns * sizeof(uint64_t));
-        for (int t = 0; t < n_tables; t++) {
-            const size_t dst = ((size_t)t * n_stacks + s0) * 3, src = (size_t)t * ns * 3;
-            if (plane_sse) memcpy(plane_sse + dst, pp + src, (size_t)ns * 3 * sizeof(uint64_t));
-            if (bits) memcpy(bits + dst, pb + src, (size_t)ns * 3 * sizeof(uint64_t));
-        }
-    }
-    batch_end(c);
-    return rc;
-}
-extern "C" {
-
-int dct3d_distortion_rgb_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int n_stacks, const int32_t* tables,
-                                    int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse,
-                                    uint64_t* bits, uint32_t* d_cube_sse) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rgb_args_ok(c, d_frames, w, h, n_stacks, tables, n_tables, cand, n_cand, sse, &g, &n_cubes)) return DCT3D_EINVAL;
-    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
-    return probe_rgb_dev(c, d_frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, plane_sse, bits, d_cube_sse);
-}
-
-int dct3d_distortion_rgb_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables,
-                                int n_tables, const uint8_t* cand, int n_cand, uint64_t* sse, uint64_t* plane_sse, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rgb_args_ok(c, frames, w, h, n_stacks, tables, n_tables, cand, n_cand, sse, &g, &n_cubes)) return DCT3D_EINVAL;
-    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
-    return probe_rgb_host(c, frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, plane_sse, bits);
-}
-
-// ---- RGB and luma SSIM probe: the SSIM probe's numbers on the RGB bytes (and the luma plane) of the stream encode
-//      + decode under (Y, Cb, Cr) table triples, in all three colour modes (dct3d.h) ----
-int dct3d_ssim_rgb_frames_dev(dct3d_ctx* c, const uint8_t* d_frames, int w, int h, int n_stacks, const int32_t* tables,
-                              int n_tables, const uint8_t* cand, int n_cand, int64_t* ssim, int64_t* ssim_y, uint64_t* sse,
-                              uint64_t* bits, int32_t* d_window_ssim) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rgb_args_ok(c, d_frames, w, h, n_stacks, tables, n_tables, cand, n_cand, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (ssim_y && !c->opt_colour) return DCT3D_EINVAL;  // planes mode has no luma plane
-    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
-    return ssim_rgb_dev(c, d_frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, bits,
-                        SsimRgbOut{ssim, ssim_y, d_window_ssim});
-}
-
-int dct3d_ssim_rgb_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, int n_stacks, const int32_t* tables, int n_tables,
-                          const uint8_t* cand, int n_cand, int64_t* ssim, int64_t* ssim_y, uint64_t* sse, uint64_t* bits) {
-    Geom g;
-    uint64_t n_cubes;
-    if (!rgb_args_ok(c, frames, w, h, n_stacks, tables, n_tables, cand, n_cand, (const uint64_t*)ssim, &g, &n_cubes)) return DCT3D_EINVAL;
-    if (ssim_y && !c->opt_colour) return DCT3D_EINVAL;
-    uint8_t own[3 * DCT3D_RATE_MAX_TABLES];
-    const SsimRgbOut sm = {ssim, ssim_y, nullptr};
-    return probe_rgb_host(c, frames, g, n_stacks, tables, n_tables, rgb_cand(cand, n_cand, own), n_cand, sse, nullptr, bits, &sm);
 }
 
 // Stream decode front: sync passes until the chunk exits converge, the scan of per-chunk code counts,

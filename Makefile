@@ -19,7 +19,7 @@ DEV_SRCS  := $(CSRC)/dct3d_kernels.hip $(CSRC)/dct3d_kernels_f.hip $(CSRC)/dct3d
              $(CSRC)/dct3d_rate.hip $(CSRC)/dct3d_distortion.hip $(CSRC)/dct3d_vq_enc.hip $(CSRC)/dct3d_vq_dec.hip \
              $(CSRC)/dct3d_ycc.hip $(CSRC)/dct3d_c420.hip $(CSRC)/dct3d_distortion_rgb.hip
 DIAG_SRCS := $(CSRC)/dct3d_diag.hip
-HOST_SRCS := $(CSRC)/dct3d_plan.cpp $(CSRC)/dct3d_runtime.cpp $(CSRC)/dct3d_router.cpp
+HOST_SRCS := $(CSRC)/dct3d_plan.cpp $(CSRC)/dct3d_runtime.cpp $(CSRC)/dct3d_probes.cpp $(CSRC)/dct3d_router.cpp
 HDRS      := $(wildcard $(CSRC)/*.h) include/dct3d.h include/dct3d_diag.h
 CODEC_SRCS := $(wildcard $(CSRC)/host/*.c)
 CODEC_LIB_SRCS := $(filter-out $(CSRC)/host/main.c,$(CODEC_SRCS))
