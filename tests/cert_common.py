@@ -1,9 +1,10 @@
-"""Shared by test_cert_common.py (CPU), test_gpu_certificates.py, test_gpu_probe_certificates.py and
-test_gpu_distortion_rgb_certificates.py (GPU): what the
+"""Shared by test_cert_common.py (CPU), test_gpu_certificates.py, test_gpu_probe_certificates.py,
+test_gpu_distortion_rgb_certificates.py and test_gpu_ssim_certificates.py (GPU): what the
 host emulations of the kernels' arithmetic predict for the counts dct3d_get_stats reports -- which coefficients the
 fp32 encode certificate leaves open, which lanes the decode certificate flags, how the 8x8x8 second certificate splits
-the open ones, what the rate and distortion probes count under several tables, and what the RGB-domain distortion
-probe counts per plane of the colour transform and coded table.
+the open ones, what the rate and distortion probes count under several tables, what the RGB-domain distortion
+probe counts per plane of the colour transform and coded table, and what the two SSIM probes count, across their
+ranges of stacks and under the planes mode's compacted tables.
 
 The emulations are tests/native/emulate_encode.cpp and emulate_decode_quant.cpp, built here as test_emulation.py
 builds them (g++ -O2 -ffp-contract=off -fno-fast-math, into a temporary directory).  With contraction off on both
@@ -628,3 +629,113 @@ COLOUR_SETS = {
     "repeat": (("q1", "q12", "seeded"), ((0, 1, 2), (2, 2, 0), (0, 1, 2)), False),
 }
 COLOUR_RICH_SETS = ("q1", "planes4", "eleven")  # the sets that code q1 on all three planes
+
+
+# ---- the SSIM probes (test_gpu_ssim_certificates.py) -------------------------------------------------------------------
+# dct3d_ssim_frames[_dev] launches distortion_kernel's SSIM = 1 instantiations from ssim_dev, the only plane probe that
+# walks the stacks in ranges (range x channel x batch of 8 tables into one counter slot, window and sum launches
+# between the counting ones); dct3d_ssim_rgb_frames[_dev] reuses rgb_ycc_dev with a second budget on the ranges and,
+# in planes mode, codes only the tables some candidate names.
+
+# the probe cases without the two 1080p ones (the host-call tests are the 1080p coverage: their count is held to the
+# distortion probe's, which test_gpu_probe_certificates.py holds to the emulation at 1080p)
+SSIM_PROBE_CASES = [c for c in PROBE_CASES if (c.w, c.h) != (1920, 1080)]
+SSIM_PROBE_SETS = ("q1", "four", "eleven")
+# 32 tables in one call: the 11 cycled.  A prediction sums per name, so a name counts with its multiplicity and 11
+# emulations pay for the 32
+RANGE_NAMES = tuple(PROBE_TABLES[i % len(PROBE_TABLES)] for i in range(32))
+RANGE_CAND = tuple((i, (i + 5) % 32, (i + 11) % 32) for i in range(32))  # every plane codes all 32
+
+
+def ssim_probe_counts(c, names, margin, shift=0):
+    """the plane SSIM probe's n_flagged, int64 [nby + 1]: "statistics are the distortion probe's"  -- the
+    SSIM arm certifies and replays exactly as distortion_kernel does, whatever the ranges, want_sse and want_bits"""
+    return distortion_probe_counts(c, names, margin, shift)
+
+
+def ssim_probe_units(c, names, rows=None):
+    """the plane SSIM probe's n_units on the frames cropped to `rows` rows (None: whole): tables x padded samples"""
+    wp, hp = qc.pkg().padded_size(c.w, c.h if rows is None else rows)
+    return len(names) * wp * hp * c.channels * c.depth * c.stacks
+
+
+def ssim_record_bytes(depth, w, h, n, planes=1):
+    """the block records of one stack (and, plane probe, one channel): D nbx nby (8 n + 4) bytes per record plane over
+    the 4 x 4 block grid (dct3d.h)"""
+    return depth * ((w + 3) // 4) * ((h + 3) // 4) * (8 * n + 4) * planes
+
+
+def ssim_ranges(depth, w, h, stacks, n, planes=1, plane_bytes=0):
+    """the stacks of each range of a call: as many as fit DCT3D_SSIM_BLOCK_BUDGET (and, colour modes, the decoded
+    planes DCT3D_RGB_PLANE_BUDGET: plane_bytes of one stack), one at least"""
+    p = qc.pkg()
+    per = max(1, min(stacks, p.DCT3D_SSIM_BLOCK_BUDGET // ssim_record_bytes(depth, w, h, n, planes)))
+    if plane_bytes:
+        per = max(1, min(per, p.DCT3D_RGB_PLANE_BUDGET // plane_bytes))
+    return [min(per, stacks - s0) for s0 in range(0, stacks, per)]
+
+
+def _range_stacks(depth):
+    """one stack more than the block budget holds at 256 x 176 under 32 tables: 3 at 8x8x8, 6 at 8x8x4"""
+    return qc.pkg().DCT3D_SSIM_BLOCK_BUDGET // ssim_record_bytes(depth, 256, 176, 32) + 1
+
+
+# the range cases, whole raster only (a band of 8 rows has no second range)
+SSIM_RANGE_CASES = [Case("uniform", d, ch, 256, 176, _range_stacks(d)) for d in (8, 4) for ch in (1, 3)]
+# test_gpu_ssim_rgb.py::test_stack_ranges' shapes: the records of 32 candidates split the stacks 3 + 2 (2 + 2 + 1 with
+# the luma's record plane), the decoded planes alone would not
+SSIM_RGB_RANGE_CASES = [ColourCase(m, d, 128, h, 5) for (d, h) in ((8, 88), (4, 176)) for m in ("ycc", "c420")]
+
+
+def stack_counts(mask, stacks):
+    """per-unit mask [cube, ...] in the calls' order (the stack outermost) -> int64 [stacks]"""
+    return mask.reshape(stacks, -1).sum(axis=1).astype(np.int64)
+
+
+def ssim_range_stack_counts(c, names, margin):
+    """the plane probe's prediction of a range case per stack, int64 [stacks] (its sum: ssim_probe_counts' last)"""
+    ms = PROBE_MARGINS
+    return sum(stack_counts(case_open(c, n)[1], c.stacks) +
+               32 * stack_counts(probe_decode_lanes(c, n, ms)[ms.index(margin)], c.stacks) for n in names)
+
+
+def colour_range_stack_counts(c, names, cand, margin):
+    """colour_distortion_counts of a colour range case per stack, int64 [stacks]"""
+    L = coded_tables(len(names), cand, False)
+    i = PROBE_MARGINS.index(margin)
+    return sum(stack_counts(colour_plane_open(c, k, names[t])[1], c.stacks) +
+               32 * stack_counts(colour_plane_lanes(c, k, names[t])[i], c.stacks) for k in range(3) for t in L[k])
+
+
+def ssim_rgb_planes_tables(n_tables, cand, want_bits):
+    """rgb_planes_dev's compaction under the SSIM probe: the tables the plane probe is run with -- the distinct tables
+    any candidate names for any plane, in the order of first use over the flattened candidate list; every table when
+    the bits are asked for or no candidates are given (candidate i = (i, i, i)).  (The RGB distortion probe's planes
+    mode does not compact: colour_distortion_counts' planes arm.)"""
+    if cand is None or want_bits:
+        return list(range(n_tables))
+    used = []
+    for cd in cand:
+        for t in cd:
+            if int(t) not in used:
+                used.append(int(t))
+    return used
+
+
+def ssim_rgb_counts(c, names, cand, margin, want_bits=False, shift=0):
+    """n_flagged of one ssim_rgb_frames[_dev] call, int64 [nb + 1].  ycc, c420: colour_distortion_counts with every
+    pair coded when the bits are asked for -- neither the luma nor want_sse changes L[k].  planes: the plane probe
+    under the compacted tables, every coded table on all three planes."""
+    if c.mode == "planes":
+        used = ssim_rgb_planes_tables(len(names), cand, want_bits)
+        return distortion_probe_counts(c.rgb, [names[t] for t in used], margin, shift)
+    return colour_distortion_counts(c, names, cand, margin, want_bits, shift)
+
+
+def ssim_rgb_units(c, names, cand, want_bits=False, rows=None):
+    """n_units of the call on the frames cropped to `rows` frame rows (None: whole).  planes: the coded tables x the
+    padded raster of the three planes"""
+    if c.mode == "planes":
+        used = ssim_rgb_planes_tables(len(names), cand, want_bits)
+        return ssim_probe_units(c.rgb, used, rows)
+    return colour_units(c, names, cand, want_bits, rows)

@@ -13,7 +13,11 @@
     the shifted threshold seen by every rich set;
   * the same for the RGB-domain distortion probe's predictions (test_gpu_distortion_rgb_certificates.py), per plane of
     the colour transform: and the rule for which (table, plane) pairs a call codes, and that a band's crop has the
-    whole frame's cubes."""
+    whole frame's cubes;
+  * the same for the SSIM probes' predictions (test_gpu_ssim_certificates.py): the range cases' arithmetic (how many
+    ranges, how many stacks in each), soundness and the decode preconditions under each of the 11 names, richness, the
+    shifted threshold seen, no per-stack count repeated, and the planes mode's compaction rule against a brute-force
+    restatement."""
 import numpy as np
 import pytest
 
@@ -325,3 +329,164 @@ def test_sum_partials_is_the_sum_kernels_partition():
     p8 = cc.sum_partials(v, 8)
     assert p8.shape == (32,) and p8[2] == p1[16:24].sum() and cc.sum_partials(v, 64).sum() == v.sum()
     assert all(h % 8 == 0 and w % 8 == 0 for w, h in cc.BIG_SUM.values())
+
+
+# ---- the SSIM probes' predictions (test_gpu_ssim_certificates.py) ------------------------------------------------------
+
+def _colour_plane_bytes(pkg, c, n_tables=32):
+    """the decoded planes of one stack with every (table, plane) pair coded"""
+    cw, ch = pkg.chroma_size(c.w, c.h) if c.mode == "c420" else (c.w, c.h)
+    return n_tables * c.depth * (c.w * c.h + 2 * cw * ch)
+
+
+def test_ssim_cases_are_the_listed_ones(pkg):
+    ids = [c.id for c in cc.SSIM_PROBE_CASES]
+    assert len(ids) == len(set(ids)) == 20
+    for d in (8, 4):
+        want = [f"uniform-{s}-grey-d{d}" for s in ("200x72x4", "24x16x5", "8x8x1", "1366x24x2", "13x11x1", "1x1x1")] + \
+               [f"uniform-{s}-rgb-d{d}" for s in ("200x72x2", "24x16x5", "13x11x1", "1x1x1")]
+        assert set(want) == {i for i in ids if i.endswith(f"d{d}")}
+    assert all(c in cc.PROBE_CASES for c in cc.SSIM_PROBE_CASES)  # the same objects: the emulations' caches are shared
+    assert all(s in cc.PROBE_SETS for s in cc.SSIM_PROBE_SETS) and cc.SSIM_PROBE_SETS == ("q1", "four", "eleven")
+    assert len(cc.RANGE_NAMES) == 32 and set(cc.RANGE_NAMES) == set(cc.PROBE_TABLES)
+    assert all(cc.RANGE_NAMES[i] == cc.PROBE_TABLES[i % 11] for i in range(32))
+    # the plane probe's range cases: >= 2 ranges, more than one stack in the first
+    ids = [c.id for c in cc.SSIM_RANGE_CASES]
+    assert ids == [f"uniform-256x176x{st}-{ch}-d{d}" for d, st in ((8, 3), (4, 6)) for ch in ("grey", "rgb")]
+    for c in cc.SSIM_RANGE_CASES:
+        assert c.stacks == pkg.DCT3D_SSIM_BLOCK_BUDGET // (c.depth * 64 * 44 * (8 * 32 + 4)) + 1
+        r = cc.ssim_ranges(c.depth, c.w, c.h, c.stacks, 32)
+        assert len(r) >= 2 and r[0] > 1 and sum(r) == c.stacks and r == [c.stacks - 1, 1]
+        assert cc.ssim_ranges(c.depth, c.w, c.h, c.stacks, 8) == [c.stacks]  # 8 tables would not have split it
+    # the colour range cases: 3 + 2 without the luma, 2 + 2 + 1 with it; the planes budget alone does not split
+    ids = [c.id for c in cc.SSIM_RGB_RANGE_CASES]
+    assert ids == [f"{m}-128x{h}x5-d{d}" for d, h in ((8, 88), (4, 176)) for m in ("ycc", "c420")] and len(set(ids)) == 4
+    for c in cc.SSIM_RGB_RANGE_CASES:
+        pb = _colour_plane_bytes(pkg, c)
+        assert pkg.DCT3D_RGB_PLANE_BUDGET // pb >= c.stacks
+        assert cc.ssim_ranges(c.depth, c.w, c.h, c.stacks, 32, 3, pb) == [3, 2]
+        assert cc.ssim_ranges(c.depth, c.w, c.h, c.stacks, 32, 4, pb) == [2, 2, 1]
+        L = cc.coded_tables(32, cc.RANGE_CAND, False)
+        assert all(sorted(x) == list(range(32)) for x in L)  # every plane codes all 32, bits or not
+    assert [cc.ssim_rgb_units(c, cc.RANGE_NAMES, cc.RANGE_CAND) for c in cc.SSIM_RGB_RANGE_CASES] == \
+        [43253760, 22282240, 43253760, 21626880]
+
+
+@pytest.mark.parametrize("c", [c for c in cc.SSIM_PROBE_CASES if c.rich], ids=repr)
+def test_ssim_probe_predictions(c):
+    """the plane SSIM probe's rule is the distortion probe's, stated once; n_units is tables x padded samples, per
+    band too; and on the rich cases the thresholds read at s + 1 change the prediction of every rich set at margin 0
+    and at MARGINS[0]: the counts can see the SSIM arm taking a table row one entry off"""
+    fr = c.frames()
+    for s in cc.SSIM_PROBE_SETS:
+        names = cc.PROBE_SETS[s]
+        assert cc.ssim_probe_units(c, names) == len(names) * cc.raster_of(fr, c.depth).size
+        for by in (0, c.nby - 1):
+            band = cc.band_frames(fr, by)
+            assert cc.ssim_probe_units(c, names, band.shape[1]) == len(names) * cc.raster_of(band, c.depth).size
+        for m in cc.PROBE_MARGINS:
+            assert np.array_equal(cc.ssim_probe_counts(c, names, m), cc.distortion_probe_counts(c, names, m))
+        if cc.probe_rich(c, s):
+            p0, p1 = (cc.ssim_probe_counts(c, names, m) for m in (0.0, cc.MARGINS[0]))
+            assert cc.is_rich(p0[:-1]) and p1[-1] > p0[-1] > 0
+            for m, pred in ((0.0, p0), (cc.MARGINS[0], p1)):
+                shifted = cc.ssim_probe_counts(c, names, m, shift=1)
+                assert shifted[-1] != pred[-1] and not np.array_equal(shifted, pred), f"{c.id} {s}: no sight of thr[s + 1]"
+
+
+@pytest.mark.parametrize("c", cc.SSIM_RANGE_CASES, ids=repr)
+def test_ssim_range_predictions(c):
+    """per range case, under each of the 11 names: the emulation is sound (what it leaves closed is the reference's q,
+    the DC never open) and decode_emulate's preconditions hold at each of PROBE_MARGINS, no lane flagged at margin 0;
+    the 32 cycled tables' prediction is the names' with their multiplicities; it is rich; thresholds read at s + 1
+    change it; and no per-stack count repeats, under q1 alone or under the 32: a dropped or doubled range, or a stack
+    counted in another's place, cannot cancel"""
+    M = cc.MARGINS[0]
+    names = cc.RANGE_NAMES
+    for n in cc.PROBE_TABLES:
+        q, op = cc.case_open(c, n)
+        bad = (q != cc.case_q_ref(c, n)) & ~op
+        assert not bad.any(), f"{n}: {int(bad.sum())} closed coefficients differ"
+        assert not op[:, 0, 0, 0].any()
+        lanes = cc.probe_decode_lanes(c, n, cc.PROBE_MARGINS)  # (asserts the preconditions)
+        assert not lanes[0].any(), f"{c.id} {n}: a lane flagged at margin 0: another seed"
+    mult = {n: names.count(n) for n in cc.PROBE_TABLES}
+    assert sorted(mult.values()) == [2] + [3] * 10
+    p0, p1 = cc.ssim_probe_counts(c, names, 0.0), cc.ssim_probe_counts(c, names, M)
+    assert np.array_equal(p0, cc.rate_probe_counts(c, names))  # the decode term at margin 0 is 0
+    assert np.array_equal(p1, sum(k * cc.ssim_probe_counts(c, (n,), M) for n, k in mult.items()))
+    assert cc.is_rich(p0[:-1]) and p1[-1] > p0[-1] >= 17444 and (p1[-1] - p0[-1]) // 32 >= 10471
+    for m, pred in ((0.0, p0), (M, p1)):
+        assert cc.ssim_probe_counts(c, names, m, shift=1)[-1] != pred[-1], f"{c.id}: no sight of thr[s + 1]"
+    per = cc.ssim_range_stack_counts(c, names, M)
+    q1 = cc.ssim_range_stack_counts(c, ("q1",), M)
+    assert per.sum() == p1[-1] and len(set(per.tolist())) == c.stacks == len(set(q1.tolist()))
+    # no proper subset of the stacks, counted once or twice, gives the whole's count by accident: checked for ranges
+    r = cc.ssim_ranges(c.depth, c.w, c.h, c.stacks, 32)
+    parts = [int(per[sum(r[:i]):sum(r[:i + 1])].sum()) for i in range(len(r))]
+    assert len(set(parts)) == len(parts) and all(0 < v < p1[-1] for v in parts)
+    assert cc.ssim_probe_units(c, names) == 32 * cc.raster_of(c.frames(), c.depth).size
+    print(f"{c.id}: open {int(p0[-1])}, at {M}: {int(p1[-1])}, per stack {per.tolist()}, per range {parts}")
+
+
+@pytest.mark.parametrize("c", cc.SSIM_RGB_RANGE_CASES, ids=repr)
+def test_ssim_rgb_range_predictions(c, pkg):
+    """the same per colour range case and plane; the prediction does not depend on the bits (every plane codes all 32
+    either way)"""
+    M = cc.MARGINS[0]
+    names, cand = cc.RANGE_NAMES, cc.RANGE_CAND
+    for k in range(3):
+        for n in cc.PROBE_TABLES:
+            q, op = cc.colour_plane_open(c, k, n)
+            bad = (q != cc.colour_plane_q_ref(c, k, n)) & ~op
+            assert not bad.any(), f"plane {k} {n}: {int(bad.sum())} closed coefficients differ"
+            assert not op[:, 0, 0, 0].any()
+            cc.colour_plane_lanes(c, k, n)  # (asserts the preconditions at each of PROBE_MARGINS)
+    assert cc.colour_rich(c, names, cand)
+    p0, p1 = cc.ssim_rgb_counts(c, names, cand, 0.0), cc.ssim_rgb_counts(c, names, cand, M)
+    assert p1[-1] > p0[-1] > 0
+    for wb in (False, True):
+        assert np.array_equal(cc.ssim_rgb_counts(c, names, cand, M, wb), cc.colour_distortion_counts(c, names, cand, M, wb))
+        assert np.array_equal(cc.ssim_rgb_counts(c, names, cand, M, wb), p1)
+        assert cc.ssim_rgb_units(c, names, cand, wb) == cc.colour_units(c, names, cand, wb) == cc.colour_units(c, names, cand)
+    for m, pred in ((0.0, p0), (M, p1)):
+        assert cc.ssim_rgb_counts(c, names, cand, m, shift=1)[-1] != pred[-1], f"{c.id}: no sight of thr[s + 1]"
+    per = cc.colour_range_stack_counts(c, names, cand, M)
+    assert per.sum() == p1[-1] and len(set(per.tolist())) == c.stacks
+    for r in ([3, 2], [2, 2, 1]):
+        parts = [int(per[sum(r[:i]):sum(r[:i + 1])].sum()) for i in range(len(r))]
+        assert len(set(parts)) == len(parts) and all(0 < v < p1[-1] for v in parts)
+    print(f"{c.id}: units {cc.ssim_rgb_units(c, names, cand)}, open {int(p0[-1])}, at {M}: {int(p1[-1])}, per stack {per.tolist()}")
+
+
+def _first_uses(seq):
+    """brute force: the distinct values of a sequence in the order of their first appearance"""
+    return [v for i, v in enumerate(seq) if v not in seq[:i]]
+
+
+def test_ssim_rgb_planes_tables():
+    """rgb_planes_dev's compaction rule against a brute-force restatement, on the colour sets; and what it predicts in
+    planes mode: the plane probe under the coded tables only, every coded table on all three planes"""
+    for s in ("subsets", "repeat", "eleven", "q1", "planes4"):
+        names, cand, _ = cc.COLOUR_SETS[s]
+        n = len(names)
+        flat = None if cand is None else [int(t) for cd in cand for t in cd]
+        want = list(range(n)) if flat is None else _first_uses(flat)
+        assert cc.ssim_rgb_planes_tables(n, cand, False) == want, s
+        assert cc.ssim_rgb_planes_tables(n, cand, True) == list(range(n)) == cc.ssim_rgb_planes_tables(n, None, False), s
+    names, cand, _ = cc.COLOUR_SETS["subsets"]
+    assert cc.ssim_rgb_planes_tables(4, cand, False) == [0, 1, 2]  # table 3 is not coded
+    assert cc.ssim_rgb_planes_tables(3, cc.COLOUR_SETS["repeat"][1], False) == [0, 1, 2]
+    assert cc.ssim_rgb_planes_tables(3, ((2, 2, 0), (0, 1, 2)), False) == [2, 0, 1]  # the order of first use
+    assert cc.ssim_rgb_planes_tables(11, None, False) == list(range(11))
+    for c in (x for x in cc.COLOUR_PROBE_CASES if x.mode == "planes"):
+        raster = cc.raster_of(c.frames(), c.depth).size
+        for m in cc.PROBE_MARGINS:
+            assert np.array_equal(cc.ssim_rgb_counts(c, names, cand, m), cc.distortion_probe_counts(c.rgb, names[:3], m))
+            assert np.array_equal(cc.ssim_rgb_counts(c, names, cand, m, True), cc.distortion_probe_counts(c.rgb, names, m))
+            # (the RGB distortion probe's planes arm codes every table whatever the candidates say: both rules stay)
+            assert np.array_equal(cc.colour_distortion_counts(c, names, cand, m), cc.distortion_probe_counts(c.rgb, names, m))
+        assert cc.ssim_rgb_units(c, names, cand) == 3 * raster and cc.ssim_rgb_units(c, names, cand, True) == 4 * raster
+        assert cc.ssim_rgb_units(c, names, cand, rows=3) == 3 * cc.raster_of(c.frames()[:, :3], c.depth).size
+        if (c.w, c.h) == (200, 72):  # the fourth table's count is what a call that does not compact adds
+            assert cc.ssim_rgb_counts(c, names, cand, 0.0, True)[-1] > cc.ssim_rgb_counts(c, names, cand, 0.0)[-1] > 0

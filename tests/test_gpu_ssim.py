@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import quant_common as qc
+from cert_common import MARGINS
 from conftest import ctx_option
 from test_gpu_edge import _rare_content
 
@@ -288,9 +289,12 @@ def test_ranges_of_stacks(pkg, gpu_ctx8, gpu_ctx4, depth):
 
 
 @pytest.mark.parametrize("depth", [8, 4])
-def test_host_call_in_several_chunks(gpu_ctx8, gpu_ctx4, depth):
+def test_host_call_in_several_chunks(pkg, gpu_ctx8, gpu_ctx4, depth):
     """7: 40 frames of 1920 x 1080 (79 MiB) go up in two chunks of whole stacks on the host-pointer path: every (table,
-    stack) sum lands at its place (the device call's numbers), and the chunks' statistics add up."""
+    stack) sum lands at its place (the device call's numbers), and the chunks' statistics add up.  At MARGINS[0], where
+    open coefficients and replayed lanes both count, the host call's n_flagged is the device call's and
+    distortion_frames_dev's on the same raster (which test_gpu_probe_certificates.py holds to the emulation at this
+    size): no chunk's or range's launches clear the slot the ones before counted into."""
     import torch
     ctx = _ctx(depth, gpu_ctx8, gpu_ctx4)
     w, h, stacks = 1920, 1080, 40 // depth
@@ -303,6 +307,18 @@ def test_host_call_in_several_chunks(gpu_ctx8, gpu_ctx4, depth):
     assert ctx.stats()["n_units"] == units == 2 * fr.size
     assert np.array_equal(hs, ssim) and np.array_equal(he, sse) and np.array_equal(hb, bits)
     assert len(set(int(v) for v in ssim[0, :, 0])) == stacks  # no two stacks alike: a misplaced chunk would show
+    with ctx_option(ctx, pkg.DCT3D_OPT_DEC_MARGIN, MARGINS[0]):
+        d_fr = torch.from_numpy(fr).cuda()
+        ds = ctx.ssim_frames_dev(d_fr, w, h, 1, stacks, tabs)
+        dev = ctx.stats()
+        hs = ctx.ssim_frames(fr, tabs)
+        host = ctx.stats()
+        de = ctx.distortion_frames_dev(d_fr, w, h, 1, stacks, tabs)
+        dist = ctx.stats()
+    assert np.array_equal(ds, ssim) and np.array_equal(hs, ssim) and np.array_equal(de, sse)
+    print(f"8x8x{depth} margin {MARGINS[0]}: n_flagged device {dev['n_flagged']}, host {host['n_flagged']}, distortion {dist['n_flagged']}")
+    assert host["n_units"] == dev["n_units"] == dist["n_units"] == units
+    assert host["n_flagged"] == dev["n_flagged"] == dist["n_flagged"] > 32 * stacks  # replays in every stack, and open coefficients
 
 
 @pytest.mark.parametrize("depth", [8, 4])

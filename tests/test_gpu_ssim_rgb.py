@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import quant_common as qc
+from cert_common import MARGINS
 from conftest import ctx_option
 from test_gpu_c420 import FOLD_SHAPE
 from test_gpu_distortion import LADDER, _table
@@ -293,7 +294,9 @@ def _big_frames():
 @pytest.mark.parametrize("mode", MODES)
 def test_host_call_in_two_chunks(pkg, gpu_ctx4, mode):
     """12 frames of 1920 x 1080 RGB24 (71 MiB) at depth 4 go up in two chunks of whole stacks (2 + 1) on the host-pointer
-    path: every sum lands at its stack's place (the device call's numbers)"""
+    path: every sum lands at its stack's place (the device call's numbers).  At MARGINS[0], where open coefficients and
+    replayed lanes both count, the host call's n_units and n_flagged are the device call's: no chunk's launches clear
+    the slot the chunk before counted into."""
     import torch
     depth, w, h, stacks = 4, 1920, 1080, 3
     assert (64 << 20) // (w * h * 3 * depth) == 2  # two stacks per chunk
@@ -309,6 +312,17 @@ def test_host_call_in_two_chunks(pkg, gpu_ctx4, mode):
     for a, b in zip(dev, host):
         assert np.array_equal(a, b)
     assert len(set(int(v) for v in dev[0][0, :, 0])) == stacks  # no two stacks alike: a misplaced chunk would show
+    with mode_on(gpu_ctx4, pkg, mode), ctx_option(gpu_ctx4, pkg.DCT3D_OPT_DEC_MARGIN, MARGINS[0]):
+        d2 = gpu_ctx4.ssim_rgb_frames_dev(torch.from_numpy(np.array(fr)).cuda(), w, h, stacks, tabs, cand, want_luma=luma)
+        st_dev = gpu_ctx4.stats()
+        h2 = gpu_ctx4.ssim_rgb_frames(fr, tabs, cand, want_luma=luma)
+        st_host = gpu_ctx4.stats()
+    for a, b in zip(d2 if luma else (d2,), h2 if luma else (h2,)):
+        assert np.array_equal(a, b)
+    assert np.array_equal(d2[0] if luma else d2, dev[0])
+    print(f"{mode} margin {MARGINS[0]}: n_flagged device {st_dev['n_flagged']}, host {st_host['n_flagged']}")
+    assert st_host["n_units"] == st_dev["n_units"] > 0
+    assert st_host["n_flagged"] == st_dev["n_flagged"] > 32 * stacks  # replays in every stack, and open coefficients
 
 
 @pytest.mark.parametrize("mode", MODES)
