@@ -6,7 +6,7 @@ Compiles each translation unit (default: every csrc/*.hip that both trees have) 
 tree and of OTHER_TREE (a checkout of the commit to compare with) to gfx950 assembly with the Makefile's
 flags, and compares every function's instruction text.  Prints one line per translation unit and the names
 of the functions that differ or exist on one side only (a function whose name alone changed is paired with
-its twin by its text); exit status 1 if any differs."""
+its twin by its text, and its callers are compared under the new name); exit status 1 if any differs."""
 import os
 import re
 import subprocess
@@ -45,14 +45,21 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         for u in units:
             a, b = functions(ROOT, u, tmp), functions(other, u, tmp)
+            # a function whose name alone changed (a template parameter added with a default, a type in its
+            # arguments renamed): paired with its twin by its text, and the other tree then speaks of it by its new
+            # name everywhere, so that its callers do not differ by the symbol they call.  Until no pair is left: a
+            # caller of a renamed function may be renamed itself.
+            paired = True
+            while paired:
+                paired = False
+                for n in sorted(set(a) - set(b)):
+                    twin = [m for m in sorted(set(b) - set(a)) if [ln.replace(m, n) for ln in b[m]] == a[n]]
+                    if twin:
+                        print(f"    renamed, same text: {twin[0]} -> {n}")
+                        b = {(n if k == twin[0] else k): [ln.replace(twin[0], n) for ln in v] for k, v in b.items()}
+                        paired = True
+                        break
             diff = sorted(n for n in set(a) | set(b) if a.get(n) != b.get(n))
-            # a function whose name alone changed (a template parameter added with a default): paired by its text
-            for n in [n for n in diff if n not in b]:
-                twin = [m for m in diff if m not in a and [ln.replace(m, n) for ln in b[m]] == a[n]]
-                if twin:
-                    print(f"    renamed, same text: {twin[0]} -> {n}")
-                    diff.remove(n)
-                    diff.remove(twin[0])
             n_ins = sum(len(v) for v in a.values())
             print(f"{u}: {len(a)} functions, {n_ins} lines, {len(diff)} differ")
             for n in diff:
