@@ -71,6 +71,7 @@ ABI_SYMBOLS = (
     "dct3d_distortion_rgb_frames", "dct3d_distortion_rgb_frames_dev",
     "dct3d_ssim_frames", "dct3d_ssim_frames_dev", "dct3d_ssim_windows",
     "dct3d_ssim_rgb_frames", "dct3d_ssim_rgb_frames_dev",
+    "dct3d_eg_sync_launches",
 )
 # Every symbol include/dct3d_diag.h declares (libdct3d_diag.so; none of them is in libdct3d.so).
 DIAG_SYMBOLS = ("dct3d_fill_synthetic_dev", "dct3d_bandwidth_probe_dev", "dct3d_encode_memonly_dev",
@@ -153,6 +154,7 @@ def lib() -> C.CDLL:
         L.dct3d_eg_decode_dev.argtypes = [vp, vp, u64, u64, u64, vp, C.POINTER(u64)]
         L.dct3d_decode_eg.argtypes = [vp, vp, u64, i32, i32, i32, i32, vp, C.POINTER(u64)]
         L.dct3d_decode_eg_dev.argtypes = [vp, vp, u64, u64, i32, i32, i32, vp, C.POINTER(u64)]
+        L.dct3d_eg_sync_launches.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         # (the per-channel arrays as plain addresses: ctypes arrays convert, None is NULL)
         L.dct3d_encode_eg_frames_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
         L.dct3d_encode_eg_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -698,6 +700,13 @@ class Context:
         st = Stats()
         _check(lib().dct3d_get_stats(self._h, C.byref(st)), "dct3d_get_stats")
         return st.as_dict()
+
+    def eg_sync_launches(self) -> tuple:
+        """(max per front, sum): the sync launches the last stream decode call's fronts issued, the speculative
+        attempt and its rerun together (dct3d_eg_sync_launches); one stream: both are its count."""
+        mx, sm = C.c_uint64(), C.c_uint64()
+        _check(lib().dct3d_eg_sync_launches(self._h, C.byref(mx), C.byref(sm)), "dct3d_eg_sync_launches")
+        return mx.value, sm.value
 
     def reset_timers(self) -> None:
         _check(lib().dct3d_reset_timers(self._h), "dct3d_reset_timers")

@@ -83,6 +83,9 @@ struct dct3d_ctx {
     // consumer zeroes the other slot for the next call (clean: known zero, no memset needed)
     int egd_slot = 0;
     bool egd_clean[2] = {true, true};
+    // the sync launches (eg_sync_kernel, eg_chain_kernel, eg_front_kernel) of the last stream decode call's
+    // fronts, per channel, the speculative attempt and its rerun together (dct3d_eg_sync_launches)
+    uint64_t egd_launches[3] = {0, 0, 0};
     // the same for the encode stream's two status words (d_eg_status: two slots of 16 bytes)
     int eg_slot = 0;
     bool eg_clean[2] = {true, true};

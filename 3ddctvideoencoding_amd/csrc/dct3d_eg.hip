@@ -1012,6 +1012,60 @@ __global__ __launch_bounds__(kEgBlock) void eg_sync_diag4_kernel(EgDecParams P) 
 __global__ __launch_bounds__(kEgBlock) void eg_sync_diag5_kernel(EgDecParams P) { sync_body<5>(P, 0, 1); }
 #endif
 
+// Confirming pass with the chain inside the block (the rerun's passes after pass 0).  A plain confirming
+// pass moves a corrected exit one chunk further per launch: on a stream whose wrong parses never meet the
+// true one (a periodic stream: `010010...` entered one bit late reads `1`, `00100`, `1`, ... for ever) that
+// is one launch and one host round trip per chunk.  Here block b owns chunks [256 b, 256 b + 256): every
+// thread parses its chunk from exit_in[t - 1] as the plain pass does, then the exits are handed on in LDS
+// and only the threads whose start moved parse again, until no start in the block moves -- at most 255
+// rounds, since after round r the first r + 1 chunks of the block follow from the block's first start.
+// Thread 0's start, exit_in[256 b - 1], is fixed for the launch: no block reads what another writes in the
+// same launch, none waits for another.  Chunk 0 starts at the true first bit, so after launch j every
+// chunk of blocks 0 .. j - 1 is final by induction: ceil(n_chunks / 256) launches finish every chunk, one
+// more sees no exit change.  status[0] as the plain pass: set when an exit differs from exit_in's.
+__global__ __launch_bounds__(kEgBlock) void eg_chain_kernel(EgDecParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[(kLutBytes + kColBytes) / 4 + kEgBlock];
+    uint8_t* const s_lut = (uint8_t*)lds;
+    uint32_t* const win = lds + kLutBytes / 4;
+    uint32_t* const s_x = win + kColBytes / 4;  // the chunks' exits, chunk-relative (~0u: invalid)
+    copy_lut(s_lut);
+    const int64_t first = (int64_t)blockIdx.x * kEgBlock;
+    stage_columns(P, win, first);
+    __syncthreads();
+    const uint64_t t = (uint64_t)first + threadIdx.x;
+    const bool live = t < P.n_chunks;
+    const int64_t b0 = (int64_t)P.start_bit + (int64_t)t * (int64_t)kChunkBits;
+    const uint32_t limit = rel_bit(P.limit_bit, b0);
+    const uint32_t stop = min((uint32_t)kChunkBits, limit);
+    const uint32_t* col = column(win);
+    uint32_t s = 0;  // chunk 0: the stream's first bit; after an invalid parse: the chunk's own (as the plain pass)
+    if (live && t > 0) {
+        const uint64_t e = P.exit_in[t - 1];
+        s = e == kNoExit ? 0u : rel_bit(e, b0);
+    }
+    uint32_t n = 0, pos = 0;
+    bool invalid = false;
+    if (live) n = parse_chunk(P, col, s_lut, b0, s, stop, limit, pos, invalid);
+    for (uint32_t round = 1; round < (uint32_t)kEgBlock; round++) {
+        s_x[threadIdx.x] = invalid ? ~0u : pos;
+        __syncthreads();
+        bool moved = false;
+        if (live && threadIdx.x > 0) {
+            const uint32_t xp = s_x[threadIdx.x - 1];  // >= 512 unless invalid: only the last chunk stops short
+            const uint32_t s2 = xp == ~0u ? 0u : xp - (uint32_t)kChunkBits;
+            moved = s2 != s;
+            s = s2;
+        }
+        if (!__syncthreads_or(moved)) break;  // (also orders the reads of s_x before the next round's writes)
+        if (moved) n = parse_chunk(P, col, s_lut, b0, s, stop, limit, pos, invalid);
+    }
+    if (!live) return;
+    const uint64_t ex = invalid ? kNoExit : (uint64_t)b0 + pos;
+    P.exit_out[t] = ex;
+    P.count[t] = n;
+    if (ex != P.exit_in[t]) atomicOr((unsigned int*)&P.status[0], 1u);
+}
+
 // Decoupled look-back over per-block descriptors (the fused front's chunk value indices):
 // desc[b] holds a flag in the top 2 bits -- 1 the block's aggregate, 2 its inclusive prefix, 3 failed --
 // and the value below (zeroed by the host before the launch).  Called by a whole wave (64 lanes) of block
@@ -1459,6 +1513,12 @@ int launch_eg_sync(const EgDecParams& P, int iteration, int resolve, hipStream_t
 #endif
     hipLaunchKernelGGL(eg_sync_kernel, dim3((uint32_t)((P.n_chunks + per - 1) / per)), dim3(kEgBlock), 0, st, P,
                        iteration, (int)rs);
+    return launched();
+}
+
+int launch_eg_chain(const EgDecParams& P, hipStream_t st) {
+    if (P.n_chunks == 0) return 0;
+    hipLaunchKernelGGL(eg_chain_kernel, dim3((uint32_t)((P.n_chunks + kEgBlock - 1) / kEgBlock)), dim3(kEgBlock), 0, st, P);
     return launched();
 }
 

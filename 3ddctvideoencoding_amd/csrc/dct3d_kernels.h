@@ -272,6 +272,9 @@ int launch_eg_encode(int D, const EgParams& P, hipStream_t st);
 // pass-0 boundary of chunk t (in the block's LDS window); status[0] = 0: every chunk met, the pass-0 exits
 // and counts are final.  Otherwise (or without resolve) confirming passes (iteration 1) follow.
 int launch_eg_sync(const EgDecParams& P, int iteration, int resolve, hipStream_t st);
+// a confirming pass that also hands the exits on inside each block of 256 chunks (eg_chain_kernel): after
+// launch j every chunk of blocks 0 .. j - 1 is final; status[0] = 0: no exit changed
+int launch_eg_chain(const EgDecParams& P, hipStream_t st);
 int launch_eg_scan(const EgParams& P, hipStream_t st);   // scan of P.bits[0..n_cubes) into P.off / P.status[0]
 int launch_eg_decode_write(int D, const EgDecParams& P, hipStream_t st);  // mark pass + emit
 int launch_eg_mark(const EgDecParams& P, hipStream_t st);

@@ -398,6 +398,16 @@ int dct3d_chroma_size(int w, int h, int* cw, int* ch) {
     return DCT3D_OK;
 }
 
+int dct3d_eg_sync_launches(const dct3d_ctx* c, uint64_t* max_per_front, uint64_t* sum) {
+    if (!c || !max_per_front || !sum) return DCT3D_EINVAL;
+    *max_per_front = *sum = 0;
+    for (uint64_t n : c->egd_launches) {
+        *max_per_front = n > *max_per_front ? n : *max_per_front;
+        *sum += n;
+    }
+    return DCT3D_OK;
+}
+
 int dct3d_ctx_set_profiling(dct3d_ctx* c, int on) {
     if (!c) return DCT3D_EINVAL;
     c->profiling = on != 0;
@@ -1218,6 +1228,12 @@ int dct3d_encode_eg_frames(dct3d_ctx* c, const uint8_t* frames, int w, int h, in
 // bit 4, the consumer skips itself, and eg_decode_status asks the caller to rerun without speculation
 // (kEgRetry).  This takes the host round trip between pass 0 and the scan off every call.
 constexpr int kEgRetry = 1000;
+#ifndef DCT3D_EG_PLAIN_CONFIRM  // A/B only: 1 = the rerun's confirming passes as plain eg_sync_kernel passes, one chunk each
+#define DCT3D_EG_PLAIN_CONFIRM 0
+#endif
+constexpr bool kEgPlainConfirm = DCT3D_EG_PLAIN_CONFIRM != 0;
+// a stream decode call begins: its fronts' sync launches are counted from here (dct3d_eg_sync_launches)
+static void egd_launches_reset(dct3d_ctx* c) { c->egd_launches[0] = c->egd_launches[1] = c->egd_launches[2] = 0; }
 // set >= 0 (a packed RGB24 stream decode: one front per channel, all three alive for the consumer): the front
 // keeps its marks in region `set` of three in d_egd_mark and its status words in d_egd_status3[set], zeroed
 // here; the other work buffers are reused from front to front in stream order.  set < 0: the grey calls' one
@@ -1270,18 +1286,25 @@ static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
             hipMemsetAsync(c->d_egd_desc.p, 0, nb * sizeof(uint64_t), c->stream) != hipSuccess)
             return DCT3D_EDEVICE;
         if (launch_eg_front(D, (uint64_t*)c->d_egd_desc.p, c->opt_eg_force_retry ? 1 : 0, c->stream)) return DCT3D_EKERNEL;
+        c->egd_launches[set < 0 ? 0 : set]++;
         return DCT3D_OK;
     }
-    // sync passes until no chunk exit changes (pass 0 parses from the nominal chunk starts and, resolving,
-    // usually proves every chunk in sync by itself; otherwise confirming passes follow); at most
-    // n_chunks + 1 passes by induction from chunk 0.  DCT3D_OPT_EG_NO_RESOLVE: always confirm (A/B, tests)
+    // sync passes until no chunk exit changes: pass 0 parses from the nominal chunk starts and, resolving,
+    // usually proves every chunk in sync by itself; otherwise confirming passes follow, each also handing the
+    // exits on inside its blocks of 256 chunks (eg_chain_kernel): after confirming pass j every chunk of blocks
+    // 0 .. j - 1 is final by induction from chunk 0, so ceil(n_chunks / 256) of them finish a stream whose wrong
+    // parses never meet the true one, and one more sees no change.  DCT3D_OPT_EG_NO_RESOLVE: always confirm (A/B, tests)
     const bool resolve = !c->opt_eg_no_resolve;
+    const uint64_t last = kEgPlainConfirm ? n_chunks + 1 : (n_chunks + 255) / 256 + 1;
+    uint64_t& launches = c->egd_launches[set < 0 ? 0 : set];
     int cur = 0;
-    for (uint64_t it = 0; it <= n_chunks + 1; it++) {
+    for (uint64_t it = 0; it <= last; it++) {
         if (!(it == 0 && clean) && hipMemsetAsync(st, 0, kEgdStatusBytes, c->stream) != hipSuccess) return DCT3D_EDEVICE;
         D.exit_in = ex[cur];
         D.exit_out = ex[cur ^ 1];
-        if (launch_eg_sync(D, (int)(it < 2 ? it : 1), resolve, c->stream)) return DCT3D_EKERNEL;
+        if ((it == 0 || kEgPlainConfirm) ? launch_eg_sync(D, it ? 1 : 0, resolve, c->stream) : launch_eg_chain(D, c->stream))
+            return DCT3D_EKERNEL;
+        launches++;
         cur ^= 1;
         if (it == 0 && !resolve) continue;
         if (it == 0 && spec) {  // speculative front: the verdict is read on the device (eg_mark_kernel)
@@ -1292,7 +1315,7 @@ static int eg_decode_front(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
         uint64_t changed = 0;
         if (read_status(c, st, 8, &changed)) return DCT3D_EDEVICE;
         if (!changed) break;
-        if (it == n_chunks + 1) return DCT3D_EINVAL;  // cannot happen: every pass fixes one more chunk
+        if (it == last) return DCT3D_EINVAL;  // cannot happen: the induction above
     }
     // value index of each chunk's first codeword
     EgParams S;
@@ -1381,6 +1404,7 @@ int dct3d_eg_decode_dev(dct3d_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, u
     if (end_bit) *end_bit = start_bit;
     if (n_cubes == 0) return DCT3D_OK;
     if (start_bit >= nbytes * 8) return DCT3D_ENODATA;
+    egd_launches_reset(c);
     for (int spec = 1;; spec = 0) {
         EgDecParams D{};
         int rc = eg_decode_front(c, d_bytes, nbytes, start_bit, n_cubes, D, spec && !c->opt_eg_no_resolve);
@@ -1450,6 +1474,7 @@ static int decode_eg_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const uint
                          uint64_t* end_bit) {
     const bool handoff = !host_out && g.px == 1;
     int rc;
+    egd_launches_reset(c);
     for (int spec = 1;; spec = 0) {
         EgDecParams E[3] = {};
         for (int ch = 0; ch < g.px; ch++)
@@ -1543,6 +1568,7 @@ static int decode_c420_run(dct3d_ctx* c, const uint8_t* const* d_bytes, const ui
                            uint8_t* host_out, uint64_t* end_bit) {
     const uint64_t cubes[3] = {n_cubes, nc, nc};
     int rc;
+    egd_launches_reset(c);
     for (int spec = 1;; spec = 0) {
         EgDecParams E[3] = {};
         for (int ch = 0; ch < 3; ch++)

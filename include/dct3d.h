@@ -425,6 +425,14 @@ int dct3d_decode_eg_dev(dct3d_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
 int dct3d_decode_eg(dct3d_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, int start_bit, int width, int height,
                     int n_stacks, uint8_t *raster, uint64_t *end_bit);
 
+/* The cost of the last stream decode call on the context (additive to ABI 9; detect by symbol; DESIGN.md
+ * section 4b): the sync launches its fronts issued, the speculative attempt and its rerun together.  A front
+ * issues 1 on a stream whose chunks all fall into step (every encoder's output), and at most
+ * ceil(n_chunks / 256) + 3 on any stream, n_chunks = ceil((8 nbytes - start_bit) / 512).  A call with three
+ * streams (packed RGB24) has a front per stream: *max_per_front is the largest of their counts, *sum their sum;
+ * one stream: both are its count.  0 before the first such call.  No device work, no synchronisation. */
+int dct3d_eg_sync_launches(const dct3d_ctx *ctx, uint64_t *max_per_front, uint64_t *sum);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused stream encode and decode for frames of any size, grey or packed RGB24 (additive to ABI 9; detect by
  * symbol): raster -> Exp-Golomb streams and back with no int32 intermediate, as dct3d_encode_eg* /

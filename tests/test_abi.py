@@ -86,6 +86,19 @@ def test_argument_validation_without_device(pkg):
     L.dct3d_ctx_destroy(None)  # no-op
 
 
+def test_eg_sync_launches_is_exported_declared_and_validates(pkg):
+    """dct3d_eg_sync_launches (additive to ABI 9): exported, declared, listed; null arguments are refused"""
+    header = open(os.path.join(REPO, "include", "dct3d.h")).read()
+    assert re.search(r"^int dct3d_eg_sync_launches\(const dct3d_ctx \*ctx, uint64_t \*max_per_front, uint64_t \*sum\);",
+                     header, re.M)
+    assert "dct3d_eg_sync_launches" in pkg.ABI_SYMBOLS and "dct3d_eg_sync_launches" in _exported(pkg.LIB_PATH)
+    assert pkg.lib().dct3d_abi_version() == 9
+    L = pkg.lib()
+    a, b = C.c_uint64(7), C.c_uint64(7)
+    assert L.dct3d_eg_sync_launches(None, C.byref(a), C.byref(b)) == pkg.DCT3D_EINVAL
+    assert (a.value, b.value) == (7, 7)
+
+
 def test_cli_usage_without_device(pkg):
     r = subprocess.run([pkg.CLI_PATH], capture_output=True, text=True)
     assert r.returncode == 0 and "Usage" in r.stdout
