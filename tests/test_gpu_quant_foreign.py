@@ -23,6 +23,7 @@ import pytest
 
 import quant_common as qc
 from conftest import ctx_option
+from foreign_common import STREAM_KINDS
 from test_gpu_eg import _expected
 from test_gpu_quant import _frames, tie_cube
 
@@ -217,69 +218,8 @@ def test_int32_decode_same_q_two_sides_of_the_guard(pkg, qctx, depth, w, h, chan
 
 # ---- streams no encoder wrote ---------------------------------------------------------------------------------------
 
-def _sparse(rng, n, depth):
-    q = rng.integers(-20, 21, size=(n, depth, 8, 8))
-    q[rng.random(q.shape) < 0.5] = 0
-    return q
-
-
-def _limit_cubes(depth, n, seed):
-    """3a: sparse small values with +-(2^15 - 1) among them (31-bit codes, the widest the unchecked parse steps take);
-    cube n // 3: all 32 values of one lane's part (kz = depth - 1, every ky, kx = 4 .. 7) are +-(2^15 - 1); cube
-    2n // 3: entirely +-(2^15 - 1)"""
-    rng = np.random.default_rng(seed)
-    q = _sparse(rng, n, depth)
-    sgn = rng.choice([-1, 1], size=q.shape)
-    edge = rng.random(q.shape) < 0.002
-    edge[0, 0, 0, 1] = True
-    q[edge] = qc.Q15 * sgn[edge]
-    q[n // 3, depth - 1, :, 4:] = qc.Q15 * sgn[n // 3, depth - 1, :, 4:]
-    q[2 * n // 3] = qc.Q15 * sgn[2 * n // 3]
-    q = q.astype(np.int32)
-    assert np.abs(q).max() == qc.Q15 and qc.code_bits(q).max() == 31
-    assert np.abs(q[n // 3, depth - 1, :, 4:]).min() == qc.Q15 and 32 * qc.Q15 * 255 < 2**28
-    return q
-
-
-def _long_cubes(depth, n, seed):
-    """3b: a few values in [2^15, 2^20) (33- to 41-bit codes) among sparse small ones and +-(2^15 - 1); the first
-    value of the stream is 2^15, the narrowest long code"""
-    rng = np.random.default_rng(seed)
-    q = _sparse(rng, n, depth)
-    sgn = rng.choice([-1, 1], size=q.shape)
-    edge = rng.random(q.shape) < 0.002
-    q[edge] = qc.Q15 * sgn[edge]
-    big = rng.random(q.shape) < 0.001
-    big[n - 1, 1, 2, 3] = True
-    q[big] = rng.integers(2**15, 2**20, size=int(big.sum())) * sgn[big]
-    q[0, 0, 0, 0] = 2**15
-    q = q.astype(np.int32)
-    bits = qc.code_bits(q)
-    assert bits[0, 0, 0, 0] == 33 and 33 <= bits.max() <= 41 and (bits > 31).sum() >= 2
-    return q
-
-
-def _all_long_cubes(depth, n, seed):
-    """3c: every |q| in [2^15, 2^16): 33-bit codes only"""
-    rng = np.random.default_rng(seed)
-    q = (rng.integers(2**15, 2**16, size=(n, depth, 8, 8)) * rng.choice([-1, 1], size=(n, depth, 8, 8))).astype(np.int32)
-    assert (qc.code_bits(q) == 33).all()
-    return q
-
-
-def _ordinary_stream_cubes(depth, n, seed):
-    """what an encoder writes even under all255: a DC of at most 11 (255 sqrt(512) / 255), one AC value in ten +-1:
-    L1 under the guard with every table"""
-    rng = np.random.default_rng(seed)
-    q = rng.choice([-1, 1], size=(n, depth, 8, 8)) * (rng.random((n, depth, 8, 8)) < 0.1)
-    q[:, 0, 0, 0] = rng.integers(0, 12, size=n)
-    assert (qc.l1(q, np.full(qc.n_steps(depth), 255), depth) < qc.l1_max(depth) / 4).all()
-    return q.astype(np.int32)
-
-
-STREAM_KINDS = {"limit": _limit_cubes, "long": _long_cubes, "all_long": _all_long_cubes, "ordinary": _ordinary_stream_cubes}
-
-
+# the cube kinds (3a: limit, 3b: long, 3c: all_long, and what an encoder writes: ordinary) live in foreign_common.py,
+# which test_gpu_foreign_modes.py shares
 @functools.lru_cache(maxsize=None)
 def _stream_clip(kinds, depth, w, h, stacks):
     """q [stack][channel][cube]: channel ch's cubes (all stacks: one stream) of kind kinds[ch]"""
